@@ -1,7 +1,7 @@
 """bench.py - GAN train steps/s of the Social Ways inner loop on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload m1|c2|c4] [--scaling weak|strong]
-                    [--no-cpu-baseline] [--no-other-workloads]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-other-workloads] [--no-sustained]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          (no launcher: the N ranks are started by self_launch() the same way)
@@ -18,15 +18,21 @@ N > 1: one process per GPU, gradients all-reduced with RCCL three times per step
                    `value` counts 256-scene batches processed per second by the whole job.
   --scaling strong ONE packed batch of --global-scenes scenes (default 2048 = 8 x m1) is sharded over the
                    ranks by data.shard_scenes (scene aligned); `value` = global steps/s, total work fixed.
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run measures the headline alone: set-up, priming, settle and warmup steps, two
+rehearsals of the region, then EXACTLY K timed steps (`value`, `ms_per_step`).  --dump-outputs DIR writes what the last
+of those K steps computed (dump_outputs).  With --full the line also carries
   config.repeats          min / median / max ms_per_step over R further blocks of K steps (spread of this box),
+  config.sustained        >= 2 s of back-to-back steps (--no-sustained skips it),
+  config.inputs_resident  the same K steps with z already in HBM (SW_BENCH_HOST_Z=0: config.pcie_inclusive, the reverse),
+  config.replicas_identical  N > 1: the replicas' weights compared after the run,
+  config.exchange         N > 1: the gradient exchange report, a child job (--no-other-workloads skips it),
   config.other_workloads  short legs of the other BASELINE shapes (c2 = --batch-size 256, c4 = dense crowd), the 1-rank
                           RCCL form of m1 and the K = 20 variety step; each the FASTEST of three regions of its n steps,
   roofline                the kernel that takes the most time per step, timed live with HIP events around every launch
                           of an eager pass (sw_kernel_timing; fp32 MFMA peak), `roofline.kernels` = the top-6 table,
                           `roofline.step_traffic` = HBM bytes per step from the committed PMC pass of these kernel sources,
   cpu_baseline            the CPU oracle on this host: block-diagonal port (all threads, 1 thread) and the
-                          reference's own dense + per-agent-loop formulation at a reduced batch.
+                          reference's own dense + per-agent-loop formulation at a reduced batch (--no-cpu-baseline skips it).
 """
 import argparse
 import ctypes
@@ -829,6 +835,27 @@ def on_rank0(world, rank, dev, backend, tmpdir, tag, fn, wait_s):
     return _read_json(path) or {"error": "rank 0 did not report within %.0f s" % wait_s}
 
 
+def dump_outputs(path, leg):
+    """--dump-outputs DIR: what the timed path handed back in its last step, one .npy file per array.  The inputs are seeded
+    (tracks, z, label noise), so the same arguments give the same inputs and two builds can be compared output for output:
+      loss_partials         the step's return value in the timed loop (out=False): (U+3, tiles, 3) float32 partial sums,
+      losses                the same summed over the tiles in float64, what step() returns by default,
+      generator_params      the generator's weights after the step: the attention, feature-embedder, encoder and decoder
+                            state_dicts in the reference's shapes and order, flattened, float32,
+      discriminator_params  the discriminator's weights after the step, likewise."""
+    os.makedirs(path, exist_ok=True)
+    ck = leg.tr.checkpoint()
+
+    def flat(keys):
+        return np.concatenate([t.detach().reshape(-1).float().cpu().numpy() for k in keys for t in ck[k].values()])
+    arrays = {"loss_partials": leg.last.float().cpu().numpy(),
+              "losses": leg.last.sum(1, dtype=torch.float64).cpu().numpy(),
+              "generator_params": flat(("attentioner_dict", "feature_embedder_dict", "encoder_dict", "decoder_dict")),
+              "discriminator_params": flat(("D_dict",))}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -837,9 +864,14 @@ def main():
     ap.add_argument("--workload", default="m1", choices=[k for k in sorted(WORKLOADS) if WORKLOADS[k][1] is not None])   # c3_ragged: a side leg only
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--global-scenes", type=int, default=2048, help="--scaling strong: scenes of the ONE global packed batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2 s sustained leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (losses, weights after it) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: repeats, sustained leg, the other z form, per-kernel "
+                         "roofline pass, CPU baseline, other workloads (N = 1) or the exchange report (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full: skip the side legs / the exchange report")
+    ap.add_argument("--no-sustained", action="store_true", help="--full: skip the >= 2 s sustained leg")
     ap.add_argument("--launch-check", action="store_true",
                     help="only launch / rendezvous / reduce over the N ranks (no GPU needed), print a JSON line with value null")
     # children of this file (run_side_children / run_exchange_child): the side legs run where they cannot take the line down
@@ -940,13 +972,16 @@ def main():
     for r in range(REHEARSALS):
         leg.timed(fence, args.warmup, args.steps)
     dt = max_over_ranks(leg.timed(fence, args.warmup, args.steps))          # THE timed region: exactly K steps
-    reps = [max_over_ranks(leg.timed(fence, args.warmup + (r + 1) * args.steps, args.steps)) for r in range(REPEATS)]
+    if args.dump_outputs and rank == 0:       # before any --full leg steps on: a plain and a full run dump the same
+        dump_outputs(args.dump_outputs, leg)
+    reps = [max_over_ranks(leg.timed(fence, args.warmup + (r + 1) * args.steps, args.steps))
+            for r in range(REPEATS if args.full else 0)]
     if os.environ.get("SW_BENCH_VERBOSE"):
         print("regions (ms per step): first %.4f, then %s" % (1e3 * dt / args.steps, ["%.4f" % (1e3 * r / args.steps) for r in reps]),
               file=sys.stderr)
     # a sustained leg (>= ~2 s of back-to-back steps): long enough for an external GPU-busy sampler to see the device
     sustained = None
-    if not args.no_sustained:
+    if args.full and not args.no_sustained:
         n_sus = 1 + max(args.steps, int(2.2 / max(dt / args.steps, 1e-5))) // KG * KG      # [1, KG, KG, ...]: no new launch size
         d_sus = max_over_ranks(leg.timed(fence, 0, n_sus))
         sustained = {"steps": n_sus, "seconds": d_sus, "steps_s": n_sus * (world if args.scaling == "weak" else 1) / d_sus,
@@ -954,7 +989,7 @@ def main():
     # the PCIe-inclusive form of the same K steps: z drawn on the host every step (train.py:473), copied into the pinned slot and
     # pulled inside the step (small launches: the host needs ~0.15 ms per step to prepare)
     pcie = None
-    if not HOST_Z:
+    if args.full and not HOST_Z:
         leg.z_host()
         leg.prime((args.steps, args.warmup))
         leg.run_steps(0, args.warmup)
@@ -964,7 +999,7 @@ def main():
         leg.z_resident()
     # ... and, when the headline is the reference's host-drawn z, the all-resident form of the same K steps as the secondary figure
     resident = None
-    if HOST_Z and args.scaling == "weak":
+    if args.full and HOST_Z and args.scaling == "weak":
         leg.z_resident()
         leg.prime((args.steps, args.warmup))
         leg.run_steps(0, args.warmup)
@@ -974,52 +1009,53 @@ def main():
                             "PCIe read inside the step); fastest of 3 regions"}
         leg.z_host()
     gc.enable()
-    # Roofline leg: the timed region replays hipGraphs, where no per-kernel event can be placed, so EVERY kernel launch
-    # of a few EAGER steps of the same workload is bracketed by HIP events on its launch stream (sw_kernel_timing); a
-    # spin kernel queued in front lets the host run ahead, so the launches reach the GPU back to back and the event
-    # intervals hold no host gaps.  profiles/ holds the rocprofv3 trace of the graph-replayed run for comparison.
     n_ev = max(4, min(args.steps, 20))
     ktimes, event_overhead_us, roofline_error = {}, None, None
-    try:
-        tr.use_graph = False
-        for i in range(2):
-            leg.one_step(i)
-        # inputs of the timed eager steps are placed on the device beforehand: a host-to-device copy inside the pass would
-        # make the host wait for the stream and the launches behind it would reach an idle GPU one by one
-        from socialways_amd import ops as sw_ops
-        scenes = sw_ops.SceneIndex.get(leg.sb, leg.B, dev)
-        ins = []
-        for i in range(n_ev):
-            o, p_, zv, ov, nz = leg.draw(i)
-            ins.append((o.contiguous(), p_.contiguous(), torch.tensor([zv, ov], dtype=torch.float32).to(dev),
-                        tr._pad_z(nz.to(dev)).contiguous()))
-        part = torch.zeros(tr.n_unrolling_steps + 3, (leg.B + 15) // 16, 3, device=dev)
-        tr._row0, tr._vnoise = 0, None
-        fence()
-        lib = L.load()
-        lib.sw_kernel_timing(1)
-        lib.sw_debug_spin(float(os.environ.get("SW_BENCH_SPIN_US", 2500.0 * n_ev)), L.stream())
-        for o, p_, tg, nz in ins:
-            leg.last = tr._step_impl(o, p_, None, scenes, tg, nz, float(leg.data.ss), float(leg.Bg), part)
-        for _ in range(32):
-            lib.sw_debug_spin(0.0, L.stream())       # calibration: the event interval of a kernel that does nothing
-        fence()
-        buf = ctypes.create_string_buffer(1 << 16)
-        lib.sw_kernel_timing_read(buf, len(buf))
-        lib.sw_kernel_timing(0)
-        for line in buf.value.decode().splitlines():
-            name, calls, total_us = line.split()
-            if name == "nop_kernel":
-                event_overhead_us = float(total_us) / int(calls)
-            elif name != "spin_kernel":
-                ktimes[name] = (int(calls), float(total_us))
-    except Exception as e:      # noqa: BLE001 - the per-kernel view is lost, the timed region is not
-        if world > 1:
-            raise               # (collectives inside the eager steps: a one-sided failure cannot be survived in place)
-        roofline_error, ktimes = _err(e)["error"], {}
+    if args.full:
+        # Roofline leg: the timed region replays hipGraphs, where no per-kernel event can be placed, so EVERY kernel launch
+        # of a few EAGER steps of the same workload is bracketed by HIP events on its launch stream (sw_kernel_timing); a
+        # spin kernel queued in front lets the host run ahead, so the launches reach the GPU back to back and the event
+        # intervals hold no host gaps.  profiles/ holds the rocprofv3 trace of the graph-replayed run for comparison.
+        try:
+            tr.use_graph = False
+            for i in range(2):
+                leg.one_step(i)
+            # inputs of the timed eager steps are placed on the device beforehand: a host-to-device copy inside the pass would
+            # make the host wait for the stream and the launches behind it would reach an idle GPU one by one
+            from socialways_amd import ops as sw_ops
+            scenes = sw_ops.SceneIndex.get(leg.sb, leg.B, dev)
+            ins = []
+            for i in range(n_ev):
+                o, p_, zv, ov, nz = leg.draw(i)
+                ins.append((o.contiguous(), p_.contiguous(), torch.tensor([zv, ov], dtype=torch.float32).to(dev),
+                            tr._pad_z(nz.to(dev)).contiguous()))
+            part = torch.zeros(tr.n_unrolling_steps + 3, (leg.B + 15) // 16, 3, device=dev)
+            tr._row0, tr._vnoise = 0, None
+            fence()
+            lib = L.load()
+            lib.sw_kernel_timing(1)
+            lib.sw_debug_spin(float(os.environ.get("SW_BENCH_SPIN_US", 2500.0 * n_ev)), L.stream())
+            for o, p_, tg, nz in ins:
+                leg.last = tr._step_impl(o, p_, None, scenes, tg, nz, float(leg.data.ss), float(leg.Bg), part)
+            for _ in range(32):
+                lib.sw_debug_spin(0.0, L.stream())       # calibration: the event interval of a kernel that does nothing
+            fence()
+            buf = ctypes.create_string_buffer(1 << 16)
+            lib.sw_kernel_timing_read(buf, len(buf))
+            lib.sw_kernel_timing(0)
+            for line in buf.value.decode().splitlines():
+                name, calls, total_us = line.split()
+                if name == "nop_kernel":
+                    event_overhead_us = float(total_us) / int(calls)
+                elif name != "spin_kernel":
+                    ktimes[name] = (int(calls), float(total_us))
+        except Exception as e:      # noqa: BLE001 - the per-kernel view is lost, the timed region is not
+            if world > 1:
+                raise               # (collectives inside the eager steps: a one-sided failure cannot be survived in place)
+            roofline_error, ktimes = _err(e)["error"], {}
     assert torch.isfinite(leg.last).all(), "non-finite losses"
     replicas_identical = None
-    if world > 1:      # data-parallel replicas must hold bit-identical weights after the same all-reduced updates
+    if args.full and world > 1:      # data-parallel replicas must hold bit-identical weights after the same all-reduced updates
         chk = torch.stack([tr.G._flat_all.double().sum(), tr.D._flat.double().sum()])
         hi, lo = chk.clone(), chk.clone()
         torch.distributed.all_reduce(hi, op=torch.distributed.ReduceOp.MAX)
@@ -1039,6 +1075,48 @@ def main():
         B, P = leg.B, leg.P
         fl = alg_flops(B, P, To, Tp)
         per_step = dt / args.steps
+        value = args.steps * (world if args.scaling == "weak" else 1) / dt
+        res = {
+            "metric": "GAN train steps/sec (%d scenes x %d agents x %d+%d T per %s step; fp32; social block on)"
+                      % ((S, A, To, Tp, "GPU") if args.scaling == "weak" else (leg.S_global, A, To, Tp, "GLOBAL")),
+            "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * per_step, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": ("%s: %d scenes x %d agents x (%d obs + %d pred) per GPU step = reference "
+                                    "--batch-size %d; use_social=True, n_unrolling_steps=1, info loss on"
+                                    % (args.workload, S, A, To, Tp, B)) if args.scaling == "weak" else
+                                   ("%s-strong: ONE packed batch of %d scenes x %d agents (reference --batch-size %d) sharded "
+                                    "scene-aligned over %d ranks; use_social=True, n_unrolling_steps=1, info loss on"
+                                    % (args.workload, leg.S_global, A, leg.Bg, world)),
+                       "full": args.full,      # the legs behind the headline ran (--full); else they are null / absent
+                       "global_batch_scenes": leg.S_global, "parallelism": "dp%d" % world, "steps_per_graph_launch": KG, "settle_steps": SETTLE, "rehearsal_regions": REHEARSALS,
+                       # everything that ran untimed in front of THE region: priming (5 passes over every launch size), settle steps,
+                       # the W warmup steps and the rehearsals of the region ("warmup" above is only W)
+                       "untimed_steps_before_region": UNTIMED_BEFORE,
+                       "collectives": collectives, "rccl_ranks": (world if pg is not None else None),
+                       "backend": backend,       # "nccl" = RCCL; "gloo" = ranks sharing devices, a rehearsal, not a measurement
+                       "allreduces_per_step": (3 if pg is not None else 0),
+                       "allreduce": allreduce_form,
+                       "collectives_probe": probe,      # N > 1 on RCCL: the child job that tried in-graph collectives before the headline
+                       "exchange": None,          # N > 1: us per all-reduce of each bucket on both forms + the step on the direct form (below)
+                       "exchange_probe": exchange_probe,      # SW_ALLREDUCE=auto: what the probe measured / chose
+                       "agent_steps_s": value * B if args.scaling == "weak" else value * leg.Bg,      # agents stepped per second, whole job
+                       "replicas_identical": replicas_identical,
+                       "step_alg_gflop": fl["step"] / 1e9,
+                       "step_frac_of_fp32_peak": fl["step"] / per_step / (PEAK_FP32_TFLOPS * 1e12),
+                       "step_alg_bytes": alg_bytes(B, To, Tp),
+                       "step_frac_of_hbm_peak": alg_bytes(B, To, Tp) / per_step / PEAK_HBM_BPS,
+                       "repeats": None,
+                       "sustained": sustained,
+                       "inputs": "z drawn on the host every step" if HOST_Z else RESIDENT,
+                       "pcie_inclusive": pcie,
+                       "inputs_resident": resident,
+                       "other_workloads": None},
+        }
+    if rank == 0 and args.full:
+        rep_ms = sorted(1e3 * r / args.steps for r in reps)
+        res["config"]["repeats"] = {"n": len(rep_ms), "steps_each": args.steps, "ms_per_step_min": rep_ms[0],
+                                    "ms_per_step_median": rep_ms[len(rep_ms) // 2], "ms_per_step_max": rep_ms[-1]}
         # per-kernel table of the eager roofline pass: launches / step, mean launch time, algorithmic GFLOP / step, fraction
         kfl = kernel_alg_flops(B, P, To, Tp, one_launch_d="disc_update_kernel" in ktimes)
         rows = []
@@ -1073,72 +1151,33 @@ def main():
         if traffic_src is None:
             traffic_src = {"file": None, "kernel_src_sha16": sha,
                            "note": "no PMC pass under profiles/ matches these kernel sources / this workload"}
-        value = args.steps * (world if args.scaling == "weak" else 1) / dt
-        rep_ms = sorted(1e3 * r / args.steps for r in reps)
-        res = {
-            "metric": "GAN train steps/sec (%d scenes x %d agents x %d+%d T per %s step; fp32; social block on)"
-                      % ((S, A, To, Tp, "GPU") if args.scaling == "weak" else (leg.S_global, A, To, Tp, "GLOBAL")),
-            "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * per_step, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("%s: %d scenes x %d agents x (%d obs + %d pred) per GPU step = reference "
-                                    "--batch-size %d; use_social=True, n_unrolling_steps=1, info loss on"
-                                    % (args.workload, S, A, To, Tp, B)) if args.scaling == "weak" else
-                                   ("%s-strong: ONE packed batch of %d scenes x %d agents (reference --batch-size %d) sharded "
-                                    "scene-aligned over %d ranks; use_social=True, n_unrolling_steps=1, info loss on"
-                                    % (args.workload, leg.S_global, A, leg.Bg, world)),
-                       "global_batch_scenes": leg.S_global, "parallelism": "dp%d" % world, "steps_per_graph_launch": KG, "settle_steps": SETTLE, "rehearsal_regions": REHEARSALS,
-                       # everything that ran untimed in front of THE region: priming (5 passes over every launch size), settle steps,
-                       # the W warmup steps and the rehearsals of the region ("warmup" above is only W)
-                       "untimed_steps_before_region": UNTIMED_BEFORE,
-                       "collectives": collectives, "rccl_ranks": (world if pg is not None else None),
-                       "backend": backend,       # "nccl" = RCCL; "gloo" = ranks sharing devices, a rehearsal, not a measurement
-                       "allreduces_per_step": (3 if pg is not None else 0),
-                       "allreduce": allreduce_form,
-                       "collectives_probe": probe,      # N > 1 on RCCL: the child job that tried in-graph collectives before the headline
-                       "exchange": None,          # N > 1: us per all-reduce of each bucket on both forms + the step on the direct form (below)
-                       "exchange_probe": exchange_probe,      # SW_ALLREDUCE=auto: what the probe measured / chose
-                       "agent_steps_s": value * B if args.scaling == "weak" else value * leg.Bg,      # agents stepped per second, whole job
-                       "replicas_identical": replicas_identical,
-                       "step_alg_gflop": fl["step"] / 1e9,
-                       "step_frac_of_fp32_peak": fl["step"] / per_step / (PEAK_FP32_TFLOPS * 1e12),
-                       "step_alg_bytes": alg_bytes(B, To, Tp),
-                       "step_frac_of_hbm_peak": alg_bytes(B, To, Tp) / per_step / PEAK_HBM_BPS,
-                       "repeats": {"n": len(rep_ms), "steps_each": args.steps, "ms_per_step_min": rep_ms[0],
-                                   "ms_per_step_median": rep_ms[len(rep_ms) // 2], "ms_per_step_max": rep_ms[-1]},
-                       "sustained": sustained,
-                       "inputs": "z drawn on the host every step" if HOST_Z else RESIDENT,
-                       "pcie_inclusive": pcie,
-                       "inputs_resident": resident,
-                       "other_workloads": None},
-            "roofline": {"bound": "mfma", "kernel": top["name"], "achieved": achieved, "error": roofline_error,
-                         "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS,
-                         "avg_launch_ms": kern_s * 1e3, "launches": int(round(top["launches_per_step"] * n_ev)),
-                         "launches_per_step": top["launches_per_step"],
-                         "how": "HIP events around every kernel launch of %d eager steps (sw_kernel_timing), host running ahead "
-                                "of the GPU behind a spin kernel; algorithmic FLOPs of all of the kernel's launches in a step "
-                                "/ their summed time" % n_ev,
-                         "kernels": rows[:int(os.environ.get("SW_BENCH_KERNEL_ROWS", "6"))],
-                         # what an event pair adds to a launch (a kernel that does nothing, same queue): subtract from avg_us
-                         # for the kernel's own duration; `frac` is computed from the RAW times (conservative)
-                         "event_overhead_us": event_overhead_us,
-                         "eager_step_kernel_us": sum(r["us_per_step"] for r in rows),
-                         # `frac` / step_frac_of_fp32_peak count the REFERENCE formulation's FLOPs and so credit work
-                         # the kernels eliminate; *_executed = matrix FLOP really issued (64 x SQ_VALU_MFMA_BUSY_CYCLES of the
-                         # committed SQ pass of these kernel sources) over the same measured times: pipe USE, never above 1
-                         "step_frac_reference_formulation": fl["step"] / per_step / (PEAK_FP32_TFLOPS * 1e12),
-                         "step_executed_mfma_gflop": (step_exec / 1e9) if step_exec else None,
-                         "step_frac_executed": (step_exec / per_step / (PEAK_FP32_TFLOPS * 1e12)) if step_exec else None,
-                         "frac_executed": top.get("frac_executed"),
-                         "traffic": traffic, "step_traffic": step_traffic,
-                         "step_traffic_vs_algorithmic": (step_traffic / alg_bytes(B, To, Tp)) if step_traffic else None,
-                         "traffic_source": traffic_src,
-                         # north_star also asks for the HBM view: measured bytes / launch time vs 8 TB/s
-                         "hbm_GBps": (traffic / kern_s / 1e9) if traffic else None,
-                         "hbm_frac": (traffic / kern_s / PEAK_HBM_BPS) if traffic else None,
-                         "step_hbm_GBps": (step_traffic / per_step / 1e9) if step_traffic else None,
-                         "step_hbm_frac": (step_traffic / per_step / PEAK_HBM_BPS) if step_traffic else None},
-        }
+        res["roofline"] = {"bound": "mfma", "kernel": top["name"], "achieved": achieved, "error": roofline_error,
+                           "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS,
+                           "avg_launch_ms": kern_s * 1e3, "launches": int(round(top["launches_per_step"] * n_ev)),
+                           "launches_per_step": top["launches_per_step"],
+                           "how": "HIP events around every kernel launch of %d eager steps (sw_kernel_timing), host running ahead "
+                                  "of the GPU behind a spin kernel; algorithmic FLOPs of all of the kernel's launches in a step "
+                                  "/ their summed time" % n_ev,
+                           "kernels": rows[:int(os.environ.get("SW_BENCH_KERNEL_ROWS", "6"))],
+                           # what an event pair adds to a launch (a kernel that does nothing, same queue): subtract from avg_us
+                           # for the kernel's own duration; `frac` is computed from the RAW times (conservative)
+                           "event_overhead_us": event_overhead_us,
+                           "eager_step_kernel_us": sum(r["us_per_step"] for r in rows),
+                           # `frac` / step_frac_of_fp32_peak count the REFERENCE formulation's FLOPs and so credit work
+                           # the kernels eliminate; *_executed = matrix FLOP really issued (64 x SQ_VALU_MFMA_BUSY_CYCLES of the
+                           # committed SQ pass of these kernel sources) over the same measured times: pipe USE, never above 1
+                           "step_frac_reference_formulation": fl["step"] / per_step / (PEAK_FP32_TFLOPS * 1e12),
+                           "step_executed_mfma_gflop": (step_exec / 1e9) if step_exec else None,
+                           "step_frac_executed": (step_exec / per_step / (PEAK_FP32_TFLOPS * 1e12)) if step_exec else None,
+                           "frac_executed": top.get("frac_executed"),
+                           "traffic": traffic, "step_traffic": step_traffic,
+                           "step_traffic_vs_algorithmic": (step_traffic / alg_bytes(B, To, Tp)) if step_traffic else None,
+                           "traffic_source": traffic_src,
+                           # north_star also asks for the HBM view: measured bytes / launch time vs 8 TB/s
+                           "hbm_GBps": (traffic / kern_s / 1e9) if traffic else None,
+                           "hbm_frac": (traffic / kern_s / PEAK_HBM_BPS) if traffic else None,
+                           "step_hbm_GBps": (step_traffic / per_step / 1e9) if step_traffic else None,
+                           "step_hbm_frac": (step_traffic / per_step / PEAK_HBM_BPS) if step_traffic else None}
 
     import shutil
     import signal
@@ -1160,12 +1199,12 @@ def main():
             emit()
             os._exit(0)
         signal.signal(signal.SIGTERM, on_term)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(leg.tracks, S if args.workload != "c4" else 16, A, To, Tp)
             except Exception as e:      # noqa: BLE001
                 res["cpu_baseline"] = dict(_err(e), value=None, unit="steps/s", cores=None, kind="port", sample=None)
-    if world == 1 and pg is None and not args.no_other_workloads:
+    if args.full and world == 1 and pg is None and not args.no_other_workloads:
         tr.close()
         del tr
         leg.tr = None
@@ -1175,7 +1214,7 @@ def main():
             res["config"]["other_workloads"] = run_side_children(args, 1e3 * dt / args.steps, tmpdir)
         except Exception as e:      # noqa: BLE001
             res["config"]["other_workloads"] = _err(e)
-    if pg is not None and world > 1 and os.environ.get("SW_ALLREDUCE", "") != "direct" and not args.no_other_workloads:
+    if args.full and pg is not None and world > 1 and os.environ.get("SW_ALLREDUCE", "") != "direct" and not args.no_other_workloads:
         # N > 1: the exchange report is a CHILD JOB of rank 0 on the same GPUs (exchange_child_main)
         ex = on_rank0(world, rank, dev, backend, tmpdir, "exchange",
                       lambda: run_child_job(args, world, tmpdir, "exchange-only", "exchange", 420.0), child_timeout(420.0) + 120.0)

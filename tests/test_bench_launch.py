@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,11 +44,11 @@ def test_world_size_mismatch_is_refused():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_two_rank_bench_line_on_one_box():
-    """`python bench.py --gpus 2 --steps 4 --warmup 2` with SW_BENCH_BACKEND=gloo (both ranks on cuda:0): exit 0, one
+    """`python bench.py --gpus 2 --steps 4 --warmup 2 --full` with SW_BENCH_BACKEND=gloo (both ranks on cuda:0): exit 0, one
     JSON line, n_gpus = 2, three all-reduces per step, replicas bit-identical after the run."""
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-other-workloads",
+    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-other-workloads",
                      "--no-sustained"], {"SW_BENCH_BACKEND": backend, "SW_BENCH_SETTLE_STEPS": "8", "SW_BENCH_FORCE_PROBE": "1"}, 850)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -67,12 +68,12 @@ def test_two_rank_bench_line_on_one_box():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_two_rank_bench_line_reports_both_gradient_exchanges():
-    """N > 1 without --no-other-workloads: the line carries config.exchange - microseconds per all-reduce of the step's three
+    """N > 1 with --full and without --no-other-workloads: the line carries config.exchange - microseconds per all-reduce of the step's three
     buckets on the process group and on the library's direct exchange (SW_ALLREDUCE=direct), and the step on the direct
     form - so that a scaling run explains itself (2 ranks sharing cuda:0 here: a rehearsal of the plumbing)."""
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-sustained"],
+    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-sustained"],
                     {"SW_BENCH_BACKEND": backend, "SW_BENCH_SETTLE_STEPS": "8"}, 850)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads(lines[-1])
@@ -95,7 +96,7 @@ def test_a_crash_in_the_exchange_report_cannot_lose_the_line():
     group's own all-reduce times (measured before the fault) kept."""
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-sustained"],
+    p, lines = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-sustained"],
                     {"SW_BENCH_BACKEND": backend, "SW_BENCH_SETTLE_STEPS": "8", "SW_COMM_FAULT_INJECT": "1"}, 850)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -109,9 +110,9 @@ def test_a_crash_in_the_exchange_report_cannot_lose_the_line():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_a_dead_side_leg_child_cannot_lose_the_single_gpu_line():
-    """The N = 1 line's side legs run in child processes: a child that cannot even start its legs (here: its time limit is
+    """The N = 1 line's side legs (--full) run in child processes: a child that cannot even start its legs (here: its time limit is
     too short for the first one) leaves {"error": ...} records, the headline, roofline and cpu_baseline are untouched."""
-    p, lines = _run(["--steps", "4", "--warmup", "2", "--no-sustained"],
+    p, lines = _run(["--steps", "4", "--warmup", "2", "--full", "--no-sustained"],
                     {"SW_BENCH_SETTLE_STEPS": "8", "SW_BENCH_CHILD_TIMEOUT_S": "1"}, 850)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -119,3 +120,34 @@ def test_a_dead_side_leg_child_cannot_lose_the_single_gpu_line():
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["roofline"]["frac"] > 0 and rec["cpu_baseline"]["value"] > 0
     ow = rec["config"]["other_workloads"]
     assert all("error" in ow["_%s_child" % g] for g in ("shapes", "dp1", "extra")), ow
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_line_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run times exactly K steps and measures nothing else (no roofline, no CPU baseline, no side legs).
+    --dump-outputs writes what the last timed step returned and the weights after it.  The inputs are seeded, so a second
+    plain run and a --full run (whose extra legs start after the dump) write the same arrays, bit for bit."""
+    runs = ([], [], ["--full", "--no-cpu-baseline", "--no-other-workloads", "--no-sustained"])
+    recs, dumps = [], []
+    for i, extra in enumerate(runs):
+        d = tmp_path / str(i)
+        p, lines = _run(["--steps", "6", "--warmup", "2", "--dump-outputs", str(d)] + extra, {"SW_BENCH_SETTLE_STEPS": "8"}, 850)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert len(lines) == 1, p.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    plain, full = recs[0], recs[2]
+    assert plain["steps"] == 6 and plain["unit"] == "steps/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["value"] > 0 and abs(plain["value"] - 1e3 / plain["ms_per_step"]) < 1e-6 * plain["value"]
+    assert "roofline" not in plain and "cpu_baseline" not in plain and plain["config"]["full"] is False
+    assert plain["config"]["repeats"] is None and plain["config"]["inputs_resident"] is None
+    assert full["config"]["full"] is True and full["roofline"]["kernel"] and full["config"]["repeats"]["n"] == 5
+    got = dumps[0]
+    assert set(got) == {"loss_partials", "losses", "generator_params", "discriminator_params"}
+    assert got["losses"].dtype == np.float64 and got["loss_partials"].dtype == np.float32
+    assert got["loss_partials"].shape == (4, 2048 // 16, 3) and got["losses"].shape == (4, 3)
+    assert all(np.isfinite(a).all() for a in got.values())
+    np.testing.assert_allclose(got["losses"], got["loss_partials"].astype(np.float64).sum(1), rtol=1e-12)
+    for other in dumps[1:]:
+        assert set(other) == set(got) and all(np.array_equal(got[k], other[k]) for k in got)

@@ -11,7 +11,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 S=$OUT/summ
 mkdir -p $S
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-other-workloads --no-sustained"
+B="--full --no-cpu-baseline --no-other-workloads --no-sustained"
 SQ="SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY"
 for W in m1 c4; do
   if [ $W = m1 ]; then N="--steps 30 --warmup 5"; else N="--workload c4 --steps 6 --warmup 3"; fi

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd $REPO
-B="--no-cpu-baseline --no-other-workloads"
+B="--full --no-cpu-baseline --no-other-workloads"
 [ $W = m1 ] && N="--steps 40 --warmup 8" || N="--workload $W --steps 12 --warmup 4"
 for i in 1 2; do for V in $VALS; do
   env $VAR=$V python bench.py $N $B 2>/dev/null | grep "^{" | python -c "
