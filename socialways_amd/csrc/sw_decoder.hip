@@ -1,6 +1,6 @@
 // sw_decoder.hip - the decode loop of predict() (reference train.py:415-432): Tp times
 // { DecoderFC on cat[h, S, z] (train.py:320-335) -> v ; p += v ; EncoderLstm step on (p, v) },
-// as ONE persistent kernel per 16-agent tile, forward and backward.
+// as ONE persistent kernel per 16-agent tile (the forward also per two tiles), forward and backward.
 //
 // Layout of the work inside a workgroup (4 waves, one per SIMD):
 //   * decoder weights live in LDS for the whole kernel (115 KB, zero padded to MFMA tiles);
@@ -61,6 +61,7 @@ static_assert(16 * FwdLds::LD128 >= 16 * LD96, "prologue alias [S|z]");
 static_assert(16 * LD64 + 4 * 16 * FwdLds::LD16 >= 1280 + 176, "prologue alias wx | bx | W43");
 static_assert(FwdLds::total >= 2 * 16 * SW_HLD + 1280, "LDS of the observation-LSTM workgroups");
 static_assert(FwdLds::total * 4 <= 160 * 1024, "LDS of a CU");
+static_assert(2 * FwdLds::total * 4 <= 160 * 1024, "LDS of a CU (two tiles per workgroup)");
 
 // the k-steps J0 .. J0+NJ-1 of layer 2's tile 4 (rows 64..79): acc += W2[64 + ln][16 j + 4 lg + r] a1[ln][16 j + 4 lg + r]
 template <int J0, int NJ>
@@ -74,45 +75,67 @@ __device__ __forceinline__ f32x4 fwd_l2_part(const f32x4 (&w2p)[3], const f32x4 
 }
 }  // namespace
 
+// The decode forward, written once for NB = 1 or 2 16-agent tiles per workgroup (dec_rollout_fwd_kernel /
+// dec_rollout_fwd2_kernel below).  With two tiles - for batches with more tiles than CUs (dense crowds, large shards) -
+// every register-resident A operand (weight) is issued against two B operands, the tiles' activation tiles, so the
+// step's four barrier / LDS turn-arounds (~0.9 K cycles each of a 10.9 K-cycle step), the prologue and the weight
+// loads are paid once per 32 agents, and each wave carries two independent chains: at 394 registers one workgroup runs
+// per CU, and with eight tiles queued per CU nothing else fills those turn-arounds.  Per-tile state is held in [NB]
+// arrays and every loop over the tiles is the innermost one, so every agent's arithmetic is the same whatever NB
+// (same accumulator order): results are bit-identical.  Workgroup v owns the tiles NB v .. NB v + NB - 1 at LDS
+// k * FwdLds::total; a tile beyond the batch is a replica of agent B - 1 (every load is clamped) and stores the same
+// values to the same rows.  Only NB == 1 has the observation-LSTM riders and the prologue without weight images (the
+// two-tile form is launched only when CUs are busy and the step's images are registered).
+//
 // SAVE (gsave given) and ADE (displacement-error sums wanted) are template parameters, the last decode step is peeled and
 // nothing in the step is stored under a lane- or wave-dependent branch (padding lanes of the last tile are replicas of
 // agent B-1 and store the same values to the same rows; values every wave holds are stored by every wave): with a
 // conditional memory operation in the loop the compiler cannot count what is in flight and waited for EVERYTHING
 // (s_waitcnt vmcnt(0)) at the head of the third layer of every step - the round trip of the ~40 KB of rows the step had
 // just stored (found in the ISA in round 3; the backward kernels had been cleaned of this in round 1).
-template <bool SAVE, bool ADE>
-__global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
-    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
+template <bool SAVE, bool ADE, int NB>
+__device__ __forceinline__ void dec_rollout_fwd_tiles(
+    float* smem, const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
     const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
     const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
     float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
     float* __restrict__ ade_part, const float* __restrict__ dobs_w, float* __restrict__ dobs_act,
     float* __restrict__ dobs_x4s, const float* __restrict__ gimg) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  // Workgroups beyond the agent tiles (only launched while the rollout leaves CUs idle): the observation LSTM of
-  // the discriminator's first pass of this step - it does not depend on the generator - with the rows disc_bwd needs
-  if (blockIdx.x * SW_TILE >= (unsigned)B) {
-    const swp::Disc O = swp::disc(Tp);
-    disc_obs_lstm_tile(smem, obsv, To, 0, dobs_w + O.wih, dobs_w + O.whh, dobs_w + O.bih, dobs_w + O.bhh, B,
-                       (int)(blockIdx.x * SW_TILE) - ((B + SW_TILE - 1) / SW_TILE) * SW_TILE, dobs_act, dobs_x4s);
-    return;
+  if constexpr (NB == 1) {
+    // Workgroups beyond the agent tiles (only launched while the rollout leaves CUs idle): the observation LSTM of
+    // the discriminator's first pass of this step - it does not depend on the generator - with the rows disc_bwd needs
+    if (blockIdx.x * SW_TILE >= (unsigned)B) {
+      const swp::Disc O = swp::disc(Tp);
+      disc_obs_lstm_tile(smem, obsv, To, 0, dobs_w + O.wih, dobs_w + O.whh, dobs_w + O.bih, dobs_w + O.bhh, B,
+                         (int)(blockIdx.x * SW_TILE) - ((B + SW_TILE - 1) / SW_TILE) * SW_TILE, dobs_act, dobs_x4s);
+      return;
+    }
   }
   constexpr int LD128 = FwdLds::LD128, LD32 = FwdLds::LD32, LD16 = FwdLds::LD16;
-  float* hbuf = smem + FwdLds::hbuf;
-  float* a1buf = smem + FwdLds::a1buf;
-  float* p1 = smem + FwdLds::p1;
-  float* a2buf = smem + FwdLds::a2buf;
-  float* q2 = smem + FwdLds::q2;
-  float* szbuf = a1buf;            // prologue alias [16][100]
-  float* wx_lds = a2buf;           // prologue alias (1024)
-  float* bx_lds = a2buf + 1024;    // prologue alias (256)
-  float* w43_lds = a2buf + 1280;   // prologue alias: [2][80] | b43[2] when no image buffer is registered
+  float *hbuf[NB], *a1buf[NB], *p1[NB], *a2buf[NB], *q2[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    float* base = smem + k * FwdLds::total;
+    hbuf[k] = base + FwdLds::hbuf;
+    a1buf[k] = base + FwdLds::a1buf;   // prologue alias: [S|z] tile [16][100]
+    p1[k] = base + FwdLds::p1;
+    a2buf[k] = base + FwdLds::a2buf;
+    q2[k] = base + FwdLds::q2;
+  }
+  float* wx_lds = a2buf[0];           // prologue aliases without weight images (1024)
+  float* bx_lds = a2buf[0] + 1024;    // (256)
+  float* w43_lds = a2buf[0] + 1280;   // [2][80] | b43[2]
 
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int u0 = wave * 16;
-  const int a0 = blockIdx.x * SW_TILE;
-  const int b = min(a0 + ln, B - 1);
-  const bool live = (a0 + ln) < B;
+  int a0[NB], b[NB];
+  bool live[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    a0[k] = (NB * (int)blockIdx.x + k) * SW_TILE;
+    b[k] = min(a0[k] + ln, B - 1);
+    live[k] = (a0[k] + ln) < B;
+  }
   const GSave gs = gsave_layout(B, To, Tp);
   // this wave's share of the layers (see above)
   const int m1a = 32 * wave, m1b = m1a + 16;              // layer-1 row tiles it owns outright
@@ -128,9 +151,9 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
 #endif
   LstmW W;
   f32x4 w1a[4], w1b[4], w1p[2], w2f[10], w2p[3];
-  f32x4 wu[3][6], ua, ub, up;    // W1[:, 64:160] rows of this wave's layer-1 tiles: operands of u (below), prologue only
+  f32x4 wu[3][6];    // W1[:, 64:160] rows of this wave's layer-1 tiles: operands of u (below), prologue only
   const int m1p = 128 + 16 * t1p;
-  if (gimg) {
+  if (NB > 1 || gimg) {
     // operand-layout images of this step (swimg::OP_*): the float4 of (row tile, k-step, lane) is one contiguous
     // 16-byte piece, so a wave's load instruction reads 1 KB of consecutive memory.  The row-per-lane loads of the
     // fallback below touch 64 cache lines per instruction - 95 of them kept the four waves' address units busy for
@@ -155,7 +178,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
       wu[1][j] = op(swimg::OP_W1SZ, 6, 2 * wave + 1, j);
       wu[2][j] = op(swimg::OP_W1SZ, 6, 8 + t1p, j);
     }
-  } else {
+  } else if constexpr (NB == 1) {
     lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
     const float* ra = dec_w + swp::DEC_W1 + (size_t)(m1a + ln) * 160 + 4 * lg;
     const float* rp = dec_w + swp::DEC_W1 + (size_t)(m1p + ln) * 160 + 4 * lg;
@@ -180,27 +203,31 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
       wu[2][j] = ld4(rp + 64 + 16 * j);
     }
   }
-  ua = ld4(dec_w + swp::DEC_B1 + m1a + 4 * lg);
-  ub = ld4(dec_w + swp::DEC_B1 + m1b + 4 * lg);
-  up = ld4(dec_w + swp::DEC_B1 + m1p + 4 * lg);
+  const f32x4 ua0 = ld4(dec_w + swp::DEC_B1 + m1a + 4 * lg);
+  const f32x4 ub0 = ld4(dec_w + swp::DEC_B1 + m1b + 4 * lg);
+  const f32x4 up0 = ld4(dec_w + swp::DEC_B1 + m1p + 4 * lg);
   const f32x4 b2f = ld4(dec_w + swp::DEC_B2 + m2 + 4 * lg), b2p = ld4(dec_w + swp::DEC_B2 + 64 + 4 * lg);
-  f32x4 c = ld4(cT + (size_t)b * 64 + u0 + 4 * lg);
-  f32x4 h = ld4(hT + (size_t)b * 64 + u0 + 4 * lg);
-  // running position of agent ln (every lane keeps a copy)
-  float px = obsv[((size_t)b * To + To - 1) * 2 + 0];
-  float py = obsv[((size_t)b * To + To - 1) * 2 + 1];
-  // [S | z] tile: both sources are read unconditionally from clamped addresses and selected afterwards - a load under a
+  f32x4 c[NB], h[NB];
+  float px[NB], py[NB];   // running position of agent ln of each tile (every lane keeps a copy)
+  // [S | z] tiles: both sources are read unconditionally from clamped addresses and selected afterwards - a load under a
   // lane-dependent branch makes the compiler wait for EVERYTHING in flight right behind it (six serial round trips here)
-  float szs[6], szz[6];
+  float szs[NB][6], szz[NB][6];
   {
     const float* sp = S_pool ? S_pool : z;     // no social block: any readable address, the value is discarded
     const int sld = S_pool ? 64 : 32;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
-      const int bb = min(a0 + a, B - 1);
-      szs[q] = sp[(size_t)bb * sld + min(cc, sld - 1)];
-      szz[q] = z[(size_t)bb * 32 + max(cc - 64, 0)];
+    for (int k = 0; k < NB; ++k) {
+      c[k] = ld4(cT + (size_t)b[k] * 64 + u0 + 4 * lg);
+      h[k] = ld4(hT + (size_t)b[k] * 64 + u0 + 4 * lg);
+      px[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 0];
+      py[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 1];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
+        const int bb = min(a0[k] + a, B - 1);
+        szs[k][q] = sp[(size_t)bb * sld + min(cc, sld - 1)];
+        szz[k][q] = z[(size_t)bb * 32 + max(cc - 64, 0)];
+      }
     }
   }
   // fc3 (80 -> 40) has NO activation in front of fc4 (40 -> 2) (train.py:327-330): the two are ONE 2 x 80 map
@@ -214,7 +241,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
   // column - 40 FMAs - and the four lane groups of an agent meet in two shuffles: ~400 cycles per decode step less
   f32x4 w43[2][5];      // [output c][j] = W43[c][16 j + 4 lg .. + 3]
   float b43i[2] = {0.f, 0.f};
-  if (gimg) {
+  if (NB > 1 || gimg) {
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
       w43[0][j] = ld4(gimg + swimg::W43 + 16 * j + 4 * lg);
@@ -222,7 +249,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
     }
     b43i[0] = gimg[swimg::W43 + 160];
     b43i[1] = gimg[swimg::W43 + 161];
-  } else {
+  } else if constexpr (NB == 1) {
     lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
                    enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
     const int t = threadIdx.x;
@@ -251,336 +278,31 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
   }
   SW_STAMP(13);
 #pragma unroll
-  for (int q = 0; q < 6; ++q) {
-    const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
-    szbuf[a * LD96 + cc] = cc < 64 ? (S_pool ? szs[q] : 0.f) : szz[q];
-  }
-  st4(&hbuf[ln * SW_ALD + 320 + u0 + 4 * lg], h);
-  sw_barrier();
-  SW_STAMP(14);
-  if (!gimg) {
-    lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      w43[0][j] = ld4(w43_lds + 16 * j + 4 * lg);
-      w43[1][j] = ld4(w43_lds + 80 + 16 * j + 4 * lg);
-    }
-    b43i[0] = w43_lds[160];
-    b43i[1] = w43_lds[161];
-  }
-  // u = W1[:, 64:160] [S; z] + b1 is constant over the steps (train.py:411,421): it is the initial accumulator of
-  // this wave's layer-1 tiles (K-half 0 carries it for the split tiles)
-  {
-    f32x4 bz[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) bz[j] = ld4(&szbuf[ln * LD96 + 16 * j + 4 * lg]);
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        ua = SW_MFMA(wu[0][j][r], bz[j][r], ua);
-        ub = SW_MFMA(wu[1][j][r], bz[j][r], ub);
-        up = SW_MFMA(wu[2][j][r], bz[j][r], up);
-      }
-    if (hf != 0) up = f32x4{0.f, 0.f, 0.f, 0.f};   // K-half 1 of the split tile starts from zero
-  }
-  SW_STAMP(15);
-  sw_barrier();  // the prologue aliases are dead from here on
-  SW_STAMP(8);
-
-  // displacement-error sums of this tile (train.py:546-551), lanes lg == 0 of wave 0
-  float e_sum = 0.f, e_last = 0.f, e_sq = 0.f;
-  const bool ade_lane = ADE && wave == 0 && lg == 0 && live;
-  int cur = 0;
-  // everything the prologue requested is waited for HERE, in front of the loop (see the note above the kernel)
-#pragma unroll
-  for (int j = 0; j < 5; ++j) asm volatile("" : "+v"(w43[0][j]), "+v"(w43[1][j]));
-  asm volatile("" : "+v"(b43i[0]), "+v"(b43i[1]), "+v"(px), "+v"(py), "+v"(c), "+v"(h));
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  auto step = [&](int i, auto last_) {
-    constexpr bool LAST = decltype(last_)::value;
-    float2 gti = {0.f, 0.f};
-    if constexpr (ADE) gti = *reinterpret_cast<const float2*>(gt + ((size_t)b * Tp + i) * 2);   // in flight under the layers
-    const float* hrow = &hbuf[cur * 16 * SW_ALD + ln * SW_ALD + 320 + 4 * lg];
-    // ---- layer 1: z1 = W1h h + u ; a1 = lrelu(z1) --------------------------------------------------
-    {
-      f32x4 bh[4], bp[2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bh[j] = ld4(hrow + 16 * j);
-      bp[0] = ld4(hrow + 32 * hf);
-      bp[1] = ld4(hrow + 32 * hf + 16);
-      f32x4 acc_a = ua, acc_b = ub, acc_p = up;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          acc_a = SW_MFMA(w1a[j][r], bh[j][r], acc_a);
-          acc_b = SW_MFMA(w1b[j][r], bh[j][r], acc_b);
-          if (j < 2) acc_p = SW_MFMA(w1p[j][r], bp[j][r], acc_p);
-        }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc_a[r] = sw_lrelu(acc_a[r]);
-        acc_b[r] = sw_lrelu(acc_b[r]);
-      }
-      st4(&a1buf[ln * LD128 + m1a + 4 * lg], acc_a);
-      st4(&a1buf[ln * LD128 + m1b + 4 * lg], acc_b);
-      st4(&p1[hf * 16 * LD32 + ln * LD32 + 16 * t1p + 4 * lg], acc_p);
-      if constexpr (SAVE) {
-        float* row = gsave + gs.a1 + ((size_t)i * B + b) * 160 + 4 * lg;
-        st4g(row + m1a, acc_a);
-        st4g(row + m1b, acc_b);
-      }
-    }
-    sw_barrier();
-    SW_STAMP(9);
-    // ---- layer 2: a2 = lrelu(W2 a1 + b2) ----------------------------------------------------------
-    {
-      f32x4 b1[10];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) b1[j] = ld4(&a1buf[ln * LD128 + 16 * j + 4 * lg]);
-#pragma unroll
-      for (int j = 8; j < 10; ++j) {     // the K-split tiles of layer 1: sum of the halves, then the LeakyReLU
-        const f32x4 s = ld4(&p1[ln * LD32 + 16 * (j - 8) + 4 * lg]) + ld4(&p1[16 * LD32 + ln * LD32 + 16 * (j - 8) + 4 * lg]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b1[j][r] = sw_lrelu(s[r]);
-      }
-      if constexpr (SAVE)    // ... whose rows of the save buffer every wave writes (even waves tile 8, odd waves tile 9)
-        st4g(gsave + gs.a1 + ((size_t)i * B + b) * 160 + 128 + 16 * (wave & 1) + 4 * lg, (wave & 1) ? b1[9] : b1[8]);
-      f32x4 acc = b2f, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        acc = SW_MFMA(w2f[j][0], b1[j][0], acc);
-        acc1 = SW_MFMA(w2f[j][1], b1[j][1], acc1);
-        acc = SW_MFMA(w2f[j][2], b1[j][2], acc);
-        acc1 = SW_MFMA(w2f[j][3], b1[j][3], acc1);
-      }
-      f32x4 accq;
-      if (wave == 0) accq = fwd_l2_part<0, 3>(w2p, b1);
-      else if (wave == 1) accq = fwd_l2_part<3, 3>(w2p, b1);
-      else if (wave == 2) accq = fwd_l2_part<6, 2>(w2p, b1);
-      else accq = fwd_l2_part<8, 2>(w2p, b1);
-      acc = acc + acc1;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
-      st4(&a2buf[ln * LD64 + m2 + 4 * lg], acc);
-      st4(&q2[wave * 16 * LD16 + ln * LD16 + 4 * lg], accq);
-      if constexpr (SAVE) st4g(gsave + gs.a2 + ((size_t)i * B + b) * 80 + m2 + 4 * lg, acc);
-    }
-    sw_barrier();
-    SW_STAMP(10);
-    // ---- layers 3+4 composed (v = W43 a2 + b43 ; p += v) and the re-fed encoder step (train.py:422-430) ----
-    // Every wave computes the 2-row map itself and keeps its own copy of the running position, so the LSTM step needs
-    // no barrier / LDS hop for its input.
-    {
-      f32x4 b2v[5];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b2v[j] = ld4(&a2buf[ln * LD64 + 16 * j + 4 * lg]);
-      {
-        const float* q = &q2[ln * LD16 + 4 * lg];
-        const f32x4 s = ((b2p + ld4(q)) + ld4(q + 16 * LD16)) + (ld4(q + 2 * 16 * LD16) + ld4(q + 3 * 16 * LD16));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b2v[4][r] = sw_lrelu(s[r]);
-      }
-      if constexpr (SAVE) st4g(gsave + gs.a2 + ((size_t)i * B + b) * 80 + 64 + 4 * lg, b2v[4]);   // every wave holds it
-      float vx0 = 0.f, vx1 = 0.f, vy0 = 0.f, vy1 = 0.f;      // this lane's 20 columns, two chains per output
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        vx0 = fmaf(w43[0][j][0], b2v[j][0], vx0);
-        vx1 = fmaf(w43[0][j][1], b2v[j][1], vx1);
-        vx0 = fmaf(w43[0][j][2], b2v[j][2], vx0);
-        vx1 = fmaf(w43[0][j][3], b2v[j][3], vx1);
-        vy0 = fmaf(w43[1][j][0], b2v[j][0], vy0);
-        vy1 = fmaf(w43[1][j][1], b2v[j][1], vy1);
-        vy0 = fmaf(w43[1][j][2], b2v[j][2], vy0);
-        vy1 = fmaf(w43[1][j][3], b2v[j][3], vy1);
-      }
-      float vx = vx0 + vx1, vy = vy0 + vy1;
-      vx += __shfl_xor(vx, 16);      // the four lane groups (k quarters) of agent ln: every lane ends with the sum
-      vy += __shfl_xor(vy, 16);
-      vx += __shfl_xor(vx, 32);
-      vy += __shfl_xor(vy, 32);
-      vx += b43i[0];
-      vy += b43i[1];
-      px += vx;
-      py += vy;
-      SW_STAMP(11);
-      if constexpr (ADE) {
-        const float dx = (px - gti.x) * inv_ss, dy = (py - gti.y) * inv_ss;
-        const float q = dx * dx + dy * dy;
-        const float e = sqrtf(q);
-        if (ade_lane) {      // arithmetic only: no memory operation under this branch
-          e_sum += e;
-          e_sq += q;
-          if (LAST) e_last = e;
-        }
-      }
-      {   // every lane of agent ln holds the same (p, v): all of them store it (no lane-dependent store)
-        const f32x4 x4 = {px, py, vx, vy};
-        st4(pred4 + ((size_t)b * Tp + i) * 4, x4);
-        if constexpr (SAVE && !LAST) st4(gsave + gs.x4s + ((size_t)(To + i) * B + b) * 4, x4);
-      }
-      auto lstm_step = [&](auto save_) {
-        const float xb = lg == 0 ? px : (lg == 1 ? py : (lg == 2 ? vx : vy));
-        f32x4 gate[4];
-        lstm_cell(W, xb, hrow, gate, c, h);
-        if constexpr (decltype(save_)::value) lstm_put_act_tile(&hbuf[(cur ^ 1) * 16 * SW_ALD], gate, c, h, ln, lg, u0);
-        else st4(&hbuf[(cur ^ 1) * 16 * SW_ALD + ln * SW_ALD + 320 + u0 + 4 * lg], h);
-        cur ^= 1;
-      };
-      if constexpr (!LAST) {
-        if constexpr (SAVE) lstm_step(T_{});
-        else lstm_step(F_{});
-      } else {
-        if (h_end) lstm_step(F_{});     // the step after the last decode is dead compute (train.py:430) unless the state is wanted
-      }
-      sw_barrier();
-      if constexpr (SAVE && !LAST)      // the saved row of LSTM step To + i, from the tile just completed
-        lstm_store_act_tile(&hbuf[cur * 16 * SW_ALD], gsave + gs.act + (size_t)(To + i) * B * 384, a0, B, wave, lane);
-      SW_STAMP(12);
-    }
-  };
-  for (int i = 0; i < Tp - 1; ++i) step(i, F_{});
-  step(Tp - 1, T_{});
-  if (h_end && live) {
-    st4(h_end + (size_t)b * 64 + u0 + 4 * lg, h);
-    if (c_end) st4(c_end + (size_t)b * 64 + u0 + 4 * lg, c);
-  }
-  if (ADE && wave == 0) {   // fixed shuffle tree over the tile's 16 agents -> one partial triple per workgroup
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      e_sum += __shfl_xor(e_sum, o);
-      e_last += __shfl_xor(e_last, o);
-      e_sq += __shfl_xor(e_sq, o);
-    }
-    if (lane == 0) {
-      ade_part[(size_t)blockIdx.x * 3 + 0] = e_sum / (float)Tp;
-      ade_part[(size_t)blockIdx.x * 3 + 1] = e_last;
-      ade_part[(size_t)blockIdx.x * 3 + 2] = e_sq;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same kernel for TWO 16-agent column blocks per workgroup (round 6): for batches with more tiles than CUs (dense
-// crowds, large shards).  At 394 registers the kernel above runs one workgroup per CU, so with eight tiles queued per CU
-// nothing fills a tile's barrier / LDS turn-arounds (4 per decode step, ~0.9 K cycles each of a 10.9 K-cycle step).  Here
-// every register-resident A operand (weight) is issued against two B operands - the blocks' activation tiles - so the
-// four turn-arounds, the prologue and the weight loads are paid once per 32 agents, and each wave carries two independent
-// chains.  Every agent's arithmetic is the 16-agent kernel's, operation for operation (same accumulator order): results
-// are bit-identical.  Workgroup v owns the tiles 2v, 2v + 1; a second block beyond the batch is a replica of agent B - 1
-// (every load is clamped) and stores the same values to the same rows.  No observation-LSTM riders (only launched when
-// CUs are idle).
-template <bool SAVE, bool ADE>
-__global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
-    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
-    const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
-    const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
-    float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
-    float* __restrict__ ade_part, const float* __restrict__ gimg) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int LD128 = FwdLds::LD128, LD32 = FwdLds::LD32, LD16 = FwdLds::LD16;
-  constexpr int NB = 2;
-  float *hbuf[NB], *a1buf[NB], *p1[NB], *a2buf[NB], *q2[NB];
-#pragma unroll
   for (int k = 0; k < NB; ++k) {
-    float* base = smem + k * FwdLds::total;
-    hbuf[k] = base + FwdLds::hbuf;
-    a1buf[k] = base + FwdLds::a1buf;
-    p1[k] = base + FwdLds::p1;
-    a2buf[k] = base + FwdLds::a2buf;
-    q2[k] = base + FwdLds::q2;
-  }
-  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  const int u0 = wave * 16;
-  const int tiles16 = (B + SW_TILE - 1) / SW_TILE;
-  int a0[NB], b[NB];
-  bool live[NB];
-#pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    a0[k] = (2 * (int)blockIdx.x + k) * SW_TILE;
-    b[k] = min(a0[k] + ln, B - 1);
-    live[k] = (a0[k] + ln) < B;
-  }
-  const GSave gs = gsave_layout(B, To, Tp);
-  const int m1a = 32 * wave, m1b = m1a + 16;
-  const int hf = wave & 1, t1p = wave >> 1;
-  const int m2 = 16 * wave;
-  const int J0 = wave < 2 ? 3 * wave : 2 + 2 * wave;
-  const int m1p = 128 + 16 * t1p;
-
-  // ---- prologue: the weights once (operand-layout images of the step: this kernel is only launched with them) ----
-  LstmW W;
-  f32x4 w1a[4], w1b[4], w1p[2], w2f[10], w2p[3];
-  f32x4 wu[3][6];
-  f32x4 ua[NB], ub[NB], up[NB];
-  auto op = [&](int base, int KJ, int tile, int j) { return ld4(gimg + base + (((size_t)tile * KJ + j) * 64 + lane) * 4); };
-  lstm_load_img(W, gimg, wave, lane);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    w1a[j] = op(swimg::OP_W1H, 4, 2 * wave, j);
-    w1b[j] = op(swimg::OP_W1H, 4, 2 * wave + 1, j);
-  }
-  w1p[0] = op(swimg::OP_W1H, 4, 8 + t1p, 2 * hf);
-  w1p[1] = op(swimg::OP_W1H, 4, 8 + t1p, 2 * hf + 1);
-#pragma unroll
-  for (int j = 0; j < 10; ++j) w2f[j] = op(swimg::OP_W2, 10, wave, j);
-  w2p[0] = op(swimg::OP_W2, 10, 4, J0);
-  w2p[1] = op(swimg::OP_W2, 10, 4, J0 + 1);
-  w2p[2] = op(swimg::OP_W2, 10, 4, J0 + (wave < 2 ? 2 : 1));
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    wu[0][j] = op(swimg::OP_W1SZ, 6, 2 * wave, j);
-    wu[1][j] = op(swimg::OP_W1SZ, 6, 2 * wave + 1, j);
-    wu[2][j] = op(swimg::OP_W1SZ, 6, 8 + t1p, j);
-  }
-  const f32x4 ua0 = ld4(dec_w + swp::DEC_B1 + m1a + 4 * lg);
-  const f32x4 ub0 = ld4(dec_w + swp::DEC_B1 + m1b + 4 * lg);
-  const f32x4 up0 = ld4(dec_w + swp::DEC_B1 + m1p + 4 * lg);
-  const f32x4 b2f = ld4(dec_w + swp::DEC_B2 + m2 + 4 * lg), b2p = ld4(dec_w + swp::DEC_B2 + 64 + 4 * lg);
-  f32x4 c[NB], h[NB];
-  float px[NB], py[NB];
-  float szs[NB][6], szz[NB][6];
-  {
-    const float* sp = S_pool ? S_pool : z;
-    const int sld = S_pool ? 64 : 32;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-      c[k] = ld4(cT + (size_t)b[k] * 64 + u0 + 4 * lg);
-      h[k] = ld4(hT + (size_t)b[k] * 64 + u0 + 4 * lg);
-      px[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 0];
-      py[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 1];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
-        const int bb = min(a0[k] + a, B - 1);
-        szs[k][q] = sp[(size_t)bb * sld + min(cc, sld - 1)];
-        szz[k][q] = z[(size_t)bb * 32 + max(cc - 64, 0)];
-      }
-    }
-  }
-  f32x4 w43[2][5];
-  float b43i[2];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    w43[0][j] = ld4(gimg + swimg::W43 + 16 * j + 4 * lg);
-    w43[1][j] = ld4(gimg + swimg::W43 + 80 + 16 * j + 4 * lg);
-  }
-  b43i[0] = gimg[swimg::W43 + 160];
-  b43i[1] = gimg[swimg::W43 + 161];
-#pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    float* szbuf = a1buf[k];      // prologue alias [16][100]
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
       const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
-      szbuf[a * LD96 + cc] = cc < 64 ? (S_pool ? szs[k][q] : 0.f) : szz[k][q];
+      a1buf[k][a * LD96 + cc] = cc < 64 ? (S_pool ? szs[k][q] : 0.f) : szz[k][q];
     }
     st4(&hbuf[k][ln * SW_ALD + 320 + u0 + 4 * lg], h[k]);
   }
   sw_barrier();
-  // u = W1[:, 64:160] [S; z] + b1: the initial accumulators of this wave's layer-1 tiles, per block
+  SW_STAMP(14);
+  if constexpr (NB == 1) {
+    if (!gimg) {
+      lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        w43[0][j] = ld4(w43_lds + 16 * j + 4 * lg);
+        w43[1][j] = ld4(w43_lds + 80 + 16 * j + 4 * lg);
+      }
+      b43i[0] = w43_lds[160];
+      b43i[1] = w43_lds[161];
+    }
+  }
+  // u = W1[:, 64:160] [S; z] + b1 is constant over the steps (train.py:411,421): it is the initial accumulator of
+  // this wave's layer-1 tiles (K-half 0 carries it for the split tiles), per 16-agent tile
+  f32x4 ua[NB], ub[NB], up[NB];
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
     f32x4 bz[6];
@@ -597,12 +319,22 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
         ub[k] = SW_MFMA(wu[1][j][r], bz[j][r], ub[k]);
         up[k] = SW_MFMA(wu[2][j][r], bz[j][r], up[k]);
       }
-    if (hf != 0) up[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (hf != 0) up[k] = f32x4{0.f, 0.f, 0.f, 0.f};   // K-half 1 of the split tile starts from zero
   }
+  SW_STAMP(15);
   sw_barrier();  // the prologue aliases are dead from here on
+  SW_STAMP(8);
 
-  float e_sum[NB] = {0.f, 0.f}, e_last[NB] = {0.f, 0.f}, e_sq[NB] = {0.f, 0.f};
+  // displacement-error sums of each tile (train.py:546-551), lanes lg == 0 of wave 0
+  float e_sum[NB], e_last[NB], e_sq[NB];
+  bool ade_lane[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    e_sum[k] = e_last[k] = e_sq[k] = 0.f;
+    ade_lane[k] = ADE && wave == 0 && lg == 0 && live[k];
+  }
   int cur = 0;
+  // everything the prologue requested is waited for HERE, in front of the loop (see the note above the kernel)
 #pragma unroll
   for (int j = 0; j < 5; ++j) asm volatile("" : "+v"(w43[0][j]), "+v"(w43[1][j]));
   asm volatile("" : "+v"(b43i[0]), "+v"(b43i[1]));
@@ -617,7 +349,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       gti[k] = float2{0.f, 0.f};
-      if constexpr (ADE) gti[k] = *reinterpret_cast<const float2*>(gt + ((size_t)b[k] * Tp + i) * 2);
+      if constexpr (ADE) gti[k] = *reinterpret_cast<const float2*>(gt + ((size_t)b[k] * Tp + i) * 2);   // in flight under the layers
       hrow[k] = &hbuf[k][cur * 16 * SW_ALD + ln * SW_ALD + 320 + 4 * lg];
     }
     // ---- layer 1: z1 = W1h h + u ; a1 = lrelu(z1) --------------------------------------------------
@@ -663,6 +395,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
       }
     }
     sw_barrier();
+    SW_STAMP(9);
     // ---- layer 2: a2 = lrelu(W2 a1 + b2) ----------------------------------------------------------
     {
       f32x4 b1[NB][10];
@@ -672,12 +405,12 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) b1[k][j] = ld4(&a1buf[k][ln * LD128 + 16 * j + 4 * lg]);
 #pragma unroll
-        for (int j = 8; j < 10; ++j) {
+        for (int j = 8; j < 10; ++j) {     // the K-split tiles of layer 1: sum of the halves, then the LeakyReLU
           const f32x4 s = ld4(&p1[k][ln * LD32 + 16 * (j - 8) + 4 * lg]) + ld4(&p1[k][16 * LD32 + ln * LD32 + 16 * (j - 8) + 4 * lg]);
 #pragma unroll
           for (int r = 0; r < 4; ++r) b1[k][j][r] = sw_lrelu(s[r]);
         }
-        if constexpr (SAVE)
+        if constexpr (SAVE)    // ... whose rows of the save buffer every wave writes (even waves tile 8, odd waves tile 9)
           st4g(gsave + gs.a1 + ((size_t)i * B + b[k]) * 160 + 128 + 16 * (wave & 1) + 4 * lg, (wave & 1) ? b1[k][9] : b1[k][8]);
         acc[k] = b2f;
         acc1[k] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -707,7 +440,10 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
       }
     }
     sw_barrier();
+    SW_STAMP(10);
     // ---- layers 3+4 composed (v = W43 a2 + b43 ; p += v) and the re-fed encoder step (train.py:422-430) ----
+    // Every wave computes the 2-row map itself and keeps its own copy of the running position, so the LSTM step needs
+    // no barrier / LDS hop for its input.
     {
       float vx[NB], vy[NB];
 #pragma unroll
@@ -721,8 +457,8 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
 #pragma unroll
           for (int r = 0; r < 4; ++r) b2v[4][r] = sw_lrelu(s[r]);
         }
-        if constexpr (SAVE) st4g(gsave + gs.a2 + ((size_t)i * B + b[k]) * 80 + 64 + 4 * lg, b2v[4]);
-        float vx0 = 0.f, vx1 = 0.f, vy0 = 0.f, vy1 = 0.f;
+        if constexpr (SAVE) st4g(gsave + gs.a2 + ((size_t)i * B + b[k]) * 80 + 64 + 4 * lg, b2v[4]);   // every wave holds it
+        float vx0 = 0.f, vx1 = 0.f, vy0 = 0.f, vy1 = 0.f;      // this lane's 20 columns, two chains per output
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
           vx0 = fmaf(w43[0][j][0], b2v[j][0], vx0);
@@ -735,7 +471,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
           vy1 = fmaf(w43[1][j][3], b2v[j][3], vy1);
         }
         float x = vx0 + vx1, y = vy0 + vy1;
-        x += __shfl_xor(x, 16);
+        x += __shfl_xor(x, 16);      // the four lane groups (k quarters) of agent ln: every lane ends with the sum
         y += __shfl_xor(y, 16);
         x += __shfl_xor(x, 32);
         y += __shfl_xor(y, 32);
@@ -745,17 +481,18 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
         vy[k] = y;
         px[k] += x;
         py[k] += y;
+        if (k == NB - 1) { SW_STAMP(11); }
         if constexpr (ADE) {
           const float dx = (px[k] - gti[k].x) * inv_ss, dy = (py[k] - gti[k].y) * inv_ss;
           const float q = dx * dx + dy * dy;
           const float e = sqrtf(q);
-          if (wave == 0 && lg == 0 && live[k]) {      // arithmetic only: no memory operation under this branch
+          if (ade_lane[k]) {      // arithmetic only: no memory operation under this branch
             e_sum[k] += e;
             e_sq[k] += q;
             if (LAST) e_last[k] = e;
           }
         }
-        {
+        {   // every lane of agent ln holds the same (p, v): all of them store it (no lane-dependent store)
           const f32x4 x4 = {px[k], py[k], x, y};
           st4(pred4 + ((size_t)b[k] * Tp + i) * 4, x4);
           if constexpr (SAVE && !LAST) st4(gsave + gs.x4s + ((size_t)(To + i) * B + b[k]) * 4, x4);
@@ -765,41 +502,11 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
         float xb[NB];
 #pragma unroll
         for (int k = 0; k < NB; ++k) xb[k] = lg == 0 ? px[k] : (lg == 1 ? py[k] : (lg == 2 ? vx[k] : vy[k]));
-        // the cell of both blocks: every W_hh operand against the two h tiles (lstm_cell, sw_lstm_dev.h, per block)
-        f32x4 acc[NB][4], bb[NB][4];
+        f32x4 gate[NB][4];
+        lstm_cell<NB>(W, xb, hrow, gate, c, h);
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bb[k][j] = ld4(hrow[k] + 16 * j);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) acc[k][g] = SW_MFMA(W.wx[g], xb[k], W.bias[g]);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-              for (int k = 0; k < NB; ++k) acc[k][g] = SW_MFMA(W.whh[g][j][r], bb[k][j][r], acc[k][g]);
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-          f32x4 gate[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float ig = sw_sigmoid(acc[k][0][r]);
-            const float fg = sw_sigmoid(acc[k][1][r]);
-            const float gg = sw_tanh(acc[k][2][r]);
-            const float og = sw_sigmoid(acc[k][3][r]);
-            const float cn = fmaf(fg, c[k][r], ig * gg);
-            gate[0][r] = ig;
-            gate[1][r] = fg;
-            gate[2][r] = gg;
-            gate[3][r] = og;
-            c[k][r] = cn;
-            h[k][r] = og * sw_tanh(cn);
-          }
-          if constexpr (decltype(save_)::value) lstm_put_act_tile(&hbuf[k][(cur ^ 1) * 16 * SW_ALD], gate, c[k], h[k], ln, lg, u0);
+          if constexpr (decltype(save_)::value) lstm_put_act_tile(&hbuf[k][(cur ^ 1) * 16 * SW_ALD], gate[k], c[k], h[k], ln, lg, u0);
           else st4(&hbuf[k][(cur ^ 1) * 16 * SW_ALD + ln * SW_ALD + 320 + u0 + 4 * lg], h[k]);
         }
         cur ^= 1;
@@ -808,39 +515,66 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
         if constexpr (SAVE) lstm_step(T_{});
         else lstm_step(F_{});
       } else {
-        if (h_end) lstm_step(F_{});
+        if (h_end) lstm_step(F_{});     // the step after the last decode is dead compute (train.py:430) unless the state is wanted
       }
       sw_barrier();
-      if constexpr (SAVE && !LAST) {
+      if constexpr (SAVE && !LAST) {    // the saved row of LSTM step To + i, from the tiles just completed
 #pragma unroll
         for (int k = 0; k < NB; ++k)
           lstm_store_act_tile(&hbuf[k][cur * 16 * SW_ALD], gsave + gs.act + (size_t)(To + i) * B * 384, a0[k], B, wave, lane);
       }
+      SW_STAMP(12);
     }
   };
   for (int i = 0; i < Tp - 1; ++i) step(i, F_{});
   step(Tp - 1, T_{});
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
     if (h_end && live[k]) {
       st4(h_end + (size_t)b[k] * 64 + u0 + 4 * lg, h[k]);
       if (c_end) st4(c_end + (size_t)b[k] * 64 + u0 + 4 * lg, c[k]);
     }
-    if (ADE && wave == 0) {   // fixed shuffle tree over the block's 16 agents -> one partial triple per 16-agent tile
+    if (ADE && wave == 0) {   // fixed shuffle tree over the tile's 16 agents -> one partial triple per 16-agent tile
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
         e_sum[k] += __shfl_xor(e_sum[k], o);
         e_last[k] += __shfl_xor(e_last[k], o);
         e_sq[k] += __shfl_xor(e_sq[k], o);
       }
-      const int t16 = 2 * (int)blockIdx.x + k;
-      if (lane == 0 && t16 < tiles16) {
+      const int t16 = NB * (int)blockIdx.x + k;
+      if (lane == 0 && (NB == 1 || t16 < tiles)) {    // (NB == 1: the riders have returned)
         ade_part[(size_t)t16 * 3 + 0] = e_sum[k] / (float)Tp;
         ade_part[(size_t)t16 * 3 + 1] = e_last[k];
         ade_part[(size_t)t16 * 3 + 2] = e_sq[k];
       }
     }
   }
+}
+
+template <bool SAVE, bool ADE>
+__global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
+    const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
+    const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
+    float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
+    float* __restrict__ ade_part, const float* __restrict__ dobs_w, float* __restrict__ dobs_act,
+    float* __restrict__ dobs_x4s, const float* __restrict__ gimg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  dec_rollout_fwd_tiles<SAVE, ADE, 1>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave,
+                                      gt, inv_ss, ade_part, dobs_w, dobs_act, dobs_x4s, gimg);
+}
+
+template <bool SAVE, bool ADE>
+__global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
+    const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
+    const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
+    float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
+    float* __restrict__ ade_part, const float* __restrict__ gimg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  dec_rollout_fwd_tiles<SAVE, ADE, 2>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave,
+                                      gt, inv_ss, ade_part, nullptr, nullptr, nullptr, gimg);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1276,54 +1010,40 @@ extern "C" int sw_dec_rollout_fwd_aux(const float* obsv, int To, const float* z,
   float* act = dsave;
   float* x4s = dsave ? dsave + (size_t)To * B * 384 : nullptr;
   const float* gimg = sw_gen_images_for(enc_w, dec_w);
-  // More tiles than CUs (dense crowds, large shards): two 16-agent column blocks per workgroup - every resident weight
-  // operand issued against both, the step's barrier / LDS turn-arounds paid once per 32 agents (dec_rollout_fwd2_kernel,
+  // One instantiation of the decode forward: NB 16-agent tiles per workgroup, NB * FwdLds::total floats of LDS (its
+  // attribute set once).  NB == 1 launches the observation-LSTM riders behind the tiles when d_w is given.
+  auto launch = [&](auto nb_, auto save_, auto ade_) -> int {
+    constexpr int NB = decltype(nb_)::value;
+    constexpr bool SV = decltype(save_)::value, AD = decltype(ade_)::value;
+    constexpr int lds = NB * FwdLds::total * 4;
+    static bool attr = false;
+    if (!attr) {
+      const void* fn = NB == 1 ? (const void*)dec_rollout_fwd_kernel<SV, AD> : (const void*)dec_rollout_fwd2_kernel<SV, AD>;
+      if (int rc = set_lds(fn, lds)) return rc;
+      attr = true;
+    }
+    if constexpr (NB == 1)
+      SW_LAUNCH((dec_rollout_fwd_kernel<SV, AD>), dim3(d_w ? 2 * tiles : tiles), dim3(SW_THREADS), lds, (hipStream_t)stream,
+                obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt, inv_ss, ade_part, d_w, act,
+                x4s, gimg);
+    else
+      SW_LAUNCH((dec_rollout_fwd2_kernel<SV, AD>), dim3((tiles + 1) / 2), dim3(SW_THREADS), lds, (hipStream_t)stream,
+                obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt, inv_ss, ade_part, gimg);
+    SW_CHECK_LAUNCH(NB == 1 ? "dec_rollout_fwd_kernel" : "dec_rollout_fwd2_kernel");
+    return SW_OK;
+  };
+  auto dispatch = [&](auto nb_) -> int {
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    if (gsave) return ade_part ? launch(nb_, T_{}, T_{}) : launch(nb_, T_{}, F_{});
+    return ade_part ? launch(nb_, F_{}, T_{}) : launch(nb_, F_{}, F_{});
+  };
+  // More tiles than CUs (dense crowds, large shards): two 16-agent tiles per workgroup - every resident weight operand
+  // issued against both, the step's barrier / LDS turn-arounds paid once per 32 agents (dec_rollout_fwd2_kernel,
   // bit-identical).  Needs the step's weight images; SW_DEC_FWD2=0 / 1 forces either kernel (A/B runs, tests).
   static const int fwd2_env = getenv("SW_DEC_FWD2") ? atoi(getenv("SW_DEC_FWD2")) : -1;
-  if (gimg && !d_w && (fwd2_env >= 0 ? fwd2_env != 0 : tiles > 256)) {
-#define SW_DEC_FWD2(SV, AD)                                                                                          \
-  do {                                                                                                               \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (int rc = set_lds((const void*)dec_rollout_fwd2_kernel<SV, AD>, 2 * FwdLds::total * 4)) return rc;          \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
-    SW_LAUNCH((dec_rollout_fwd2_kernel<SV, AD>), dim3((tiles + 1) / 2), dim3(SW_THREADS), 2 * FwdLds::total * 4,     \
-              (hipStream_t)stream, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt,  \
-              inv_ss, ade_part, gimg);                                                                               \
-  } while (0)
-    if (gsave) {
-      if (ade_part) SW_DEC_FWD2(true, true);
-      else SW_DEC_FWD2(true, false);
-    } else {
-      if (ade_part) SW_DEC_FWD2(false, true);
-      else SW_DEC_FWD2(false, false);
-    }
-#undef SW_DEC_FWD2
-    SW_CHECK_LAUNCH("dec_rollout_fwd2_kernel");
-    return SW_OK;
-  }
-#define SW_DEC_FWD(SV, AD)                                                                                           \
-  do {                                                                                                               \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (int rc = set_lds((const void*)dec_rollout_fwd_kernel<SV, AD>, FwdLds::total * 4)) return rc;               \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
-    SW_LAUNCH((dec_rollout_fwd_kernel<SV, AD>), dim3(d_w ? 2 * tiles : tiles), dim3(SW_THREADS), FwdLds::total * 4,  \
-              (hipStream_t)stream, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt,  \
-              inv_ss, ade_part, d_w, act, x4s, gimg);                                                                \
-  } while (0)
-  if (gsave) {
-    if (ade_part) SW_DEC_FWD(true, true);
-    else SW_DEC_FWD(true, false);
-  } else {
-    if (ade_part) SW_DEC_FWD(false, true);
-    else SW_DEC_FWD(false, false);
-  }
-#undef SW_DEC_FWD
-  SW_CHECK_LAUNCH("dec_rollout_fwd_kernel");
-  return SW_OK;
+  if (gimg && !d_w && (fwd2_env >= 0 ? fwd2_env != 0 : tiles > 256)) return dispatch(std::integral_constant<int, 2>{});
+  return dispatch(std::integral_constant<int, 1>{});
 }
 
 extern "C" int sw_dec_rollout_fwd(const float* obsv, int To, const float* z, const float* S_pool,

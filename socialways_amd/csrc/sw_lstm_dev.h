@@ -95,23 +95,36 @@ __device__ __forceinline__ void lstm_load_img(LstmW& W, const float* __restrict_
   }
 }
 
-// One cell step.  xb = x4[agent ln][component lg]; hrow = &h_lds[ln*SW_HLD + 4*lg] (previous h).
-// On return gate[] holds the post-activation gates i,f,g,o, c the new cell state, h the new h.
-__device__ __forceinline__ void lstm_cell(const LstmW& W, float xb, const float* hrow, f32x4 gate[4],
-                                          f32x4& c, f32x4& h) {
-  f32x4 acc[4], b[4];
+// The products of one cell step for NB 16-agent tiles: acc[k][g] = Wx x_k + b + W_hh h_k (pre-activation rows of gate g),
+// every W_hh operand issued against the NB h tiles in turn.  xb[k] = x4[agent ln][component lg] of tile k;
+// hrow[k] = &h_lds_k[ln*ld + 4*lg] (previous h).
+template <int NB>
+__device__ __forceinline__ void lstm_products(const LstmW& W, const float (&xb)[NB], const float* const (&hrow)[NB],
+                                              f32x4 (&acc)[NB][4]) {
+  f32x4 b[NB][4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) b[j] = ld4(hrow + 16 * j);   // one LDS round trip for the whole step
+  for (int k = 0; k < NB; ++k) {
 #pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = SW_MFMA(W.wx[g], xb, W.bias[g]);
+    for (int j = 0; j < 4; ++j) b[k][j] = ld4(hrow[k] + 16 * j);   // one LDS round trip for the whole step
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[k][g] = SW_MFMA(W.wx[g], xb[k], W.bias[g]);
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = SW_MFMA(W.whh[g][j][r], b[j][r], acc[g]);
+      for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) acc[k][g] = SW_MFMA(W.whh[g][j][r], b[k][j][r], acc[k][g]);
+      }
     }
   }
+}
+
+// The elementwise part of a cell step on the pre-activation gates acc[].  On return gate[] holds the post-activation
+// gates i,f,g,o, c the new cell state, h the new h.
+__device__ __forceinline__ void lstm_gates(const f32x4 acc[4], f32x4 gate[4], f32x4& c, f32x4& h) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float i = sw_sigmoid(acc[0][r]);
@@ -126,6 +139,24 @@ __device__ __forceinline__ void lstm_cell(const LstmW& W, float xb, const float*
     c[r] = cn;
     h[r] = o * sw_tanh(cn);
   }
+}
+
+// One cell step of NB tiles: the products, then the gate step per tile.  On return gate[k] holds tile k's post-activation
+// gates i,f,g,o, c[k] its new cell state, h[k] its new h.
+template <int NB>
+__device__ __forceinline__ void lstm_cell(const LstmW& W, const float (&xb)[NB], const float* const (&hrow)[NB],
+                                          f32x4 (&gate)[NB][4], f32x4 (&c)[NB], f32x4 (&h)[NB]) {
+  f32x4 acc[NB][4];
+  lstm_products<NB>(W, xb, hrow, acc);
+#pragma unroll
+  for (int k = 0; k < NB; ++k) lstm_gates(acc[k], gate[k], c[k], h[k]);
+}
+// ... of one tile: xb = x4[agent ln][component lg]; hrow = &h_lds[ln*SW_HLD + 4*lg] (previous h).
+__device__ __forceinline__ void lstm_cell(const LstmW& W, float xb, const float* hrow, f32x4 gate[4],
+                                          f32x4& c, f32x4& h) {
+  f32x4 acc[1][4];
+  lstm_products<1>(W, {xb}, {hrow}, acc);
+  lstm_gates(acc[0], gate, c, h);
 }
 
 // Backward of one cell step (elementwise part).  In: dh, dc (gradients w.r.t. h_t, c_t), saved
