@@ -152,6 +152,17 @@ __device__ __forceinline__ void stage_wT(float* dst, int ld, int Kp, const float
   }
 }
 
+// Workgroups beyond the 16-agent tiles of a BPTT launch run an auxiliary masked copy dst[i] = mask[i] > 0 ? src[i] : dst[i]
+// (the training step's D.load(backup), train.py:541-542) instead; true for those workgroups.
+__device__ __forceinline__ bool sw_aux_masked_copy(int B, const float* src, float* dst, const float* mask, long long n) {
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
+  if ((int)blockIdx.x < tiles) return false;
+  const long long stride = (long long)(gridDim.x - tiles) * SW_THREADS;
+  for (long long i = (long long)(blockIdx.x - tiles) * SW_THREADS + threadIdx.x; i < n; i += stride)
+    if (mask[i] > 0.f) dst[i] = src[i];
+  return true;
+}
+
 // Split forms of stage_w / stage_wT: a prologue issues the loads of ALL its matrices first (NV float4 registers
 // per matrix and thread, NV = ceil(#float4 / 256)) and stores them afterwards - one L2 round trip for the whole
 // prologue instead of one per matrix (each staging call used to wait for its own loads before its LDS stores).
@@ -394,7 +405,10 @@ extern bool g_sw_ktime_on;
 
 // host-side error plumbing ---------------------------------------------------------------------
 void sw_set_error(const char* what, hipError_t e);
-#define SW_CHECK_LAUNCH(name)                         \
+// Raises fn's dynamic-LDS limit to `bytes` unless `have` (one per kernel, per process) already covers it: set once per
+// kernel, again only when a launch needs more than before (sw_misc.hip)
+int sw_set_lds(const void* fn, int bytes, int& have);
+#define SW_CHECK_LAUNCH(name)                        \
   do {                                                \
     hipError_t _e = hipGetLastError();                \
     if (_e != hipSuccess) {                           \

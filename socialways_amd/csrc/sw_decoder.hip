@@ -620,17 +620,8 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_bwd_kernel(
     float* __restrict__ dhT, float* __restrict__ dcT, float* __restrict__ dS_pool, const float* __restrict__ aux_src,
     float* __restrict__ aux_dst, const float* __restrict__ aux_mask, long long aux_n, const float* __restrict__ gimg,
     DecDiscFuse df) {
-  // Workgroups beyond the agent tiles run an auxiliary masked copy dst[i] = mask[i] > 0 ? src[i] : dst[i]
-  // (the training step's D.load(backup), train.py:541-542, on CUs this latency-bound launch leaves idle)
-  {
-    const int tiles = (B + SW_TILE - 1) / SW_TILE;
-    if ((int)blockIdx.x >= tiles) {
-      const long long stride = (long long)(gridDim.x - tiles) * SW_THREADS;
-      for (long long i = (long long)(blockIdx.x - tiles) * SW_THREADS + threadIdx.x; i < aux_n; i += stride)
-        if (aux_mask[i] > 0.f) aux_dst[i] = aux_src[i];
-      return;
-    }
-  }
+  // (the masked copy of the training step's D.load(backup) on CUs this latency-bound launch leaves idle)
+  if (sw_aux_masked_copy(B, aux_src, aux_dst, aux_mask, aux_n)) return;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if constexpr (DFUSE) {
     disc_fwd_tile(smem, blockIdx.x, gridDim.x, df.obsv, To, 0, df.pred_hat, nullptr, 1, df.d_w, B, Tp, nullptr, nullptr, nullptr,
@@ -987,15 +978,6 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_bwd_kernel(
   }
 }
 
-static int set_lds(const void* fn, int bytes) {
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    sw_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    return SW_EHIP;
-  }
-  return SW_OK;
-}
-
 extern "C" int sw_dec_rollout_fwd_aux(const float* obsv, int To, const float* z, const float* S_pool,
                                       const float* hT, const float* cT, const float* enc_w, const float* dec_w,
                                       int B, int Tp, float* pred4, float* h_end, float* c_end, float* gsave,
@@ -1016,12 +998,9 @@ extern "C" int sw_dec_rollout_fwd_aux(const float* obsv, int To, const float* z,
     constexpr int NB = decltype(nb_)::value;
     constexpr bool SV = decltype(save_)::value, AD = decltype(ade_)::value;
     constexpr int lds = NB * FwdLds::total * 4;
-    static bool attr = false;
-    if (!attr) {
-      const void* fn = NB == 1 ? (const void*)dec_rollout_fwd_kernel<SV, AD> : (const void*)dec_rollout_fwd2_kernel<SV, AD>;
-      if (int rc = set_lds(fn, lds)) return rc;
-      attr = true;
-    }
+    static int have = 0;
+    const void* fn = NB == 1 ? (const void*)dec_rollout_fwd_kernel<SV, AD> : (const void*)dec_rollout_fwd2_kernel<SV, AD>;
+    if (int rc = sw_set_lds(fn, lds, have)) return rc;
     if constexpr (NB == 1)
       SW_LAUNCH((dec_rollout_fwd_kernel<SV, AD>), dim3(d_w ? 2 * tiles : tiles), dim3(SW_THREADS), lds, (hipStream_t)stream,
                 obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt, inv_ss, ade_part, d_w, act,
@@ -1054,12 +1033,6 @@ extern "C" int sw_dec_rollout_fwd(const float* obsv, int To, const float* z, con
                                 ade_part, nullptr, nullptr, stream);
 }
 
-static int set_lds_bwd(const void* fn, int bytes, int& have) {
-  if (have >= bytes) return SW_OK;
-  if (int rc = set_lds(fn, bytes)) return rc;
-  have = bytes;
-  return SW_OK;
-}
 extern "C" int sw_dec_rollout_bwd_aux(const float* dpred4, const float* enc_w, const float* dec_w,
                                       const float* gsave, int B, int To, int Tp, float* gdelta, float* dhT,
                                       float* dcT, float* dS_pool, const float* aux_src, float* aux_dst,
@@ -1069,7 +1042,7 @@ extern "C" int sw_dec_rollout_bwd_aux(const float* dpred4, const float* enc_w, c
   if (aux_n < 0 || (aux_n > 0 && (!aux_src || !aux_dst || !aux_mask))) return SW_EARG;
   if (B == 0) return SW_OK;
   static int have = 0;
-  if (int rc = set_lds_bwd((const void*)dec_rollout_bwd_kernel<false>, BwdLds::total * 4, have)) return rc;
+  if (int rc = sw_set_lds((const void*)dec_rollout_bwd_kernel<false>, BwdLds::total * 4, have)) return rc;
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   int extra = aux_n > 0 ? (int)((aux_n + SW_THREADS - 1) / SW_THREADS) : 0;
   if (extra > 64) extra = 64;
@@ -1097,7 +1070,7 @@ extern "C" int sw_dec_rollout_bwd_dfuse(const float* obsv, const float* pred4, c
   if (lds < BwdLds::total * 4) lds = BwdLds::total * 4;
   if (lds > 163840) return SW_ESHAPE;
   static int have = 0;
-  if (int rc = set_lds_bwd((const void*)dec_rollout_bwd_kernel<true>, lds, have)) return rc;
+  if (int rc = sw_set_lds((const void*)dec_rollout_bwd_kernel<true>, lds, have)) return rc;
   DecDiscFuse df;
   df.obsv = obsv; df.pred_hat = pred4; df.d_w = d_w; df.dimg = sw_disc_images_for(d_w, Tp).img;
   df.gl = DiscLoss{targets, z, t_idx, t_idx, g_label, g_code, 1, loss_part};

@@ -9,7 +9,6 @@
 #include "sw_lstm_dev.h"
 #include "sw_wgrad.h"
 #include "sw_wgrad_dev.h"
-#include <type_traits>
 #include <cstdlib>
 #ifdef SW_PHASE_STAMPS
 __device__ long long sw_disc_stamps[16];
@@ -104,45 +103,13 @@ __global__ __launch_bounds__(SW_THREADS, 2) void disc_bwd_kernel(
     rz[0] = zsrc[(size_t)bb * SW_Z];
     rz[1] = zsrc[(size_t)bb * SW_Z + 1];
   }
-  if (dimg) {
-    // registered images (swdimg::HEADT): the eight transposed, zero-padded head matrices are ONE contiguous block in
-    // the LDS layout of this kernel - a float4 copy, no zero fill, no scalar scatter
-    constexpr int HB = 12;
-    const int n4 = L.dlab >> 2;
-    f32x4 hbv[HB];
-#pragma unroll
-    for (int e = 0; e < HB; ++e) hbv[e] = ld4(dimg + swdimg::HEADT + 4 * (size_t)min((int)threadIdx.x + SW_THREADS * e, n4 - 1));
-#pragma unroll
-    for (int e = 0; e < HB; ++e) {
-      const int f = threadIdx.x + SW_THREADS * e;
-      if (f < n4) st4(smem + 4 * f, hbv[e]);
-    }
-    for (int f = threadIdx.x + SW_THREADS * HB; f < n4; f += SW_THREADS) st4(smem + 4 * f, ld4(dimg + swdimg::HEADT + 4 * (size_t)f));
-  } else {
-  // transposed weight images: all global loads are issued before the zero fill and its barrier
-  f32x4 t_of0[2], t_of1[1], t_pe0[2], t_pe1[1], t_cl0[2], t_la0[2], t_cl1[1], t_la1[1];
-  const bool pe0_small = 8 * K4 <= 2 * SW_THREADS;
-  stage_wT_load<2>(t_of0, d_w + O.of0w, 64, 32, 64);
-  stage_wT_load<1>(t_of1, d_w + O.of1w, 32, 32, 32);
-  if (pe0_small) stage_wT_load<2>(t_pe0, d_w + O.pe0w, K4, 32, K4);
-  stage_wT_load<1>(t_pe1, d_w + O.pe1w, 32, 32, 32);
-  stage_wT_load<2>(t_cl0, d_w + O.cl0w, 64, 32, 64);
-  stage_wT_load<2>(t_la0, d_w + O.la0w, 64, 32, 64);
-  stage_wT_load<1>(t_cl1, d_w + O.cl1w, 32, 1, 32);
-  stage_wT_load<1>(t_la1, d_w + O.la1w, 32, 2, 32);
-  stage_zero(smem + L.of0T, L.dlab - L.of0T);  // transposed images are zero padded
-  sw_barrier();
-  stage_wT_store<2>(t_of0, smem + L.of0T, LD32, 32, 64);
-  stage_wT_store<1>(t_of1, smem + L.of1T, LD32, 32, 32);
-  if (pe0_small) stage_wT_store<2>(t_pe0, smem + L.pe0T, LD32, 32, K4);
-  else stage_wT(smem + L.pe0T, LD32, L.kp, d_w + O.pe0w, K4, 32, K4);
-  stage_wT_store<1>(t_pe1, smem + L.pe1T, LD32, 32, 32);
-  stage_wT_store<2>(t_cl0, smem + L.cl0T, LD32, 32, 64);
-  stage_wT_store<2>(t_la0, smem + L.la0T, LD32, 32, 64);
-  stage_wT_store<1>(t_cl1, smem + L.cl1T, LD16, 1, 32);
-  stage_wT_store<1>(t_la1, smem + L.la1T, LD16, 2, 32);
-  }
   for (int i = threadIdx.x; i < 16 * LD32; i += blockDim.x) smem[L.docode + i] = 0.f;
+  // the eight transposed head matrices: with the registered images ONE contiguous block in the LDS layout of this kernel
+  // (a float4 copy, no zero fill, no scalar scatter); from the weights every global load is issued before the zero fill
+  disc_stage_headT(smem, L, true, d_w, O, K4, dimg, true, [&] {
+    stage_zero(smem + L.of0T, L.dlab - L.of0T);  // transposed images are zero padded
+    sw_barrier();
+  });
 
   for (int k = 0; k < nb; ++k) {
     float* dpred = k == 0 ? dpred_a : dpred_b;
@@ -246,77 +213,14 @@ __global__ __launch_bounds__(SW_THREADS, 2) void disc_bwd_kernel(
   SW_STAMP(9);
   // ---- observation path: of1, of0, LSTM BPTT -------------------------------------------------
   if (live && wave < 2) st4(ddelta + dd.docode + (size_t)b * 32 + u0 + 4 * lg, ld4(smem + L.docode + ln * LD32 + u0 + 4 * lg));
-  if (wave < 2) {
-    int m0 = 16 * wave;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = tile_mm_rt(smem + L.of1T + (m0 + ln) * LD32 + 4 * lg, smem + L.docode + ln * LD32 + 4 * lg, 2, acc);
-    const f32x4 a = po1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu_grad(a[r], acc[r]);
-    st4(smem + L.do1 + ln * LD32 + m0 + 4 * lg, acc);
-    if (live) st4(ddelta + dd.do1 + (size_t)b * 32 + m0 + 4 * lg, acc);
-  }
-  sw_barrier();
-  f32x4 dh = {0.f, 0.f, 0.f, 0.f}, dc = {0.f, 0.f, 0.f, 0.f};
-  dh = tile_mm_rt(smem + L.of0T + (u0 + ln) * LD32 + 4 * lg, smem + L.do1 + ln * LD32 + 4 * lg, 2, dh);
+  f32x4 dh = disc_obs_bwd_tail(smem + L.of1T, smem + L.of0T, smem + L.docode, smem + L.do1, po1, ddelta + dd.do1 + (size_t)b * 32, live);
+  f32x4 dc = {0.f, 0.f, 0.f, 0.f};
   LstmWT WT;
-  if (dimg) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) WT.whhT[j] = ld4(dimg + swdimg::OP_WHHT + (((size_t)wave * 16 + j) * 64 + lane) * 4);
-  } else {
-    lstm_load_wT(WT, d_w + O.whh, u0, ln, lg);
-  }
-  // Saved rows are fetched one step ahead.  Every memory operation of the loop body is UNCONDITIONAL (the two
-  // boundary steps are peeled; padding lanes of the last tile store to a trash row): with conditional loads or
-  // stores the compiler cannot count what is in flight and waits for everything (s_waitcnt vmcnt(0)) right after
-  // issuing the prefetch - that exposed one HBM round trip in every BPTT step.
-  const float* act_b = dsave + ds.act + (size_t)b * 384 + u0 + 4 * lg;
-  const size_t tstep = (size_t)B * 384;
-  auto load_row = [&](int t, f32x4 g[4], f32x4& ct_, f32x4& cp_, auto has_prev) {
-    const float* row = act_b + (size_t)t * tstep;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) g[q] = ld4(row + q * 64);
-    ct_ = ld4(row + 256);
-    if constexpr (decltype(has_prev)::value) cp_ = ld4(row - tstep + 256);
-    else cp_ = f32x4{0.f, 0.f, 0.f, 0.f};   // c_{-1} = 0
-  };
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  f32x4 gate[4], ct, cprev;
-  if (To > 1) load_row(To - 1, gate, ct, cprev, T_{});
-  else load_row(0, gate, ct, cprev, F_{});
-  SW_STAMP(10);
-  // one BPTT step; pf: rows of step t-1 are prefetched (pp: they have a predecessor row), nx: dh_{t-1} is needed
-  auto step = [&](int t, auto pf, auto pp, auto nx) {
-    f32x4 dgate[4];
-    lstm_cell_bwd(gate, ct, cprev, dh, dc, dgate);
-    if constexpr (decltype(pf)::value) {      // rolling prefetch: the rows of step t - 1 into the registers just consumed
-      load_row(t - 1, gate, ct, cprev, pp);
-      asm volatile("" ::: "memory");
-    }
-    float* dgl = &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + u0 + 4 * lg];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
-    SW_STAMP(12);
-    sw_barrier();
-    lstm_store_dgates_tile(&dgbuf[(t & 1) * 16 * SW_GLD], ddelta + dd.dgates + ((size_t)t * B + a0) * 256, ddelta + dd.trash,
-                           a0, B, wave, lane);
-    SW_STAMP(13);
-    if constexpr (decltype(nx)::value) dh = lstm_dh_prev(WT, &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + 4 * lg]);
-    if constexpr (decltype(pf)::value)
-      asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
-    SW_STAMP(14);
-  };
-  // every load issued so far (the saved rows of the first step, W_hh^T) is waited for HERE: behind the heads' conditional
-  // stores the compiler cannot count what is pending on the way into the loop, and a loop header with an unknown state
-  // gets s_waitcnt vmcnt(0) - which every BPTT step then pays as the round trip of the dgates rows it has just stored
-  asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
-#pragma unroll
-  for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(WT.whhT[j]));
-  for (int t = To - 1; t >= 2; --t) step(t, T_{}, T_{}, T_{});
-  if (To > 1) step(1, T_{}, F_{}, T_{});
-  step(0, F_{}, F_{}, F_{});
-  SW_STAMP(11);
+  lstm_load_whhT(WT, dimg, swdimg::OP_WHHT, d_w + O.whh, wave, lane);
+  // the BPTT over the saved rows (sw_lstm_dev.h): c_{-1} = 0, padding lanes of the last tile store to the trash row
+  const LstmBptt S{dsave + ds.act + (size_t)b * 384 + u0 + 4 * lg, nullptr, dgbuf, ddelta + dd.dgates + (size_t)a0 * 256,
+                   ddelta + dd.trash, a0, B};
+  lstm_bptt_rows<false>(WT, S, To, dh, dc, SwNop{}, [&](int k) { SW_STAMP(k); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -385,96 +289,26 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   const int b = min(a0 + ln, B - 1);
   const bool live = (a0 + ln) < B;
   const int K4 = 4 * Tp, ldp = U.ldp;
-  auto hwp = [&](int off) { return smem + U.hw + (off - F.of0); };      // forward head matrix at HeadLds offset `off`
-  auto hwT = [&](int off) { return smem + U.hwT + (off - T.of0T); };    // transposed head matrix at HeadLdsB offset `off`
+  float* hw = smem + U.hw - F.of0;      // forward head matrices and bias slots at their HeadLds offsets
+  float* hwT = smem + U.hwT - T.of0T;   // transposed head matrices at their HeadLdsB offsets
 
   // ---- prologue: every global load first --------------------------------------------------------------------------
-  float xpre[2][4];       // prediction rows of both branches (unconditional loads from clamped addresses; Tp <= 12 here)
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    const float* pk = kk == 0 ? pred_a : pred_b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = min((int)threadIdx.x + SW_THREADS * e, 16 * ldp - 1);
-      const int a = i / ldp, cc = i - a * ldp;
-      xpre[kk][e] = pk[(size_t)min(a0 + a, B - 1) * K4 + min(cc, K4 - 1)];
-    }
-  }
+  float xpre[2][4];       // prediction rows of both branches (Tp <= 12 here)
+  disc_xpre_load(xpre, pred_a, pred_b, a0, B, K4, ldp);
   const float tg0 = gl.targets[gl.t0], tg1 = gl.targets[gl.t1];
   const float z0 = gl.z[(size_t)b * SW_Z], z1 = gl.z[(size_t)b * SW_Z + 1];
   LstmW W;
-  if (!obs_pre) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) W.whh[g][j] = ld4(dimg + swdimg::OP_WHH + ((((size_t)4 * g + wave) * 4 + j) * 64 + lane) * 4);
-      W.wx[g] = d_w[O.wih + (g * 64 + u0 + ln) * 4 + lg];
-      W.bias[g] = ld4(d_w + O.bih + g * 64 + u0 + 4 * lg) + ld4(d_w + O.bhh + g * 64 + u0 + 4 * lg);
-    }
-  }
+  if (!obs_pre) disc_obs_operands(W, d_w, O, dimg);
   if (w_snap)   // deepcopy(D) of train.py:499: the weights this pass runs with
     for (int i = blockIdx.x * SW_THREADS + threadIdx.x; i < O.n; i += gridDim.x * SW_THREADS) w_snap[i] = d_w[i];
-  {
-    f32x4 s_of0[3], s_of1[2], s_pe0[2], s_pe1[2], s_cl0[3], s_la0[3], s_cl1[1], s_la1[1];
-    stage_w_load<3>(s_of0, LD64, 32, d_w + O.of0w, 64, 32, 64);
-    stage_w_load<2>(s_of1, LD32, 32, d_w + O.of1w, 32, 32, 32);
-    stage_w_load<2>(s_pe0, ldp, 32, d_w + O.pe0w, K4, 32, K4);
-    stage_w_load<2>(s_pe1, LD32, 32, d_w + O.pe1w, 32, 32, 32);
-    stage_w_load<3>(s_cl0, LD64, 32, d_w + O.cl0w, 64, 32, 64);
-    stage_w_load<3>(s_la0, LD64, 32, d_w + O.la0w, 64, 32, 64);
-    stage_w_load<1>(s_cl1, LD32, 16, d_w + O.cl1w, 32, 1, 32);
-    stage_w_load<1>(s_la1, LD32, 16, d_w + O.la1w, 32, 2, 32);
-    stage_w_store<3>(s_of0, hwp(F.of0), LD64, 32);
-    stage_w_store<2>(s_of1, hwp(F.of1), LD32, 32);
-    stage_w_store<2>(s_pe0, hwp(F.pe0), ldp, 32);
-    stage_w_store<2>(s_pe1, hwp(F.pe1), LD32, 32);
-    stage_w_store<3>(s_cl0, hwp(F.cl0), LD64, 32);
-    stage_w_store<3>(s_la0, hwp(F.la0), LD64, 32);
-    stage_w_store<1>(s_cl1, hwp(F.cl1), LD32, 16);
-    stage_w_store<1>(s_la1, hwp(F.la1), LD32, 16);
-  }
-  {
-    const int i = threadIdx.x;  // 256 = 8 x 32 bias slots
-    const int q = i >> 5, k = i & 31;
-    const int boff = q == 0 ? O.of0b : q == 1 ? O.of1b : q == 2 ? O.pe0b : q == 3 ? O.pe1b : q == 4 ? O.cl0b
-                     : q == 5 ? O.la0b : q == 6 ? O.cl1b : O.la1b;
-    const int lim = q < 6 ? 32 : (q == 6 ? 1 : 2);
-    const float v = d_w[boff + min(k, lim - 1)];
-    smem[U.bias + i] = k < lim ? v : 0.f;
-  }
-  {   // the transposed block of the images: one contiguous float4 copy (zero padding included)
-    constexpr int HB = 12;
-    const int n4 = (T.dlab - T.of0T) >> 2;
-    f32x4 hbv[HB];
-#pragma unroll
-    for (int e = 0; e < HB; ++e) hbv[e] = ld4(dimg + swdimg::HEADT + 4 * (size_t)min((int)threadIdx.x + SW_THREADS * e, n4 - 1));
-#pragma unroll
-    for (int e = 0; e < HB; ++e) {
-      const int f = threadIdx.x + SW_THREADS * e;
-      if (f < n4) st4(smem + U.hwT + 4 * f, hbv[e]);
-    }
-  }
+  disc_stage_heads(hw, F, d_w, O, K4, true);
+  disc_stage_headT(hwT, T, true, nullptr, O, K4, dimg, false);   // the image block: one float4 copy (zero padding included)
   // prediction rows into LDS (zero padded) and into the save buffer (rows of the pe0 weight gradient)
 #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = threadIdx.x + SW_THREADS * e;
-      if (i < 16 * ldp) {
-        const int a = i / ldp, cc = i - a * ldp;
-        const float v = cc < K4 ? xpre[kk][e] : 0.f;
-        smem[U.x + kk * 16 * ldp + i] = v;
-        if (cc < K4 && a0 + a < B) dsave[ds.px + ((size_t)kk * B + a0 + a) * K4 + cc] = v;
-      }
-    }
-  }
+  for (int kk = 0; kk < 2; ++kk)
+    disc_xpre_put(xpre, kk == 1, smem + U.x + kk * 16 * ldp, dsave + ds.px + (size_t)kk * B * K4, a0, B, K4, ldp);
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
-  if (!obs_pre) {
-    st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], h);
-  } else {   // h_T of the tile from the rows the decode launch left
-    st4(&hbuf[(To & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg],
-        ld4(dsave + ds.act + ((size_t)(To - 1) * B + b) * 384 + 320 + u0 + 4 * lg));
-  }
+  disc_seed_h(hbuf, obs_pre, dsave + ds.act, To, B, b);
   sw_barrier();
   // The usual horizon (8 observed steps, train.py:44): the gates and cell states of the eight steps STAY IN REGISTERS
   // (160 of the 512 a wave owns at one wave per SIMD) for the BPTT below - only h (the operand of the LSTM's weight
@@ -506,26 +340,8 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   }
   const float* hlast = &hbuf[(To & 1) * 16 * SW_HLD];
 
-  // ---- observation fc (waves 0, 1): o1 = lrelu(of0 h + b), obsv_code = of1 o1 + b -> both[0 | 1][:, 0:32] --------------
-  f32x4 o1reg = {0.f, 0.f, 0.f, 0.f};
-  if (wave < 2) {
-    const int m0 = 16 * wave;
-    f32x4 acc = ld4(smem + U.bias + 0 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(hwp(F.of0) + (m0 + ln) * LD64 + 4 * lg, hlast + ln * SW_HLD + 4 * lg, 4, acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
-    o1reg = acc;
-    st4(smem + U.o1 + ln * LD32 + m0 + 4 * lg, acc);
-    if (live) st4(dsave + ds.o1 + (size_t)b * 32 + m0 + 4 * lg, acc);
-  }
-  sw_barrier();
-  if (wave < 2) {
-    const int m0 = 16 * wave;
-    f32x4 acc = ld4(smem + U.bias + 1 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(hwp(F.of1) + (m0 + ln) * LD32 + 4 * lg, smem + U.o1 + ln * LD32 + 4 * lg, 2, acc);
-    st4(smem + U.both + ln * LD64 + m0 + 4 * lg, acc);
-    st4(smem + U.both + 16 * LD64 + ln * LD64 + m0 + 4 * lg, acc);
-  }
+  // ---- observation fc (waves 0, 1) -> both[0 | 1][:, 0:32] --------------------------------------------------------------
+  const f32x4 o1reg = disc_obs_fc(hw, F, hlast, smem + U.o1, dsave + ds.o1 + (size_t)b * 32, live, smem + U.both, 2);
   // ---- prediction heads, the two branches side by side: wave pair br, wave wp of the pair ------------------------------
   float* xb_ = smem + U.x + br * 16 * ldp;
   float* q1_ = smem + U.q1 + br * 16 * LD32;
@@ -537,7 +353,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   {   // q1 = lrelu(pe0 x + b): row tile wp
     const int m0 = 16 * wp;
     f32x4 acc = ld4(smem + U.bias + 2 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(hwp(F.pe0) + (m0 + ln) * ldp + 4 * lg, xb_ + ln * ldp + 4 * lg, (ldp - 4) / 16, acc);
+    acc = tile_mm_rt(hw + F.pe0 + (m0 + ln) * ldp + 4 * lg, xb_ + ln * ldp + 4 * lg, (ldp - 4) / 16, acc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
     q1reg = acc;
@@ -551,7 +367,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     stage_zero(smem + U.dlab, U.dc1 - U.dlab);
     const int m0 = 16 * wp;
     f32x4 acc = ld4(smem + U.bias + 3 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(hwp(F.pe1) + (m0 + ln) * LD32 + 4 * lg, q1_ + ln * LD32 + 4 * lg, 2, acc);
+    acc = tile_mm_rt(hw + F.pe1 + (m0 + ln) * LD32 + 4 * lg, q1_ + ln * LD32 + 4 * lg, 2, acc);
     st4(both_ + ln * LD64 + 32 + m0 + 4 * lg, acc);
   }
   sw_barrier();
@@ -562,8 +378,8 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     }
     const int m0 = 16 * wp;
     f32x4 ac = ld4(smem + U.bias + 4 * 32 + m0 + 4 * lg), al = ld4(smem + U.bias + 5 * 32 + m0 + 4 * lg);
-    ac = tile_mm_rt(hwp(F.cl0) + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, ac);
-    al = tile_mm_rt(hwp(F.la0) + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, al);
+    ac = tile_mm_rt(hw + F.cl0 + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, ac);
+    al = tile_mm_rt(hw + F.la0 + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, al);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       ac[r] = sw_lrelu(ac[r]);
@@ -583,7 +399,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   {
     const bool cls = wp == 0;
     f32x4 acc = ld4(smem + U.bias + (cls ? 6 : 7) * 32 + 4 * lg);
-    acc = tile_mm_rt(hwp(cls ? F.cl1 : F.la1) + ln * LD32 + 4 * lg, (cls ? c1_ : l1_) + ln * LD32 + 4 * lg, 2, acc);
+    acc = tile_mm_rt(hw + (cls ? F.cl1 : F.la1) + ln * LD32 + 4 * lg, (cls ? c1_ : l1_) + ln * LD32 + 4 * lg, 2, acc);
     float* label = br == 0 ? label_a : label_b;
     float* code = br == 0 ? code_a : code_b;
     float sl = 0.f;
@@ -622,8 +438,8 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   {   // dc1 = (cl1^T dlabel) * lrelu'(c1), dl1 = (la1^T dcode) * lrelu'(l1): row tile wp each
     const int m0 = 16 * wp;
     f32x4 ac = {0.f, 0.f, 0.f, 0.f}, al = ac;
-    ac = tile_mm_rt(hwT(T.cl1T) + (m0 + ln) * LD16 + 4 * lg, dlab_ + ln * LD16 + 4 * lg, 1, ac);
-    al = tile_mm_rt(hwT(T.la1T) + (m0 + ln) * LD16 + 4 * lg, dcod_ + ln * LD16 + 4 * lg, 1, al);
+    ac = tile_mm_rt(hwT + T.cl1T + (m0 + ln) * LD16 + 4 * lg, dlab_ + ln * LD16 + 4 * lg, 1, ac);
+    al = tile_mm_rt(hwT + T.la1T + (m0 + ln) * LD16 + 4 * lg, dcod_ + ln * LD16 + 4 * lg, 1, al);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       ac[r] = sw_lrelu_grad(c1reg[r], ac[r]);
@@ -642,8 +458,8 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     for (int q = 0; q < 2; ++q) {
       const int m0 = 16 * (2 * wp + q);
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tile_mm_rt(hwT(T.cl0T) + (m0 + ln) * LD32 + 4 * lg, dc1_ + ln * LD32 + 4 * lg, 2, acc);
-      acc = tile_mm_rt(hwT(T.la0T) + (m0 + ln) * LD32 + 4 * lg, dl1_ + ln * LD32 + 4 * lg, 2, acc);
+      acc = tile_mm_rt(hwT + T.cl0T + (m0 + ln) * LD32 + 4 * lg, dc1_ + ln * LD32 + 4 * lg, 2, acc);
+      acc = tile_mm_rt(hwT + T.la0T + (m0 + ln) * LD32 + 4 * lg, dl1_ + ln * LD32 + 4 * lg, 2, acc);
       st4(dboth_ + ln * LD64 + m0 + 4 * lg, acc);
       if (wp == 1 && live) st4(ddelta + dd.dpcode + kb * 32 + (m0 - 32) + 4 * lg, acc);   // the prediction-code half
     }
@@ -652,7 +468,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   {   // dq1 = (pe1^T dpcode) * lrelu'(q1): row tile wp (only the weight gradient needs it: D updates want no d/dpred)
     const int m0 = 16 * wp;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = tile_mm_rt(hwT(T.pe1T) + (m0 + ln) * LD32 + 4 * lg, dboth_ + ln * LD64 + 32 + 4 * lg, 2, acc);
+    acc = tile_mm_rt(hwT + T.pe1T + (m0 + ln) * LD32 + 4 * lg, dboth_ + ln * LD64 + 32 + 4 * lg, 2, acc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu_grad(q1reg[r], acc[r]);
     if (live) st4(ddelta + dd.dq1 + kb * 32 + m0 + 4 * lg, acc);
@@ -664,99 +480,32 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     if (live) st4(ddelta + dd.docode + (size_t)b * 32 + m0 + 4 * lg, v);
   }
   sw_barrier();
-  if (wave < 2) {
-    const int m0 = 16 * wave;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = tile_mm_rt(hwT(T.of1T) + (m0 + ln) * LD32 + 4 * lg, smem + U.docode + ln * LD32 + 4 * lg, 2, acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu_grad(o1reg[r], acc[r]);
-    st4(smem + U.do1 + ln * LD32 + m0 + 4 * lg, acc);
-    if (live) st4(ddelta + dd.do1 + (size_t)b * 32 + m0 + 4 * lg, acc);
-  }
-  sw_barrier();
-  // ---- observation LSTM backward (as disc_bwd_kernel): dh_T = of0^T do1, then BPTT over the saved rows ------------------
-  f32x4 dh = {0.f, 0.f, 0.f, 0.f}, dc = {0.f, 0.f, 0.f, 0.f};
-  dh = tile_mm_rt(hwT(T.of0T) + (u0 + ln) * LD32 + 4 * lg, smem + U.do1 + ln * LD32 + 4 * lg, 2, dh);
+  // ---- observation backward: do1, dh_T = of0^T do1, then the BPTT (sw_lstm_dev.h: c_{-1} = 0, padding rows to the trash row)
+  f32x4 dh = disc_obs_bwd_tail(hwT + T.of1T, hwT + T.of0T, smem + U.docode, smem + U.do1, o1reg, ddelta + dd.do1 + (size_t)b * 32, live);
+  f32x4 dc = {0.f, 0.f, 0.f, 0.f};
   LstmWT WT;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) WT.whhT[j] = ld4(dimg + swdimg::OP_WHHT + (((size_t)wave * 16 + j) * 64 + lane) * 4);
-  float* dgbuf = smem + U.hwT + (T.pe0T - T.of0T);   // [2][16][SW_GLD] over the prediction heads' transposed images (dead now)
-  const float* act_b = dsave + ds.act + (size_t)b * 384 + u0 + 4 * lg;
-  const size_t tstep = (size_t)B * 384;
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  auto load_row = [&](int t, f32x4 g[4], f32x4& ct_, f32x4& cp_, auto has_prev) {
-    const float* row = act_b + (size_t)t * tstep;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) g[q] = ld4(row + q * 64);
-    ct_ = ld4(row + 256);
-    if constexpr (decltype(has_prev)::value) cp_ = ld4(row - tstep + 256);
-    else cp_ = f32x4{0.f, 0.f, 0.f, 0.f};   // c_{-1} = 0
-  };
+  lstm_load_whhT(WT, dimg, swdimg::OP_WHHT, nullptr, wave, lane);
+  // the dgates tiles [2][16][SW_GLD] lie over the prediction heads' transposed images (dead now)
+  const LstmBptt S{dsave + ds.act + (size_t)b * 384 + u0 + 4 * lg, nullptr, hwT + T.pe0T, ddelta + dd.dgates + (size_t)a0 * 256,
+                   ddelta + dd.trash, a0, B};
+  // (both paths: a barrier in front of the first step - every wave has read of0T / do1; the dgates tiles start behind
+  //  of0T / of1T, kept for symmetry with disc_bwd)
   if (reg8) {        // the eight steps' gates / cell states are in registers: no row traffic at all
     sw_barrier();
 #pragma unroll
     for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(WT.whhT[j]));
 #pragma unroll
-    for (int t = 7; t >= 0; --t) {
-      f32x4 dgate[4];
-      lstm_cell_bwd(sg[t], sc[t], t > 0 ? sc[t > 0 ? t - 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f}, dh, dc, dgate);
-      float* dgl = &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + u0 + 4 * lg];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
-      sw_barrier();
-      lstm_store_dgates_tile(&dgbuf[(t & 1) * 16 * SW_GLD], ddelta + dd.dgates + ((size_t)t * B + a0) * 256, ddelta + dd.trash,
-                             a0, B, wave, lane);
-      if (t > 0) dh = lstm_dh_prev(WT, &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + 4 * lg]);
-    }
+    for (int t = 7; t >= 1; --t) lstm_bptt_step<false, false, true>(WT, S, t, sg[t], sc[t], sc[t - 1], dh, dc);
+    f32x4 c_1 = {0.f, 0.f, 0.f, 0.f};   // c_{-1} = 0
+    lstm_bptt_step<false, false, false>(WT, S, 0, sg[0], sc[0], c_1, dh, dc);
     return;
   }
-  f32x4 gate[4], ct, cprev;
-  if (To > 1) load_row(To - 1, gate, ct, cprev, T_{});
-  else load_row(0, gate, ct, cprev, F_{});
-  sw_barrier();      // every wave has read of0T / do1: (the dgates tiles start behind of0T / of1T; kept for symmetry with disc_bwd)
-  asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
-#pragma unroll
-  for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(WT.whhT[j]));
-  auto step = [&](int t, auto pf, auto pp, auto nx) {
-    f32x4 dgate[4];
-    lstm_cell_bwd(gate, ct, cprev, dh, dc, dgate);
-    if constexpr (decltype(pf)::value) {      // rolling prefetch: the rows of step t - 1 into the registers just consumed
-      load_row(t - 1, gate, ct, cprev, pp);
-      asm volatile("" ::: "memory");
-    }
-    float* dgl = &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + u0 + 4 * lg];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
-    sw_barrier();
-    lstm_store_dgates_tile(&dgbuf[(t & 1) * 16 * SW_GLD], ddelta + dd.dgates + ((size_t)t * B + a0) * 256, ddelta + dd.trash,
-                           a0, B, wave, lane);
-    if constexpr (decltype(nx)::value) dh = lstm_dh_prev(WT, &dgbuf[(t & 1) * 16 * SW_GLD + ln * SW_GLD + 4 * lg]);
-    if constexpr (decltype(pf)::value)
-      asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
-  };
-  for (int t = To - 1; t >= 2; --t) step(t, T_{}, T_{}, T_{});
-  if (To > 1) step(1, T_{}, F_{}, T_{});
-  step(0, F_{}, F_{}, F_{});
+  lstm_bptt_rows<false>(WT, S, To, dh, dc, SwNop{}, [](int k) {
+    if (k == 10) sw_barrier();   // behind the request of the first rows
+  });
 }
 
-static int set_lds(const void* fn, int bytes) {
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    sw_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    return SW_EHIP;
-  }
-  return SW_OK;
-}
-
-static int g_disc_fwd_lds = 0;   // largest dynamic-LDS size disc_fwd_kernel has been enabled for (plain + fused launches)
-static int disc_fwd_lds(int bytes) {
-  if (g_disc_fwd_lds < bytes) {
-    if (int rc = set_lds((const void*)disc_fwd_kernel, bytes)) return rc;
-    g_disc_fwd_lds = bytes;
-  }
-  return SW_OK;
-}
+static int g_disc_fwd_lds = 0;   // dynamic-LDS limit of disc_fwd_kernel (plain + fused launches, sw_set_lds)
 
 size_t sw_dsave_floats(int B, int To, int Tp, int nb) { return dsave_layout(B, To, Tp, nb).total; }
 size_t sw_ddelta_floats(int B, int To, int Tp, int nb) { return ddelta_layout(B, To, Tp, nb).total; }
@@ -773,7 +522,7 @@ extern "C" int sw_disc_fwd(const float* obsv, int To, int x_mode, const float* c
   if (B == 0) return SW_OK;
   int lds = head_lds(Tp, 2 * 16 * SW_HLD + 1280).total * 4;
   if (lds > 163840) return SW_ESHAPE;
-  if (int rc = disc_fwd_lds(lds)) return rc;
+  if (int rc = sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds)) return rc;
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   const int split = (nb == 2 && 2 * tiles <= SW_SPLIT_MAX_WGS) ? 1 : 0;   // idle CUs: one workgroup per (tile, branch)
   SW_LAUNCH(disc_fwd_kernel, dim3(split ? 2 * tiles : tiles), dim3(SW_THREADS), lds, (hipStream_t)stream,
@@ -796,7 +545,7 @@ extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float*
   if (B == 0) return SW_OK;
   const int lds = head_lds_b(Tp, head_lds(Tp, 2 * 16 * SW_HLD + 1280).total).total * 4;
   if (lds > 163840) return SW_ESHAPE;
-  if (int rc = disc_fwd_lds(lds)) return rc;
+  if (int rc = sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds)) return rc;
   DiscLoss gl{targets, z, t_idx, t_idx, g_label, g_code, 1, loss_part};
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   SW_LAUNCH(disc_fwd_kernel, dim3(tiles), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode, pred4,
@@ -840,11 +589,8 @@ static int disc_bwd_impl(const float* d_w, const float* dsave, const float* cons
   if (B == 0) return SW_OK;
   int lds = head_lds_b(Tp, 0).total * 4;
   if (lds > 163840) return SW_ESHAPE;
-  static int attr = 0;
-  if (attr < lds) {
-    if (int rc = set_lds((const void*)disc_bwd_kernel, lds)) return rc;
-    attr = lds;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)disc_bwd_kernel, lds, have)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   WgBatch wb;
@@ -858,6 +604,19 @@ static int disc_bwd_impl(const float* d_w, const float* dsave, const float* cons
   if (!d_d_w) return SW_OK;
   WgAdam ad = adam;
   return wg_launch_adam(wb, wgrad_ws, ad, st);
+}
+
+// The Adam update riding in the weight-gradient reduction (none without adam_w); D's registered images follow it element by element
+static WgAdam disc_adam(float* w, float* m, float* v, const float* step, float* g, double lr, double beta1, double beta2, double eps,
+                        int Tp) {
+  WgAdam ad;
+  if (!w) return ad;
+  ad.w = w; ad.m = m; ad.v = v; ad.g0 = g; ad.step = step;
+  ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps;
+  const DiscImages di = sw_disc_images_for(w, Tp);
+  ad.img = const_cast<float*>(di.img);
+  ad.tab = di.tab;
+  return ad;
 }
 
 // Can sw_disc_update run this pass (else: sw_disc_fwd + sw_disc_bwd_gan*)?  Built in round 3 for the shapes that leave CUs
@@ -884,11 +643,8 @@ extern "C" int sw_disc_update(const float* obsv, int To, const float* const* pre
   if (B == 0) return SW_OK;
   if (!sw_disc_update_supported(d_w, B, To, Tp)) return SW_ESHAPE;
   const int lds = upd_lds(Tp).total * 4;
-  static int attr = 0;
-  if (attr < lds) {
-    if (int rc = set_lds((const void*)disc_update_kernel, lds)) return rc;
-    attr = lds;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)disc_update_kernel, lds, have)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const DiscImages di = sw_disc_images_for(d_w, Tp);
   DiscLoss gl{targets, z, t0, t1, g_label, g_code, 1, loss_part};
@@ -898,13 +654,7 @@ extern "C" int sw_disc_update(const float* obsv, int To, const float* const* pre
   SW_LAUNCH(disc_update_kernel, dim3(tiles), dim3(SW_THREADS), lds, st, obsv, To, pred4[0], pred4[1], d_w, B, Tp, label[0],
             label[1], code[0], code[1], dsave, obs_pre ? 1 : 0, w_snapshot, gl, ddelta, di.img);
   SW_CHECK_LAUNCH("disc_update_kernel");
-  WgAdam ad;
-  if (adam_w) {
-    ad.w = adam_w; ad.m = adam_m; ad.v = adam_v; ad.g0 = d_d_w; ad.step = adam_step;
-    ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps;
-    ad.img = const_cast<float*>(di.img);
-    ad.tab = di.tab;
-  }
+  WgAdam ad = disc_adam(adam_w, adam_m, adam_v, adam_step, d_d_w, lr, beta1, beta2, eps, Tp);
   return wg_launch_adam(wb, wgrad_ws, ad, st);
 }
 
@@ -926,14 +676,7 @@ extern "C" int sw_disc_bwd_gan_adam(const float* d_w, const float* dsave, const 
   if (!targets || !z || t0 < 0 || t1 < 0) return SW_EARG;
   if (adam_w && (!adam_m || !adam_v || !adam_step || !d_d_w || adam_w != d_w)) return SW_EARG;
   DiscLoss gl{targets, z, t0, t1, g_label, g_code, 1, loss_part};
-  WgAdam ad;
-  if (adam_w) {
-    ad.w = adam_w; ad.m = adam_m; ad.v = adam_v; ad.g0 = d_d_w; ad.step = adam_step;
-    ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps;
-    const DiscImages di = sw_disc_images_for(adam_w, Tp);   // registered images follow the update element by element
-    ad.img = const_cast<float*>(di.img);
-    ad.tab = di.tab;
-  }
+  const WgAdam ad = disc_adam(adam_w, adam_m, adam_v, adam_step, d_d_w, lr, beta1, beta2, eps, Tp);
   return disc_bwd_impl(d_w, dsave, label, code, nb, B, To, Tp, ddelta, d_d_w, dpred4, wgrad_ws, stream, gl, ad);
 }
 extern "C" int sw_disc_bwd_gan(const float* d_w, const float* dsave, const float* const* label,

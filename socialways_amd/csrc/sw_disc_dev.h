@@ -1,6 +1,6 @@
 // sw_disc_dev.h - device code of Discriminator.forward (reference train.py:294-309) shared by sw_disc.hip and the launches
-// that run a discriminator pass in front of their own work (sw_decoder.hip): LDS carves, save / delta layouts, the
-// per-tile forward body.
+// that run a discriminator pass in front of their own work (sw_decoder.hip): LDS carves, save / delta layouts, the phases
+// the forward body, disc_bwd and disc_update share, the per-tile forward body.
 #pragma once
 #include "../../include/socialways_hip.h"
 #include "sw_lstm_dev.h"
@@ -154,6 +154,191 @@ struct DiscLoss {
   float* loss_part;      // [tiles][3] per-tile sums of the squared errors (reporting), or null
 };
 
+// ---- phases of a D pass, written once for disc_fwd_tile, disc_bwd_kernel and disc_update_kernel ----------------------
+// The prediction rows of two branch slots (p0, p1: [B][4 Tp]) of the tile at a0, requested at the top of a pass (staged
+// where the heads start they cost one global round trip per branch behind the observation LSTM): unconditional loads
+// from clamped addresses, 4 per thread and slot cover the [16][ldp] tile up to Tp = 12.
+__device__ __forceinline__ void disc_xpre_load(float (&xpre)[2][4], const float* p0, const float* p1, int a0, int B, int K4, int ldp) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const float* pk = kk == 0 ? p0 : p1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = min((int)threadIdx.x + SW_THREADS * e, 16 * ldp - 1);
+      const int a = i / ldp, cc = i - a * ldp;
+      xpre[kk][e] = pk[(size_t)min(a0 + a, B - 1) * K4 + min(cc, K4 - 1)];
+    }
+  }
+}
+// ... slot s1 of them into the LDS tile x (zero padded) and, given px (the branch's rows in the save buffer), into the
+// rows of the pe0 weight gradient
+__device__ __forceinline__ void disc_xpre_put(const float (&xpre)[2][4], bool s1, float* x, float* px, int a0, int B, int K4, int ldp) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int i = threadIdx.x + SW_THREADS * e;
+    if (i < 16 * ldp) {
+      const int a = i / ldp, cc = i - a * ldp;
+      const float v = cc < K4 ? (s1 ? xpre[1][e] : xpre[0][e]) : 0.f;
+      x[i] = v;
+      if (px && cc < K4 && a0 + a < B) px[(size_t)(a0 + a) * K4 + cc] = v;
+    }
+  }
+}
+
+// The observation LSTM's operands: W_hh from the OP_WHH image (a wave's load = 1 KB of consecutive memory) or, without
+// one, from the weights; W_ih [256][4] and b_ih + b_hh straight into their registers (no LDS staging, nothing behind a
+// barrier).  Issued at the top of a pass, the loads are in flight during the LDS staging.
+__device__ __forceinline__ void disc_obs_operands(LstmW& W, const float* d_w, const swp::Disc& O, const float* dimg) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4, u0 = wave * 16;
+  if (!dimg) lstm_load_whh(W, d_w + O.whh, u0, ln, lg);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    if (dimg) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) W.whh[g][j] = ld4(dimg + swdimg::OP_WHH + ((((size_t)4 * g + wave) * 4 + j) * 64 + lane) * 4);
+    }
+    W.wx[g] = d_w[O.wih + (g * 64 + u0 + ln) * 4 + lg];
+    W.bias[g] = ld4(d_w + O.bih + g * 64 + u0 + 4 * lg) + ld4(d_w + O.bhh + g * 64 + u0 + 4 * lg);
+  }
+}
+
+// The eight forward head matrices (row-major, zero padded) at hw + their HeadLds offsets and the eight bias slots at
+// hw + L.bias: ALL global loads first, then the LDS stores (one L2 round trip for the eight matrices instead of one each).
+// pe0_small: pe0 fits the register staging (4 Tp <= 48, the usual horizons), else it is staged on the spot.
+__device__ __forceinline__ void disc_stage_heads(float* hw, const HeadLds& L, const float* d_w, const swp::Disc& O, int K4,
+                                                 bool pe0_small) {
+  f32x4 s_of0[3], s_of1[2], s_pe0[2], s_pe1[2], s_cl0[3], s_la0[3], s_cl1[1], s_la1[1];
+  stage_w_load<3>(s_of0, LD64, 32, d_w + O.of0w, 64, 32, 64);
+  stage_w_load<2>(s_of1, LD32, 32, d_w + O.of1w, 32, 32, 32);
+  if (pe0_small) stage_w_load<2>(s_pe0, L.ldp, 32, d_w + O.pe0w, K4, 32, K4);
+  stage_w_load<2>(s_pe1, LD32, 32, d_w + O.pe1w, 32, 32, 32);
+  stage_w_load<3>(s_cl0, LD64, 32, d_w + O.cl0w, 64, 32, 64);
+  stage_w_load<3>(s_la0, LD64, 32, d_w + O.la0w, 64, 32, 64);
+  stage_w_load<1>(s_cl1, LD32, 16, d_w + O.cl1w, 32, 1, 32);
+  stage_w_load<1>(s_la1, LD32, 16, d_w + O.la1w, 32, 2, 32);
+  stage_w_store<3>(s_of0, hw + L.of0, LD64, 32);
+  stage_w_store<2>(s_of1, hw + L.of1, LD32, 32);
+  if (pe0_small) stage_w_store<2>(s_pe0, hw + L.pe0, L.ldp, 32);
+  else stage_w(hw + L.pe0, L.ldp, 32, d_w + O.pe0w, K4, 32, K4);
+  stage_w_store<2>(s_pe1, hw + L.pe1, LD32, 32);
+  stage_w_store<3>(s_cl0, hw + L.cl0, LD64, 32);
+  stage_w_store<3>(s_la0, hw + L.la0, LD64, 32);
+  stage_w_store<1>(s_cl1, hw + L.cl1, LD32, 16);
+  stage_w_store<1>(s_la1, hw + L.la1, LD32, 16);
+  // the eight bias vectors: ONE unconditional load per thread from a selected offset (eight loads under lane branches
+  // compiled to eight serial round trips, each behind an s_waitcnt vmcnt(0))
+  const int i = threadIdx.x;  // 256 = 8 x 32
+  const int q = i >> 5, k = i & 31;
+  const int boff = q == 0 ? O.of0b : q == 1 ? O.of1b : q == 2 ? O.pe0b : q == 3 ? O.pe1b : q == 4 ? O.cl0b
+                   : q == 5 ? O.la0b : q == 6 ? O.cl1b : O.la1b;
+  const int lim = q < 6 ? 32 : (q == 6 ? 1 : 2);
+  const float v = d_w[boff + min(k, lim - 1)];
+  hw[L.bias + i] = k < lim ? v : 0.f;
+}
+
+// The transposed head matrices at base + their HeadLdsB offsets, from of0T (obs: all eight) or from pe0T (the prediction,
+// classifier and code heads) up to dlab.  With the registered images (swdimg::HEADT) one contiguous float4 copy, zero
+// padding included (tail: the block can exceed HB float4 per thread, Tp > 12); else from the weights d_w (nullptr: the
+// images are always there) into a zero-filled block: the loads, then between() (where a caller that has not zero-filled
+// the block does so, behind a barrier), then the stores.
+template <class Between = SwNop>
+__device__ __forceinline__ void disc_stage_headT(float* base, const HeadLdsB& L, bool obs, const float* d_w, const swp::Disc& O,
+                                                 int K4, const float* dimg, bool tail, Between between = {}) {
+  const int from = obs ? L.of0T : L.pe0T;
+  if (dimg || !d_w) {
+    constexpr int HB = 12;
+    const int n4 = (L.dlab - from) >> 2;
+    const float* src = dimg + swdimg::HEADT + (from - L.of0T);
+    float* dst = base + from;
+    f32x4 hbv[HB];
+#pragma unroll
+    for (int e = 0; e < HB; ++e) hbv[e] = ld4(src + 4 * (size_t)min((int)threadIdx.x + SW_THREADS * e, n4 - 1));
+#pragma unroll
+    for (int e = 0; e < HB; ++e) {
+      const int f = threadIdx.x + SW_THREADS * e;
+      if (f < n4) st4(dst + 4 * f, hbv[e]);
+    }
+    if (tail)
+      for (int f = threadIdx.x + SW_THREADS * HB; f < n4; f += SW_THREADS) st4(dst + 4 * f, ld4(src + 4 * (size_t)f));
+  } else {
+    f32x4 t_of0[2], t_of1[1], t_pe0[2], t_pe1[1], t_cl0[2], t_la0[2], t_cl1[1], t_la1[1];
+    const bool pe0_small = 8 * K4 <= 2 * SW_THREADS;
+    if (obs) {
+      stage_wT_load<2>(t_of0, d_w + O.of0w, 64, 32, 64);
+      stage_wT_load<1>(t_of1, d_w + O.of1w, 32, 32, 32);
+    }
+    if (pe0_small) stage_wT_load<2>(t_pe0, d_w + O.pe0w, K4, 32, K4);
+    stage_wT_load<1>(t_pe1, d_w + O.pe1w, 32, 32, 32);
+    stage_wT_load<2>(t_cl0, d_w + O.cl0w, 64, 32, 64);
+    stage_wT_load<2>(t_la0, d_w + O.la0w, 64, 32, 64);
+    stage_wT_load<1>(t_cl1, d_w + O.cl1w, 32, 1, 32);
+    stage_wT_load<1>(t_la1, d_w + O.la1w, 32, 2, 32);
+    between();
+    if (obs) {
+      stage_wT_store<2>(t_of0, base + L.of0T, LD32, 32, 64);
+      stage_wT_store<1>(t_of1, base + L.of1T, LD32, 32, 32);
+    }
+    if (pe0_small) stage_wT_store<2>(t_pe0, base + L.pe0T, LD32, 32, K4);
+    else stage_wT(base + L.pe0T, LD32, L.kp, d_w + O.pe0w, K4, 32, K4);
+    stage_wT_store<1>(t_pe1, base + L.pe1T, LD32, 32, 32);
+    stage_wT_store<2>(t_cl0, base + L.cl0T, LD32, 32, 64);
+    stage_wT_store<2>(t_la0, base + L.la0T, LD32, 32, 64);
+    stage_wT_store<1>(t_cl1, base + L.cl1T, LD16, 1, 32);
+    stage_wT_store<1>(t_la1, base + L.la1T, LD16, 2, 32);
+  }
+}
+
+// The h tile [2][16][SW_HLD] the observation LSTM starts from: h0 = 0 (train.py:296-297) in slot 0 or, when its rows are
+// already saved (obs_pre: the decode launch ran it), h_T from them in the slot the LSTM would have left it in
+__device__ __forceinline__ void disc_seed_h(float* hbuf, bool obs_pre, const float* act, int To, int B, int b) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4, u0 = wave * 16;
+  if (!obs_pre) st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
+  else st4(&hbuf[(To & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], ld4(act + ((size_t)(To - 1) * B + b) * 384 + 320 + u0 + 4 * lg));
+}
+
+// The observation fc on waves 0, 1 (train.py:300-301): o1 = lrelu(of0 h_T + b) into the o1 tile (and, given o1s, the
+// agent's save row), a barrier, obsv_code = of1 o1 + b into columns 0:32 of nboth `both` tiles.  hw: the forward head
+// matrices and bias slots at their HeadLds offsets.  Returns o1 (waves 0, 1).
+__device__ __forceinline__ f32x4 disc_obs_fc(const float* hw, const HeadLds& L, const float* hlast, float* o1, float* o1s, bool live,
+                                             float* both, int nboth) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4, m0 = 16 * wave;
+  f32x4 o1r = {0.f, 0.f, 0.f, 0.f};
+  if (wave < 2) {
+    f32x4 acc = ld4(hw + L.bias + 0 * 32 + m0 + 4 * lg);
+    acc = tile_mm_rt(hw + L.of0 + (m0 + ln) * LD64 + 4 * lg, hlast + ln * SW_HLD + 4 * lg, 4, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
+    o1r = acc;
+    st4(o1 + ln * LD32 + m0 + 4 * lg, acc);
+    if (o1s && live) st4(o1s + m0 + 4 * lg, acc);
+  }
+  sw_barrier();
+  if (wave < 2) {
+    f32x4 acc = ld4(hw + L.bias + 1 * 32 + m0 + 4 * lg);
+    acc = tile_mm_rt(hw + L.of1 + (m0 + ln) * LD32 + 4 * lg, o1 + ln * LD32 + 4 * lg, 2, acc);
+    for (int k = 0; k < nboth; ++k) st4(both + k * 16 * LD64 + ln * LD64 + m0 + 4 * lg, acc);
+  }
+  return o1r;
+}
+
+// The observation backward tail (disc_bwd, disc_update): do1 = (of1^T docode) * lrelu'(o1) on waves 0, 1 into the do1
+// tile and the agent's delta row do1s, a barrier, then dh_T = of0^T do1 (rows u0 .. of every wave): the BPTT's first dh.
+__device__ __forceinline__ f32x4 disc_obs_bwd_tail(const float* of1T, const float* of0T, const float* docode, float* do1, f32x4 o1,
+                                                   float* do1s, bool live) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  if (wave < 2) {
+    const int m0 = 16 * wave;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = tile_mm_rt(of1T + (m0 + ln) * LD32 + 4 * lg, docode + ln * LD32 + 4 * lg, 2, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu_grad(o1[r], acc[r]);
+    st4(do1 + ln * LD32 + m0 + 4 * lg, acc);
+    if (live) st4(do1s + m0 + 4 * lg, acc);
+  }
+  sw_barrier();
+  return tile_mm_rt(of0T + (16 * wave + ln) * LD32 + 4 * lg, do1 + ln * LD32 + 4 * lg, 2, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
 // The forward pass of D for the 16-agent tile(s) of workgroup index `bx` of `nbx` (see disc_fwd_kernel, sw_disc.hip); with
 // `fuse` (generator phase, one branch) also the backward of the prediction heads down to d(loss)/d(pred).  A device function
 // so that another launch can run the generator-phase pass of a tile in front of its own work (dec_rollout_bwd_kernel<true>,
@@ -185,22 +370,11 @@ __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, co
   // its transposed weight images and delta buffers follow the forward carve in LDS, the activations never leave LDS
   const HeadLdsB LB = head_lds_b(Tp, L.total);
   SW_DSTAMP_INIT;
-  // The prediction rows of this workgroup's branches (inputs of the pred_encoder heads) are requested NOW: staged
-  // where the heads start they cost one global round trip per branch behind the observation LSTM.  Unconditional loads
-  // from clamped addresses (4 per thread and branch cover the [16][4 Tp + pad] tile up to Tp = 12; longer horizons
-  // load in place).
+  // The prediction rows of this workgroup's branches (inputs of the pred_encoder heads) are requested NOW (longer
+  // horizons than Tp = 12 load in place)
   const bool x_pre = 16 * L.ldp <= 4 * SW_THREADS;
   float xpre[2][4];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    const float* pk = (k_lo + kk == 0 || nb == 1) ? pred_a : pred_b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = min((int)threadIdx.x + SW_THREADS * e, 16 * L.ldp - 1);
-      const int a = i / L.ldp, cc = i - a * L.ldp;
-      xpre[kk][e] = pk[(size_t)min(a0 + a, B - 1) * K4 + min(cc, K4 - 1)];
-    }
-  }
+  disc_xpre_load(xpre, (k_lo == 0 || nb == 1) ? pred_a : pred_b, nb == 1 ? pred_a : pred_b, a0, B, K4, L.ldp);
   // (generator phase) the label target and the agent's latent code for the loss gradients formed behind the heads
   const float* ztop = fuse ? gl.z + (size_t)b * SW_Z : d_w;
   const float ftg = (fuse ? gl.targets + gl.t0 : d_w)[0], fz0 = ztop[0], fz1 = ztop[1];
@@ -210,100 +384,17 @@ __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, co
   }
   const bool obs_pre = save_lstm == 2;   // LSTM rows already in dsave (sw_dec_rollout_fwd_aux ran the observation LSTM)
   LstmW W;
-  if (!obs_pre) {   // global loads in flight during the LDS staging
-    if (dimg) {     // operand-layout image: a wave's load = 1 KB of consecutive memory
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) W.whh[g][j] = ld4(dimg + swdimg::OP_WHH + ((((size_t)4 * g + wave) * 4 + j) * 64 + lane) * 4);
-    } else {
-      lstm_load_whh(W, d_w + O.whh, u0, ln, lg);
-    }
-    // input matrix W_ih [256][4] and b_ih + b_hh straight into their registers (no LDS staging, nothing behind a barrier)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      W.wx[g] = d_w[O.wih + (g * 64 + u0 + ln) * 4 + lg];
-      W.bias[g] = ld4(d_w + O.bih + g * 64 + u0 + 4 * lg) + ld4(d_w + O.bhh + g * 64 + u0 + 4 * lg);
-    }
-  }
+  if (!obs_pre) disc_obs_operands(W, d_w, O, dimg);
   if (w_snap)   // deepcopy(D) of train.py:499: the weights this pass runs with, a few floats per thread
     for (int i = bx * SW_THREADS + threadIdx.x; i < O.n; i += nbx * SW_THREADS) w_snap[i] = d_w[i];
-  // ---- stage head weights / biases: ALL global loads first, then the LDS stores (one L2 round trip for the eight
-  //      matrices instead of one each) --------------------------------------------------------------------------
-  {
-    f32x4 s_of0[3], s_of1[2], s_pe0[2], s_pe1[2], s_cl0[3], s_la0[3], s_cl1[1], s_la1[1];
-    const bool pe0_small = 32 * (L.ldp >> 2) <= 2 * SW_THREADS;   // 4 Tp <= 48: the usual horizons
-    stage_w_load<3>(s_of0, LD64, 32, d_w + O.of0w, 64, 32, 64);
-    stage_w_load<2>(s_of1, LD32, 32, d_w + O.of1w, 32, 32, 32);
-    if (pe0_small) stage_w_load<2>(s_pe0, L.ldp, 32, d_w + O.pe0w, K4, 32, K4);
-    stage_w_load<2>(s_pe1, LD32, 32, d_w + O.pe1w, 32, 32, 32);
-    stage_w_load<3>(s_cl0, LD64, 32, d_w + O.cl0w, 64, 32, 64);
-    stage_w_load<3>(s_la0, LD64, 32, d_w + O.la0w, 64, 32, 64);
-    stage_w_load<1>(s_cl1, LD32, 16, d_w + O.cl1w, 32, 1, 32);
-    stage_w_load<1>(s_la1, LD32, 16, d_w + O.la1w, 32, 2, 32);
-    stage_w_store<3>(s_of0, smem + L.of0, LD64, 32);
-    stage_w_store<2>(s_of1, smem + L.of1, LD32, 32);
-    if (pe0_small) stage_w_store<2>(s_pe0, smem + L.pe0, L.ldp, 32);
-    else stage_w(smem + L.pe0, L.ldp, 32, d_w + O.pe0w, K4, 32, K4);
-    stage_w_store<2>(s_pe1, smem + L.pe1, LD32, 32);
-    stage_w_store<3>(s_cl0, smem + L.cl0, LD64, 32);
-    stage_w_store<3>(s_la0, smem + L.la0, LD64, 32);
-    stage_w_store<1>(s_cl1, smem + L.cl1, LD32, 16);
-    stage_w_store<1>(s_la1, smem + L.la1, LD32, 16);
-  }
-  {   // the eight bias vectors: ONE unconditional load per thread from a selected offset (eight loads under lane branches
-      // compiled to eight serial round trips, each behind an s_waitcnt vmcnt(0))
-    const int i = threadIdx.x;  // 256 = 8 x 32
-    const int q = i >> 5, k = i & 31;
-    const int boff = q == 0 ? O.of0b : q == 1 ? O.of1b : q == 2 ? O.pe0b : q == 3 ? O.pe1b : q == 4 ? O.cl0b
-                     : q == 5 ? O.la0b : q == 6 ? O.cl1b : O.la1b;
-    const int lim = q < 6 ? 32 : (q == 6 ? 1 : 2);
-    const float v = d_w[boff + min(k, lim - 1)];
-    smem[L.bias + i] = k < lim ? v : 0.f;
-  }
-  if (fuse && dimg) {
-    // transposed head images of the fused backward (swdimg::HEADT): the block pe0T .. la1T is one contiguous float4
-    // copy, zero padding included - requested behind every other load of the prologue, so nothing waits for it alone
-    constexpr int HB = 12;
-    const int n4 = (LB.dlab - LB.pe0T) >> 2;
-    const float* src = dimg + swdimg::HEADT + (LB.pe0T - LB.of0T);
-    f32x4 hbv[HB];
-#pragma unroll
-    for (int e = 0; e < HB; ++e) hbv[e] = ld4(src + 4 * (size_t)min((int)threadIdx.x + SW_THREADS * e, n4 - 1));
-#pragma unroll
-    for (int e = 0; e < HB; ++e) {
-      const int f = threadIdx.x + SW_THREADS * e;
-      if (f < n4) st4(smem + LB.pe0T + 4 * f, hbv[e]);
-    }
-    for (int f = threadIdx.x + SW_THREADS * HB; f < n4; f += SW_THREADS) st4(smem + LB.pe0T + 4 * f, ld4(src + 4 * (size_t)f));
-  }
+  disc_stage_heads(smem, L, d_w, O, K4, 32 * (L.ldp >> 2) <= 2 * SW_THREADS);
+  // transposed head images of the fused backward: the image block is requested behind every other load of the prologue,
+  // so nothing waits for it alone; from the weights they are staged behind the barrier below (block zero-filled above)
+  if (fuse && dimg) disc_stage_headT(smem, LB, false, d_w, O, K4, dimg, true);
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};  // h0 = c0 = 0 (train.py:296-297)
-  if (!obs_pre) {
-    st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], h);
-  } else {   // h_T of the tile from the saved rows
-    st4(&hbuf[(To & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg],
-        ld4(dsave + ds.act + ((size_t)(To - 1) * B + b) * 384 + 320 + u0 + 4 * lg));
-  }
+  disc_seed_h(hbuf, obs_pre, dsave + ds.act, To, B, b);
   sw_barrier();
-  if (fuse && dimg) {
-    // (copied from the image block in front of the barrier above)
-  } else if (fuse) {
-    f32x4 t_pe0[2], t_pe1[1], t_cl0[2], t_la0[2], t_cl1[1], t_la1[1];
-    const bool pe0_small = 8 * K4 <= 2 * SW_THREADS;
-    if (pe0_small) stage_wT_load<2>(t_pe0, d_w + O.pe0w, K4, 32, K4);
-    stage_wT_load<1>(t_pe1, d_w + O.pe1w, 32, 32, 32);
-    stage_wT_load<2>(t_cl0, d_w + O.cl0w, 64, 32, 64);
-    stage_wT_load<2>(t_la0, d_w + O.la0w, 64, 32, 64);
-    stage_wT_load<1>(t_cl1, d_w + O.cl1w, 32, 1, 32);
-    stage_wT_load<1>(t_la1, d_w + O.la1w, 32, 2, 32);
-    if (pe0_small) stage_wT_store<2>(t_pe0, smem + LB.pe0T, LD32, 32, K4);
-    else stage_wT(smem + LB.pe0T, LD32, LB.kp, d_w + O.pe0w, K4, 32, K4);
-    stage_wT_store<1>(t_pe1, smem + LB.pe1T, LD32, 32, 32);
-    stage_wT_store<2>(t_cl0, smem + LB.cl0T, LD32, 32, 64);
-    stage_wT_store<2>(t_la0, smem + LB.la0T, LD32, 32, 64);
-    stage_wT_store<1>(t_cl1, smem + LB.cl1T, LD16, 1, 32);
-    stage_wT_store<1>(t_la1, smem + LB.la1T, LD16, 2, 32);
-  }
+  if (fuse && !dimg) disc_stage_headT(smem, LB, false, d_w, O, K4, nullptr, true);
 
   // ---- LSTM over the observation (4-d state formed on the fly, train.py:130-133): lstm_obs_loop, chosen once ----
   SW_DSTAMP(0);
@@ -323,43 +414,17 @@ __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, co
   SW_DSTAMP(1);
 
   // ---- heads ------------------------------------------------------------------------------------
-  // pred branches into LDS rows [16][ldp] (zero padded), saved flat for the pe0 weight gradient
-  // phase A: o1 = lrelu(of0 h + b)  (waves 0,1)
-  if (wave < 2) {
-    int m0 = 16 * wave;
-    f32x4 acc = ld4(smem + L.bias + 0 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(smem + L.of0 + (m0 + ln) * LD64 + 4 * lg, hlast + ln * SW_HLD + 4 * lg, 4, acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
-    st4(smem + L.o1 + ln * LD32 + m0 + 4 * lg, acc);
-    if (dsave && live && save_obs) st4(dsave + ds.o1 + (size_t)b * 32 + m0 + 4 * lg, acc);
-  }
-  sw_barrier();
-  // phase B: obsv_code = of1 o1 + b  -> both[:, 0:32]  (waves 0,1)
-  if (wave < 2) {
-    int m0 = 16 * wave;
-    f32x4 acc = ld4(smem + L.bias + 1 * 32 + m0 + 4 * lg);
-    acc = tile_mm_rt(smem + L.of1 + (m0 + ln) * LD32 + 4 * lg, smem + L.o1 + ln * LD32 + 4 * lg, 2, acc);
-    st4(smem + L.both + ln * LD64 + m0 + 4 * lg, acc);
-  }
+  // observation fc (waves 0, 1) -> both[:, 0:32]
+  disc_obs_fc(smem, L, hlast, smem + L.o1, dsave && save_obs ? dsave + ds.o1 + (size_t)b * 32 : nullptr, live, smem + L.both, 1);
   SW_DSTAMP(2);
+  // pred branches into LDS rows [16][ldp] (zero padded), saved flat for the pe0 weight gradient
   for (int k = k_lo; k < k_hi; ++k) {
     const float* pred = k == 0 ? pred_a : pred_b;
     float* label = k == 0 ? label_a : label_b;
     float* code = k == 0 ? code_a : code_b;
     sw_barrier();
     if (x_pre) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int i = threadIdx.x + SW_THREADS * e;
-        if (i < 16 * L.ldp) {
-          const int a = i / L.ldp, cc = i - a * L.ldp;
-          const int bb = min(a0 + a, B - 1);
-          const float v = cc < K4 ? (k == k_lo ? xpre[0][e] : xpre[1][e]) : 0.f;
-          smem[L.x + i] = v;
-          if (dsave && cc < K4 && a0 + a < B) dsave[ds.px + ((size_t)k * B + bb) * K4 + cc] = v;
-        }
-      }
+      disc_xpre_put(xpre, k != k_lo, smem + L.x, dsave ? dsave + ds.px + (size_t)k * B * K4 : nullptr, a0, B, K4, L.ldp);
     } else {
       for (int i = threadIdx.x; i < 16 * L.ldp; i += blockDim.x) {
         int a = i / L.ldp, cc = i - a * L.ldp;

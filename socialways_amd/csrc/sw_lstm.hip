@@ -3,7 +3,6 @@
 // registers, h exchanged through a double-buffered 4 KB LDS tile: one barrier per time step.
 #include "../../include/socialways_hip.h"
 #include "sw_lstm_dev.h"
-#include <type_traits>
 #include <cstdlib>
 
 // XMODE 0: x = positions [B][T][2] (4-d state formed on the fly); 1: x = [B][T][4].  ACT / Y / X4S: which per-step
@@ -197,41 +196,23 @@ __global__ __launch_bounds__(512) void enc_lstm_fwd8_kernel(
   *reinterpret_cast<float2*>(cT + (size_t)b * 64 + ub) = c;
 }
 
-// BPTT.  Per step: elementwise gate gradients (lane-local) -> dgates row to HBM (for the
-// deferred weight-gradient GEMM) and to LDS -> dh_{t-1} = W_hh^T dgates on the matrix cores.
-// The saved rows of step t-1 are fetched while step t computes.  As in enc_lstm_fwd the loop body has NO conditional
-// memory operation (DY is a template parameter, the two boundary steps are peeled, padding lanes of the last tile are
-// replicas of agent B-1 and store the same values): with conditional loads / stores the compiler waited for
-// everything in flight (s_waitcnt vmcnt(0)) behind every step's barrier - the dgates rows just stored included.
+// BPTT over the saved rows (lstm_bptt_rows, sw_lstm_dev.h): dy (DY, a template parameter: no conditional load in the
+// loop) joins dh in front of every step's cell backward.
 template <bool DY>
 __global__ __launch_bounds__(SW_THREADS) void enc_lstm_bwd_kernel(
     const float* __restrict__ whh, const float* __restrict__ act, const float* __restrict__ c0,
     const float* __restrict__ dhT, const float* __restrict__ dcT, const float* __restrict__ dy, int B, int T,
     int t0, float* __restrict__ dgates, float* __restrict__ dh0, float* __restrict__ dc0, const float* __restrict__ gimg,
     const float* __restrict__ aux_src, float* __restrict__ aux_dst, const float* __restrict__ aux_mask, long long aux_n) {
-  // Workgroups beyond the agent tiles run an auxiliary masked copy dst[i] = mask[i] > 0 ? src[i] : dst[i] (the training
-  // step's D.load(backup), train.py:541-542, when the decode BPTT launch - its usual place - also reads D's weights)
-  {
-    const int tiles = (B + SW_TILE - 1) / SW_TILE;
-    if ((int)blockIdx.x >= tiles) {
-      const long long stride = (long long)(gridDim.x - tiles) * SW_THREADS;
-      for (long long i = (long long)(blockIdx.x - tiles) * SW_THREADS + threadIdx.x; i < aux_n; i += stride)
-        if (aux_mask[i] > 0.f) aux_dst[i] = aux_src[i];
-      return;
-    }
-  }
+  // (the masked copy of the training step's D.load(backup) when the decode BPTT launch - its usual place - reads D's weights)
+  if (sw_aux_masked_copy(B, aux_src, aux_dst, aux_mask, aux_n)) return;
   __shared__ __attribute__((aligned(16))) float dgbuf[2][SW_TILE * SW_GLD];
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int u0 = wave * 16;
   const int a0 = blockIdx.x * SW_TILE;
   const int b = min(a0 + ln, B - 1);
   LstmWT W;
-  if (gimg) {   // operand-layout image of W_hh^T of this step (swimg::OP_WHHT): 16 contiguous 1 KB loads per wave
-#pragma unroll
-    for (int j = 0; j < 16; ++j) W.whhT[j] = ld4(gimg + swimg::OP_WHHT + (((size_t)wave * 16 + j) * 64 + lane) * 4);
-  } else {
-    lstm_load_wT(W, whh, u0, ln, lg);
-  }
+  lstm_load_whhT(W, gimg, swimg::OP_WHHT, whh, wave, lane);   // W_hh^T of this step (operand-layout image when there is one)
   // optional inputs are read unconditionally from a selected address (a load under a branch costs the exact vmcnt
   // bookkeeping of everything behind it) and zeroed afterwards
   const float* act_b = act + ((size_t)t0 * B + b) * 384 + u0 + 4 * lg;
@@ -239,53 +220,16 @@ __global__ __launch_bounds__(SW_THREADS) void enc_lstm_bwd_kernel(
   f32x4 dc = ld4(dcT ? dcT + (size_t)b * 64 + u0 + 4 * lg : act_b);
   if (!dhT) dh = f32x4{0.f, 0.f, 0.f, 0.f};
   if (!dcT) dc = f32x4{0.f, 0.f, 0.f, 0.f};
-  const size_t tstep = (size_t)B * 384;
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  // rows of local step t; has_prev: row t-1 exists in `act` (always for t >= 1; for t = 0 only if t0 > 0)
-  auto load_row = [&](int t, f32x4 g[4], f32x4& ct_, f32x4& cp_, auto has_prev) {
-    const float* row = act_b + (size_t)t * tstep;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) g[q] = ld4(row + q * 64);
-    ct_ = ld4(row + 256);
-    if constexpr (decltype(has_prev)::value) {
-      cp_ = ld4(row - tstep + 256);
-    } else {   // the sequence start: c_{-1} = c0 or zero (or the row in front of t0)
-      cp_ = ld4(t0 > 0 ? row - tstep + 256 : c0 ? c0 + (size_t)b * 64 + u0 + 4 * lg : row + 256);
-      if (t0 <= 0 && !c0) cp_ = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  f32x4 gate[4], ct, cprev;
-  if (T > 1) load_row(T - 1, gate, ct, cprev, T_{});
-  else load_row(0, gate, ct, cprev, F_{});
+  // c_{-1} of the sequence start: the row in front of t0, c0 or zero
+  const float* cstart = t0 > 0 ? act_b - (size_t)B * 384 + 256 : c0 ? c0 + (size_t)b * 64 + u0 + 4 * lg : nullptr;
+  const LstmBptt S{act_b, cstart, dgbuf[0], dgates + ((size_t)t0 * B + a0) * 256, nullptr, a0, B};
   const float* dyp = DY ? dy + ((size_t)b * T + T - 1) * 64 + u0 + 4 * lg : nullptr;
-  auto step = [&](int t, auto pf, auto pp) {   // pf: prefetch the rows of step t-1 (pp: which have a predecessor row)
-    f32x4 dgate[4];
+  lstm_bptt_rows<true>(W, S, T, dh, dc, [&](f32x4& d) {
     if constexpr (DY) {
-      dh += ld4(dyp);
+      d += ld4(dyp);
       dyp -= 64;
     }
-    lstm_cell_bwd(gate, ct, cprev, dh, dc, dgate);
-    // ROLLING prefetch (round 6, as in dec_rollout_bwd_kernel): the rows of step t - 1 are requested right behind the last
-    // use of the rows of step t, into the same registers (no second row set)
-    if constexpr (decltype(pf)::value) {
-      load_row(t - 1, gate, ct, cprev, pp);
-      asm volatile("" ::: "memory");
-    }
-    float* dgl = &dgbuf[t & 1][ln * SW_GLD + u0 + 4 * lg];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
-    sw_barrier();
-    lstm_store_dgates_tile(dgbuf[t & 1], dgates + ((size_t)(t0 + t) * B + a0) * 256, nullptr, a0, B, wave, lane);
-    dh = lstm_dh_prev(W, &dgbuf[t & 1][ln * SW_GLD + 4 * lg]);
-    if constexpr (decltype(pf)::value) {
-      // the prefetched rows are not touched before the matrix products above have been issued
-      asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
-    }
-  };
-  for (int t = T - 1; t >= 2; --t) step(t, T_{}, T_{});
-  if (T > 1) step(1, T_{}, F_{});
-  step(0, F_{}, F_{});
+  });
   if (dh0) st4(dh0 + (size_t)b * 64 + u0 + 4 * lg, dh);
   if (dc0) st4(dc0 + (size_t)b * 64 + u0 + 4 * lg, dc);
 }

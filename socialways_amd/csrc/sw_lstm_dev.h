@@ -248,6 +248,103 @@ __device__ __forceinline__ f32x4 lstm_dh_prev(const LstmWT& W, const float* dgro
   }
   return a0 + a1;
 }
+// W_hh^T from the operand-layout image at img + off (16 contiguous 1 KB loads per wave) or, without an image, from the
+// weights Whh (Whh == nullptr: the image is always there)
+__device__ __forceinline__ void lstm_load_whhT(LstmWT& W, const float* img, int off, const float* Whh, int wave, int lane) {
+  if (img || !Whh) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) W.whhT[j] = ld4(img + off + (((size_t)wave * 16 + j) * 64 + lane) * 4);
+  } else {
+    lstm_load_wT(W, Whh, wave * 16, lane & 15, lane >> 4);
+  }
+}
+
+// ---- the BPTT over saved rows (enc_lstm_bwd_kernel, disc_bwd_kernel, disc_update_kernel) ------------------------------
+// Per step: elementwise gate gradients (lane-local) -> dgates tile in LDS -> dgates rows to HBM (for the deferred
+// weight-gradient GEMM) -> dh_{t-1} = W_hh^T dgates on the matrix cores.  As in enc_lstm_fwd the loop body has NO
+// conditional memory operation (the boundary steps are peeled, padding lanes of the last tile are replicas of agent B-1
+// and store the same values or go to `trash`): with conditional loads / stores the compiler waited for everything in
+// flight (s_waitcnt vmcnt(0)) behind every step's barrier - the dgates rows just stored included.
+struct LstmBptt {
+  const float* act;     // saved row of the lane's agent at step 0 (column u0 + 4 lg); one step = B * 384 floats
+  const float* cstart;  // c_{-1} of the sequence start (same column), or nullptr: zero
+  float* tile;          // [2][16][SW_GLD] dgates tiles in LDS
+  float* dg;            // dgates row of agent a0 at step 0; one step = B * 256 floats
+  float* trash;         // see lstm_store_dgates_tile
+  int a0, B;
+};
+struct SwNop {
+  template <class... A> __device__ void operator()(A&&...) const {}
+};
+// The rows of step t: gates and c_t, c_{t-1} from the row in front (HP) or, at the sequence start, from cstart (one load
+// from a selected address, zeroed afterwards: a load under a branch costs the exact vmcnt bookkeeping of everything behind it)
+template <bool HP>
+__device__ __forceinline__ void lstm_bptt_load(const LstmBptt& S, int t, f32x4 (&gate)[4], f32x4& ct, f32x4& cprev) {
+  const size_t tstep = (size_t)S.B * 384;
+  const float* row = S.act + (size_t)t * tstep;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) gate[q] = ld4(row + q * 64);
+  ct = ld4(row + 256);
+  if constexpr (HP) {
+    cprev = ld4(row - tstep + 256);
+  } else {
+    cprev = ld4(S.cstart ? S.cstart : row + 256);
+    if (!S.cstart) cprev = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+// One step t on the rows in gate / ct / cprev, dh and dc carried.  PF: the rows of step t-1 (HP: with a row in front) are
+// requested right behind the last use of step t's, into the same registers (rolling prefetch, DESIGN section 3 "one
+// register set"); NX: dh_{t-1} is formed.  stamp(k): the phase stamps 12-14 of disc_bwd (SW_PHASE_STAMPS).
+template <bool PF, bool HP, bool NX, class Stamp = SwNop>
+__device__ __forceinline__ void lstm_bptt_step(const LstmWT& W, const LstmBptt& S, int t, f32x4 (&gate)[4], f32x4& ct,
+                                               f32x4& cprev, f32x4& dh, f32x4& dc, Stamp stamp = {}) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  f32x4 dgate[4];
+  lstm_cell_bwd(gate, ct, cprev, dh, dc, dgate);
+  if constexpr (PF) {
+    lstm_bptt_load<HP>(S, t - 1, gate, ct, cprev);
+    asm volatile("" ::: "memory");
+  }
+  float* tile = S.tile + (t & 1) * 16 * SW_GLD;
+  float* dgl = tile + ln * SW_GLD + 16 * wave + 4 * lg;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
+  stamp(12);
+  sw_barrier();
+  lstm_store_dgates_tile(tile, S.dg + (size_t)t * S.B * 256, S.trash, S.a0, S.B, wave, lane);
+  stamp(13);
+  if constexpr (NX) dh = lstm_dh_prev(W, tile + ln * SW_GLD + 4 * lg);
+  // the prefetched rows are not touched before the matrix products above have been issued
+  if constexpr (PF) asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev));
+  stamp(14);
+}
+// The whole BPTT of T steps: the first rows, steps T-1 .. 2 in a loop, the peeled steps 1 and 0 (DH0: dh of step 0 too, for
+// dh0).  pre(dh) runs in front of every step's cell backward.  Every load issued so far (the first rows, W_hh^T) is waited
+// for in front of the loop: a loop header with an unknown count of pending operations gets s_waitcnt vmcnt(0), which every
+// step then pays as the round trip of the dgates rows it has just stored.  stamp(k): called at points 10-14 (the phase
+// stamps of disc_bwd; disc_update puts its barrier at 10, behind the request of the first rows).
+template <bool DH0, class Pre = SwNop, class Stamp = SwNop>
+__device__ __forceinline__ void lstm_bptt_rows(LstmWT& W, const LstmBptt& S, int T, f32x4& dh, f32x4& dc, Pre pre = {},
+                                               Stamp stamp = {}) {
+  f32x4 gate[4], ct, cprev;
+  if (T > 1) lstm_bptt_load<true>(S, T - 1, gate, ct, cprev);
+  else lstm_bptt_load<false>(S, 0, gate, ct, cprev);
+  stamp(10);
+  pre(dh);
+  asm volatile("" : "+v"(gate[0]), "+v"(gate[1]), "+v"(gate[2]), "+v"(gate[3]), "+v"(ct), "+v"(cprev), "+v"(dh));
+#pragma unroll
+  for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(W.whhT[j]));
+  for (int t = T - 1; t >= 2; --t) {
+    lstm_bptt_step<true, true, true>(W, S, t, gate, ct, cprev, dh, dc, stamp);
+    pre(dh);
+  }
+  if (T > 1) {
+    lstm_bptt_step<true, false, true>(W, S, 1, gate, ct, cprev, dh, dc, stamp);
+    pre(dh);
+  }
+  lstm_bptt_step<false, false, DH0>(W, S, 0, gate, ct, cprev, dh, dc, stamp);
+  stamp(11);
+}
 
 // x4[agent][t][comp] for the observation rule of get_traj_4d (train.py:131-133): v_0 := v_1, as two raw loads
 // (a, q) with x = a - (comp >= 2 ? q : 0).  Branch-free and split from the arithmetic on purpose: memory operations

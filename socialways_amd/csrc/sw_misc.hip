@@ -14,6 +14,17 @@ void sw_set_error(const char* what, hipError_t e) {
 }
 extern "C" const char* sw_last_error(void) { return g_err; }
 
+int sw_set_lds(const void* fn, int bytes, int& have) {
+  if (have >= bytes) return SW_OK;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    sw_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+    return SW_EHIP;
+  }
+  have = bytes;
+  return SW_OK;
+}
+
 // ---- per-kernel timing with HIP events on the launch stream (SW_LAUNCH, sw_common.h) ----------------------------------
 #include <string>
 #include <vector>

@@ -1418,15 +1418,6 @@ extern "C" int sw_pair_features(const float* x4_last, const int* scene_off, cons
   return SW_OK;
 }
 
-static int set_lds(const void* fn, int bytes) {
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    sw_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    return SW_EHIP;
-  }
-  return SW_OK;
-}
-
 // ---- module-level API helpers (dense layouts of the reference, small batches) -----------------
 // AttentionPooling.forward on a dense (B,B,64) embedding tensor: only in-scene blocks are read.
 __global__ __launch_bounds__(SW_THREADS) void attention_pool_dense_kernel(
@@ -1594,11 +1585,8 @@ extern "C" int sw_embed_features_bwd(const float* feat, long long R, const float
                                      float* dfeat, void* stream) {
   if (!feat || !emb_w || !dout || !rows || R < 0) return SW_EARG;
   if (R == 0) return SW_OK;
-  static bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds((const void*)embed_features_bwd_kernel, soc_lds(16).fwd_total * 4)) return rc;
-    attr = true;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)embed_features_bwd_kernel, soc_lds(16).fwd_total * 4, have)) return rc;
   SW_LAUNCH(embed_features_bwd_kernel, dim3((unsigned)((R + 63) / 64)), dim3(SW_THREADS), soc_lds(16).fwd_total * 4,
                      (hipStream_t)stream, feat, R, emb_w, dout, rows, dfeat);
   SW_CHECK_LAUNCH("embed_features_bwd_kernel");
@@ -1609,11 +1597,8 @@ extern "C" int sw_attention_pool_dense(const float* f, const float* h, const int
                                        const float* att_w, float* S_out, void* stream) {
   if (!f || !h || !scene_off || !att_w || !S_out || S < 0 || B < 0) return SW_EARG;
   if (S == 0 || B == 0) return SW_OK;
-  static bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds((const void*)attention_pool_dense_kernel, soc_lds(SW_AMAX).fwd_total * 4)) return rc;
-    attr = true;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)attention_pool_dense_kernel, soc_lds(SW_AMAX).fwd_total * 4, have)) return rc;
   SW_LAUNCH(attention_pool_dense_kernel, dim3(S), dim3(SW_THREADS), soc_lds(SW_AMAX).fwd_total * 4,
                      (hipStream_t)stream, f, h, scene_off, B, att_w, S_out, SW_AMAX);
   SW_CHECK_LAUNCH("attention_pool_dense_kernel");
@@ -1623,11 +1608,8 @@ extern "C" int sw_attention_pool_dense(const float* f, const float* h, const int
 extern "C" int sw_embed_features(const float* feat, long long R, const float* emb_w, float* out, void* stream) {
   if (!feat || !emb_w || !out || R < 0) return SW_EARG;
   if (R == 0) return SW_OK;
-  static bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds((const void*)embed_features_kernel, soc_lds(16).fwd_total * 4)) return rc;
-    attr = true;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)embed_features_kernel, soc_lds(16).fwd_total * 4, have)) return rc;
   SW_LAUNCH(embed_features_kernel, dim3((unsigned)((R + 63) / 64)), dim3(SW_THREADS), soc_lds(16).fwd_total * 4,
                      (hipStream_t)stream, feat, R, emb_w, out);
   SW_CHECK_LAUNCH("embed_features_kernel");
@@ -1653,11 +1635,8 @@ extern "C" int sw_social_pool_fwd_aux(const float* obsv, int To, const float* h,
   if (NB > 0 && (!big_blocks || !wh_ws)) return SW_EARG;
   if (Amax > SW_AMAX) return SW_ESHAPE;      // Amax = largest scene handled by the one-workgroup-per-scene kernel
   if (S == 0 || B == 0) return SW_OK;
-  static bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds((const void*)social_pool_fwd_kernel, soc_lds(SW_AMAX).fwd_total * 4)) return rc;
-    attr = true;
-  }
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)social_pool_fwd_kernel, soc_lds(SW_AMAX).fwd_total * 4, have)) return rc;
   const int a16 = Amax < 16 ? 16 : ((Amax + 15) & ~15);
   int extra = aux_n > 0 ? (int)((aux_n / 4 + SW_THREADS - 1) / SW_THREADS) : 0;
   if (extra > 64) extra = 64;
@@ -1703,20 +1682,15 @@ extern "C" int sw_social_pool_bwd(const float* obsv, int To, const float* h, con
   const int lds_big = (soc_lds(16).fwd_total + 64 * SW_SOC_W2LD + 64 * SW_SOC_W1LD + 4 * SW_SOC_SCR + 16 * SW_BIG_PROW + SW_SOC_WT) * 4;
   static_assert(SW_SOC_WT + 4 * SW_SOC_SCR >= SW_SOC_PART, "epilogue staging area");
   static_assert(64 * SW_SOC_W2LD + 64 * SW_SOC_W1LD + 4 * SW_SOC_SCR >= SW_SOC_PART, "epilogue staging area (row-block kernel)");
-  static bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds((const void*)social_pool_bwd_kernel, (soc_lds(SW_AMAX).bwd_total + extra) * 4)) return rc;
-    if (int rc = set_lds((const void*)social_big_bwd_kernel, lds_big)) return rc;
-    attr = true;
-  }
+  static int have_scene = 0;
+  if (int rc = sw_set_lds((const void*)social_pool_bwd_kernel, (soc_lds(SW_AMAX).bwd_total + extra) * 4, have_scene)) return rc;
+  static int have_big = 0;
+  if (int rc = sw_set_lds((const void*)social_big_bwd_kernel, lds_big, have_big)) return rc;
   // pair_ws: [B][64] dWh rows, then the pair rows
   float* dwh_rows = pair_ws;
   if (NB == 0 && P < (long long)S * SW_SOC_FUSE_MIN_PAIRS) {   // small scenes only: per-pair rows + deferred GEMM
-    static bool attr2 = false;
-    if (!attr2) {
-      if (int rc = set_lds((const void*)social_pool_bwd_rows_kernel, soc_lds(SW_AMAX).bwd_total * 4)) return rc;
-      attr2 = true;
-    }
+    static int have_rows = 0;
+    if (int rc = sw_set_lds((const void*)social_pool_bwd_rows_kernel, soc_lds(SW_AMAX).bwd_total * 4, have_rows)) return rc;
     float* wh_rows = pair_ws + (size_t)B * 64;
     float* q_rows = pair_ws + (size_t)B * 128;
     float* sd_rows = pair_ws + (size_t)B * 192;

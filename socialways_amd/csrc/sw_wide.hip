@@ -1481,12 +1481,8 @@ static int wide_heads_launch(const long long* p, int backward, void* stream) {
   const int lds = backward ? lds_b : lds_f;
   static int have_f = 0, have_b = 0;
   int& have = backward ? have_b : have_f;
-  if (have < lds) {
-    hipError_t e = hipFuncSetAttribute(backward ? (const void*)wide_disc_heads_bwd_kernel : (const void*)wide_disc_heads_fwd_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { sw_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e); return SW_EHIP; }
-    have = lds;
-  }
+  if (int rc = sw_set_lds(backward ? (const void*)wide_disc_heads_bwd_kernel : (const void*)wide_disc_heads_fwd_kernel, lds, have))
+    return rc;
   const dim3 grid((A.B + 15) / 16), block(256);
   if (backward) SW_LAUNCH(wide_disc_heads_bwd_kernel, grid, block, lds, (hipStream_t)stream, A);
   else SW_LAUNCH(wide_disc_heads_fwd_kernel, grid, block, lds, (hipStream_t)stream, A);
