@@ -269,8 +269,8 @@ int sw_disc_bwd_gan_adam(const float* d_w, const float* dsave, const float* cons
  *      save_lstm = obs_pre ? 2 : 1; w_snapshot) + sw_disc_bwd_gan[_adam](no d/dpred) fused per 16-agent tile - forward,
  *      LSGAN / InfoGAN loss gradients, backward, the two branches' heads side by side on the two wave pairs - followed by
  *      the weight-gradient GEMM (and the Adam update when adam_w = d_w).  Same buffers, same rows, same arguments as the
- *      two calls.  For the shapes that leave CUs idle: sw_disc_update_supported() says whether this (d_w with registered
- *      images - sw_disc_images -, B <= 2048, Tp <= 12) can run; SW_ESHAPE otherwise.                                 */
+ *      two calls.  sw_disc_update_supported() says whether this (d_w with registered images - sw_disc_images -,
+ *      Tp <= 12; any B) can run; SW_ESHAPE otherwise.                                                                */
 int sw_disc_update_supported(const float* d_w, int B, int To, int Tp);
 int sw_disc_update(const float* obsv /*[B,To,2]*/, int To, const float* const* pred4 /*2 x [B,Tp,4]*/, const float* d_w, int B,
                    int Tp, float* const* label, float* const* code, float* dsave, int obs_pre, float* w_snapshot /*or NULL*/,
@@ -281,7 +281,13 @@ int sw_disc_update(const float* obsv /*[B,To,2]*/, int To, const float* const* p
 /* ---- generator phase in one launch (train.py:510-523, 538): D forward on (obsv, pred_hat) fused with the backward of
  *      its prediction heads: dpred4 = d(g_loss)/d(pred_hat) with g_loss = mse(label, targets[t_idx]) +
  *      w mse(code, z[:, :2]) expressed through g_label = 1/B_global, g_code = w/(2 B_global).  No saves; label / code /
- *      loss_part ([ceil(B/16)][3]: columns 0, 1 = per-tile sums of the squared errors) are optional outputs.   */
+ *      loss_part ([ceil(B/16)][3]: columns 0, 1 = per-tile sums of the squared errors) are optional outputs.
+ *      LDS per workgroup: the forward carve behind the observation LSTM's tiles plus the backward's transposed head
+ *      images and delta tiles, 4 352 B more per 4 steps of Tp: 146 688 B at Tp = 12, 159 744 B at Tp = 24, 164 096 B at
+ *      Tp = 25 - over the 163 840 B limit, so this and sw_dec_rollout_bwd_dfuse return SW_ESHAPE for Tp = 25 .. 64.
+ *      sw_disc_dpred_supported(Tp) says whether they run; otherwise sw_disc_fwd + sw_disc_bwd_gan (nb = 1, dpred4) give
+ *      the same d/dpred and loss sums.                                                                              */
+int sw_disc_dpred_supported(int Tp);
 int sw_disc_dpred(const float* obsv, int To, int x_mode, const float* pred4 /*[B,Tp,4]*/, const float* d_w, int B, int Tp,
                   const float* targets, int t_idx, const float* z /*[B,32]*/, float g_label, float g_code,
                   float* dpred4 /*[B,Tp,4]*/, float* label /*[B,1] or NULL*/, float* code /*[B,2] or NULL*/,
@@ -423,7 +429,8 @@ int sw_enc_lstm_bwd_aux(const float* enc_w, const float* act, const float* c0, c
 /* sw_disc_dpred (generator phase of train.py:510-523: D forward on obsv [B,To,2] / pred4 + the backward of its prediction
  * heads, loss gradients formed in the kernel, per-tile loss sums to loss_part) and sw_dec_rollout_bwd in ONE launch: the
  * pass is tile-local and the decode BPTT of the same 16 agents is its only consumer.  dpred4 [B,Tp,4] = scratch that
- * receives d(g_loss)/d(pred4).  Same results as the two calls, bit for bit.                                           */
+ * receives d(g_loss)/d(pred4).  Same results as the two calls, bit for bit.  The LDS of the D pass is sw_disc_dpred's
+ * (159 744 B at Tp = 24, 164 096 B at Tp = 25): SW_ESHAPE wherever sw_disc_dpred_supported(Tp) is 0.                  */
 int sw_dec_rollout_bwd_dfuse(const float* obsv, const float* pred4, const float* d_w, const float* targets, int t_idx,
                              const float* z, float g_label, float g_code, float* loss_part, float* dpred4, const float* enc_w,
                              const float* dec_w, const float* gsave, int B, int To, int Tp, float* gdelta, float* dhT, float* dcT,

@@ -1066,7 +1066,7 @@ extern "C" int sw_dec_rollout_bwd_dfuse(const float* obsv, const float* pred4, c
     return SW_EARG;
   if (Tp > 64) return SW_ESHAPE;
   if (B == 0) return SW_OK;
-  int lds = head_lds_b(Tp, head_lds(Tp, 2 * 16 * SW_HLD + 1280).total).total * 4;
+  int lds = disc_dpred_lds(Tp);
   if (lds < BwdLds::total * 4) lds = BwdLds::total * 4;
   if (lds > 163840) return SW_ESHAPE;
   static int have = 0;

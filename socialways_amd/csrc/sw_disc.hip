@@ -543,7 +543,7 @@ extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float*
     return SW_EARG;
   if (Tp > 64) return SW_ESHAPE;
   if (B == 0) return SW_OK;
-  const int lds = head_lds_b(Tp, head_lds(Tp, 2 * 16 * SW_HLD + 1280).total).total * 4;
+  const int lds = disc_dpred_lds(Tp);
   if (lds > 163840) return SW_ESHAPE;
   if (int rc = sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds)) return rc;
   DiscLoss gl{targets, z, t_idx, t_idx, g_label, g_code, 1, loss_part};
@@ -554,6 +554,8 @@ extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float*
   SW_CHECK_LAUNCH("disc_fwd_kernel");
   return SW_OK;
 }
+
+extern "C" int sw_disc_dpred_supported(int Tp) { return Tp >= 1 && Tp <= 64 && disc_dpred_lds(Tp) <= 163840 ? 1 : 0; }
 
 // the weight-gradient problems of a discriminator pass over its saved / delta rows (dW = delta^T act per layer)
 static int disc_wgrad_problems(WgBatch& wb, const float* dsave, float* ddelta, int nb, int B, int To, int Tp, float* d_d_w) {

@@ -141,6 +141,14 @@ __host__ __device__ inline HeadLdsB head_lds_b(int Tp, int base) {
 // delta tiles were (all dead once the heads are done, one barrier earlier): 33 KB less LDS, and with <= 256 VGPRs two
 // workgroups fit a CU - what dense crowds (8+ tiles per CU) need to hide one tile's latencies behind another's work
 static_assert(7040 + 36 * 16 + 320 + 320 + 576 + 576 + 1088 + 576 >= 2 * 16 * SW_GLD, "dgates tiles fit the dead region");
+
+// Bytes of LDS of the generator-phase pass (sw_disc_dpred, sw_dec_rollout_bwd_dfuse): the forward carve behind the
+// observation LSTM's tiles, the transposed head images and delta tiles of the backward behind that.  It grows by
+// 4 352 B per 4 steps of Tp (the pe0 / pe0T rows) and once more by the prediction tile of its own (Tp > 32): 146 688 B at
+// Tp = 12, 159 744 B at 24, 164 096 B at 25 - above the 160 KB of one workgroup from Tp = 25 on (sw_disc_dpred_supported).
+__host__ __device__ inline int disc_dpred_lds(int Tp) {
+  return head_lds_b(Tp, head_lds(Tp, 2 * 16 * SW_HLD + 1280).total).total * 4;
+}
 }  // namespace
 
 // GAN mode of the backward kernel: dlabel_* / dcode_* then carry the forward OUTPUTS (label, code) and

@@ -416,6 +416,12 @@ def disc_dpred(d_w, obsv, pred_hat, targets, t_idx, z, g_label, g_code, loss_par
     return dpred
 
 
+def disc_dpred_supported(Tp):
+    """Does the generator-phase D pass (disc_dpred, gen_backward(dfuse=...)) fit one workgroup's LDS at this horizon?
+    (Tp <= 24; longer horizons form d/dpred with disc_forward + disc_backward_gan.)"""
+    return bool(L.load().sw_disc_dpred_supported(int(Tp)))
+
+
 def disc_backward_gan(d_w, ctx, labels, codes, targets, t_idx, z, g_label, g_code, d_d_w=None, want_dpred=(), ws=None,
                       tag="d", loss_part=None, adam=None):
     """disc_backward with the LSGAN / InfoGAN loss gradients formed inside the kernel from the forward

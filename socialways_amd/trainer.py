@@ -725,10 +725,20 @@ class SocialWaysTrainer:
         # D forward on the prediction + backward of its heads down to d(g_loss)/d(pred_hat), one launch, nothing saved
         # ... which is tile-local and feeds only the decode BPTT of the same tile: in the plain step (no extra terms on
         # d/d(pred_hat)) it runs inside that launch (ops.gen_backward(dfuse=...): one graph node less)
+        # ... when its LDS fits one workgroup (Tp <= 24); longer horizons run the forward with saves and the backward of
+        # the heads as two launches (same d/d(pred_hat), same loss sums)
         dfuse = None
-        if (ops.DFUSE and KV == 1 and not self.use_l2_loss and self.use_variety_loss is False and obsv.shape[2] == 2):
+        one_pass = ops.disc_dpred_supported(Tp)
+        if (ops.DFUSE and one_pass and KV == 1 and not self.use_l2_loss and self.use_variety_loss is False
+                and obsv.shape[2] == 2):
             dfuse = (D._flat, pred_hat, targets, 1, noise, g_label, g_code, out[U + 1])
-        dpred = None if dfuse else ops.disc_dpred(D._flat, obsv, pred_hat, targets, 1, noise, g_label, g_code, loss_part=out[U + 1])
+        dpred = None
+        if dfuse is None and one_pass:
+            dpred = ops.disc_dpred(D._flat, obsv, pred_hat, targets, 1, noise, g_label, g_code, loss_part=out[U + 1])
+        elif dfuse is None:
+            labels, codes, dctx = ops.disc_forward(D._flat, obsv, [pred_hat], save=True, ws=ws, save_lstm=0)
+            dpred = ops.disc_backward_gan(D._flat, dctx, labels, codes, targets, (1,), noise, g_label, g_code, None, (True,),
+                                          ws=ws, loss_part=out[U + 1])[0]
         if self.use_l2_loss:                                                 # train.py:525-526
             L.call("sw_l2_grad", L.ptr(pred_hat), L.ptr(pred), B, Tp, 0, B, self.loss_l2_w / (Bg * Tp), L.ptr(dpred), L.stream())
         if self.use_variety_loss is True:                                    # train.py:527-536 as written

@@ -1,0 +1,493 @@
+"""The discriminator kernels (sw_disc_fwd / _bwd / _bwd_gan / _update / _dpred) and the generator-phase D pass inside the
+decode BPTT (sw_dec_rollout_bwd_dfuse) against a FLOAT64 reference: the oracle's modules (oracle/sw_oracle.py) cast to
+double, loaded from the HIP modules' state_dicts, fed the exact fp32 inputs.  Other tests compare one launch form with
+another bit for bit; both sides of those share the device code of sw_disc_dev.h / sw_lstm_dev.h, so only a reference
+catches a shared phase that is wrong.
+
+LeakyReLU / ReLU kinks: where a pre-activation lies within fp32 rounding of 0 the fp32 kernel and the float64 reference
+may take different branches.  Every case draws its inputs from the first seed of SEEDS whose float64
+forward keeps all of them at least MARGIN away from 0; the seed and margin are in every assertion message.
+
+Tolerances (float64 reference): outputs elementwise rtol OUT_RT + atol OUT_AT * max|ref|; gradients per tensor
+max|err| <= GRAD_REL * max|ref|."""
+import contextlib
+
+import numpy as np
+import pytest
+import torch
+
+import sw_oracle as O
+from _util import assert_close
+
+pytestmark = pytest.mark.gpu
+
+SEEDS = (1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233)
+MARGIN = 2e-7
+OUT_RT, OUT_AT = 1e-5, 1e-6
+GRAD_REL = 2e-5
+W_INFO = 0.5
+TARGETS = (0.03, 0.96)
+
+_observed = {}      # group -> {"out": max err / max|ref|, "grad": ...}: printed at the end of the module (pytest -s)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    for group, v in sorted(_observed.items()):
+        print("observed max error  %-12s outputs %.2e  gradients %.2e" % (group, v.get("out", 0.0), v.get("grad", 0.0)))
+
+
+def _note(group, kind, ratio):
+    g = _observed.setdefault(group, {})
+    g[kind] = max(g.get(kind, 0.0), ratio)
+
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+@contextlib.contextmanager
+def _f64():
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)     # the oracle builds its zero states with the default dtype
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(old)
+
+
+def _close_out(got, ref, what, group, tag):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    scale = max(float(ref.abs().max()), 1e-30)
+    _note(group, "out", float((got - ref).abs().max()) / scale)
+    assert_close(got.numpy(), ref.numpy(), OUT_RT, OUT_AT * scale, "%s (%s)" % (what, tag))
+
+
+def _close_grad(got, ref, what, group, tag, rel=GRAD_REL):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert bool(torch.isfinite(got).all()), "%s: non-finite entries (%s)" % (what, tag)
+    scale = float(ref.abs().max())
+    err = float((got - ref).abs().max())
+    if scale > 0:
+        _note(group, "grad", err / scale)
+    assert err <= rel * scale, "%s: max|err| %.3e > %.1e * max|ref| %.3e (%s)" % (what, err, rel, scale, tag)
+
+
+def _d64(D):
+    """The float64 reference discriminator with the HIP module's weights."""
+    with _f64():
+        ref = O.Discriminator(D.n_next, 64, 2)
+    ref.load_state_dict({k: v.detach().cpu().double() for k, v in D.state_dict().items()})
+    return ref
+
+
+@contextlib.contextmanager
+def _kink_margin(*mods):
+    """Yields a list that ends up holding the smallest |input| of every (Leaky)ReLU run inside the block."""
+    seen, hooks = [], []
+    for mod in mods:
+        for m in mod.modules():
+            if isinstance(m, (torch.nn.LeakyReLU, torch.nn.ReLU)):
+                hooks.append(m.register_forward_hook(lambda m_, inp, out: seen.append(float(inp[0].detach().abs().min()))
+                                                     if inp[0].numel() else None))
+    box = [float("inf")]
+    try:
+        yield box
+    finally:
+        for h in hooks:
+            h.remove()
+        box[0] = min(seen, default=float("inf"))
+
+
+def _forward64(Dref, obsv, x_mode, preds):
+    """float64 D forward of every branch -> ([label], [code], preds64 (leaves that collect d/dpred), kink margin)."""
+    o = obsv.detach().cpu().double()
+    o4 = O.get_traj_4d(o, []) if x_mode == 0 else o
+    p64 = [p.detach().cpu().double().requires_grad_() for p in preds]
+    with _f64(), _kink_margin(Dref) as margin:
+        outs = [Dref(o4, p) for p in p64]
+    return [l for l, _ in outs], [c for _, c in outs], p64, margin[0]
+
+
+def _pick(make, margin_of):
+    """First seed of SEEDS whose float64 forward keeps every kink input above MARGIN: (seed, inputs, margin)."""
+    best = (None, 0.0)
+    for seed in SEEDS:
+        inp = make(seed)
+        m = margin_of(inp)
+        if m > MARGIN:
+            return seed, inp, m
+        best = max(best, (seed, m), key=lambda t: t[1])
+    raise AssertionError("no seed of %s keeps the kink inputs above %.1e (best: seed %s, %.2e)" % (SEEDS, MARGIN, *best))
+
+
+def _disc(Tp, wseed=0):
+    import socialways_amd as sw
+    torch.manual_seed(1000 + Tp + wseed)
+    return sw.Discriminator(Tp, 64, 2, device=_dev())
+
+
+@contextlib.contextmanager
+def _images(D, on=True):
+    """Register D's weight images (sw_disc_images) as the training step does; dropped on exit."""
+    from socialways_amd import _lib as L
+    if not on:
+        yield
+        return
+    lib = L.load()
+    Tp = D.n_next
+    tab_h = np.empty((D._flat.numel(), 2), dtype=np.int32)
+    assert lib.sw_disc_image_table(Tp, tab_h.ctypes.data) == 0
+    tab = torch.from_numpy(tab_h).to(_dev())
+    img = torch.zeros(lib.sw_disc_image_floats(Tp), device=_dev())
+    L.call("sw_disc_images", L.ptr(D._flat), L.ptr(img), L.ptr(tab), Tp, L.stream())
+    try:
+        yield
+    finally:
+        L.call("sw_disc_images", None, None, None, 0, None)
+
+
+def _disc_inputs(B, To, Tp, nb, x_mode):
+    def make(seed):
+        g = torch.Generator().manual_seed(seed)
+        if x_mode == 0:
+            obsv = (torch.randn(B, To, 2, generator=g) * 0.1).cumsum(1)
+        else:
+            obsv = torch.randn(B, To, 4, generator=g) * 0.2
+        preds = [torch.randn(B, Tp, 4, generator=g) * 0.2 for _ in range(nb)]
+        z = torch.rand(B, 32, generator=g)
+        cot = [(torch.randn(B, 1, generator=g), torch.randn(B, 2, generator=g)) for _ in range(nb)]
+        return obsv, preds, z, cot
+    return make
+
+
+def _grads_of(D, dflat):
+    return dict(zip([k for k, _ in D.named_parameters()], D.split_grad(dflat)))
+
+
+def _check_dgrads(D, dflat, Dref, group, tag):
+    got = _grads_of(D, dflat)
+    for k, q in Dref.named_parameters():
+        _close_grad(got[k], q.grad, "dD/d%s" % k, group, tag)
+
+
+def _tile_sums(v, B):
+    """(B,) per-agent values -> (ceil(B/16),) per-tile sums."""
+    tiles = (B + 15) // 16
+    pad = torch.zeros(tiles * 16, dtype=v.dtype)
+    pad[:B] = v
+    return pad.view(tiles, 16).sum(1)
+
+
+# ---- a. sw_disc_fwd ------------------------------------------------------------------------------------------------
+# (nb, x_mode, To, Tp, B, images): both branch counts, both input forms, To 1..12, Tp 1..64 across the staging branches
+# (4 Tp <= 48 / 16 ldp <= 32 LD64), ragged last tiles, the split form (nb 2, <= 128 tiles) next to the unsplit one (129)
+@pytest.mark.parametrize("nb,x_mode,To,Tp,B,images", [
+    (2, 0, 8, 12, 17, True), (1, 1, 1, 1, 1, False), (2, 1, 2, 4, 15, False), (2, 0, 3, 5, 2048, True),
+    (2, 0, 5, 13, 2049, True), (1, 0, 12, 32, 17, True), (2, 0, 8, 33, 33, False), (2, 1, 5, 64, 17, True),
+    (2, 0, 2, 64, 2048, False), (2, 0, 8, 12, 2049, False)])
+def test_disc_forward_against_float64(nb, x_mode, To, Tp, B, images):
+    from socialways_amd import ops
+    D = _disc(Tp)
+    Dref = _d64(D)
+    seed, (obsv, preds, z, cot), margin = _pick(_disc_inputs(B, To, Tp, nb, x_mode),
+                                                lambda inp: _forward64(Dref, inp[0], x_mode, inp[1])[3])
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    with _images(D, images):
+        labels, codes, _ = ops.disc_forward(D._flat, obsv.to(_dev()), [p.to(_dev()) for p in preds], save=False)
+        torch.cuda.synchronize()
+    rl, rc, _, _ = _forward64(Dref, obsv, x_mode, preds)
+    for k in range(nb):
+        _close_out(labels[k], rl[k], "label[%d]" % k, "fwd", tag)
+        _close_out(codes[k], rc[k], "code[%d]" % k, "fwd", tag)
+
+
+# ---- b. sw_disc_bwd: random cotangents, every weight gradient and each branch's d/dpred --------------------------------
+@pytest.mark.parametrize("nb,x_mode,To,Tp,B,images", [
+    (2, 1, 1, 5, 17, False), (2, 0, 2, 12, 33, True), (1, 0, 3, 13, 15, False), (2, 0, 5, 32, 17, True),
+    (2, 1, 12, 33, 17, False), (2, 0, 8, 64, 2049, True), (1, 1, 8, 1, 1, False), (2, 0, 3, 4, 2048, True)])
+def test_disc_backward_against_float64(nb, x_mode, To, Tp, B, images):
+    from socialways_amd import ops
+    D = _disc(Tp)
+    Dref = _d64(D)
+    seed, (obsv, preds, z, cot), margin = _pick(_disc_inputs(B, To, Tp, nb, x_mode),
+                                                lambda inp: _forward64(Dref, inp[0], x_mode, inp[1])[3])
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    dev = _dev()
+    ws = ops.Workspaces(dev)
+    dflat = torch.full_like(D._flat, float("nan"))         # every gradient must be written
+    with _images(D, images):
+        _, _, ctx = ops.disc_forward(D._flat, obsv.to(dev), [p.to(dev) for p in preds], save=True, ws=ws)
+        dpreds = ops.disc_backward(D._flat, ctx, [c[0].to(dev) for c in cot], [c[1].to(dev) for c in cot], dflat,
+                                   [True] * nb, ws=ws)
+        torch.cuda.synchronize()
+    rl, rc, p64, _ = _forward64(Dref, obsv, x_mode, preds)
+    sum((l * c[0].double()).sum() + (cc * c[1].double()).sum() for l, cc, c in zip(rl, rc, cot)).backward()
+    _check_dgrads(D, dflat, Dref, "bwd", tag)
+    for k in range(nb):
+        _close_out(dpreds[k], p64[k].grad, "d/dpred[%d]" % k, "bwd", tag)
+
+
+def _gan_ref(Dref, obsv, preds, z, w_info):
+    """float64 of the D update loss (train.py:482-495): mse(fake, t0) + mse(real, t1) + w_info mse(code_fake, z[:, :2])."""
+    rl, rc, p64, margin = _forward64(Dref, obsv, 0, preds)
+    z2 = z.double()[:, :2]
+    t0, t1 = (float(torch.tensor(t, dtype=torch.float32)) for t in TARGETS)
+    loss = ((rl[0] - t0) ** 2).mean() + ((rl[1] - t1) ** 2).mean() + w_info * ((rc[0] - z2) ** 2).mean()
+    loss.backward()
+    parts = torch.stack([((rl[0] - t0) ** 2).sum(1), ((rc[0] - z2) ** 2).sum(1), ((rl[1] - t1) ** 2).sum(1)], 1).detach()
+    return rl, rc, p64, parts
+
+
+def _check_parts(part, parts64, B, cols, group, tag):
+    for c in cols:
+        _close_out(part[:, c], _tile_sums(parts64[:, c], B), "loss_part column %d" % c, group, tag)
+
+
+# ---- c. sw_disc_bwd_gan: the loss gradients formed in the kernel ---------------------------------------------------------
+@pytest.mark.parametrize("To,Tp,B,info", [(8, 12, 17, True), (3, 5, 2049, False), (2, 33, 40, True), (12, 1, 1, True),
+                                          (5, 64, 33, False)])
+def test_disc_backward_gan_against_float64(To, Tp, B, info):
+    from socialways_amd import ops
+    D = _disc(Tp)
+    Dref = _d64(D)
+    seed, (obsv, preds, z, _), margin = _pick(_disc_inputs(B, To, Tp, 2, 0),
+                                              lambda inp: _forward64(Dref, inp[0], 0, inp[1])[3])
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    dev = _dev()
+    ws = ops.Workspaces(dev)
+    w_info = W_INFO if info else 0.0
+    targets = torch.tensor(TARGETS, device=dev)
+    dflat = torch.full_like(D._flat, float("nan"))
+    part = torch.full(((B + 15) // 16, 3), float("nan"), device=dev)
+    with _images(D):
+        labels, codes, ctx = ops.disc_forward(D._flat, obsv.to(dev), [p.to(dev) for p in preds], save=True, ws=ws)
+        dpreds = ops.disc_backward_gan(D._flat, ctx, labels, codes, targets, (0, 1), z.to(dev), 1.0 / B, w_info / (2.0 * B),
+                                       dflat, (True, True), ws=ws, loss_part=part)
+        torch.cuda.synchronize()
+    rl, rc, p64, parts64 = _gan_ref(Dref, obsv, preds, z, w_info)
+    _check_dgrads(D, dflat, Dref, "bwd_gan", tag)
+    _close_out(dpreds[0], p64[0].grad, "d/dpred (fake)", "bwd_gan", tag)
+    _close_out(dpreds[1], p64[1].grad, "d/dpred (real)", "bwd_gan", tag)
+    _check_parts(part.cpu(), parts64, B, (0, 1, 2), "bwd_gan", tag)
+
+
+# ---- d. sw_disc_update: one update pass in one launch against float64 ----------------------------------------------------
+# obs_pre: the observation-LSTM rows are already in the save buffer, put there by the production producer (the decode
+# launch, gen_forward(d_obs=...), up to D_OBS_MAX_TILES tiles) or by a plain disc_forward(save_lstm=1)
+@pytest.mark.parametrize("To,Tp,B,pre", [(2, 1, 17, None), (3, 4, 1, "disc"), (5, 12, 2048, "gen"), (8, 5, 2049, "disc"),
+                                         (12, 12, 17, None), (8, 12, 40, None), (3, 5, 100, "gen"), (5, 4, 2049, None)])
+def test_disc_update_against_float64(To, Tp, B, pre):
+    import socialways_amd as sw
+    from socialways_amd import ops
+    dev = _dev()
+    D = _disc(Tp)
+    Dref = _d64(D)
+    G = None
+    if pre == "gen":
+        torch.manual_seed(7)
+        G = sw.Generator(use_social=True, device=dev)
+        G.unify()
+        s0 = np.arange(0, B, 8)
+        scenes = ops.SceneIndex.get(np.stack([s0, np.minimum(s0 + 8, B)], 1), B, dev)
+
+    def make(seed):
+        obsv, preds, z, cot = _disc_inputs(B, To, Tp, 2, 0)(seed)
+        if G is not None:        # the fake branch is the rollout the producer launch computed
+            ws = ops.Workspaces(dev)
+            pre_buf = ops.d_obs_buffer(ws, B, To, Tp)
+            assert pre_buf is not None
+            ph, _ = ops.gen_forward(G.encoder._flat, G.feature_embedder._flat, G.attention._flat, G.decoder._flat,
+                                    obsv.to(dev), z.to(dev), scenes, Tp, True, save=True, ws=ws,
+                                    d_obs=(D._flat, pre_buf))
+            preds = [ph.cpu(), preds[1]]
+            return obsv, preds, z, ws
+        return obsv, preds, z, None
+
+    seed, (obsv, preds, z, ws), margin = _pick(make, lambda inp: _forward64(Dref, inp[0], 0, inp[1])[3])
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    ws = ws or ops.Workspaces(dev)
+    targets = torch.tensor(TARGETS, device=dev)
+    w0 = D._flat.clone()
+    dflat = torch.full_like(D._flat, float("nan"))
+    part = torch.full(((B + 15) // 16, 3), float("nan"), device=dev)
+    snap = torch.full_like(D._flat, float("nan"))
+    o, p = obsv.to(dev), [x.to(dev) for x in preds]
+    with _images(D):
+        assert ops.disc_update_supported(D._flat, B, To, Tp)
+        if pre == "gen":      # the rows the decode launch left: re-run it on the chosen inputs (same buffer)
+            ph, _ = ops.gen_forward(G.encoder._flat, G.feature_embedder._flat, G.attention._flat, G.decoder._flat, o, z.to(dev),
+                                    scenes, Tp, True, save=True, ws=ws,
+                                    d_obs=(D._flat, ops.d_obs_buffer(ws, B, To, Tp)))
+            assert torch.equal(ph, p[0])
+        elif pre == "disc":
+            ops.disc_forward(D._flat, o, p, save=True, ws=ws, save_lstm=1)
+        labels, codes = ops.disc_update(D._flat, o, p, targets, (0, 1), z.to(dev), 1.0 / B, W_INFO / (2.0 * B), dflat, ws,
+                                        obs_pre=pre is not None, w_snapshot=snap, loss_part=part)
+        torch.cuda.synchronize()
+    assert torch.equal(snap, w0), "w_snapshot differs from the pre-pass weights"
+    assert torch.equal(D._flat, w0), "adam=None: the weights must not move"
+    rl, rc, p64, parts64 = _gan_ref(Dref, obsv, preds, z, W_INFO)
+    for k in range(2):
+        _close_out(labels[k], rl[k], "label[%d]" % k, "update", tag)
+        _close_out(codes[k], rc[k], "code[%d]" % k, "update", tag)
+    _check_dgrads(D, dflat, Dref, "update", tag)
+    _check_parts(part.cpu(), parts64, B, (0, 1, 2), "update", tag)
+
+
+# ---- e. generator-phase d/dpred: sw_disc_dpred where its LDS fits (Tp <= 24), else the two launches the trainer uses ----
+def _dpred_ref(Dref, obsv, pred, z):
+    """float64 of the D part of g_loss (train.py:512-523): mse(label, t1) + w_info mse(code, z[:, :2])."""
+    rl, rc, p64, margin = _forward64(Dref, obsv, 0, [pred])
+    z2 = z.double()[:, :2]
+    t1 = float(torch.tensor(TARGETS[1], dtype=torch.float32))
+    (((rl[0] - t1) ** 2).mean() + W_INFO * ((rc[0] - z2) ** 2).mean()).backward()
+    parts = torch.stack([((rl[0] - t1) ** 2).sum(1), ((rc[0] - z2) ** 2).sum(1)], 1).detach()
+    return p64[0].grad, parts
+
+
+@pytest.mark.parametrize("Tp,B", [(1, 17), (5, 1), (12, 40), (13, 33), (20, 15), (24, 17), (25, 17), (32, 40), (64, 33)])
+def test_generator_phase_dpred_against_float64(Tp, B):
+    from socialways_amd import ops
+    dev = _dev()
+    To = 8
+    assert ops.disc_dpred_supported(Tp) == (Tp <= 24)     # LDS of the one-launch pass (include/socialways_hip.h)
+    D = _disc(Tp)
+    Dref = _d64(D)
+    seed, (obsv, preds, z, _), margin = _pick(_disc_inputs(B, To, Tp, 1, 0),
+                                              lambda inp: _forward64(Dref, inp[0], 0, inp[1])[3])
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    targets = torch.tensor(TARGETS, device=dev)
+    part = torch.full(((B + 15) // 16, 3), float("nan"), device=dev)
+    o, p, zd = obsv.to(dev), preds[0].to(dev), z.to(dev)
+    with _images(D):
+        if ops.disc_dpred_supported(Tp):
+            dpred = ops.disc_dpred(D._flat, o, p, targets, 1, zd, 1.0 / B, W_INFO / (2.0 * B), loss_part=part)
+        else:
+            with pytest.raises(Exception, match="unsupported shape"):
+                ops.disc_dpred(D._flat, o, p, targets, 1, zd, 1.0 / B, W_INFO / (2.0 * B))
+            ws = ops.Workspaces(dev)
+            labels, codes, ctx = ops.disc_forward(D._flat, o, [p], save=True, ws=ws, save_lstm=0)
+            dpred = ops.disc_backward_gan(D._flat, ctx, labels, codes, targets, (1,), zd, 1.0 / B, W_INFO / (2.0 * B), None,
+                                          (True,), ws=ws, loss_part=part)[0]
+        torch.cuda.synchronize()
+    dp64, parts64 = _dpred_ref(Dref, obsv, preds[0], z)
+    _close_out(dpred, dp64, "d/dpred", "dpred", tag)
+    _check_parts(part.cpu(), parts64, B, (0, 1), "dpred", tag)
+
+
+# ---- f. the generator phase inside the decode BPTT launch (gen_backward(dfuse=...)) ----------------------------------------
+def _gen_pair(Tp):
+    import socialways_amd as sw
+    torch.manual_seed(2000 + Tp)
+    G = sw.Generator(use_social=True, device=_dev())
+    G.unify()
+    D = _disc(Tp)
+    with _f64():
+        orc = O.SocialWaysOracle(Tp, use_social=True)
+    for name in ("encoder", "feature_embedder", "attention", "decoder"):
+        m = getattr(orc, name).double()
+        m.load_state_dict({k: v.detach().cpu().double() for k, v in getattr(G, name).state_dict().items()})
+    orc.D = _d64(D)
+    return G, D, orc
+
+
+def _gen_ref(orc, obsv, z, sb, Tp):
+    """float64 rollout and g_loss = mse(label, t1) + w_info mse(code, z[:, :2]) through the oracle's predict() and D."""
+    for name in ("encoder", "feature_embedder", "attention", "decoder"):
+        getattr(orc, name).zero_grad()
+    o, z64 = obsv.double(), z.double()
+    with _f64(), _kink_margin(orc.encoder, orc.feature_embedder, orc.attention, orc.decoder, orc.D) as margin:
+        pred = orc.predict(o, z64, Tp, sb)
+        label, code = orc.D(O.get_traj_4d(o, []), pred)
+    t1 = float(torch.tensor(TARGETS[1], dtype=torch.float32))
+    ((label - t1) ** 2).mean().add(W_INFO * ((code - z64[:, :2]) ** 2).mean()).backward()
+    parts = torch.stack([((label - t1) ** 2).sum(1), ((code - z64[:, :2]) ** 2).sum(1)], 1).detach()
+    return pred.detach(), parts, margin[0]
+
+
+@pytest.mark.parametrize("To,Tp,sizes", [(8, 12, [1, 5, 16, 2, 13, 1, 40, 7]), (2, 1, [3, 1, 1, 9]),
+                                         (5, 20, [8] * 20 + [1, 3]), (5, 5, [2] * 30 + [1]), (2, 12, [1, 1, 1])])
+def test_generator_phase_inside_the_decode_bptt_against_float64(To, Tp, sizes):
+    from socialways_amd import ops
+    dev = _dev()
+    B = int(np.sum(sizes))
+    sb = np.stack([np.cumsum([0] + sizes[:-1]), np.cumsum(sizes)], 1).astype(np.int64)
+    G, D, orc = _gen_pair(Tp)
+
+    def make(seed):
+        g = torch.Generator().manual_seed(seed)
+        return (torch.randn(B, To, 2, generator=g) * 0.1).cumsum(1), torch.rand(B, 32, generator=g)
+
+    seed, (obsv, z), margin = _pick(make, lambda inp: _gen_margin(orc, inp[0], inp[1], sb, Tp))
+    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    enc, emb, att, dec = G.encoder, G.feature_embedder, G.attention, G.decoder
+    grads = {m: torch.full_like(m._flat, float("nan")) for m in (enc, emb, att, dec)}
+    targets = torch.tensor(TARGETS, device=dev)
+    part = torch.full(((B + 15) // 16, 3), float("nan"), device=dev)
+    ws = ops.Workspaces(dev)
+    o, zd = obsv.to(dev), z.to(dev)
+    with _images(D):
+        pred_hat, ctx = ops.gen_forward(enc._flat, emb._flat, att._flat, dec._flat, o, zd, ops.SceneIndex.get(sb, B, dev), Tp,
+                                        True, save=True, ws=ws)
+        ops.gen_backward(enc._flat, emb._flat, att._flat, dec._flat, ctx, None, grads[enc], grads[emb], grads[att], grads[dec],
+                         ws=ws, dfuse=(D._flat, pred_hat, targets, 1, zd, 1.0 / B, W_INFO / (2.0 * B), part))
+        torch.cuda.synchronize()
+    pred64, parts64, _ = _gen_ref(orc, obsv, z, sb, Tp)
+    _close_out(pred_hat, pred64, "rollout", "gen_phase", tag)
+    _check_parts(part.cpu(), parts64, B, (0, 1), "gen_phase", tag)
+    for name, m in (("encoder", enc), ("feature_embedder", emb), ("attention", att), ("decoder", dec)):
+        got = dict(zip([k for k, _ in m.named_parameters()], m.split_grad(grads[m])))
+        for k, q in getattr(orc, name).named_parameters():
+            ref = torch.zeros_like(q) if q.grad is None else q.grad      # single-agent scenes only: no social pairs
+            _close_grad(got[k], ref, "dG/d%s.%s" % (name, k), "gen_phase", tag)
+
+
+def _gen_margin(orc, obsv, z, sb, Tp):
+    o, z64 = obsv.double(), z.double()
+    with torch.no_grad(), _f64(), _kink_margin(orc.encoder, orc.feature_embedder, orc.attention, orc.decoder, orc.D) as m:
+        pred = orc.predict(o, z64, Tp, sb)
+        orc.D(O.get_traj_4d(o, []), pred)
+    return m[0]
+
+
+# ---- §2: long horizons through the trainer (the one-launch generator-phase pass does not fit from Tp = 25 on) -----------
+@pytest.mark.parametrize("Tp", [24, 25, 32, 64])
+def test_training_step_at_long_horizons_matches_oracle(Tp):
+    """One whole step at Tp = 24 (the last horizon the fused generator-phase pass fits) and 25 / 32 / 64 (forward with
+    saves + backward of the heads instead): the 9 MSE terms, ADE/FDE sums, the rollout, every generator gradient and the
+    weights after Adam against the fp32 oracle (as tests/test_gpu_edge_and_fullsize.py::test_step_matches_oracle_on_odd_shapes)."""
+    import socialways_amd as sw
+    from socialways_amd import ops
+    To, sizes = 8, [5, 1, 9, 4]
+    t = sw.synth_tracks(len(sizes) + 2, sizes + [2, 2], To, Tp, seed=11)
+    data = sw.SceneDataset(t["obsvs"], t["preds"], t["batches"], device="cuda:0")
+    torch.manual_seed(0)
+    tr = sw.SocialWaysTrainer(Tp, use_social=True, device="cuda:0")
+    orc = O.SocialWaysOracle(Tp, use_social=True)
+    orc.load_state({k: {kk: vv.cpu() for kk, vv in v.items()} for k, v in tr.checkpoint().items() if k.endswith("_dict")})
+    B = int(np.sum(sizes))
+    sb = data.the_batches[:len(sizes)]
+    torch.manual_seed(3)
+    noise = torch.rand(B, 32)
+    rec = {}
+    out = tr.step(data.obsv[:B], data.pred[:B], sb, 0.07, 0.91, noise, data.ss)
+    got = tr.losses_from(out, [B], Tp, data.ss)[0]
+    want, ade, fde = orc.train_step(data.obsv[:B].cpu(), data.pred[:B].cpu(), sb, 0.07, 0.91, noise, data.ss, record=rec)
+    assert ops.disc_dpred_supported(Tp) == (Tp <= 24)
+    assert_close(got, np.asarray(want), 5e-5, 2e-6, "9 MSE terms")
+    o = out.double().cpu().numpy()
+    assert abs(o[-1, 0] - ade) < 1e-4 * max(1.0, abs(ade)) and abs(o[-1, 1] - fde) < 1e-4 * max(1.0, abs(fde))
+    assert_close(tr.last_pred_hat.cpu(), rec["pred_hat_4d"], 3e-5, 3e-6, "rollout")
+    for name in ("attention", "feature_embedder", "encoder", "decoder"):
+        for k, p in getattr(tr.G, name).named_parameters():
+            w = rec["g_grads"][name + "." + k]
+            assert_close(p.grad.cpu(), w, 2e-4, 2e-4 * max(float(w.abs().max()), 1e-12), "dG %s.%s" % (name, k))
+    for name, mod in (("encoder", tr.G.encoder), ("decoder", tr.G.decoder), ("D", tr.D)):
+        ref = getattr(orc, name).state_dict()
+        for k, v in mod.state_dict().items():      # after Adam: elementwise agreement bounded by ~lr (see check_weights)
+            bad = (v.cpu() - ref[k]).abs() > 2e-3 * 1.01
+            assert bad.float().mean().item() == 0.0, (name, k)
