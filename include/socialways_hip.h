@@ -193,6 +193,23 @@ int sw_dec_rollout_fwd_aux(const float* obsv, int To, const float* z, const floa
                            const float* cT, const float* enc_w, const float* dec_w, int B, int Tp, float* pred4,
                            float* h_end, float* c_end, float* gsave, const float* gt, float inv_ss, float* ade_part,
                            const float* d_w /*or NULL*/, float* dsave /*or NULL*/, void* stream);
+/* The SAMPLING form of the decode loop: K rollouts of B encoded agents in one launch (test(), train.py:563-616).
+ * ROW ORDER: K*B rows, row r = k*B + a (k-major: copy k of agent a - the order of preds_our).  PER ROW: z and the
+ * outputs.  PER AGENT (read at a = r % B, never replicated): obsv, S_pool, hT, cT, gt.  Row r equals row r of
+ * sw_dec_rollout_fwd on inputs replicated K times, bit for bit.
+ *   pred4  [K*B,Tp,4] or NULL (metrics only);
+ *   err    [K*B][2] or NULL (needs gt): per row { mean over t of |(p_hat - gt) * inv_ss|, the same norm at step Tp-1 }
+ *          (train.py:587, 602-607).  pred4 == NULL && err == NULL is SW_EARG.
+ * Both tile forms of sw_dec_rollout_fwd (two tiles per workgroup above 256 tiles needs registered images).       */
+int sw_dec_sample_fwd(const float* obsv /*[B,To,2]*/, int To, const float* z /*[K*B,32]*/,
+                      const float* S_pool /*[B,64] or NULL = zeros*/, const float* hT, const float* cT /*[B,64]*/,
+                      const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4, const float* gt /*[B,Tp,2]*/,
+                      float inv_ss, float* err, void* stream);
+/* Best-of-K reduction of err [K][B][2] (sw_dec_sample_fwd): per_agent [B][4] = { mean_k ADE, mean_k FDE, min_k ADE,
+ * min_k FDE }, best [B] (int32, or NULL) = the k of the smallest ADE, the lowest k on ties.  Sums run over k ascending
+ * in fp32 (s = s + e_k, then s / K): deterministic.  Sums over agents are the caller's (test() keeps them in float64). */
+int sw_sample_reduce(const float* err /*[K,B,2]*/, int B, int K, float* per_agent /*[B,4]*/, int* best /*[B] or NULL*/,
+                     void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

@@ -93,15 +93,23 @@ __device__ __forceinline__ f32x4 fwd_l2_part(const f32x4 (&w2p)[3], const f32x4 
 // conditional memory operation in the loop the compiler cannot count what is in flight and waited for EVERYTHING
 // (s_waitcnt vmcnt(0)) at the head of the third layer of every step - the round trip of the ~40 KB of rows the step had
 // just stored (found in the ISA in round 3; the backward kernels had been cleaned of this in round 1).
-template <bool SAVE, bool ADE, int NB>
+//
+// SAMPLE: the sampling form (dec_sample_fwd_kernel) - B = K * BA ROWS over BA encoded agents, row r = k BA + a (k-major).
+// Only z is per row; hT, cT, S_pool, the last observed point and gt are read at agent a = r % BA, so no replicated tensor
+// exists anywhere (a tile may straddle two copies: the index is per lane).  Nothing else differs in the step, so a row
+// equals the plain form's on replicated inputs bit for bit.  ADE then means per-ROW errors: ade_part is err [B][2] =
+// { mean over t of the scaled displacement error, the error at the last step }, the per-lane sums the tile epilogue would
+// have folded.  PRED = false (metrics only) drops the pred4 stores at compile time.  No riders, no saved rows, no h_end.
+template <bool SAVE, bool ADE, int NB, bool SAMPLE = false, bool PRED = true>
 __device__ __forceinline__ void dec_rollout_fwd_tiles(
     float* smem, const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
     const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
     const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
     float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
     float* __restrict__ ade_part, const float* __restrict__ dobs_w, float* __restrict__ dobs_act,
-    float* __restrict__ dobs_x4s, const float* __restrict__ gimg) {
-  if constexpr (NB == 1) {
+    float* __restrict__ dobs_x4s, const float* __restrict__ gimg, int BA) {
+  static_assert(!SAMPLE || (!SAVE && (ADE || PRED)), "sampling form: nothing saved, and something wanted");
+  if constexpr (NB == 1 && !SAMPLE) {
     // Workgroups beyond the agent tiles (only launched while the rollout leaves CUs idle): the observation LSTM of
     // the discriminator's first pass of this step - it does not depend on the generator - with the rows disc_bwd needs
     if (blockIdx.x * SW_TILE >= (unsigned)B) {
@@ -128,12 +136,13 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
 
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int u0 = wave * 16;
-  int a0[NB], b[NB];
+  int a0[NB], b[NB], ag[NB];   // first row of the tile; this lane's row; the agent whose encoding the row reads
   bool live[NB];
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
     a0[k] = (NB * (int)blockIdx.x + k) * SW_TILE;
     b[k] = min(a0[k] + ln, B - 1);
+    ag[k] = SAMPLE ? b[k] % BA : b[k];
     live[k] = (a0[k] + ln) < B;
   }
   const GSave gs = gsave_layout(B, To, Tp);
@@ -217,15 +226,16 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
     const int sld = S_pool ? 64 : 32;
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-      c[k] = ld4(cT + (size_t)b[k] * 64 + u0 + 4 * lg);
-      h[k] = ld4(hT + (size_t)b[k] * 64 + u0 + 4 * lg);
-      px[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 0];
-      py[k] = obsv[((size_t)b[k] * To + To - 1) * 2 + 1];
+      c[k] = ld4(cT + (size_t)ag[k] * 64 + u0 + 4 * lg);
+      h[k] = ld4(hT + (size_t)ag[k] * 64 + u0 + 4 * lg);
+      px[k] = obsv[((size_t)ag[k] * To + To - 1) * 2 + 0];
+      py[k] = obsv[((size_t)ag[k] * To + To - 1) * 2 + 1];
 #pragma unroll
       for (int q = 0; q < 6; ++q) {
         const int i = threadIdx.x + q * SW_THREADS, a = i / 96, cc = i - a * 96;
         const int bb = min(a0[k] + a, B - 1);
-        szs[k][q] = sp[(size_t)bb * sld + min(cc, sld - 1)];
+        const int sb = S_pool ? (SAMPLE ? bb % BA : bb) : bb;    // (without S_pool the dummy source is z: per row)
+        szs[k][q] = sp[(size_t)sb * sld + min(cc, sld - 1)];
         szz[k][q] = z[(size_t)bb * 32 + max(cc - 64, 0)];
       }
     }
@@ -349,7 +359,7 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       gti[k] = float2{0.f, 0.f};
-      if constexpr (ADE) gti[k] = *reinterpret_cast<const float2*>(gt + ((size_t)b[k] * Tp + i) * 2);   // in flight under the layers
+      if constexpr (ADE) gti[k] = *reinterpret_cast<const float2*>(gt + ((size_t)ag[k] * Tp + i) * 2);   // in flight under the layers
       hrow[k] = &hbuf[k][cur * 16 * SW_ALD + ln * SW_ALD + 320 + 4 * lg];
     }
     // ---- layer 1: z1 = W1h h + u ; a1 = lrelu(z1) --------------------------------------------------
@@ -494,7 +504,7 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
         }
         {   // every lane of agent ln holds the same (p, v): all of them store it (no lane-dependent store)
           const f32x4 x4 = {px[k], py[k], x, y};
-          st4(pred4 + ((size_t)b[k] * Tp + i) * 4, x4);
+          if constexpr (PRED) st4(pred4 + ((size_t)b[k] * Tp + i) * 4, x4);
           if constexpr (SAVE && !LAST) st4(gsave + gs.x4s + ((size_t)(To + i) * B + b[k]) * 4, x4);
         }
       }
@@ -535,7 +545,12 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
       st4(h_end + (size_t)b[k] * 64 + u0 + 4 * lg, h[k]);
       if (c_end) st4(c_end + (size_t)b[k] * 64 + u0 + 4 * lg, c[k]);
     }
-    if (ADE && wave == 0) {   // fixed shuffle tree over the tile's 16 agents -> one partial triple per 16-agent tile
+    if constexpr (SAMPLE) {
+      if (ade_lane[k]) {      // per row, not per tile: the lane that summed the row's errors stores them
+        ade_part[(size_t)b[k] * 2 + 0] = e_sum[k] / (float)Tp;
+        ade_part[(size_t)b[k] * 2 + 1] = e_last[k];
+      }
+    } else if (ADE && wave == 0) {   // fixed shuffle tree over the tile's 16 agents -> one partial triple per 16-agent tile
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
         e_sum[k] += __shfl_xor(e_sum[k], o);
@@ -562,7 +577,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd_kernel(
     float* __restrict__ dobs_x4s, const float* __restrict__ gimg) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   dec_rollout_fwd_tiles<SAVE, ADE, 1>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave,
-                                      gt, inv_ss, ade_part, dobs_w, dobs_act, dobs_x4s, gimg);
+                                      gt, inv_ss, ade_part, dobs_w, dobs_act, dobs_x4s, gimg, B);
 }
 
 template <bool SAVE, bool ADE>
@@ -574,7 +589,19 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_fwd2_kernel(
     float* __restrict__ ade_part, const float* __restrict__ gimg) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   dec_rollout_fwd_tiles<SAVE, ADE, 2>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave,
-                                      gt, inv_ss, ade_part, nullptr, nullptr, nullptr, gimg);
+                                      gt, inv_ss, ade_part, nullptr, nullptr, nullptr, gimg, B);
+}
+
+// The sampling form: R = K * BA rows over BA encoded agents (see dec_rollout_fwd_tiles), NB tiles of 16 rows per workgroup.
+template <bool ERR, bool PRED, int NB>
+__global__ __launch_bounds__(SW_THREADS) void dec_sample_fwd_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
+    const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
+    const float* __restrict__ dec_w, int R, int BA, int Tp, float* __restrict__ pred4, const float* __restrict__ gt,
+    float inv_ss, float* __restrict__ err, const float* __restrict__ gimg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  dec_rollout_fwd_tiles<false, ERR, NB, true, PRED>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, R, Tp, pred4, nullptr, nullptr,
+                                                    nullptr, gt, inv_ss, err, nullptr, nullptr, nullptr, gimg, BA);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1031,6 +1058,40 @@ extern "C" int sw_dec_rollout_fwd(const float* obsv, int To, const float* z, con
                                   const float* gt, float inv_ss, float* ade_part, void* stream) {
   return sw_dec_rollout_fwd_aux(obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, Tp, pred4, h_end, c_end, gsave, gt, inv_ss,
                                 ade_part, nullptr, nullptr, stream);
+}
+
+// K rollouts of B encoded agents in one launch (sampling / evaluation): row k B + a reads z at the row and everything
+// else at agent a.  The tile forms are chosen as in sw_dec_rollout_fwd_aux (two tiles per workgroup above 256 tiles,
+// with registered images; SW_DEC_FWD2=0 / 1 forces either).
+extern "C" int sw_dec_sample_fwd(const float* obsv, int To, const float* z, const float* S_pool, const float* hT,
+                                 const float* cT, const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
+                                 const float* gt, float inv_ss, float* err, void* stream) {
+  if (!obsv || !z || !hT || !cT || !enc_w || !dec_w || B < 0 || K < 1 || To < 2 || Tp < 1) return SW_EARG;
+  if ((!pred4 && !err) || (err && !gt)) return SW_EARG;
+  if ((long long)K * B > 0x7fffffffLL - 2 * SW_TILE) return SW_ESHAPE;     // row and tile indices are ints
+  if (B == 0) return SW_OK;
+  const int R = K * B, tiles = (R + SW_TILE - 1) / SW_TILE;
+  const float* gimg = sw_gen_images_for(enc_w, dec_w);
+  auto launch = [&](auto nb_, auto err_, auto pred_) -> int {
+    constexpr int NB = decltype(nb_)::value;
+    constexpr bool ER = decltype(err_)::value, PR = decltype(pred_)::value;
+    constexpr int lds = NB * FwdLds::total * 4;
+    static int have = 0;
+    if (int rc = sw_set_lds((const void*)dec_sample_fwd_kernel<ER, PR, NB>, lds, have)) return rc;
+    SW_LAUNCH((dec_sample_fwd_kernel<ER, PR, NB>), dim3((tiles + NB - 1) / NB), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv,
+              To, z, S_pool, hT, cT, enc_w, dec_w, R, B, Tp, pred4, gt, inv_ss, err, gimg);
+    SW_CHECK_LAUNCH("dec_sample_fwd_kernel");
+    return SW_OK;
+  };
+  auto dispatch = [&](auto nb_) -> int {
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    if (!err) return launch(nb_, F_{}, T_{});
+    return pred4 ? launch(nb_, T_{}, T_{}) : launch(nb_, T_{}, F_{});
+  };
+  static const int fwd2_env = getenv("SW_DEC_FWD2") ? atoi(getenv("SW_DEC_FWD2")) : -1;
+  if (gimg && (fwd2_env >= 0 ? fwd2_env != 0 : tiles > 256)) return dispatch(std::integral_constant<int, 2>{});
+  return dispatch(std::integral_constant<int, 1>{});
 }
 
 extern "C" int sw_dec_rollout_bwd_aux(const float* dpred4, const float* enc_w, const float* dec_w,

@@ -684,6 +684,40 @@ extern "C" int sw_variety_grad(const float* predK, const float* gt, int K, int B
   return SW_OK;
 }
 
+// ---- best-of-K reduction of the sampling path (test(), train.py:587-614) -----------------------------------------------
+//   err [K][B][2] = per-row { ADE, FDE } of sw_dec_sample_fwd  ->  per_agent [B][4] = { mean_k ADE, mean_k FDE, min_k ADE,
+//   min_k FDE }, best [B] = the k of the smallest ADE (the lowest k on ties).  One thread per agent, k ascending: the sums
+//   are plain float additions in that order (s = s + e_k, then s / K), so a torch loop over k reproduces them.
+__global__ __launch_bounds__(256) void sample_reduce_kernel(const float* __restrict__ err, int B, int K,
+                                                             float* __restrict__ per_agent, int* __restrict__ best) {
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= B) return;
+  const float2* e = reinterpret_cast<const float2*>(err) + a;
+  float2 v = e[0];
+  float sa = v.x, sf = v.y, ma = v.x, mf = v.y;
+  int kb = 0;
+#pragma unroll 8
+  for (int k = 1; k < K; ++k) {
+    v = e[(size_t)k * B];
+    sa += v.x;
+    sf += v.y;
+    if (v.x < ma) {
+      ma = v.x;
+      kb = k;
+    }
+    mf = v.y < mf ? v.y : mf;
+  }
+  st4(per_agent + (size_t)a * 4, f32x4{sa / (float)K, sf / (float)K, ma, mf});
+  if (best) best[a] = kb;
+}
+extern "C" int sw_sample_reduce(const float* err, int B, int K, float* per_agent, int* best, void* stream) {
+  if (!err || !per_agent || B < 0 || K < 1) return SW_EARG;
+  if (B == 0) return SW_OK;
+  SW_LAUNCH(sample_reduce_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, err, B, K, per_agent, best);
+  SW_CHECK_LAUNCH("sample_reduce_kernel");
+  return SW_OK;
+}
+
 // ---- toy statistics: pairwise mean displacement between sample sets (calc_statistics.py:28-32, 56-60) ----
 //   D[k][i][j] = mean_{t >= t0} || a[i][k][t] - b[j][k][t] ||
 __global__ __launch_bounds__(256) void traj_dist_kernel(const float* __restrict__ a, const float* __restrict__ b, int Na,

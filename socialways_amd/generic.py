@@ -26,11 +26,12 @@ as the module classes of both, and as the cross-check of the wide engine (tests)
 """
 import copy
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .model import _scene_index, _wgrad_ws, get_traj_4d
+from .model import _sample_noise, _scene_index, _wgrad_ws, get_traj_4d
 from .trainer import SocialWaysTrainer
 
 
@@ -373,6 +374,19 @@ class Generator(nn.Module):
                 h, c = self.encoder.step(last, h, c)
         return torch.stack(out, dim=1)
 
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None):
+        """n_samples futures per agent, (K, B, n_next, 4) - the call of the 64-unit Generator.sample().  At these widths it is
+        forward() on K copies of the batch, each copy with its scenes (no sampling kernels here).  No gradients."""
+        L.require_gpu(obsv_p)
+        K, B = int(n_samples), obsv_p.shape[0]
+        noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
+        sb = np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2)
+        if len(sb) == 0:
+            sb = np.array([[0, B]], dtype=np.int64)
+        with torch.no_grad():
+            ph = self.forward(obsv_p.repeat(K, 1, 1), noise.reshape(K * B, -1), n_next, np.concatenate([sb + k * B for k in range(K)]))
+        return ph.view(K, B, n_next, 4)
+
 
 # ------------------------------------------------------------------------------------------------------------------------
 class GenericTrainer(SocialWaysTrainer):
@@ -483,6 +497,10 @@ class GenericTrainer(SocialWaysTrainer):
         res[U + 2] = ade.double()
         self.last_pred_hat = fake
         return res
+
+    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None):
+        """The contract of SocialWaysTrainer.evaluate(); at these widths it is test() (no sampling kernels)."""
+        return self.test(data, n_gen_samples, False, write_to_file, just_one, collect)
 
     def step_many(self, batches, sub_batches, ss=1.0, global_B=None, out=None, global_row0=0):
         return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0) for o, p, zv, ov, nz in batches]

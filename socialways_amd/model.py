@@ -764,6 +764,35 @@ class Generator(nn.Module):
                                    self.decoder.packed(), obsv_p, noise, scenes, n_next, self.use_social, save=False)
         return pred4
 
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None):
+        """n_samples futures per agent: pred_hat_4d (K, B, n_next, 4), sample k of agent a at [k, a] - what K calls of
+        forward() on the same observations give, with the observation encoding and the social block computed once
+        (ops.gen_sample).  noise (K, B, noise_len) or None = torch.rand on the device.  No gradients."""
+        L.require_gpu(obsv_p)
+        if obsv_p.dim() != 3 or obsv_p.shape[2] != 2 or obsv_p.shape[1] < 2:
+            raise ValueError("obsv_p must be (B, To >= 2, 2), got %s" % (tuple(obsv_p.shape),))
+        K, B = int(n_samples), obsv_p.shape[0]
+        noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
+        if noise.shape[-1] < 32:     # as forward(): zero-padded to the kernels' 32 noise columns
+            noise = nn.functional.pad(noise, (0, 32 - noise.shape[-1]))
+        scenes = _scene_index(sub_batches, B, obsv_p.device)
+        with torch.no_grad():
+            pred4, _ = ops.gen_sample(self.encoder.packed(), self.feature_embedder.packed(), self.attention.packed(),
+                                      self.decoder.packed(), obsv_p, noise.reshape(K * B, 32), scenes, n_next, self.use_social, K)
+        return pred4.view(K, B, n_next, 4)
+
+
+def _sample_noise(noise, K, B, noise_len, device):
+    """The (K, B, noise_len) noise of Generator.sample(): checked, or drawn with torch.rand on the device."""
+    if K < 1:
+        raise ValueError("n_samples must be at least 1")
+    if noise is None:
+        return torch.rand(K, B, noise_len, device=device)
+    if noise.dim() != 3 or tuple(noise.shape) != (K, B, noise_len):
+        raise ValueError("noise must be (n_samples, B, %d) = (%d, %d, %d), got %s"
+                         % (noise_len, K, B, noise_len, tuple(noise.shape)))
+    return noise.to(device=device, dtype=torch.float32)
+
 
 _default_generator = None
 
@@ -780,6 +809,14 @@ def predict(obsv_p, noise, n_next, sub_batches=[], generator=None):
     if g is None:
         raise RuntimeError("no generator: pass generator= or call set_default_generator()")
     return g(obsv_p, noise, n_next, sub_batches)
+
+
+def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None):
+    """Module-level Generator.sample(): n_samples futures per agent, (K, B, n_next, 4), from `generator` (or the default one)."""
+    g = generator or _default_generator
+    if g is None:
+        raise RuntimeError("no generator: pass generator= or call set_default_generator()")
+    return g.sample(obsv_p, n_samples, n_next, sub_batches, noise)
 
 
 def predict_cv(obsv, n_next):

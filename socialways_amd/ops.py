@@ -336,6 +336,66 @@ def gen_backward_k(enc_w, emb_w, att_w, dec_w, ctx, dpred4_k, d_enc, d_emb, d_at
            L.ptr(d_enc), L.ptr(d_dec), 2, L.ptr(wgrad), L.ptr(tmp), pending, L.stream())
 
 
+_sample_img = {}      # device -> the image buffer the sampling path owns (sw_gen_images)
+
+
+def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, gt=None, inv_ss=1.0,
+               want_pred=True):
+    """K sampled futures of predict() for B agents (test(), train.py:563-616): the encoder over the observed steps and the
+    social block run ONCE on the B agents, then ONE sampling launch rolls out the K * B rows (row k * B + a = draw k of
+    agent a) reading the encoding per agent - nothing is replicated.  noise_k (K * B, 32).
+    gt (B, n_next, 2): the per-row errors are formed in the launch and reduced over k on the device.
+    Returns (pred4 (K * B, n_next, 4) or None when not want_pred,
+             (per_agent (B, 4) = mean_k ADE | mean_k FDE | min_k ADE | min_k FDE, best (B,) int32, err (K, B, 2)) or None).
+    The launches run with the weight images registered, the protocol of the training step: derived into a buffer this path
+    owns in front of them, dropped behind them on the same host thread - no image outlives a weight change."""
+    L.require_gpu(obsv)
+    obsv = obsv.contiguous()
+    noise_k = noise_k.contiguous()
+    B, To = obsv.shape[0], obsv.shape[1]
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    if noise_k.shape != (K * B, 32):
+        raise ValueError("noise must be (K * B, 32)")
+    if gt is None and not want_pred:
+        raise ValueError("nothing asked for: neither trajectories nor errors")
+    if gt is not None:
+        gt = gt.contiguous()
+        if gt.shape != (B, n_next, 2):
+            raise ValueError("gt must be (B, n_next, 2)")
+    dev = obsv.device
+    st = L.stream()
+    pred4 = torch.empty(K * B, n_next, 4, device=dev) if want_pred else None
+    if B == 0:
+        return pred4, None
+    img = _sample_img.get(str(dev))
+    if img is None:
+        img = _sample_img[str(dev)] = torch.empty(L.load().sw_gen_image_floats(), device=dev)
+    hT, cT = torch.empty(B, 64, device=dev), torch.empty(B, 64, device=dev)
+    err = torch.empty(K, B, 2, device=dev) if gt is not None else None
+    L.call("sw_gen_images", L.ptr(enc_w), L.ptr(dec_w), L.ptr(emb_w), L.ptr(att_w), L.ptr(img), st)
+    try:
+        L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
+               None, None, 0, None, None, 0, st)
+        S = None                                                                 # NULL = zeros (train.py:413)
+        if use_social:
+            S = torch.empty(B, 64, device=dev)
+            wh = torch.empty(B * 132, device=dev) if scenes.NB else None
+            L.call("sw_social_pool_fwd_aux", L.ptr(obsv), To, L.ptr(hT), L.ptr(scenes.scene_off), scenes.S, B, scenes.amax,
+                   L.ptr(emb_w), L.ptr(att_w), L.ptr(S), None, L.ptr(scenes.big_blocks), scenes.NB, L.ptr(wh), None,
+                   None, None, 0, st)
+        L.call("sw_dec_sample_fwd", L.ptr(obsv), To, L.ptr(noise_k), L.ptr(S), L.ptr(hT), L.ptr(cT), L.ptr(enc_w),
+               L.ptr(dec_w), B, K, n_next, L.ptr(pred4), L.ptr(gt), float(inv_ss), L.ptr(err), st)
+    finally:
+        L.call("sw_gen_images", None, None, None, None, None, None)
+    if err is None:
+        return pred4, None
+    per_agent = torch.empty(B, 4, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("sw_sample_reduce", L.ptr(err), B, K, L.ptr(per_agent), L.ptr(best), st)
+    return pred4, (per_agent, best, err)
+
+
 class DiscCtx:
     __slots__ = ("dsave", "B", "To", "Tp", "nb")
 

@@ -952,6 +952,73 @@ class SocialWaysTrainer:
         ade_avg, fde_avg, ade_min, fde_min = (sums / n).tolist()
         return ade_avg, fde_avg, ade_min, fde_min
 
+    @staticmethod
+    def eval_chunks(batches, K, chunk):
+        """The folding of test(): runs [i, j) of consecutive held-out scenes whose K copies fit `chunk` rows."""
+        i = 0
+        while i < len(batches):
+            j, tot = i + 1, batches[i][1] - batches[i][0]
+            while (j < len(batches) and batches[j][0] == batches[j - 1][1]
+                   and (tot + batches[j][1] - batches[j][0]) * K <= chunk):
+                tot += batches[j][1] - batches[j][0]
+                j += 1
+            yield i, j
+            i = j
+
+    @staticmethod
+    def eval_noise(batches, K, noise_len):
+        """The host noise of one chunk of test(): scene by scene, K draws of (n, noise_len) each from the torch CPU generator
+        (train.py:584) -> (K, rows of the chunk, noise_len).  Needs no device."""
+        lo, hi = batches[0][0], batches[-1][1]
+        noise = torch.empty(K, hi - lo, noise_len)
+        for a, b in batches:
+            for k in range(K):
+                noise[k, a - lo:b - lo] = torch.rand(b - a, noise_len)
+        return noise
+
+    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None):
+        """The contract of test() (train.py:563-616; without its `linear` branch) on the sampling path: the same four
+        return values, prediction files, host noise stream and folding of scenes.  Per chunk the observations are encoded
+        and pooled ONCE, one launch rolls out the K copies and forms their errors (ops.gen_sample), the mean / min over K
+        is reduced on the device; the K x n trajectories leave the kernel only when a file or `collect` wants them."""
+        ss, dev, K = data.ss, self.device, n_gen_samples
+        G = self.G
+        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
+        if just_one:
+            batches = batches[:1]
+        want_pred = bool(write_to_file) or collect is not None
+        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
+            lo, hi = batches[i][0], batches[j - 1][1]
+            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
+            n = hi - lo
+            with torch.no_grad():
+                noise = self._pad_z(self.eval_noise(batches[i:j], K, self.noise_len)).view(K * n, -1).to(dev)
+                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
+                scenes = ops.SceneIndex.get(sb, n, obsv.device)
+                ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(),
+                                         G.decoder.packed(), obsv, noise, scenes, self.n_next, G.use_social, K,
+                                         gt=pred, inv_ss=1.0 / float(ss), want_pred=want_pred)
+                if want_pred:
+                    preds_k = ph.view(K, n, self.n_next, 4)
+                    linear_preds = predict_cv(obsv, self.n_next)
+                    sc = data.scale
+                    for si, (a, b) in enumerate(batches[i:j]):
+                        t = data.times[a] if data.times is not None else i + si
+                        r = slice(a - lo, b - lo)
+                        rec = dict(timestamp=t, obsvs=sc.denormalize(obsv[r, :, :2].cpu().numpy()),
+                                   preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
+                                   preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
+                                   preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
+                        if collect is not None:
+                            collect.append(rec)
+                        if write_to_file:
+                            os.makedirs(write_to_file, exist_ok=True)
+                            np.savez(os.path.join(write_to_file, str(self.epoch) + '-' + str(t) + '.npz'), **rec)
+                sums += red[0].double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
+        ade_avg, fde_avg, ade_min, fde_min = (sums / data.n_test_samples).tolist()
+        return ade_avg, fde_avg, ade_min, fde_min
+
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
         """The reference's checkpoint dict (train.py:653-663)."""
