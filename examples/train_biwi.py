@@ -75,6 +75,11 @@ def main(argv=None):
         if rank == 0 and (epoch % args.test_every == 0 or epoch == args.epochs):
             m = tr.test(data, n_gen_samples=args.k, write_to_file=os.path.join(args.out, "preds", str(epoch)))
             print("Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f)" % (m[0], m[1], args.k, m[2], m[3]))
+            sm = tr.evaluate_scenes(data, n_gen_samples=args.k)      # the K draws as JOINT futures of each scene
+            print("Scene level: joint Min(%d) ADE,FDE = (%.3f, %.3f) | collisions < 0.1: %.1f %% of draws, %.1f %% of best draws, "
+                  "%.1f %% of agents (ground truth %.1f %%) | %d scenes, %d with company"
+                  % (args.k, sm["jade_min"], sm["jfde_min"], 100 * sm["col_joint"], 100 * sm["col_best"], 100 * sm["col_agent"],
+                     100 * sm["col_gt"], sm["n_scenes"], sm["n_multi"]))
             tr.save(os.path.join(args.out, "socialWays-crowd.pt"), epoch=epoch)
     if world > 1:
         tr.close()              # captured collectives and the direct exchange's buffers go before their process group

@@ -210,6 +210,31 @@ int sw_dec_sample_fwd(const float* obsv /*[B,To,2]*/, int To, const float* z /*[
  * in fp32 (s = s + e_k, then s / K): deterministic.  Sums over agents are the caller's (test() keeps them in float64). */
 int sw_sample_reduce(const float* err /*[K,B,2]*/, int B, int K, float* per_agent /*[B,4]*/, int* best /*[B] or NULL*/,
                      void* stream);
+/* SCENE-LEVEL metrics of K joint draws (draw k of a scene = draw k of every agent in it).  B agents in S scenes,
+ * scene_off [S+1] int32 prefix offsets (scene s = agents scene_off[s] .. scene_off[s+1]-1).
+ *
+ * sw_scene_clearance: clear [K,B], clear[k][a] = inv_ss * the closest approach of agent a to any other agent of its
+ * scene in draw k; +inf for a single-agent scene or a path without segments.  The path of (k, a) is P_0 = start[a]
+ * (when start != NULL), then pos[k][a][0 .. Tp-1]: Tp segments with start, Tp - 1 without.  Within a segment both agents
+ * move linearly: r0 = P_{t-1}(a) - P_{t-1}(b), dv = (P_t(a) - P_t(b)) - r0, tau = clamp(-(r0.dv) / (dv.dv), 0, 1)
+ * (0 when dv.dv = 0), distance |r0 + tau dv| - two agents that swap places inside a segment have distance 0.
+ *   pos    [K,B,Tp,pstride], pstride 2 or 4 floats (x, y first; pred4 of sw_dec_sample_fwd has 4), 8-byte aligned;
+ *   start  [B,sstride] or NULL, x, y first, sstride >= 2 (the last observed step of obsv [B,To,2]: obsv + 2*(To-1),
+ *          sstride 2*To);  inv_ss > 0.
+ * Plain trajectories in, so the same launch serves sampled futures, the ground truth (K = 1) and anything else.  Any
+ * scene size: up to 32 agents a wave holds 64 / n_pad draws side by side, above 64 it loops over agent tiles.  Each
+ * clear[k][a] has one owner (no atomics): deterministic.                                                           */
+int sw_scene_clearance(const float* pos, int pstride, const float* start /*or NULL*/, int sstride, const int* scene_off,
+                       int S, int B, int K, int Tp, float inv_ss, float* clear /*[K,B]*/, void* stream);
+/* sw_scene_reduce: with sade[k][s] / sfde[k][s] = the mean over the scene's agents of err[k][a][0] / [1] and
+ * sclear[k][s] = the minimum over them of clear[k][a],
+ *   per_scene [S,6] = { min_k sade, min_k sfde, share of k with sclear < coll_dist, 1 if draw kbest collides else 0,
+ *                       min_k sclear, mean over (k, a in s) of [clear[k][a] < coll_dist] },
+ *   best [S] (int32, or NULL) = kbest = the first k that attains min_k sade.
+ * clear == NULL, and every single-agent scene: columns 2, 3, 5 are 0 and column 4 is +inf.  Fixed summation order: two
+ * calls give the same bits.                                                                                          */
+int sw_scene_reduce(const float* err /*[K,B,2]*/, const float* clear /*[K,B] or NULL*/, const int* scene_off, int S, int B,
+                    int K, float coll_dist, float* per_scene /*[S,6]*/, int* best /*[S] or NULL*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

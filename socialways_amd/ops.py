@@ -340,12 +340,14 @@ _sample_img = {}      # device -> the image buffer the sampling path owns (sw_ge
 
 
 def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, gt=None, inv_ss=1.0,
-               want_pred=True):
+               want_pred=True, keep_pred=False):
     """K sampled futures of predict() for B agents (test(), train.py:563-616): the encoder over the observed steps and the
     social block run ONCE on the B agents, then ONE sampling launch rolls out the K * B rows (row k * B + a = draw k of
     agent a) reading the encoding per agent - nothing is replicated.  noise_k (K * B, 32).
     gt (B, n_next, 2): the per-row errors are formed in the launch and reduced over k on the device.
-    Returns (pred4 (K * B, n_next, 4) or None when not want_pred,
+    keep_pred: pred4 is written and returned although the caller wants no trajectories (want_pred False) - it stays on
+    the device for a consumer there (scene_metrics).
+    Returns (pred4 (K * B, n_next, 4) or None when neither want_pred nor keep_pred,
              (per_agent (B, 4) = mean_k ADE | mean_k FDE | min_k ADE | min_k FDE, best (B,) int32, err (K, B, 2)) or None).
     The launches run with the weight images registered, the protocol of the training step: derived into a buffer this path
     owns in front of them, dropped behind them on the same host thread - no image outlives a weight change."""
@@ -357,6 +359,7 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
         raise ValueError("K must be at least 1")
     if noise_k.shape != (K * B, 32):
         raise ValueError("noise must be (K * B, 32)")
+    want_pred = want_pred or keep_pred
     if gt is None and not want_pred:
         raise ValueError("nothing asked for: neither trajectories nor errors")
     if gt is not None:
@@ -394,6 +397,55 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
     best = torch.empty(B, dtype=torch.int32, device=dev)
     L.call("sw_sample_reduce", L.ptr(err), B, K, L.ptr(per_agent), L.ptr(best), st)
     return pred4, (per_agent, best, err)
+
+
+def scene_clearance(pos, start, scenes, K, inv_ss=1.0):
+    """clear (K, B): per draw and agent the closest approach to another agent of its scene, times inv_ss; +inf in
+    single-agent scenes (sw_scene_clearance).  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or
+    None: the point in front of the Tp positions (any row stride: a view such as obsv[:, -1] is read in place)."""
+    L.require_gpu(pos)
+    pos = pos.contiguous()
+    Tp, pstride, B = pos.shape[-2], pos.shape[-1], scenes.B
+    if pstride not in (2, 4) or pos.numel() != K * B * Tp * pstride:
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
+    sstride = 0
+    if start is not None:
+        if start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != pos.device:
+            raise ValueError("start must be (B, >= 2) on the device of pos, got %s" % (tuple(start.shape),))
+        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
+            start = start[:, :2].float().contiguous()
+        sstride = start.stride(0)
+    clear = torch.empty(K, B, device=pos.device)
+    L.call("sw_scene_clearance", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, K,
+           Tp, float(inv_ss), L.ptr(clear), L.stream())
+    return clear
+
+
+def scene_reduce(err, clear, scenes, K, coll_dist):
+    """per_scene (S, 6) = joint min ADE | joint min FDE | share of colliding draws | does draw kbest collide | min_k of the
+    scene's clearance | share of colliding (draw, agent), and kbest (S,) int32 (sw_scene_reduce); clear may be None."""
+    L.require_gpu(err)
+    err = err.contiguous()
+    B = scenes.B
+    if err.numel() != K * B * 2 or (clear is not None and tuple(clear.shape) != (K, B)):
+        raise ValueError("err must be (K, B, 2) and clear (K, B)")
+    per_scene = torch.empty(scenes.S, 6, device=err.device)
+    kbest = torch.empty(scenes.S, dtype=torch.int32, device=err.device)
+    L.call("sw_scene_reduce", L.ptr(err), L.ptr(clear), L.ptr(scenes.scene_off), scenes.S, B, K, float(coll_dist),
+           L.ptr(per_scene), L.ptr(kbest), L.stream())
+    return per_scene, kbest
+
+
+def scene_metrics(err, pred4, obsv, scenes, K, n_next, inv_ss, coll_dist):
+    """Scene-level metrics of K joint draws (draw k of a scene = draw k of each of its agents) behind gen_sample, two
+    launches: the clearance of every (draw, agent) along pred4 (K * B, n_next, 4), each path starting at the agent's last
+    observed position, and the reduction per scene.  err (K, B, 2) = the row errors of gen_sample.
+    Returns (per_scene (S, 6), kbest (S,) int32, clear (K, B)) - the columns of scene_reduce."""
+    if pred4.shape[-2] != n_next:
+        raise ValueError("pred4 must hold n_next = %d steps" % n_next)
+    clear = scene_clearance(pred4, obsv[:, -1], scenes, K, inv_ss)
+    per_scene, kbest = scene_reduce(err, clear, scenes, K, coll_dist)
+    return per_scene, kbest, clear
 
 
 class DiscCtx:

@@ -2,13 +2,17 @@
 two-sample test and the per-pedestrian assignment cost ("EMD") between real and generated futures.
 The O(K^2 T) distance matrices are computed on the GPU (`sw_traj_dist`), the nearest-neighbour votes
 with device reductions; the K x K assignment problems go to scipy's Hungarian solver on the host, as in
-the reference (calc_statistics.py:62)."""
+the reference (calc_statistics.py:62).
+
+Beyond the reference: `scene_clearance`, the closest approach between the agents of a scene along K joint futures - the
+quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere."""
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import ops
 
 
 def _dev(x, device):
@@ -94,3 +98,27 @@ def calc_and_store_stats(main_dir, real_samples, n_past=2, n_next=2, stats_file=
         np.savez(stats_file, stats_1nn=[stats_1nn[k] for k in sorted(stats_1nn)],
                  stats_wst=[stats_wst[k] for k in sorted(stats_wst)])
     return stats_1nn, stats_wst
+
+
+def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
+    """Closest approach of every agent to the other agents of its scene, per joint draw (`sw_scene_clearance`).
+    trajs (K, B, T, 2 | 4) or (B, T, 2 | 4): K joint futures of B agents, x and y first (prediction files, `collect`
+    records, ground truth); sub_batches (S, 2) [start, end) rows tiling [0, B), [] = one scene; start (B, 2) or None: a
+    point in front of every path (the last observed position), giving T segments instead of T - 1.  Within a segment
+    both agents move linearly, so two agents that swap places between two frames have clearance 0.  The distance is
+    multiplied by `scale`.  Returns a device tensor (K, B), or (B,) for a 3-d input; +inf in single-agent scenes."""
+    t = _dev(trajs, device)
+    L.require_gpu(t)
+    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
+        raise ValueError("trajs must be (K, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    t4 = t if t.dim() == 4 else t.unsqueeze(0)
+    K, B = t4.shape[0], t4.shape[1]
+    if K < 1:
+        raise ValueError("no draws")
+    if start is not None:
+        start = _dev(start, device)
+        if tuple(start.shape) != (B, 2):
+            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    clear = ops.scene_clearance(t4, start, scenes, K, float(scale))
+    return clear if t.dim() == 4 else clear[0]

@@ -976,6 +976,19 @@ class SocialWaysTrainer:
                 noise[k, a - lo:b - lo] = torch.rand(b - a, noise_len)
         return noise
 
+    def _eval_records(self, data, chunk, first, obsv, pred, preds_k):
+        """The prediction records of one chunk of evaluate(): (index in the chunk, the dict test() writes per held-out scene -
+        timestamp, obsvs, preds_our (K, n, n_next, 2), preds_gtt, preds_lnr, all denormalised)."""
+        linear_preds = predict_cv(obsv, self.n_next)
+        sc, lo = data.scale, chunk[0][0]
+        for si, (a, b) in enumerate(chunk):
+            t = data.times[a] if data.times is not None else first + si
+            r = slice(a - lo, b - lo)
+            yield si, dict(timestamp=t, obsvs=sc.denormalize(obsv[r, :, :2].cpu().numpy()),
+                           preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
+                           preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
+                           preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
+
     def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None):
         """The contract of test() (train.py:563-616; without its `linear` branch) on the sampling path: the same four
         return values, prediction files, host noise stream and folding of scenes.  Per chunk the observations are encoded
@@ -1000,16 +1013,8 @@ class SocialWaysTrainer:
                                          G.decoder.packed(), obsv, noise, scenes, self.n_next, G.use_social, K,
                                          gt=pred, inv_ss=1.0 / float(ss), want_pred=want_pred)
                 if want_pred:
-                    preds_k = ph.view(K, n, self.n_next, 4)
-                    linear_preds = predict_cv(obsv, self.n_next)
-                    sc = data.scale
-                    for si, (a, b) in enumerate(batches[i:j]):
-                        t = data.times[a] if data.times is not None else i + si
-                        r = slice(a - lo, b - lo)
-                        rec = dict(timestamp=t, obsvs=sc.denormalize(obsv[r, :, :2].cpu().numpy()),
-                                   preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
-                                   preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
-                                   preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
+                    for _, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
+                        t = rec["timestamp"]
                         if collect is not None:
                             collect.append(rec)
                         if write_to_file:
@@ -1018,6 +1023,76 @@ class SocialWaysTrainer:
                 sums += red[0].double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
         ade_avg, fde_avg, ade_min, fde_min = (sums / data.n_test_samples).tolist()
         return ade_avg, fde_avg, ade_min, fde_min
+
+    def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):
+        """K draws of one chunk for evaluate_scenes(), by the launches of evaluate(): noise (K, n, noise_len) on the host ->
+        (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4), err (K, n, 2))."""
+        G = self.G
+        z = self._pad_z(noise).view(K * obsv.shape[0], -1).to(self.device)
+        ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
+                                 obsv, z, scenes, self.n_next, G.use_social, K, gt=pred, inv_ss=1.0 / float(ss),
+                                 want_pred=False, keep_pred=True)
+        return ph, red[0], red[2]
+
+    def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
+        """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
+        its agents - the joint future that copy k of the scene rolls out.  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          jade_min, jfde_min   joint min ADE / FDE: per scene the minimum over k of the scene's MEAN error (one k for the
+                               whole scene, where ade_min picks a k per agent), summed with the scene's agent count and
+                               divided by data.n_test_samples like the four above: ade_min <= jade_min <= ade_avg;
+          col_joint            mean over the scenes of two or more agents of the share of draws in which two agents come
+                               closer than coll_dist (world units, the units of the errors) at any moment of the future,
+                               moving linearly between frames and starting at the last observed position;
+          col_best             share of those scenes whose jade_min draw collides;
+          col_agent            share of colliding (draw, agent) over those scenes, agent-weighted;
+          col_gt               share of those scenes whose ground-truth future collides (the same kernel, K = 1);
+          n_scenes, n_multi    scenes evaluated, and those of two or more agents (0: the col_* are 0).
+        Chunking, host noise and sampling launches are evaluate()'s; per chunk two more launches (ops.scene_metrics) work on
+        the draws where they are and the same two on the ground truth; sums are float64 on the device, one host sync at the end.  With `collect` every
+        record of evaluate() also has `clear` (K, n), `per_scene` (6,) and `kbest` (columns: ops.scene_reduce)."""
+        ss, dev, K = data.ss, self.device, n_gen_samples
+        inv_ss = 1.0 / float(ss)
+        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        # sum n * jade | sum n * jfde | then over multi-agent scenes: colliding share | kbest flag | n * agent share | gt flag
+        acc = torch.zeros(6, dtype=torch.float64, device=dev)
+        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
+        if just_one:
+            batches = batches[:1]
+        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
+            lo, hi = batches[i][0], batches[j - 1][1]
+            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
+            n = hi - lo
+            with torch.no_grad():
+                noise = self.eval_noise(batches[i:j], K, self.noise_len)
+                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
+                scenes = ops.SceneIndex.get(sb, n, obsv.device)
+                ph, per_agent, err = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
+                per_scene, kbest, clear = ops.scene_metrics(err, ph, obsv, scenes, K, self.n_next, inv_ss, coll_dist)
+                gt_scene, _ = ops.scene_reduce(torch.zeros(1, n, 2, device=dev),
+                                               ops.scene_clearance(pred, obsv[:, -1], scenes, 1, inv_ss), scenes, 1, coll_dist)
+                cnt = (scenes.scene_off[1:] - scenes.scene_off[:-1]).double()
+                multi = (cnt > 1).double()
+                ps = per_scene.double()
+                acc += torch.stack([(cnt * ps[:, 0]).sum(), (cnt * ps[:, 1]).sum(), (multi * ps[:, 2]).sum(),
+                                    (multi * ps[:, 3]).sum(), (multi * cnt * ps[:, 5]).sum(),
+                                    (multi * gt_scene[:, 2].double()).sum()])
+                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
+                if collect is not None:
+                    clear_h, ps_h, kb_h = clear.cpu().numpy(), per_scene.cpu().numpy(), kbest.cpu().numpy()
+                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
+                        a, b = batches[i + si]
+                        rec.update(clear=clear_h[:, a - lo:b - lo].copy(), per_scene=ps_h[si].copy(), kbest=int(kb_h[si]))
+                        collect.append(rec)
+        n_multi = sum(1 for a, b in batches if b - a > 1)
+        agents_multi = sum(b - a for a, b in batches if b - a > 1)
+        ade_avg, fde_avg, ade_min, fde_min = (sums / data.n_test_samples).tolist()
+        jade, jfde, joint, best, agent, gt = acc.tolist()
+        return dict(ade_avg=ade_avg, fde_avg=fde_avg, ade_min=ade_min, fde_min=fde_min,
+                    jade_min=jade / data.n_test_samples, jfde_min=jfde / data.n_test_samples,
+                    col_joint=joint / n_multi if n_multi else 0.0, col_best=best / n_multi if n_multi else 0.0,
+                    col_agent=agent / agents_multi if n_multi else 0.0, col_gt=gt / n_multi if n_multi else 0.0,
+                    n_scenes=len(batches), n_multi=n_multi)
 
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
