@@ -210,6 +210,18 @@ int sw_dec_sample_fwd(const float* obsv /*[B,To,2]*/, int To, const float* z /*[
  * in fp32 (s = s + e_k, then s / K): deterministic.  Sums over agents are the caller's (test() keeps them in float64). */
 int sw_sample_reduce(const float* err /*[K,B,2]*/, int B, int K, float* per_agent /*[B,4]*/, int* best /*[B] or NULL*/,
                      void* stream);
+/* Ranking of the K draws of every agent by a score (sw_disc_score; any [K,B] score works): order [B,M] int32,
+ * order[a][m] = the draw with the (m+1)-th HIGHEST score of agent a - for the raw LSGAN score higher is more realistic
+ * (targets 0 = generated, 1 = real; the optimal D is monotone in the density ratio).  Equal scores: the lowest k first,
+ * as in sw_sample_reduce; the order is that of a stable descending sort.  1 <= M <= K <= 4096 (SW_ESHAPE above).
+ * With err (the row errors [K,B,2] of sw_dec_sample_fwd), per_agent [B,5] = { ADE of order[a][0], FDE of order[a][0],
+ * min over the top M of ADE, min over the top M of FDE, the 0-based rank of draw best[a] in the full descending order:
+ * the number of k with score[k] > score[best], or == and k < best }.  best [B] = the min-ADE draw of sw_sample_reduce;
+ * NULL (or an index outside 0 .. K-1): column 4 is 0.  per_agent needs err (SW_EARG).  Columns 0-3 are selections and
+ * column 4 an integer count: no rounding anywhere, one owner per agent, two calls give the same bits.  Scores are
+ * expected to be ordered (no NaN).                                                                                  */
+int sw_sample_rank(const float* score /*[K,B]*/, const float* err /*[K,B,2] or NULL*/, const int* best /*[B] or NULL*/,
+                   int B, int K, int M, int* order /*[B,M]*/, float* per_agent /*[B,5] or NULL*/, void* stream);
 /* SCENE-LEVEL metrics of K joint draws (draw k of a scene = draw k of every agent in it).  B agents in S scenes,
  * scene_off [S+1] int32 prefix offsets (scene s = agents scene_off[s] .. scene_off[s+1]-1).
  *
@@ -334,6 +346,23 @@ int sw_disc_dpred(const float* obsv, int To, int x_mode, const float* pred4 /*[B
                   const float* targets, int t_idx, const float* z /*[B,32]*/, float g_label, float g_code,
                   float* dpred4 /*[B,Tp,4]*/, float* label /*[B,1] or NULL*/, float* code /*[B,2] or NULL*/,
                   float* loss_part /*or NULL*/, void* stream);
+
+/* ---- Discriminator.forward on K sampled futures per agent in one launch: the scoring twin of sw_dec_sample_fwd.
+ *      ROW ORDER: K*B rows, row r = k*B + a (the layout of sw_dec_sample_fwd's pred4).  PER ROW: pred4, score, code.
+ *      PER AGENT (read at a, never replicated): obsv - positions [B,To,2] (x_mode 0) or obsv_4d [B,To,4] (x_mode 1).
+ *        score [K*B]          the raw LSGAN score (higher = more realistic);
+ *        code  [K*B,2] or NULL  the InfoGAN head's estimate of the latent code z[:, :2] behind the draw.
+ *      score[k*B + a] / code[k*B + a] are the bits sw_disc_fwd(nb = 1) writes to label[a] / code[a] given
+ *      pred4 + k*B*Tp*4, with and without registered weight images (sw_disc_images): every row passes through the same
+ *      product chains in the same order.  Grid: ceil(B/16) tiles x k-groups workgroups; a workgroup runs the observation
+ *      LSTM and fc of its tile ONCE and the prediction heads for the draws of its k-range, two draws side by side on
+ *      its two wave pairs.  Every k-group repeats the observation pass, so their number is chosen from what is
+ *      there - min(CUs of the device / tiles, ceil(K/2)), at least 1: a small chunk fills the chip, a large one runs the
+ *      LSTM once per tile.  No save buffers, no atomics, one owner per output: deterministic.
+ *      SW_EARG: a NULL pointer (code may be NULL), K < 1, B < 0, To < 1, Tp < 1, x_mode not 0 / 1, To < 2 with x_mode 0;
+ *      SW_ESHAPE: Tp > 64.  B == 0: SW_OK without a launch.  LDS per workgroup: 89 600 B at Tp = 12, 149 504 B at 64.   */
+int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4 /*[K*B,Tp,4]*/, const float* d_w, int B, int K,
+                  int Tp, float* score /*[K*B]*/, float* code /*[K*B,2] or NULL*/, void* stream);
 
 /* ---- LSGAN + InfoGAN losses of train.py:484-494 / 512-523 and their gradients -------------- */
 /* t_a = targets[ia], t_b = targets[ib] (read on the device, so a captured hipGraph sees new values).

@@ -555,6 +555,165 @@ extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float*
   return SW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Scoring K sampled futures per agent (sw_disc_score): the discriminator-side twin of dec_sample_fwd_kernel.  Workgroup
+// (tile, k-group) runs the observation LSTM and the observation fc of its 16-agent tile ONCE, then the prediction heads
+// for every draw of its k-range, reading row k B + a of pred4 in place: two draws per pass, side by side on the two wave
+// pairs (waves 0, 1: draw k; 2, 3: draw k + 1 - a head layer is 2 row tiles, as in disc_update_kernel).  Every row goes
+// through the tile_mm_rt chains of disc_fwd_tile in its order, so score / code carry the bits of sw_disc_fwd(nb = 1) on
+// that draw.  Nothing is saved, every output element has one owner.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct ScoreLds {
+  HeadLds F;                            // forward head matrices, bias slots, o1 (at their HeadLds offsets)
+  int x, q1, both, c1, l1, total;       // two draw tiles each
+};
+__host__ __device__ inline ScoreLds score_lds(int Tp) {
+  ScoreLds S;
+  S.F = head_lds(Tp, 2 * 16 * SW_HLD);
+  int o = S.F.o1 + 16 * LD32;
+  // the prediction rows and q1 lie over of0 / of1 (their only readers, the observation fc, are done by then)
+  if (2 * 16 * S.F.ldp <= 32 * LD64) S.x = S.F.of0;
+  else { S.x = o; o += 2 * 16 * S.F.ldp; }
+  S.q1 = S.F.of1;                       // 32 * LD32 = 2 x [16][LD32]
+  S.both = o; o += 2 * 16 * LD64;
+  S.c1 = o; o += 2 * 16 * LD32;
+  S.l1 = o; o += 2 * 16 * LD32;
+  S.total = o;
+  return S;
+}
+}  // namespace
+
+__global__ __launch_bounds__(SW_THREADS) void disc_score_kernel(
+    const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred4, const float* __restrict__ d_w, int B, int K,
+    int Tp, float* __restrict__ score, float* __restrict__ code, int tiles, int kgroups, const float* __restrict__ dimg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* hbuf = smem;                   // [2][16][SW_HLD]
+  const ScoreLds S = score_lds(Tp);
+  const HeadLds& F = S.F;
+  const swp::Disc O = swp::disc(Tp);
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int br = wave >> 1, wp = wave & 1;              // br: the draw slot this wave's pair owns, wp: wave in the pair
+  const int kg = blockIdx.x / tiles;
+  const int a0 = (blockIdx.x - kg * tiles) * SW_TILE;
+  const int k_lo = (int)(((long long)kg * K) / kgroups), k_hi = (int)(((long long)(kg + 1) * K) / kgroups);
+  const int b = min(a0 + ln, B - 1);
+  const bool live = (a0 + ln) < B;
+  const int K4 = 4 * Tp, ldp = F.ldp;
+  const size_t draw = (size_t)B * K4;                    // floats of one draw of pred4
+
+  // the first two draws' prediction rows are requested now (longer horizons than Tp = 12 load in place)
+  const bool x_pre = 16 * ldp <= 4 * SW_THREADS;
+  float xpre[2][4];
+  disc_xpre_load(xpre, pred4 + (size_t)k_lo * draw, pred4 + (size_t)min(k_lo + 1, k_hi - 1) * draw, a0, B, K4, ldp);
+  LstmW W;
+  disc_obs_operands(W, d_w, O, dimg);
+  disc_stage_heads(smem, F, d_w, O, K4, 32 * (ldp >> 2) <= 2 * SW_THREADS);
+  f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};   // h0 = c0 = 0 (train.py:296-297)
+  disc_seed_h(hbuf, false, nullptr, To, B, b);
+  sw_barrier();
+  if (x_mode == 0) lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
+  else lstm_obs_loop<1, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
+  // observation fc (waves 0, 1) -> both[0 | 1][:, 0:32]
+  disc_obs_fc(smem, F, &hbuf[(To & 1) * 16 * SW_HLD], smem + F.o1, nullptr, live, smem + S.both, 2);
+
+  float* x_ = smem + S.x + br * 16 * ldp;
+  float* q1_ = smem + S.q1 + br * 16 * LD32;
+  float* both_ = smem + S.both + br * 16 * LD64;
+  float* c1_ = smem + S.c1 + br * 16 * LD32;
+  float* l1_ = smem + S.l1 + br * 16 * LD32;
+  const int m0 = 16 * wp;
+  for (int k = k_lo; k < k_hi; k += 2) {
+    const int k1 = min(k + 1, k_hi - 1);                 // an odd tail: slot 1 repeats draw k and stores nothing
+    sw_barrier();                                        // the observation fc / the previous pair are done with these tiles
+    if (x_pre) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) disc_xpre_put(xpre, s == 1, smem + S.x + s * 16 * ldp, nullptr, a0, B, K4, ldp);
+      if (k + 2 < k_hi)                                  // the next pair's rows arrive under this pair's heads
+        disc_xpre_load(xpre, pred4 + (size_t)(k + 2) * draw, pred4 + (size_t)min(k + 3, k_hi - 1) * draw, a0, B, K4, ldp);
+    } else {
+      for (int i = threadIdx.x; i < 2 * 16 * ldp; i += SW_THREADS) {
+        const int s = i / (16 * ldp), r = i - s * 16 * ldp;
+        const int a = r / ldp, cc = r - a * ldp;
+        smem[S.x + i] = cc < K4 ? pred4[(size_t)(s ? k1 : k) * draw + (size_t)min(a0 + a, B - 1) * K4 + cc] : 0.f;
+      }
+    }
+    sw_barrier();
+    {   // q1 = lrelu(pe0 x + b): row tile wp
+      f32x4 acc = ld4(smem + F.bias + 2 * 32 + m0 + 4 * lg);
+      acc = tile_mm_rt(smem + F.pe0 + (m0 + ln) * ldp + 4 * lg, x_ + ln * ldp + 4 * lg, (ldp - 4) / 16, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[r] = sw_lrelu(acc[r]);
+      st4(q1_ + ln * LD32 + m0 + 4 * lg, acc);
+    }
+    sw_barrier();
+    {   // pred_code = pe1 q1 + b -> both[br][:, 32:64]
+      f32x4 acc = ld4(smem + F.bias + 3 * 32 + m0 + 4 * lg);
+      acc = tile_mm_rt(smem + F.pe1 + (m0 + ln) * LD32 + 4 * lg, q1_ + ln * LD32 + 4 * lg, 2, acc);
+      st4(both_ + ln * LD64 + 32 + m0 + 4 * lg, acc);
+    }
+    sw_barrier();
+    {   // c1 = lrelu(cl0 both + b), l1 = lrelu(la0 both + b): row tile wp each
+      f32x4 ac = ld4(smem + F.bias + 4 * 32 + m0 + 4 * lg), al = ld4(smem + F.bias + 5 * 32 + m0 + 4 * lg);
+      ac = tile_mm_rt(smem + F.cl0 + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, ac);
+      al = tile_mm_rt(smem + F.la0 + (m0 + ln) * LD64 + 4 * lg, both_ + ln * LD64 + 4 * lg, 4, al);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        ac[r] = sw_lrelu(ac[r]);
+        al[r] = sw_lrelu(al[r]);
+      }
+      st4(c1_ + ln * LD32 + m0 + 4 * lg, ac);
+      st4(l1_ + ln * LD32 + m0 + 4 * lg, al);
+    }
+    sw_barrier();
+    {   // score = cl1 c1 + b (wave wp = 0), code_hat = la1 l1 + b (wp = 1)
+      const bool cls = wp == 0;
+      f32x4 acc = ld4(smem + F.bias + (cls ? 6 : 7) * 32 + 4 * lg);
+      acc = tile_mm_rt(smem + (cls ? F.cl1 : F.la1) + ln * LD32 + 4 * lg, (cls ? c1_ : l1_) + ln * LD32 + 4 * lg, 2, acc);
+      if (lg == 0 && live && k + br < k_hi) {
+        const size_t r = (size_t)(k + br) * B + b;
+        if (cls) score[r] = acc[0];
+        else if (code) { code[r * 2] = acc[0]; code[r * 2 + 1] = acc[1]; }
+      }
+    }
+  }
+}
+
+// The k-groups of a scoring launch: every group repeats the observation pass of its tile (8 LSTM steps against 2 head
+// passes per draw pair), so groups are added only while the launch leaves CUs idle, and never below one draw pair each.
+static int disc_score_kgroups(int tiles, int K) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+      n = SW_SPLIT_MAX_WGS;
+    cus = n;
+  }
+  const int by_cu = cus / tiles, by_k = (K + 1) / 2;
+  const int g = by_cu < by_k ? by_cu : by_k;
+  return g < 1 ? 1 : g;
+}
+
+extern "C" int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4, const float* d_w, int B, int K, int Tp,
+                             float* score, float* code, void* stream) {
+  if (!obsv || !pred4 || !d_w || !score || K < 1 || B < 0 || To < 1 || Tp < 1 || (x_mode != 0 && x_mode != 1) ||
+      (x_mode == 0 && To < 2))
+    return SW_EARG;
+  if (Tp > 64) return SW_ESHAPE;
+  if (B == 0) return SW_OK;
+  const int lds = score_lds(Tp).total * 4;
+  if (lds > 163840) return SW_ESHAPE;
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)disc_score_kernel, lds, have)) return rc;
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
+  const int kgroups = disc_score_kgroups(tiles, K);
+  if ((long long)tiles * kgroups > 0x7fffffffLL) return SW_ESHAPE;
+  SW_LAUNCH(disc_score_kernel, dim3((unsigned)(tiles * kgroups)), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode, pred4,
+            d_w, B, K, Tp, score, code, tiles, kgroups, sw_disc_images_for(d_w, Tp).img);
+  SW_CHECK_LAUNCH("disc_score_kernel");
+  return SW_OK;
+}
+
 extern "C" int sw_disc_dpred_supported(int Tp) { return Tp >= 1 && Tp <= 64 && disc_dpred_lds(Tp) <= 163840 ? 1 : 0; }
 
 // the weight-gradient problems of a discriminator pass over its saved / delta rows (dW = delta^T act per layer)

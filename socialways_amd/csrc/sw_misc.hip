@@ -718,6 +718,71 @@ extern "C" int sw_sample_reduce(const float* err, int B, int K, float* per_agent
   return SW_OK;
 }
 
+// ---- ranking K draws per agent by a score (sw_disc_score) ----------------------------------------------------------------
+//   score [K][B] -> order [B][M]: the draws of agent a by descending score, the lowest k first among equal scores.  One wave
+//   per agent, its K scores in LDS; lane l owns the draws k = l, l + 64, ... and counts for each the draws in front of it
+//   (score[j] > score[k], or == and j < k): a strict total order, so every rank 0 .. K-1 occurs once and order[a][rank] has
+//   one writer.  per_agent [B][5] = { ADE, FDE of order[a][0] | min over the top M of ADE, of FDE | the rank of best[a] }:
+//   selections and an integer count, combined by min / max / integer-sum reductions - no rounding, no summation order.
+#define SW_RANK_MAXK 4096
+__global__ __launch_bounds__(256) void sample_rank_kernel(const float* __restrict__ score, const float* __restrict__ err,
+                                                           const int* __restrict__ best, int B, int K, int M,
+                                                           int* __restrict__ order, float* __restrict__ per_agent) {
+  extern __shared__ __attribute__((aligned(16))) float rank_s[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int a = min((int)blockIdx.x * 4 + wave, B - 1);
+  const bool live = (int)blockIdx.x * 4 + wave < B;
+  float* s = rank_s + wave * K;
+  for (int k = lane; k < K; k += 64) s[k] = score[(size_t)k * B + a];
+  __syncthreads();
+  const float2* e = reinterpret_cast<const float2*>(err);
+  const float inf = __builtin_inff();
+  float ma = inf, mf = inf;
+  int k0 = -1, rb = 0;
+  const int kb = best ? best[a] : -1;
+  for (int k = lane; k < K; k += 64) {
+    const float v = s[k];
+    int r = 0;
+    for (int j = 0; j < K; ++j) {
+      const float u = s[j];
+      r += (u > v || (u == v && j < k)) ? 1 : 0;
+    }
+    if (r < M) {
+      if (live) order[(size_t)a * M + r] = k;
+      if (per_agent) {
+        const float2 ek = e[(size_t)k * B + a];
+        ma = fminf(ma, ek.x);
+        mf = fminf(mf, ek.y);
+      }
+    }
+    if (r == 0) k0 = k;
+    if (k == kb) rb = r;
+  }
+  if (!per_agent) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ma = fminf(ma, __shfl_xor(ma, o));
+    mf = fminf(mf, __shfl_xor(mf, o));
+    k0 = max(k0, __shfl_xor(k0, o));
+    rb = max(rb, __shfl_xor(rb, o));
+  }
+  if (lane == 0 && live) {
+    const float2 e0 = e[(size_t)max(k0, 0) * B + a];
+    float* p = per_agent + (size_t)a * 5;
+    p[0] = e0.x; p[1] = e0.y; p[2] = ma; p[3] = mf; p[4] = (float)rb;
+  }
+}
+extern "C" int sw_sample_rank(const float* score, const float* err, const int* best, int B, int K, int M, int* order,
+                              float* per_agent, void* stream) {
+  if (!score || !order || B < 0 || K < 1 || M < 1 || M > K || (per_agent && !err)) return SW_EARG;
+  if (K > SW_RANK_MAXK) return SW_ESHAPE;
+  if (B == 0) return SW_OK;
+  SW_LAUNCH(sample_rank_kernel, dim3((B + 3) / 4), dim3(256), 4 * K * sizeof(float), (hipStream_t)stream, score, err, best, B, K,
+            M, order, per_agent);
+  SW_CHECK_LAUNCH("sample_rank_kernel");
+  return SW_OK;
+}
+
 // ---- toy statistics: pairwise mean displacement between sample sets (calc_statistics.py:28-32, 56-60) ----
 //   D[k][i][j] = mean_{t >= t0} || a[i][k][t] - b[j][k][t] ||
 __global__ __launch_bounds__(256) void traj_dist_kernel(const float* __restrict__ a, const float* __restrict__ b, int Na,

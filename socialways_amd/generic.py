@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .model import _sample_noise, _scene_index, _wgrad_ws, get_traj_4d
+from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d
 from .trainer import SocialWaysTrainer
 
 
@@ -314,6 +314,15 @@ class Discriminator(nn.Module):                             # train.py:272-316
         both = torch.cat([obsv_code, pred_code], dim=1)
         return _mlp(self.classifier, both), _mlp(self.latent_decoder, both)
 
+    def score_samples(self, obsv, preds):
+        """The call of the 64-unit Discriminator.score_samples(): obsv (B, To, 2 | 4), preds (K, B, Tp, 4) -> (score (K, B),
+        code_hat (K, B, n_latent_code)).  At these widths it is forward() once per draw (no scoring kernel here).  No gradients."""
+        check_score_samples(obsv, preds, self.n_next)
+        with torch.no_grad():
+            o4 = get_traj_4d(obsv, []) if obsv.shape[2] == 2 else obsv
+            outs = [self.forward(o4, preds[k]) for k in range(preds.shape[0])]
+        return torch.stack([l[:, 0] for l, _ in outs]), torch.stack([c for _, c in outs])
+
     def load(self, backup):
         """Restore nn.Linear weights/biases only; the LSTM keeps its update (train.py:311-316)."""
         for m_from, m_to in zip(backup.modules(), self.modules()):
@@ -511,8 +520,9 @@ class GenericTrainer(SocialWaysTrainer):
         err = torch.stack([e.mean(2), e[:, :, -1]], dim=2).contiguous()
         n = obsv.shape[0]
         per_agent = torch.empty(n, 4, device=err.device)
-        L.call("sw_sample_reduce", L.ptr(err), n, K, L.ptr(per_agent), None, L.stream())
-        return ph.reshape(K * n, self.n_next, 4), per_agent, err
+        best = torch.empty(n, dtype=torch.int32, device=err.device)
+        L.call("sw_sample_reduce", L.ptr(err), n, K, L.ptr(per_agent), L.ptr(best), L.stream())
+        return ph.reshape(K * n, self.n_next, 4), per_agent, err, best
 
     def step_many(self, batches, sub_batches, ss=1.0, global_B=None, out=None, global_row0=0):
         return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0) for o, p, zv, ov, nz in batches]

@@ -652,6 +652,15 @@ class Discriminator(_Packed):
         labels, codes, _ = ops.disc_forward(self.packed(), obsv, [pred], save=False)
         return labels[0], codes[0]
 
+    def score_samples(self, obsv, preds):
+        """K futures per agent scored in one launch (ops.disc_score): obsv (B, To, 2) positions or (B, To, 4), preds
+        (K, B, Tp, 4) - what Generator.sample() returns -> (score (K, B) raw LSGAN score, higher = more realistic,
+        code_hat (K, B, 2)).  What K calls of forward(get_traj_4d(obsv), preds[k]) return, bit for bit, with the observation
+        encoded once.  No gradients."""
+        check_score_samples(obsv, preds, self.n_next)
+        with torch.no_grad():
+            return ops.disc_score(self.packed(), obsv, preds, preds.shape[0])
+
     def load(self, backup):
         """Restore nn.Linear weights/biases only; the LSTM keeps its update (train.py:311-316)."""
         for m_from, m_to in zip(backup.modules(), self.modules()):
@@ -780,6 +789,15 @@ class Generator(nn.Module):
             pred4, _ = ops.gen_sample(self.encoder.packed(), self.feature_embedder.packed(), self.attention.packed(),
                                       self.decoder.packed(), obsv_p, noise.reshape(K * B, 32), scenes, n_next, self.use_social, K)
         return pred4.view(K, B, n_next, 4)
+
+
+def check_score_samples(obsv, preds, n_next):
+    """The argument shapes of Discriminator.score_samples()."""
+    if obsv.dim() != 3 or obsv.shape[2] not in (2, 4) or obsv.shape[1] < (2 if obsv.shape[2] == 2 else 1):
+        raise ValueError("obsv must be (B, To >= 2, 2) or (B, To >= 1, 4), got %s" % (tuple(obsv.shape),))
+    if preds.dim() != 4 or preds.shape[0] < 1 or tuple(preds.shape[1:]) != (obsv.shape[0], n_next, 4):
+        raise ValueError("preds must be (K >= 1, B, n_next, 4) = (K, %d, %d, 4), got %s"
+                         % (obsv.shape[0], n_next, tuple(preds.shape)))
 
 
 def _sample_noise(noise, K, B, noise_len, device):

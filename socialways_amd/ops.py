@@ -493,6 +493,69 @@ def disc_forward(d_w, obsv, preds, save, ws=None, tag="d", save_lstm=True, w_sna
     return labels, codes, ctx
 
 
+def disc_score(d_w, obsv, pred4, K, want_code=True):
+    """Discriminator.forward on K futures per agent in ONE launch (sw_disc_score): obsv (B, To, 2 | 4) is read per agent -
+    its LSTM and fc run once per 16-agent tile -, pred4 (K * B, Tp, 4) or (K, B, Tp, 4) per row (row k * B + a = draw k of
+    agent a: what gen_sample returns, scored where it lies).  Returns (score (K, B) raw LSGAN score, code_hat (K, B, 2) or
+    None): the bits of K calls of disc_forward on the draws, with the weight images a caller has registered or without."""
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    if obsv.dim() != 3 or obsv.shape[2] not in (2, 4) or (obsv.shape[2] == 2 and obsv.shape[1] < 2) or obsv.shape[1] < 1:
+        raise ValueError("obsv must be (B, To >= 2, 2) or (B, To >= 1, 4), got %s" % (tuple(obsv.shape),))
+    B, To = obsv.shape[0], obsv.shape[1]
+    if pred4.dim() not in (3, 4) or pred4.shape[-1] != 4 or pred4.shape[-2] < 1 or pred4.numel() != K * B * pred4.shape[-2] * 4 \
+            or (pred4.dim() == 4 and tuple(pred4.shape[:2]) != (K, B)):
+        raise ValueError("pred4 must be (K * B, Tp, 4) or (K, B, Tp, 4) with K = %d, B = %d, got %s" % (K, B, tuple(pred4.shape)))
+    if pred4.device != obsv.device:
+        raise ValueError("pred4 must be on the device of obsv")
+    L.require_gpu(obsv)
+    obsv, pred4 = obsv.float().contiguous(), pred4.float().contiguous()
+    Tp = pred4.shape[-2]
+    score = torch.empty(K, B, device=obsv.device)
+    code = torch.empty(K, B, 2, device=obsv.device) if want_code else None
+    if B == 0:
+        return score, code
+    L.call("sw_disc_score", L.ptr(obsv), To, {2: 0, 4: 1}[obsv.shape[2]], L.ptr(pred4), L.ptr(d_w), B, K, Tp, L.ptr(score),
+           L.ptr(code), L.stream())
+    return score, code
+
+
+RANK_MAX_K = 4096      # sw_sample_rank holds an agent's K scores in LDS
+
+
+def sample_rank(score, K, M, err=None, best=None):
+    """order (B, M) int32: per agent its M highest-scored draws of K, best first, equal scores by ascending k - the first M
+    columns of a stable descending sort of score (K, B) over k (sw_sample_rank).  With err (K, B, 2), the row errors of
+    gen_sample, also per_agent (B, 5) = ADE | FDE of the top-scored draw, min over the top M of ADE | of FDE, the rank the
+    scores give draw best[a] (best (B,) int32, the min-ADE draw of gen_sample; 0 without it).  Returns (order, per_agent or None)."""
+    if score.dim() != 2 or score.shape[0] != K or K < 1:
+        raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
+    B = score.shape[1]
+    if not 1 <= M <= K:
+        raise ValueError("M must lie in 1 .. K = %d, got %d" % (K, M))
+    if K > RANK_MAX_K:
+        raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
+    if err is not None and (tuple(err.shape) != (K, B, 2) or err.device != score.device):
+        raise ValueError("err must be (K, B, 2) = (%d, %d, 2) on the device of score, got %s" % (K, B, tuple(err.shape)))
+    if best is not None:
+        if err is None:
+            raise ValueError("best is only used with err")
+        if tuple(best.shape) != (B,) or best.dtype != torch.int32 or best.device != score.device:
+            raise ValueError("best must be (B,) = (%d,) int32 on the device of score, got %s %s" % (B, tuple(best.shape), best.dtype))
+        best = best.contiguous()
+    L.require_gpu(score)
+    score = score.float().contiguous()
+    order = torch.empty(B, M, dtype=torch.int32, device=score.device)
+    per_agent = None
+    if err is not None:
+        err = err.float().contiguous()
+        per_agent = torch.empty(B, 5, device=score.device)
+    if B == 0:
+        return order, per_agent
+    L.call("sw_sample_rank", L.ptr(score), L.ptr(err), L.ptr(best), B, K, M, L.ptr(order), L.ptr(per_agent), L.stream())
+    return order, per_agent
+
+
 def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None, tag="d"):
     """Backward of Discriminator.forward.  d_d_w (packed, overwritten) None = no weight gradients;
     want_dpred[k] True = return d loss / d pred4 of branch k."""

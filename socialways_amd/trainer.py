@@ -26,7 +26,7 @@ import torch.optim as opt
 from . import _lib as L
 from . import ops
 from .data import shard_scenes
-from .model import Discriminator, Generator, predict_cv
+from .model import Discriminator, Generator, get_traj_4d, predict_cv
 
 
 class PackedAdam:
@@ -1026,13 +1026,13 @@ class SocialWaysTrainer:
 
     def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):
         """K draws of one chunk for evaluate_scenes(), by the launches of evaluate(): noise (K, n, noise_len) on the host ->
-        (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4), err (K, n, 2))."""
+        (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4), err (K, n, 2), best (n,) int32 = the min-ADE draw)."""
         G = self.G
         z = self._pad_z(noise).view(K * obsv.shape[0], -1).to(self.device)
         ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
                                  obsv, z, scenes, self.n_next, G.use_social, K, gt=pred, inv_ss=1.0 / float(ss),
                                  want_pred=False, keep_pred=True)
-        return ph, red[0], red[2]
+        return ph, red[0], red[2], red[1]
 
     def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
         """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
@@ -1067,7 +1067,7 @@ class SocialWaysTrainer:
                 noise = self.eval_noise(batches[i:j], K, self.noise_len)
                 sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
                 scenes = ops.SceneIndex.get(sb, n, obsv.device)
-                ph, per_agent, err = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
+                ph, per_agent, err, _ = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
                 per_scene, kbest, clear = ops.scene_metrics(err, ph, obsv, scenes, K, self.n_next, inv_ss, coll_dist)
                 gt_scene, _ = ops.scene_reduce(torch.zeros(1, n, 2, device=dev),
                                                ops.scene_clearance(pred, obsv[:, -1], scenes, 1, inv_ss), scenes, 1, coll_dist)
@@ -1093,6 +1093,77 @@ class SocialWaysTrainer:
                     col_joint=joint / n_multi if n_multi else 0.0, col_best=best / n_multi if n_multi else 0.0,
                     col_agent=agent / agents_multi if n_multi else 0.0, col_gt=gt / n_multi if n_multi else 0.0,
                     n_scenes=len(batches), n_multi=n_multi)
+
+    def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None):
+        """The deployment call - K draws, no ground truth, pick a few: the top_m of n_samples futures per agent that the
+        discriminator scores highest, best first.  obsv_p (B, To, 2), noise (K, B, noise_len) or None as Generator.sample().
+        Returns (trajs (M, B, n_next, 4), score (M, B) raw LSGAN score, non-increasing along M, order (B, M) int32: trajs[m, a]
+        is draw order[a, m]).  A sampling launch (Generator.sample), a scoring launch (Discriminator.score_samples), a
+        ranking launch (ops.sample_rank) and a gather."""
+        K, M = int(n_samples), int(top_m)
+        if not 1 <= M <= K:
+            raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
+        with torch.no_grad():
+            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise)
+            score, _ = self.D.score_samples(obsv_p, ph)
+            order, _ = ops.sample_rank(score, K, M)
+            idx = order.t().long()
+            trajs = ph.gather(0, idx[:, :, None, None].expand(M, ph.shape[1], self.n_next, 4))
+            return trajs, score.gather(0, idx), order
+
+    RANKED_KEYS = ("ade_top1", "fde_top1", "ade_topm", "fde_topm", "best_rank", "score_draws", "score_gt", "code_mse")
+
+    def evaluate_ranked(self, data, n_gen_samples=20, top_m=5, just_one=False, collect=None):
+        """evaluate() plus what the discriminator makes of its K draws WITHOUT the ground truth: it scores every draw
+        (Discriminator.score_samples: one launch, the observation encoded once), ranks them per agent (ops.sample_rank) and
+        the errors of the draws it prefers are read off.  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          ade_top1, fde_top1   the error of each agent's top-scored draw - what shipping D's choice costs;
+          ade_topm, fde_topm   per agent the minimum over its top_m highest-scored draws: ade_min <= ade_topm <= ade_top1;
+          best_rank            mean over agents of the rank D gives the min-ADE draw: 0 = always first, (K - 1) / 2 = a ranker
+                               without information;
+          score_draws, score_gt   mean raw LSGAN score over (draw, agent), and over the agents' ground-truth futures;
+          code_mse             mean over (draw, agent) of the mean squared difference between D's code_hat and the first
+                               columns of that draw's z: the InfoGAN term of the training losses, unweighted;
+          n_agents, K, top_m.
+        Per-agent sums are divided by data.n_test_samples like evaluate()'s, per-(draw, agent) sums by K times that; float64
+        sums on the device, one host sync at the end.  Chunking, host noise and sampling launches are evaluate()'s.  With
+        `collect` every record of evaluate() also has `score` (K, n), `order` (n, top_m) and `code_hat` (K, n, codes)."""
+        ss, dev, K, M = data.ss, self.device, int(n_gen_samples), int(top_m)
+        if not 1 <= M <= K:
+            raise ValueError("top_m must lie in 1 .. n_gen_samples = %d, got %d" % (K, M))
+        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        acc = torch.zeros(len(self.RANKED_KEYS), dtype=torch.float64, device=dev)
+        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
+        if just_one:
+            batches = batches[:1]
+        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
+            lo, hi = batches[i][0], batches[j - 1][1]
+            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
+            n = hi - lo
+            with torch.no_grad():
+                noise = self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
+                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
+                scenes = ops.SceneIndex.get(sb, n, obsv.device)
+                ph, per_agent, err, best = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
+                score, code = self.D.score_samples(obsv, ph.view(K, n, self.n_next, 4))
+                order, ranked = ops.sample_rank(score, K, M, err=err, best=best)
+                gt_score, _ = self.D.score_samples(obsv, get_traj_4d(obsv, pred)[1].unsqueeze(0))
+                csq = (code.double() - noise[:, :, :code.shape[-1]].double()).pow(2).mean(dim=2)
+                acc += torch.cat([ranked.double().sum(0), torch.stack([score.double().sum(), gt_score.double().sum(), csq.sum()])])
+                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
+                if collect is not None:
+                    sc_h, or_h, co_h = score.cpu().numpy(), order.cpu().numpy(), code.cpu().numpy()
+                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
+                        a, b = batches[i + si]
+                        rec.update(score=sc_h[:, a - lo:b - lo].copy(), order=or_h[a - lo:b - lo].copy(),
+                                   code_hat=co_h[:, a - lo:b - lo].copy())
+                        collect.append(rec)
+        nt = data.n_test_samples
+        out = dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min"), (sums / nt).tolist()))
+        out.update(zip(self.RANKED_KEYS, (acc / torch.tensor([nt] * 5 + [K * nt, nt, K * nt], dtype=torch.float64, device=dev)).tolist()))
+        out.update(n_agents=sum(b - a for a, b in batches), K=K, top_m=M)
+        return out
 
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
