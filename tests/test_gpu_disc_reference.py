@@ -8,6 +8,9 @@ LeakyReLU / ReLU kinks: where a pre-activation lies within fp32 rounding of 0 th
 may take different branches.  Every case draws its inputs from the first seed of SEEDS whose float64
 forward keeps all of them at least MARGIN away from 0; the seed and margin are in every assertion message.
 
+The two big-scene cases of the fused generator phase have no such seed: they take the seed with the fewest such inputs and
+compare gradients with close_grads_branch_consistent (tests/_ref64.py, which holds the shared pieces of this module).
+
 Tolerances (float64 reference): outputs elementwise rtol OUT_RT + atol OUT_AT * max|ref|; gradients per tensor
 max|err| <= GRAD_REL * max|ref|."""
 import contextlib
@@ -17,63 +20,18 @@ import pytest
 import torch
 
 import sw_oracle as O
+from _ref64 import (GRAD_REL, MARGIN, OUT_AT, OUT_RT, SEEDS, _close_grad, _close_out, _f64, _kink_margin, _observed,  # noqa: F401
+                    _pick, _report, close_grads_branch_consistent, gen_ambiguous, gen_mods, gen_params, pick_fewest, run64)
 from _util import assert_close
 
 pytestmark = pytest.mark.gpu
 
-SEEDS = (1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233)
-MARGIN = 2e-7
-OUT_RT, OUT_AT = 1e-5, 1e-6
-GRAD_REL = 2e-5
 W_INFO = 0.5
 TARGETS = (0.03, 0.96)
-
-_observed = {}      # group -> {"out": max err / max|ref|, "grad": ...}: printed at the end of the module (pytest -s)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for group, v in sorted(_observed.items()):
-        print("observed max error  %-12s outputs %.2e  gradients %.2e" % (group, v.get("out", 0.0), v.get("grad", 0.0)))
-
-
-def _note(group, kind, ratio):
-    g = _observed.setdefault(group, {})
-    g[kind] = max(g.get(kind, 0.0), ratio)
 
 
 def _dev():
     return torch.device("cuda:0")
-
-
-@contextlib.contextmanager
-def _f64():
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)     # the oracle builds its zero states with the default dtype
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
-
-
-def _close_out(got, ref, what, group, tag):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = max(float(ref.abs().max()), 1e-30)
-    _note(group, "out", float((got - ref).abs().max()) / scale)
-    assert_close(got.numpy(), ref.numpy(), OUT_RT, OUT_AT * scale, "%s (%s)" % (what, tag))
-
-
-def _close_grad(got, ref, what, group, tag, rel=GRAD_REL):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), "%s: non-finite entries (%s)" % (what, tag)
-    scale = float(ref.abs().max())
-    err = float((got - ref).abs().max())
-    if scale > 0:
-        _note(group, "grad", err / scale)
-    assert err <= rel * scale, "%s: max|err| %.3e > %.1e * max|ref| %.3e (%s)" % (what, err, rel, scale, tag)
 
 
 def _d64(D):
@@ -84,24 +42,6 @@ def _d64(D):
     return ref
 
 
-@contextlib.contextmanager
-def _kink_margin(*mods):
-    """Yields a list that ends up holding the smallest |input| of every (Leaky)ReLU run inside the block."""
-    seen, hooks = [], []
-    for mod in mods:
-        for m in mod.modules():
-            if isinstance(m, (torch.nn.LeakyReLU, torch.nn.ReLU)):
-                hooks.append(m.register_forward_hook(lambda m_, inp, out: seen.append(float(inp[0].detach().abs().min()))
-                                                     if inp[0].numel() else None))
-    box = [float("inf")]
-    try:
-        yield box
-    finally:
-        for h in hooks:
-            h.remove()
-        box[0] = min(seen, default=float("inf"))
-
-
 def _forward64(Dref, obsv, x_mode, preds):
     """float64 D forward of every branch -> ([label], [code], preds64 (leaves that collect d/dpred), kink margin)."""
     o = obsv.detach().cpu().double()
@@ -110,18 +50,6 @@ def _forward64(Dref, obsv, x_mode, preds):
     with _f64(), _kink_margin(Dref) as margin:
         outs = [Dref(o4, p) for p in p64]
     return [l for l, _ in outs], [c for _, c in outs], p64, margin[0]
-
-
-def _pick(make, margin_of):
-    """First seed of SEEDS whose float64 forward keeps every kink input above MARGIN: (seed, inputs, margin)."""
-    best = (None, 0.0)
-    for seed in SEEDS:
-        inp = make(seed)
-        m = margin_of(inp)
-        if m > MARGIN:
-            return seed, inp, m
-        best = max(best, (seed, m), key=lambda t: t[1])
-    raise AssertionError("no seed of %s keeps the kink inputs above %.1e (best: seed %s, %.2e)" % (SEEDS, MARGIN, *best))
 
 
 def _disc(Tp, wseed=0):
@@ -395,22 +323,28 @@ def _gen_pair(Tp):
     return G, D, orc
 
 
-def _gen_ref(orc, obsv, z, sb, Tp):
-    """float64 rollout and g_loss = mse(label, t1) + w_info mse(code, z[:, :2]) through the oracle's predict() and D."""
-    for name in ("encoder", "feature_embedder", "attention", "decoder"):
-        getattr(orc, name).zero_grad()
+def _gen_ref(orc, obsv, z, sb, Tp, seed):
+    """float64 rollout and g_loss = mse(label, t1) + w_info mse(code, z[:, :2]) through the oracle's predict() and D, kept
+    with its graph and its (Leaky)ReLU records (D's included) for close_grads_branch_consistent."""
     o, z64 = obsv.double(), z.double()
-    with _f64(), _kink_margin(orc.encoder, orc.feature_embedder, orc.attention, orc.decoder, orc.D) as margin:
+    t1 = float(torch.tensor(TARGETS[1], dtype=torch.float32))
+
+    def fn():
         pred = orc.predict(o, z64, Tp, sb)
         label, code = orc.D(O.get_traj_4d(o, []), pred)
-    t1 = float(torch.tensor(TARGETS[1], dtype=torch.float32))
-    ((label - t1) ** 2).mean().add(W_INFO * ((code - z64[:, :2]) ** 2).mean()).backward()
-    parts = torch.stack([((label - t1) ** 2).sum(1), ((code - z64[:, :2]) ** 2).sum(1)], 1).detach()
-    return pred.detach(), parts, margin[0]
+        loss = ((label - t1) ** 2).mean().add(W_INFO * ((code - z64[:, :2]) ** 2).mean())
+        parts = torch.stack([((label - t1) ** 2).sum(1), ((code - z64[:, :2]) ** 2).sum(1)], 1).detach()
+        return loss, (pred.detach(), parts)
+
+    run, (pred, parts) = run64(gen_params(orc), gen_mods(orc) + [orc.D], fn, seed)
+    return pred, parts, run
 
 
 @pytest.mark.parametrize("To,Tp,sizes", [(8, 12, [1, 5, 16, 2, 13, 1, 40, 7]), (2, 1, [3, 1, 1, 9]),
-                                         (5, 20, [8] * 20 + [1, 3]), (5, 5, [2] * 30 + [1]), (2, 12, [1, 1, 1])])
+                                         (5, 20, [8] * 20 + [1, 3]), (5, 5, [2] * 30 + [1]), (2, 12, [1, 1, 1]),
+                                         # big scenes: the row-block social kernels / the metric shape under the fused D
+                                         # pass.  No seed clears MARGIN there: fewest ambiguous units, flips assigned
+                                         (8, 12, [70, 5, 130, 64, 1]), (8, 12, [8] * 256)])
 def test_generator_phase_inside_the_decode_bptt_against_float64(To, Tp, sizes):
     from socialways_amd import ops
     dev = _dev()
@@ -422,8 +356,9 @@ def test_generator_phase_inside_the_decode_bptt_against_float64(To, Tp, sizes):
         g = torch.Generator().manual_seed(seed)
         return (torch.randn(B, To, 2, generator=g) * 0.1).cumsum(1), torch.rand(B, 32, generator=g)
 
-    seed, (obsv, z), margin = _pick(make, lambda inp: _gen_margin(orc, inp[0], inp[1], sb, Tp))
-    tag = "seed %d, kink margin %.2e" % (seed, margin)
+    # the first seed of SEEDS that clears MARGIN (the first five cases have one), else the one with the fewest ambiguous units
+    seed, (obsv, z), n_amb = pick_fewest(make, lambda inp: _gen_ambiguous(orc, inp[0], inp[1], sb, Tp))
+    tag = "seed %d, %d kink inputs within %.1e of 0" % (seed, n_amb, MARGIN)
     enc, emb, att, dec = G.encoder, G.feature_embedder, G.attention, G.decoder
     grads = {m: torch.full_like(m._flat, float("nan")) for m in (enc, emb, att, dec)}
     targets = torch.tensor(TARGETS, device=dev)
@@ -436,22 +371,20 @@ def test_generator_phase_inside_the_decode_bptt_against_float64(To, Tp, sizes):
         ops.gen_backward(enc._flat, emb._flat, att._flat, dec._flat, ctx, None, grads[enc], grads[emb], grads[att], grads[dec],
                          ws=ws, dfuse=(D._flat, pred_hat, targets, 1, zd, 1.0 / B, W_INFO / (2.0 * B), part))
         torch.cuda.synchronize()
-    pred64, parts64, _ = _gen_ref(orc, obsv, z, sb, Tp)
+    pred64, parts64, run = _gen_ref(orc, obsv, z, sb, Tp, seed)
     _close_out(pred_hat, pred64, "rollout", "gen_phase", tag)
     _check_parts(part.cpu(), parts64, B, (0, 1), "gen_phase", tag)
+    got = {}
     for name, m in (("encoder", enc), ("feature_embedder", emb), ("attention", att), ("decoder", dec)):
-        got = dict(zip([k for k, _ in m.named_parameters()], m.split_grad(grads[m])))
-        for k, q in getattr(orc, name).named_parameters():
-            ref = torch.zeros_like(q) if q.grad is None else q.grad      # single-agent scenes only: no social pairs
-            _close_grad(got[k], ref, "dG/d%s.%s" % (name, k), "gen_phase", tag)
+        got.update(zip([name + "." + k for k, _ in m.named_parameters()], m.split_grad(grads[m])))
+    # no ambiguous unit (the first five cases): _close_grad on every tensor; a parameter without a reference gradient
+    # (single-agent scenes only: no social pairs) must come out as zeros
+    close_grads_branch_consistent(got, run, "gen_phase", tag)
 
 
-def _gen_margin(orc, obsv, z, sb, Tp):
+def _gen_ambiguous(orc, obsv, z, sb, Tp):
     o, z64 = obsv.double(), z.double()
-    with torch.no_grad(), _f64(), _kink_margin(orc.encoder, orc.feature_embedder, orc.attention, orc.decoder, orc.D) as m:
-        pred = orc.predict(o, z64, Tp, sb)
-        orc.D(O.get_traj_4d(o, []), pred)
-    return m[0]
+    return gen_ambiguous(orc, lambda: orc.D(O.get_traj_4d(o, []), orc.predict(o, z64, Tp, sb)), [orc.D])
 
 
 # ---- §2: long horizons through the trainer (the one-launch generator-phase pass does not fit from Tp = 25 on) -----------

@@ -35,12 +35,19 @@ def test_step_matches_oracle_on_odd_shapes(sizes, To, Tp):
     sb = data.the_batches[:len(sizes)]
     torch.manual_seed(3)
     noise = torch.rand(B, 32)
+    rec = {}
     out = tr.step(data.obsv[:B], data.pred[:B], sb, 0.07, 0.91, noise, data.ss)
     got = tr.losses_from(out, [B], Tp, data.ss)[0]
-    want, ade, fde = orc.train_step(data.obsv[:B].cpu(), data.pred[:B].cpu(), sb, 0.07, 0.91, noise, data.ss)
+    want, ade, fde = orc.train_step(data.obsv[:B].cpu(), data.pred[:B].cpu(), sb, 0.07, 0.91, noise, data.ss, record=rec)
     assert_close(got, np.asarray(want), 5e-5, 2e-6, "9 MSE terms")
     o = out.double().cpu().numpy()
     assert abs(o[-1, 0] - ade) < 1e-4 * max(1.0, abs(ade)) and abs(o[-1, 1] - fde) < 1e-4 * max(1.0, abs(fde))
+    # the weights after the first Adam step only carry the SIGN of each gradient: compare the gradients themselves
+    assert_close(tr.last_pred_hat.cpu(), rec["pred_hat_4d"], 3e-5, 3e-6, "rollout")
+    for name in ("attention", "feature_embedder", "encoder", "decoder"):
+        for k, p in getattr(tr.G, name).named_parameters():
+            w = rec["g_grads"][name + "." + k]
+            assert_close(p.grad.cpu(), w, 2e-4, 2e-4 * max(float(w.abs().max()), 1e-12), "dG %s.%s" % (name, k))
     for name, mod in (("encoder", tr.G.encoder), ("decoder", tr.G.decoder), ("D", tr.D)):
         ref = getattr(orc, name).state_dict()
         for k, v in mod.state_dict().items():      # after Adam: elementwise agreement bounded by ~lr (see check_weights)
