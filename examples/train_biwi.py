@@ -37,6 +37,9 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--out", default="/tmp/sw_biwi")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device-noise", type=int, default=None, metavar="SEED",
+                    help="draw z on the device from the counter-based stream with this seed (sw.DeviceNoise: every rank fills "
+                         "the rows of its shard, evaluation repeats call to call); default: the reference's host streams")
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -65,6 +68,8 @@ def main(argv=None):
     np.random.seed(args.seed)
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
                               process_group=pg)
+    if args.device_noise is not None:     # the same seed on every rank: the union of the shards is the single-process z
+        tr.noise = sw.DeviceNoise(args.device_noise)
     for epoch in range(1, args.epochs + 1):
         t0 = time.perf_counter()
         ade, fde, losses, sizes = tr.train_epoch(data, args.batch_size)
@@ -73,7 +78,8 @@ def main(argv=None):
                   % (epoch, ade, fde, time.perf_counter() - t0, len(sizes), losses[:, 0].mean() + losses[:, 2].mean(),
                      losses[:, -2].mean()))
         if rank == 0 and (epoch % args.test_every == 0 or epoch == args.epochs):
-            m = tr.test(data, n_gen_samples=args.k, write_to_file=os.path.join(args.out, "preds", str(epoch)))
+            run_test = tr.test if tr.noise is None else tr.evaluate      # evaluate(): test()'s contract, z from tr.noise
+            m = run_test(data, n_gen_samples=args.k, write_to_file=os.path.join(args.out, "preds", str(epoch)))
             print("Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f)" % (m[0], m[1], args.k, m[2], m[3]))
             sm = tr.evaluate_scenes(data, n_gen_samples=args.k)      # the K draws as JOINT futures of each scene
             print("Scene level: joint Min(%d) ADE,FDE = (%.3f, %.3f) | collisions < 0.1: %.1f %% of draws, %.1f %% of best draws, "

@@ -34,6 +34,9 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=20, help="samples per scene in test()")
     ap.add_argument("--out", default="/tmp/sw_toy")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device-noise", type=int, default=None, metavar="SEED",
+                    help="draw z on the device from the counter-based stream with this seed (sw.DeviceNoise); default: the "
+                         "reference's host streams")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -43,6 +46,8 @@ def main(argv=None):
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social),
                               n_unrolling_steps=args.unrolling_steps,
                               device="cuda:0")
+    if args.device_noise is not None:     # z of training and evaluation from the device stream; saved with the checkpoint
+        tr.noise = sw.DeviceNoise(args.device_noise)
     real = np.concatenate((toy["obsvs"], toy["preds"]), axis=1).reshape((-1, 6, 4, 2))[:args.k]
     pred_root = os.path.join(args.out, "preds")
     os.makedirs(args.out, exist_ok=True)
@@ -53,7 +58,8 @@ def main(argv=None):
               % (epoch, ade, fde, time.perf_counter() - t0, losses[:, 0].mean() + losses[:, 2].mean(),
                  losses[:, -2].mean(), losses[:, -1].mean()))
         if epoch % args.test_every == 0 or epoch == args.epochs:
-            m = tr.test(data, n_gen_samples=args.k, write_to_file=os.path.join(pred_root, str(epoch)))
+            run_test = tr.test if tr.noise is None else tr.evaluate      # evaluate(): test()'s contract, z from tr.noise
+            m = run_test(data, n_gen_samples=args.k, write_to_file=os.path.join(pred_root, str(epoch)))
             print("Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f)" % (m[0], m[1], args.k, m[2], m[3]))
             tr.save(os.path.join(args.out, "toy.pt"))
     s1, sw_ = sw.stats.calc_and_store_stats(pred_root, real, 2, 2, stats_file=os.path.join(args.out, "stats%d.npz" % args.k))

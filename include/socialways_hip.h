@@ -620,6 +620,22 @@ int sw_allreduce_direct_adam(void* const* peer_bufs, int rank, int world, long l
 int sw_ade_fde(const float* pred4 /*[B,Tp,4]*/, const float* gt /*[B,Tp,2]*/, int B, int Tp, float inv_ss,
                float* out /*[3]*/, float* scratch /*[3*SW_RED_BLOCKS] or NULL*/, void* stream);
 
+/* ---- the counter-based device noise stream (csrc/sw_noise.hip; train.py:473 / :584 draw z ~ U[0,1) from torch's CPU generator,
+ *      which stays the default): every z value is a pure function of (seed, domain, step, draw, row, column), so any rank,
+ *      chunk or tile produces exactly its rows in one launch, evaluation repeats call to call and a checkpoint that carries
+ *      {seed, step} continues the same stream.  Philox4x32-10, standard constants (multipliers 0xD2511F53 / 0xCD9E8D57, key
+ *      increments 0x9E3779B9 / 0xBB67AE85): key = (seed low, seed high 32 bits), counter = (row, draw, step,
+ *      (column >> 2) + 256 domain); the four output words are columns 4b .. 4b+3 of column block b; value =
+ *      float(word >> 8) * 2^-24 - exact, in [0, 1), torch.rand's 24-bit grid.  domain 0 = training, 1 = evaluation / sampling.
+ *        out[((t n_draws + k) rows + i) ld + j] = the value at (step0 + t, draw0 + k, row0 + i, j) for j < cols, 0 for
+ *        cols <= j < ld (the zero padding to the kernels' SW_Z noise columns comes out of the same launch).
+ *      One thread per (row, 4-column block), one 16-byte store each; no LDS, no atomics, no host synchronisation, no
+ *      allocation: capturable in a hipGraph.  Checked before any device call - SW_EARG: domain outside 0 .. 1, cols outside
+ *      1 .. 1024, ld < cols or ld % 4, out NULL or not 16-byte aligned, a count below 1, row0 + rows / draw0 + n_draws /
+ *      step0 + n_steps past 2^32; SW_ESHAPE: n_steps n_draws rows ld / 4 above 2^31 - 1 (the kernel's 32-bit float4 index). */
+int sw_noise_uniform(unsigned long long seed, int domain, unsigned step0, int n_steps, unsigned draw0, int n_draws,
+                     unsigned row0, int rows, int cols, int ld, float* out /*[n_steps][n_draws][rows][ld]*/, void* stream);
+
 /* ==== MEASUREMENT SECTION - not part of the product surface (the drop-in boundary ends above this line; tests/test_abi.py
  *      checks the two lists separately).  sw_kernel_timing(1): every kernel launch of the library is bracketed by two HIP
  *      events on its own stream (never inside a graph capture) until sw_kernel_timing(0); sw_kernel_timing_read(buf, cap)

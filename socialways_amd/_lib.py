@@ -124,6 +124,7 @@ PROTOTYPES = {
     "sw_allreduce_direct": (_i, [_vp, _i, _i, _ll, _vp, _ll, _vp]),
     "sw_allreduce_direct_adam": (_i, [_vp, _i, _i, _ll, _vp, _ll, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, ctypes.c_double, _i, _vp]),
+    "sw_noise_uniform": (_i, [ctypes.c_ulonglong, _i, ctypes.c_uint, _i, ctypes.c_uint, _i, ctypes.c_uint, _i, _i, _i, _vp, _vp]),
 }
 
 # the header's MEASUREMENT section (include/socialways_hip.h, behind the product surface): bench.py's per-kernel event pass

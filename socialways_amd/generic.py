@@ -383,9 +383,10 @@ class Generator(nn.Module):
                 h, c = self.encoder.step(last, h, c)
         return torch.stack(out, dim=1)
 
-    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None):
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0):
         """n_samples futures per agent, (K, B, n_next, 4) - the call of the 64-unit Generator.sample().  At these widths it is
-        forward() on K copies of the batch, each copy with its scenes (no sampling kernels here).  No gradients."""
+        forward() on K copies of the batch, each copy with its scenes (no sampling kernels here).  No gradients.  A DeviceNoise
+        is refused (the device noise stream belongs to the fused 64-unit path)."""
         L.require_gpu(obsv_p)
         K, B = int(n_samples), obsv_p.shape[0]
         noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
@@ -507,8 +508,25 @@ class GenericTrainer(SocialWaysTrainer):
         self.last_pred_hat = fake
         return res
 
-    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None):
+    # the device noise stream (DeviceNoise) is wired into the fused 64-unit trainer only: these paths are frozen
+    @property
+    def noise(self):
+        return None
+
+    @noise.setter
+    def noise(self, value):
+        self._device_noise(value)
+
+    def _device_noise(self, noise):
+        if noise is not None:
+            raise L.SocialWaysHipError("%s does not take a DeviceNoise: the device noise stream is implemented for the fused "
+                                       "64-unit SocialWaysTrainer only (hidden_size <= 64, n_latent_codes = 2); leave noise = None "
+                                       "for the reference's host stream" % type(self).__name__)
+        return None
+
+    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None, noise=None):
         """The contract of SocialWaysTrainer.evaluate(); at these widths it is test() (no sampling kernels)."""
+        self._device_noise(noise)
         return self.test(data, n_gen_samples, False, write_to_file, just_one, collect)
 
     def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):

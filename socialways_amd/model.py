@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .noise import EVAL, DeviceNoise
 
 
 # ------------------------------------------------------------------------------------------------
@@ -773,15 +774,22 @@ class Generator(nn.Module):
                                    self.decoder.packed(), obsv_p, noise, scenes, n_next, self.use_social, save=False)
         return pred4
 
-    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None):
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0):
         """n_samples futures per agent: pred_hat_4d (K, B, n_next, 4), sample k of agent a at [k, a] - what K calls of
         forward() on the same observations give, with the observation encoding and the social block computed once
-        (ops.gen_sample).  noise (K, B, noise_len) or None = torch.rand on the device.  No gradients."""
+        (ops.gen_sample).  noise (K, B, noise_len), None = torch.rand on the device, or a DeviceNoise: its evaluation
+        domain at step 0, draws 0 .. K-1, rows row0 .. row0 + B-1 (one launch that also writes the zero padding; the same
+        agents at the same rows get the same futures whatever else is in the batch's other scenes).  No gradients."""
         L.require_gpu(obsv_p)
         if obsv_p.dim() != 3 or obsv_p.shape[2] != 2 or obsv_p.shape[1] < 2:
             raise ValueError("obsv_p must be (B, To >= 2, 2), got %s" % (tuple(obsv_p.shape),))
         K, B = int(n_samples), obsv_p.shape[0]
-        noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
+        if isinstance(noise, DeviceNoise):
+            if K < 1:
+                raise ValueError("n_samples must be at least 1")
+            noise = noise.fill(B, self.noise_len, domain=EVAL, n_draws=K, row0=row0, ld=32, device=obsv_p.device)[0]
+        else:
+            noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
         if noise.shape[-1] < 32:     # as forward(): zero-padded to the kernels' 32 noise columns
             noise = nn.functional.pad(noise, (0, 32 - noise.shape[-1]))
         scenes = _scene_index(sub_batches, B, obsv_p.device)
@@ -806,6 +814,9 @@ def _sample_noise(noise, K, B, noise_len, device):
         raise ValueError("n_samples must be at least 1")
     if noise is None:
         return torch.rand(K, B, noise_len, device=device)
+    if isinstance(noise, DeviceNoise):      # Generator.sample() of the fused path fills from it before it gets here
+        raise L.SocialWaysHipError("this Generator does not take a DeviceNoise: the device noise stream is implemented for the "
+                                   "fused 64-unit path only; pass a (n_samples, B, %d) tensor or None" % noise_len)
     if noise.dim() != 3 or tuple(noise.shape) != (K, B, noise_len):
         raise ValueError("noise must be (n_samples, B, %d) = (%d, %d, %d), got %s"
                          % (noise_len, K, B, noise_len, tuple(noise.shape)))
@@ -829,12 +840,12 @@ def predict(obsv_p, noise, n_next, sub_batches=[], generator=None):
     return g(obsv_p, noise, n_next, sub_batches)
 
 
-def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None):
+def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None, row0=0):
     """Module-level Generator.sample(): n_samples futures per agent, (K, B, n_next, 4), from `generator` (or the default one)."""
     g = generator or _default_generator
     if g is None:
         raise RuntimeError("no generator: pass generator= or call set_default_generator()")
-    return g.sample(obsv_p, n_samples, n_next, sub_batches, noise)
+    return g.sample(obsv_p, n_samples, n_next, sub_batches, noise, row0=row0)
 
 
 def predict_cv(obsv, n_next):

@@ -27,6 +27,7 @@ from . import _lib as L
 from . import ops
 from .data import shard_scenes
 from .model import Discriminator, Generator, get_traj_4d, predict_cv
+from .noise import EVAL, TRAIN, DeviceNoise
 
 
 class PackedAdam:
@@ -161,6 +162,7 @@ class SocialWaysTrainer:
     Z_COLS = 32             # noise columns of the kernels (hidden size 64: train.py:81); smaller models are zero-padded
     _direct = None          # the direct gradient exchange (SW_ALLREDUCE=direct / auto; the fused trainer only) and what the
     exchange_probe = None   # auto mode's probe measured - class-level defaults: the wider trainers have their own __init__
+    noise = None            # a DeviceNoise: z of train_epoch() / evaluate*() from the device stream; None = the reference's host streams
 
     def __new__(cls, n_next=None, hidden_size=64, *args, **kw):
         """Widths above the fused kernels' 64 units and latent-code counts other than 2 (train.py:42-44, 65) train on
@@ -175,6 +177,21 @@ class SocialWaysTrainer:
                 return object.__new__(WideTrainer)
             return object.__new__(GenericTrainer)
         return object.__new__(cls)
+
+    def _device_noise(self, noise):
+        """The DeviceNoise a call works with: its `noise` argument, else self.noise; None = the host stream."""
+        dn = self.noise if noise is None else noise
+        if dn is not None and not isinstance(dn, DeviceNoise):
+            raise TypeError("noise must be a DeviceNoise or None, got %s" % type(dn).__name__)
+        return dn
+
+    def _eval_z(self, dn, batches, K, lo, n):
+        """The (K * n, Z_COLS) z of one evaluation chunk, rows lo .. lo + n-1 of the held-out tracks: from the device stream
+        (evaluation domain, row = the ABSOLUTE held-out row, so a scene's draws do not depend on the chunking; one launch
+        that also writes the padding), else the reference's host stream (eval_noise), padded and copied."""
+        if dn is not None:
+            return dn.fill(n, self.noise_len, domain=EVAL, n_draws=K, row0=lo, ld=self.Z_COLS, device=self.device).view(K * n, -1)
+        return self._pad_z(self.eval_noise(batches, K, self.noise_len)).view(K * n, -1).to(self.device)
 
     def _pad_z(self, z):
         return z if z.shape[-1] == self.Z_COLS else torch.nn.functional.pad(z, (0, self.Z_COLS - z.shape[-1]))
@@ -456,7 +473,7 @@ class SocialWaysTrainer:
         self._vnoise = None
         if self.use_variety_loss == "fixed":          # z of the samples 1..K-1: ((K-1)*B, 32), drawn like train.py:473 if not given
             vn = variety_noise if variety_noise is not None else torch.rand((self.variety_k - 1) * B, self.noise_len)
-            if vn.shape != ((self.variety_k - 1) * B, self.noise_len):
+            if vn.dim() != 2 or vn.shape[0] != (self.variety_k - 1) * B or vn.shape[1] not in (self.noise_len, self.Z_COLS):
                 raise ValueError("variety_noise must be ((variety_k - 1) * B, %d)" % self.noise_len)
             self._vnoise = self._pad_z(vn.to(dev, non_blocking=True)).contiguous()
         part = None
@@ -803,9 +820,16 @@ class SocialWaysTrainer:
 
     def train_epoch(self, data, batch_size, draw=None):
         """train() (train.py:439-557).  `draw(bs)` -> (zeros_val, ones_val, noise_cpu) overrides the
-        RNG draws of train.py:471-473 (tests feed the reference's recorded values)."""
+        RNG draws of train.py:471-473 (tests feed the reference's recorded values).
+        With `self.noise` (a DeviceNoise) and no `draw`, z comes from the device stream's training domain: step =
+        noise.step, counted once per packed batch on every rank; draw 0 = the step's z, draws 1 .. variety_k-1 the extra
+        samples of use_variety_loss="fixed"; row = the row in the GLOBAL packed batch, so a rank fills only its shard and
+        the union over ranks is the single-process z.  The z of the batches that share a step_many launch is one fill
+        launch in front of the graph launch on the same stream, read by the steps through their z-resident path (no
+        pinned-slot copy).  The label-noise scalars stay the reference's two host draws."""
         outs, sizes = [], []
         pend, pend_key = [], None        # consecutive packed batches of one layout share a graph launch
+        dn = self._device_noise(None) if draw is None else None
         if self.world > 1 and draw is None:
             self.sync_rng()
         if self._direct is not None and self.world > 1:
@@ -816,19 +840,30 @@ class SocialWaysTrainer:
         def flush():
             nonlocal pend, pend_key
             if pend:
-                outs.extend(self.step_many([p[0] for p in pend], pend[0][1], data.ss, global_B=pend[0][2],
-                                           global_row0=pend[0][3]))
+                items = [p[0] for p in pend]
+                if dn is not None:      # the z of these consecutive steps: one fill launch in front of their graph launch
+                    r0 = pend[0][3]
+                    z = dn.fill(items[0][0].shape[0], self.noise_len, domain=TRAIN, step=pend[0][4], n_steps=len(pend), row0=r0,
+                                ld=self.Z_COLS, device=self.device)
+                    items = [it[:4] + (z[j, 0],) for j, it in enumerate(items)]
+                outs.extend(self.step_many(items, pend[0][1], data.ss, global_B=pend[0][2], global_row0=pend[0][3]))
                 pend, pend_key = [], None
         for a, b, sb in data.packed_steps(batch_size):
             bs = b - a
+            vn = step_i = None
             if draw is None:
                 zv = np.random.uniform(0, 0.1)                               # train.py:471
                 ov = np.random.uniform(0.9, 1.0)                             # train.py:472
-                noise = torch.rand(bs, self.noise_len)                       # train.py:473 (CPU generator)
+                if dn is None:
+                    noise = torch.rand(bs, self.noise_len)                   # train.py:473 (CPU generator)
+                else:                   # every rank counts every packed batch, with or without a scene of it
+                    noise, step_i = None, dn.step
+                    dn.step += 1
             else:
-                zv, ov, noise = draw(bs)
-            vn = None
-            if self.use_variety_loss == "fixed":      # z of the extra samples, drawn for the whole packed batch
+                zv, ov, noise, *extra = draw(bs)
+                vn = extra[0] if extra else None      # optional 4th value: the (variety_k - 1, bs, noise_len) z of "fixed"
+            fixed = self.use_variety_loss == "fixed"
+            if fixed and vn is None and dn is None:   # z of the extra samples, drawn for the whole packed batch
                 vn = torch.rand(self.variety_k - 1, bs, self.noise_len)
             sizes.append((bs, len(sb)))
             r0, r1, sbl = 0, bs, sb
@@ -840,18 +875,23 @@ class SocialWaysTrainer:
                     continue
                 r0, r1 = int(sb[lo, 0]), int(sb[hi - 1, 1])
                 sbl = sb[lo:hi] - r0
-            item = (data.obsv[a + r0:a + r1], data.pred[a + r0:a + r1], zv, ov, noise[r0:r1])
-            if vn is not None:        # the folded K-sample step is not graph-captured: one step() per packed batch
+            item = (data.obsv[a + r0:a + r1], data.pred[a + r0:a + r1], zv, ov, noise[r0:r1] if noise is not None else None)
+            if fixed:                 # the folded K-sample step is not graph-captured: one step() per packed batch
                 flush()
-                outs.append(self.step(*item[:2], sbl, zv, ov, item[4], data.ss, global_B=bs, global_row0=r0,
-                                      variety_noise=vn[:, r0:r1].reshape(-1, self.noise_len)))
+                if dn is not None:    # draws 0 .. variety_k-1 of this rank's rows in one launch, padded to the kernels' width
+                    z = dn.fill(r1 - r0, self.noise_len, domain=TRAIN, step=step_i, n_draws=self.variety_k, row0=r0,
+                                ld=self.Z_COLS, device=self.device)[0]
+                    z0, vnl = z[0], z[1:].reshape(-1, self.Z_COLS)
+                else:
+                    z0, vnl = item[4], vn[:, r0:r1].reshape(-1, self.noise_len)
+                outs.append(self.step(*item[:2], sbl, zv, ov, z0, data.ss, global_B=bs, global_row0=r0, variety_noise=vnl))
                 continue
             # consecutive packed batches with the same local layout share one graph launch (step_many)
             key = (bs, r0, np.asarray(sbl).tobytes())
             if key != pend_key or len(pend) == self.STEPS_PER_LAUNCH:
                 flush()
                 pend_key = key
-            pend.append((item, sbl, bs, r0))
+            pend.append((item, sbl, bs, r0, step_i))
         flush()
         allo = torch.stack(outs)
         self._allreduce(allo)
@@ -989,11 +1029,15 @@ class SocialWaysTrainer:
                            preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
                            preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
 
-    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None):
+    def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None, noise=None):
         """The contract of test() (train.py:563-616; without its `linear` branch) on the sampling path: the same four
-        return values, prediction files, host noise stream and folding of scenes.  Per chunk the observations are encoded
-        and pooled ONCE, one launch rolls out the K copies and forms their errors (ops.gen_sample), the mean / min over K
-        is reduced on the device; the K x n trajectories leave the kernel only when a file or `collect` wants them."""
+        return values, prediction files, host noise stream and folding of scenes.  `noise` (default self.noise): a
+        DeviceNoise replaces the host stream by the device stream's evaluation domain - draw k of held-out row r is a
+        function of (seed, k, r) alone, so two calls agree and TEST_CHUNK / just_one do not change a scene's draws.
+        Per chunk the observations are encoded and pooled ONCE, one launch rolls out the K copies and forms their errors
+        (ops.gen_sample), the mean / min over K is reduced on the device; the K x n trajectories leave the kernel only when a
+        file or `collect` wants them."""
+        dn = self._device_noise(noise)
         ss, dev, K = data.ss, self.device, n_gen_samples
         G = self.G
         sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
@@ -1006,11 +1050,11 @@ class SocialWaysTrainer:
             obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
             n = hi - lo
             with torch.no_grad():
-                noise = self._pad_z(self.eval_noise(batches[i:j], K, self.noise_len)).view(K * n, -1).to(dev)
+                z = self._eval_z(dn, batches[i:j], K, lo, n)
                 sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
                 scenes = ops.SceneIndex.get(sb, n, obsv.device)
                 ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(),
-                                         G.decoder.packed(), obsv, noise, scenes, self.n_next, G.use_social, K,
+                                         G.decoder.packed(), obsv, z, scenes, self.n_next, G.use_social, K,
                                          gt=pred, inv_ss=1.0 / float(ss), want_pred=want_pred)
                 if want_pred:
                     for _, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
@@ -1025,8 +1069,9 @@ class SocialWaysTrainer:
         return ade_avg, fde_avg, ade_min, fde_min
 
     def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):
-        """K draws of one chunk for evaluate_scenes(), by the launches of evaluate(): noise (K, n, noise_len) on the host ->
-        (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4), err (K, n, 2), best (n,) int32 = the min-ADE draw)."""
+        """K draws of one chunk for evaluate_scenes(), by the launches of evaluate(): noise (K, n, noise_len) on the host, or
+        (K, n, Z_COLS) already padded on the device -> (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4),
+        err (K, n, 2), best (n,) int32 = the min-ADE draw)."""
         G = self.G
         z = self._pad_z(noise).view(K * obsv.shape[0], -1).to(self.device)
         ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
@@ -1050,7 +1095,10 @@ class SocialWaysTrainer:
           n_scenes, n_multi    scenes evaluated, and those of two or more agents (0: the col_* are 0).
         Chunking, host noise and sampling launches are evaluate()'s; per chunk two more launches (ops.scene_metrics) work on
         the draws where they are and the same two on the ground truth; sums are float64 on the device, one host sync at the end.  With `collect` every
-        record of evaluate() also has `clear` (K, n), `per_scene` (6,) and `kbest` (columns: ops.scene_reduce)."""
+        record of evaluate() also has `clear` (K, n), `per_scene` (6,) and `kbest` (columns: ops.scene_reduce).
+        With self.noise set (a DeviceNoise) the draws are evaluate()'s from that stream.  This call's argument list is pinned
+        (tests/test_scene_host.py), so the stream reaches it through the attribute only, not through a keyword."""
+        dn = self._device_noise(None)
         ss, dev, K = data.ss, self.device, n_gen_samples
         inv_ss = 1.0 / float(ss)
         sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
@@ -1064,7 +1112,8 @@ class SocialWaysTrainer:
             obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
             n = hi - lo
             with torch.no_grad():
-                noise = self.eval_noise(batches[i:j], K, self.noise_len)
+                noise = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
+                    self.eval_noise(batches[i:j], K, self.noise_len)
                 sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
                 scenes = ops.SceneIndex.get(sb, n, obsv.device)
                 ph, per_agent, err, _ = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
@@ -1094,9 +1143,10 @@ class SocialWaysTrainer:
                     col_agent=agent / agents_multi if n_multi else 0.0, col_gt=gt / n_multi if n_multi else 0.0,
                     n_scenes=len(batches), n_multi=n_multi)
 
-    def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None):
+    def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None, row0=0):
         """The deployment call - K draws, no ground truth, pick a few: the top_m of n_samples futures per agent that the
-        discriminator scores highest, best first.  obsv_p (B, To, 2), noise (K, B, noise_len) or None as Generator.sample().
+        discriminator scores highest, best first.  obsv_p (B, To, 2), noise (K, B, noise_len), None or a DeviceNoise (rows from
+        `row0`) as Generator.sample().
         Returns (trajs (M, B, n_next, 4), score (M, B) raw LSGAN score, non-increasing along M, order (B, M) int32: trajs[m, a]
         is draw order[a, m]).  A sampling launch (Generator.sample), a scoring launch (Discriminator.score_samples), a
         ranking launch (ops.sample_rank) and a gather."""
@@ -1104,7 +1154,7 @@ class SocialWaysTrainer:
         if not 1 <= M <= K:
             raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
         with torch.no_grad():
-            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise)
+            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0)
             score, _ = self.D.score_samples(obsv_p, ph)
             order, _ = ops.sample_rank(score, K, M)
             idx = order.t().long()
@@ -1113,7 +1163,7 @@ class SocialWaysTrainer:
 
     RANKED_KEYS = ("ade_top1", "fde_top1", "ade_topm", "fde_topm", "best_rank", "score_draws", "score_gt", "code_mse")
 
-    def evaluate_ranked(self, data, n_gen_samples=20, top_m=5, just_one=False, collect=None):
+    def evaluate_ranked(self, data, n_gen_samples=20, top_m=5, just_one=False, collect=None, noise=None):
         """evaluate() plus what the discriminator makes of its K draws WITHOUT the ground truth: it scores every draw
         (Discriminator.score_samples: one launch, the observation encoded once), ranks them per agent (ops.sample_rank) and
         the errors of the draws it prefers are read off.  Returns a dict:
@@ -1128,7 +1178,9 @@ class SocialWaysTrainer:
           n_agents, K, top_m.
         Per-agent sums are divided by data.n_test_samples like evaluate()'s, per-(draw, agent) sums by K times that; float64
         sums on the device, one host sync at the end.  Chunking, host noise and sampling launches are evaluate()'s.  With
-        `collect` every record of evaluate() also has `score` (K, n), `order` (n, top_m) and `code_hat` (K, n, codes)."""
+        `collect` every record of evaluate() also has `score` (K, n), `order` (n, top_m) and `code_hat` (K, n, codes).
+        `noise`: as evaluate() - a DeviceNoise (default self.noise) gives evaluate(noise=...)'s draws."""
+        dn = self._device_noise(noise)
         ss, dev, K, M = data.ss, self.device, int(n_gen_samples), int(top_m)
         if not 1 <= M <= K:
             raise ValueError("top_m must lie in 1 .. n_gen_samples = %d, got %d" % (K, M))
@@ -1142,7 +1194,8 @@ class SocialWaysTrainer:
             obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
             n = hi - lo
             with torch.no_grad():
-                noise = self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
+                noise = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
+                    self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
                 sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
                 scenes = ops.SceneIndex.get(sb, n, obsv.device)
                 ph, per_agent, err, best = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
@@ -1167,16 +1220,19 @@ class SocialWaysTrainer:
 
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
-        """The reference's checkpoint dict (train.py:653-663)."""
+        """The reference's checkpoint dict (train.py:653-663), plus a 'noise' entry ({seed, step}) when self.noise is set."""
         G = self.G
-        return {'epoch': self.epoch if epoch is None else epoch,
-                'attentioner_dict': G.attention.state_dict(),
-                'feature_embedder_dict': G.feature_embedder.state_dict(),
-                'encoder_dict': G.encoder.state_dict(),
-                'decoder_dict': G.decoder.state_dict(),
-                'pred_optimizer': self.predictor_optimizer.state_dict(),
-                'D_dict': self.D.state_dict(),
-                'D_optimizer': self.D_optimizer.state_dict()}
+        ck = {'epoch': self.epoch if epoch is None else epoch,
+              'attentioner_dict': G.attention.state_dict(),
+              'feature_embedder_dict': G.feature_embedder.state_dict(),
+              'encoder_dict': G.encoder.state_dict(),
+              'decoder_dict': G.decoder.state_dict(),
+              'pred_optimizer': self.predictor_optimizer.state_dict(),
+              'D_dict': self.D.state_dict(),
+              'D_optimizer': self.D_optimizer.state_dict()}
+        if self.noise is not None:       # the device stream continues where it stood; without one the dict is the reference's
+            ck['noise'] = self.noise.state_dict()
+        return ck
 
     def save(self, path, epoch=None):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -1202,6 +1258,10 @@ class SocialWaysTrainer:
                 for k, v in keep.items():
                     optim.param_groups[0][k] = v
         self.epoch = int(ck.get('epoch', 0))
+        if 'noise' in ck:                # written by a trainer with a DeviceNoise: the same stream goes on
+            if self.noise is None:
+                self.noise = DeviceNoise(0)
+            self.noise.load_state_dict(ck['noise'])
         if self.pg is not None and self.world > 1:
             self.sync_replicas()
         return self.epoch + 1
