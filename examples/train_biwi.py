@@ -40,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--device-noise", type=int, default=None, metavar="SEED",
                     help="draw z on the device from the counter-based stream with this seed (sw.DeviceNoise: every rank fills "
                          "the rows of its shard, evaluation repeats call to call); default: the reference's host streams")
+    ap.add_argument("--diverse", type=float, default=None, metavar="RADIUS",
+                    help="also report the diverse top-5 of the K draws: modes kept by suppressing, in the discriminator's score "
+                         "order, every draw whose end point lies within RADIUS (world units) of a kept one")
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -86,6 +89,12 @@ def main(argv=None):
                   "%.1f %% of agents (ground truth %.1f %%) | %d scenes, %d with company"
                   % (args.k, sm["jade_min"], sm["jfde_min"], 100 * sm["col_joint"], 100 * sm["col_best"], 100 * sm["col_agent"],
                      100 * sm["col_gt"], sm["n_scenes"], sm["n_multi"]))
+            if args.diverse is not None:
+                dv = tr.evaluate_diverse(data, n_gen_samples=args.k, top_m=min(5, args.k), radius=args.diverse)
+                print("Diverse top-%d (radius %.2f): ADE,FDE first = (%.3f, %.3f), best mode = (%.3f, %.3f) | %.2f modes per agent, "
+                      "first mode holds %.0f %% of the draws, the min-ADE mode %.0f %%"
+                      % (dv["top_m"], args.diverse, dv["ade_div1"], dv["fde_div1"], dv["ade_divm"], dv["fde_divm"], dv["n_modes"],
+                         100 * dv["w_first"], 100 * dv["w_hit"]))
             tr.save(os.path.join(args.out, "socialWays-crowd.pt"), epoch=epoch)
     if world > 1:
         tr.close()              # captured collectives and the direct exchange's buffers go before their process group

@@ -247,6 +247,36 @@ int sw_scene_clearance(const float* pos, int pstride, const float* start /*or NU
  * calls give the same bits.                                                                                          */
 int sw_scene_reduce(const float* err /*[K,B,2]*/, const float* clear /*[K,B] or NULL*/, const int* scene_off, int S, int B,
                     int K, float coll_dist, float* per_scene /*[S,6]*/, int* best /*[S] or NULL*/, void* stream);
+/* DIVERSE top-M of K draws: greedy non-maximum suppression in score order, and the share of the K draws behind every kept
+ * mode.  A GROUP is a scene (scene_off [S+1] as above: its rows scene_off[s] .. scene_off[s+1]-1, G = S groups) or, with
+ * scene_off == NULL, a single row (G = B).  All fp32:
+ *   d_a(j,k)  between draws j and k of row a: metric 0 ("fde") inv_ss * the Euclidean distance at step Tp-1; metric 1 ("ade")
+ *             inv_ss * the mean over the Tp steps of that distance (summed over t ascending, divided by Tp);
+ *   D_g(j,k)  = the maximum over the rows a of group g of d_a(j,k): two joint futures are one mode only if every agent agrees;
+ *   s_g(k)    = the minimum over the rows of g of score[k][a]: a joint future is as realistic as its least realistic agent.
+ * Both are selections: no sum over agents, no order dependence (over no rows: s_g = +inf, D_g = 0).  The loop: all K draws
+ * start alive; for m = 0 .. M-1, unless none is alive, the pick c_m is the alive draw with the largest s_g (the lowest k of
+ * equal ones), and every alive k with D_g(k, c_m) <= radius - c_m among them - is removed with assign[k] = m.  count[g] =
+ * the number of picks.  Draws that are still alive then (only with count == M) get assign[k] = the m with the smallest
+ * D_g(k, c_m), the lowest m of equal ones.
+ *   pos     [K,B,Tp,pstride], pstride 2 or 4 floats, x and y first (pred4 of sw_dec_sample_fwd, read where it lies), 8-byte
+ *           aligned;  score [K,B] (sw_disc_score; ordered, no NaN);  1 <= M <= K <= 4096;  inv_ss > 0;  radius >= 0 in the
+ *           units of inv_ss * distance;
+ *   order   [G,M] int32: c_m, -1 from count[g] on;   count [G] int32;   assign [G,K] int32;
+ *   weight  [G,M]: #{k : assign[k] == m} / K, one integer-to-float division, 0 from count[g] on; every row sums to 1;
+ *   per_row [B,6] or NULL, needs err [K,B,2] (the row errors of sw_dec_sample_fwd, 8-byte aligned): for row a of group g
+ *           { ADE of draw c_0, FDE of draw c_0, min over the picks of ADE, of FDE, weight[g][assign[g][best[a]]],
+ *           (float) assign[g][best[a]] } - best [B] int32 = the min-ADE draw of sw_sample_reduce; NULL or an index outside
+ *           0 .. K-1: columns 4 and 5 are 0.  Rows outside every scene are not written.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, score, order, count, weight, assign; B < 0;
+ * K < 1; M < 1 or M > K; Tp < 1; pstride not 2 or 4; metric not 0 or 1; radius < 0 or NaN; inv_ss <= 0 or NaN; per_row without
+ * err; scene_off with S < 0; pos or err off their 8-byte alignment.  SW_ESHAPE: K > 4096.  B == 0 (or no scenes): SW_OK
+ * without a launch.  One wave per group, one writer per output element, no atomics: two calls give the same bits.
+ * LDS per workgroup: 4 * (6 * roundup(K, 8) + 2 * roundup(M, 8)) bytes, 131 072 at K = M = 4096.                        */
+int sw_sample_nms(const float* pos, int pstride, const float* score /*[K,B]*/, const int* scene_off /*[S+1] or NULL*/, int S,
+                  int B, int K, int Tp, int M, int metric, float inv_ss, float radius, const float* err /*[K,B,2] or NULL*/,
+                  const int* best /*[B] or NULL*/, int* order /*[G,M]*/, int* count /*[G]*/, float* weight /*[G,M]*/,
+                  int* assign /*[G,K]*/, float* per_row /*[B,6] or NULL*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

@@ -556,6 +556,68 @@ def sample_rank(score, K, M, err=None, best=None):
     return order, per_agent
 
 
+NMS_METRICS = {"fde": 0, "ade": 1}
+
+
+def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, err=None, best=None):
+    """Diverse top-M of K draws (sw_sample_nms): greedy suppression in score order - the highest-scored draw is kept, every
+    draw within `radius` of it (metric "fde": inv_ss * the distance at the last step, "ade": inv_ss * the mean distance over
+    the steps) joins its mode, and so on among the rest, M times at most.  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y
+    first; score (K, B).  scenes (a SceneIndex): a group is a scene - draw k of a scene is draw k of each of its agents, two
+    joint draws are one mode only if every agent is within the radius, and a joint draw scores as its lowest-scored agent;
+    None: every row is a group.  With G groups returns (order (G, M) int32: the kept draws, best first, -1 past count;
+    count (G,) int32; weight (G, M): the share of the K draws assigned to each kept mode, rows sum to 1; assign (G, K) int32:
+    the mode of every draw; per_row (B, 6) or None without err: ADE | FDE of the first pick, min over the picks of ADE | of
+    FDE, the weight | the index of the mode that holds draw best[a]).  err (K, B, 2) and best (B,) int32 as gen_sample
+    returns them."""
+    if score.dim() != 2 or score.shape[0] != K or K < 1:
+        raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
+    B = score.shape[1]
+    if not 1 <= M <= K:
+        raise ValueError("M must lie in 1 .. K = %d, got %d" % (K, M))
+    if K > RANK_MAX_K:
+        raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
+    if metric not in NMS_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (sorted(NMS_METRICS), metric))
+    if not float(radius) >= 0.0:
+        raise ValueError("radius must be >= 0, got %r" % (radius,))
+    if not float(inv_ss) > 0.0:
+        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    if pos.dim() not in (3, 4) or pos.shape[-1] not in (2, 4) or pos.shape[-2] < 1 \
+            or pos.numel() != K * B * pos.shape[-2] * pos.shape[-1] or (pos.dim() == 4 and tuple(pos.shape[:2]) != (K, B)):
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
+    if pos.device != score.device:
+        raise ValueError("pos must be on the device of score")
+    if scenes is not None and scenes.B != B:
+        raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
+    if err is not None and (tuple(err.shape) != (K, B, 2) or err.device != score.device):
+        raise ValueError("err must be (K, B, 2) = (%d, %d, 2) on the device of score, got %s" % (K, B, tuple(err.shape)))
+    if best is not None:
+        if err is None:
+            raise ValueError("best is only used with err")
+        if tuple(best.shape) != (B,) or best.dtype != torch.int32 or best.device != score.device:
+            raise ValueError("best must be (B,) = (%d,) int32 on the device of score, got %s %s" % (B, tuple(best.shape), best.dtype))
+        best = best.contiguous()
+    L.require_gpu(score)
+    score, pos = score.float().contiguous(), pos.float().contiguous()
+    dev = score.device
+    G = scenes.S if scenes is not None else B
+    order = torch.empty(G, M, dtype=torch.int32, device=dev)
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    weight = torch.empty(G, M, device=dev)
+    assign = torch.empty(G, K, dtype=torch.int32, device=dev)
+    per_row = None
+    if err is not None:
+        err = err.float().contiguous()
+        per_row = torch.empty(B, 6, device=dev)
+    if B == 0:
+        return order, count, weight, assign, per_row
+    L.call("sw_sample_nms", L.ptr(pos), pos.shape[-1], L.ptr(score), L.ptr(scenes.scene_off) if scenes is not None else None,
+           G if scenes is not None else 0, B, K, pos.shape[-2], M, NMS_METRICS[metric], float(inv_ss), float(radius), L.ptr(err),
+           L.ptr(best), L.ptr(order), L.ptr(count), L.ptr(weight), L.ptr(assign), L.ptr(per_row), L.stream())
+    return order, count, weight, assign, per_row
+
+
 def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None, tag="d"):
     """Backward of Discriminator.forward.  d_d_w (packed, overwritten) None = no weight gradients;
     want_dpred[k] True = return d loss / d pred4 of branch k."""

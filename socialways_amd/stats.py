@@ -5,7 +5,8 @@ with device reductions; the K x K assignment problems go to scipy's Hungarian so
 the reference (calc_statistics.py:62).
 
 Beyond the reference: `scene_clearance`, the closest approach between the agents of a scene along K joint futures - the
-quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere."""
+quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere - and
+`sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise."""
 import os
 
 import numpy as np
@@ -122,3 +123,26 @@ def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
     scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
     clear = ops.scene_clearance(t4, start, scenes, K, float(scale))
     return clear if t.dim() == 4 else clear[0]
+
+
+def sample_modes(trajs, score, radius, top_m, metric="fde", sub_batches=None, scale=1.0, device="cuda"):
+    """The modes among K scored futures (`sw_sample_nms`), for trajectories and scores from anywhere: the highest-scored
+    draw is kept, every draw within `radius` of it is counted to its mode, then the highest-scored of the rest, top_m times
+    at most.  trajs (K, B, T, 2 | 4), x and y first; score (K, B), higher = better; the distance between two draws is `scale`
+    times the Euclidean distance at the last step (metric "fde") or its mean over the T steps ("ade").  sub_batches None:
+    every agent on its own; (S, 2) [start, end) rows tiling [0, B), [] = one scene: per scene, draw k of a scene being
+    draw k of each of its agents - one mode only if every agent is within the radius, scored as the lowest-scored agent.
+    Returns device tensors over the G = B or S groups: order (G, top_m) int32 (the kept draws, best first, -1 past count),
+    count (G,) int32, weight (G, top_m) (the share of the K draws in each mode, rows sum to 1), assign (G, K) int32 (the
+    mode of every draw)."""
+    t, s = _dev(trajs, device), _dev(score, device)
+    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    K, B = t.shape[0], t.shape[1]
+    if tuple(s.shape) != (K, B):
+        raise ValueError("score must be (K, B) = (%d, %d), got %s" % (K, B, tuple(s.shape)))
+    L.require_gpu(t)
+    scenes = None
+    if sub_batches is not None:
+        scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    return ops.sample_nms(t, s, K, int(top_m), radius, metric, scenes, inv_ss=float(scale))[:4]

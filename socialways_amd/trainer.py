@@ -1218,6 +1218,125 @@ class SocialWaysTrainer:
         out.update(n_agents=sum(b - a for a, b in batches), K=K, top_m=M)
         return out
 
+    @staticmethod
+    def _gather_picks(values, idx, fill):
+        """values (K, B, ...) at idx (M, B) along K; `fill` where idx is -1 (a slot past the group's count)."""
+        tail = (1,) * (values.dim() - 2)
+        valid = (idx >= 0).view(idx.shape + tail)
+        at = idx.clamp(min=0).view(idx.shape + tail).expand(idx.shape + tuple(values.shape[2:]))
+        return torch.where(valid, values.gather(0, at), torch.full((), fill, dtype=values.dtype, device=values.device))
+
+    def sample_diverse(self, obsv_p, n_samples, top_m, radius, metric="fde", joint=False, sub_batches=[], noise=None, row0=0,
+                       scale=1.0):
+        """sample_ranked() without the near-duplicates: of n_samples futures the highest-scored one is kept, every draw within
+        `radius` of it (metric "fde": distance at the last step, "ade": mean distance over the steps, both times `scale` -
+        the `scale` of stats.scene_clearance) counts as the same mode, then the highest-scored of the rest, top_m times at
+        most (ops.sample_nms).  joint=False: per agent.  joint=True: per scene of sub_batches - draw k of a scene is draw k of
+        each of its agents; two joint draws are one mode only if every agent is within the radius, and a joint draw scores
+        as its lowest-scored agent.  obsv_p, noise, row0 as sample_ranked().
+        Returns (trajs (M, B, n_next, 4), weight, score (M, B), order, count): order (B, M) int32, weight (B, M) = the share of
+        the n_samples draws that fell to each kept mode (rows sum to 1) and count (B,) int32 = the modes found - per scene
+        with joint=True: (S, M), (S, M), (S,), and trajs[m, a] is draw order[scene of a, m] of agent a, score[m, a] that draw's
+        own score.  Per agent the scores do not increase along M.  Slots from count on: zeros in trajs, -inf in score, 0 in
+        weight, -1 in order.  Sampling, scoring, one suppression launch and a gather."""
+        K, M = int(n_samples), int(top_m)
+        if not 1 <= M <= K:
+            raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
+        with torch.no_grad():
+            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0)
+            score, _ = self.D.score_samples(obsv_p, ph)
+            B = ph.shape[1]
+            scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device) if joint else None
+            order, count, weight, _, _ = ops.sample_nms(ph, score, K, M, radius, metric, scenes, inv_ss=scale)
+            rows = order
+            if joint:      # the scene of every row: the number of scene ends at or below it
+                rows = order[torch.bucketize(torch.arange(B, device=ph.device), scenes.scene_off[1:].long(), right=True)]
+            idx = rows.t().long()
+            return self._gather_picks(ph, idx, 0.0), weight, self._gather_picks(score, idx, float("-inf")), order, count
+
+    DIVERSE_KEYS = ("ade_div1", "fde_div1", "ade_divm", "fde_divm", "rank_hit", "w_hit", "n_modes", "w_first")
+
+    def evaluate_diverse(self, data, n_gen_samples=20, top_m=5, radius=0.5, metric="fde", joint=False, just_one=False,
+                         collect=None, noise=None):
+        """evaluate() plus what a diverse selection of its K draws is worth: the draws are scored as in evaluate_ranked() and
+        reduced to at most top_m modes per group by greedy suppression in score order (ops.sample_nms; `radius` in world
+        units through data.ss like the coll_dist of evaluate_scenes(), metric "fde" or "ade").  A group is an agent, or with
+        joint=True a held-out scene (draw k of a scene is draw k of each of its agents).  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          ade_div1, fde_div1   the error of each agent's draw in the first pick of its group;
+          ade_divm, fde_divm   per agent the minimum over the kept modes: ade_min <= ade_divm <= ade_div1;
+          n_modes              mean over the groups of the modes found (<= top_m);
+          w_first              mean over the groups of the weight of the first pick (its share of the K draws);
+          w_hit                mean over the agents of the weight of the mode that holds the agent's min-ADE draw: the
+                               probability the selection gives the right mode;
+          rank_hit             mean over the agents of the index of that mode (0 = the first pick);
+          jade_divm, jfde_divm (joint=True only) per scene the minimum over the picks of the scene's MEAN error, summed with
+                               the scene's agent count like jade_min of evaluate_scenes(): jade_min <= jade_divm;
+          n_agents, n_groups, K, top_m, radius, metric.
+        Per-agent sums are divided by data.n_test_samples like evaluate_ranked()'s (at radius 0 ade_div1 / ade_divm are its
+        ade_top1 / ade_topm bit for bit; like them, ade_divm at top_m = K and radius 0 is ade_min up to the last bit of that
+        division and to the bit where 1 / n_test_samples is exact), per-group sums by n_groups; float64 sums on the
+        device, one host sync at the end.  Chunking, noise streams and sampling launches are evaluate_ranked()'s.  With
+        `collect` every record of evaluate() also has `order`, `count`, `weight` and `assign` of its scene: (n, top_m), (n,),
+        (n, top_m), (n, K) per agent, or (top_m,), a number, (top_m,), (K,) with joint=True."""
+        dn = self._device_noise(noise)
+        ss, dev, K, M = data.ss, self.device, int(n_gen_samples), int(top_m)
+        if not 1 <= M <= K:
+            raise ValueError("top_m must lie in 1 .. n_gen_samples = %d, got %d" % (K, M))
+        if metric not in ops.NMS_METRICS:
+            raise ValueError("metric must be one of %s, got %r" % (sorted(ops.NMS_METRICS), metric))
+        inv_ss = 1.0 / float(ss)
+        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        acc = torch.zeros(len(self.DIVERSE_KEYS) + 2, dtype=torch.float64, device=dev)      # ... | sum n * jade | sum n * jfde
+        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
+        if just_one:
+            batches = batches[:1]
+        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
+            lo, hi = batches[i][0], batches[j - 1][1]
+            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
+            n = hi - lo
+            with torch.no_grad():
+                z = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
+                    self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
+                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
+                scenes = ops.SceneIndex.get(sb, n, obsv.device)
+                ph, per_agent, err, best = self._sample_chunk(obsv, pred, z, scenes, sb, K, ss)
+                score, _ = self.D.score_samples(obsv, ph.view(K, n, self.n_next, 4))
+                order, count, weight, assign, per_row = ops.sample_nms(ph, score, K, M, radius, metric, scenes if joint else None,
+                                                                       inv_ss=inv_ss, err=err, best=best)
+                # the first five columns summed in the shape evaluate_ranked() sums its own: the same bits at radius 0
+                part = [torch.cat([per_row[:, :4], per_row[:, 5:6]], dim=1).double().sum(0),
+                        torch.stack([per_row[:, 4].double().sum(), count.double().sum(), weight[:, 0].double().sum()])]
+                if joint:
+                    off = scenes.scene_off.long()
+                    cnt = (off[1:] - off[:-1]).double()
+                    run = torch.cat([torch.zeros(K, 1, 2, dtype=torch.float64, device=dev), err.double().cumsum(1)], dim=1)
+                    mean = ((run[:, off[1:]] - run[:, off[:-1]]) / cnt[None, :, None]).permute(1, 0, 2)      # (S, K, 2)
+                    at = order.long().clamp(min=0)[:, :, None].expand(-1, -1, 2)
+                    picked = torch.where((order >= 0)[:, :, None], mean.gather(1, at), torch.full_like(mean[:, :1], float("inf")))
+                    part.append((cnt[:, None] * picked.min(dim=1)[0]).sum(0))
+                else:
+                    part.append(torch.zeros(2, dtype=torch.float64, device=dev))
+                acc += torch.cat(part)
+                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
+                if collect is not None:
+                    or_h, cn_h, we_h, as_h = order.cpu().numpy(), count.cpu().numpy(), weight.cpu().numpy(), assign.cpu().numpy()
+                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
+                        a, b = batches[i + si]
+                        r = si if joint else slice(a - lo, b - lo)
+                        rec.update(order=or_h[r].copy(), count=cn_h[r].copy(), weight=we_h[r].copy(), assign=as_h[r].copy())
+                        collect.append(rec)
+        nt, n_agents = data.n_test_samples, sum(b - a for a, b in batches)
+        n_groups = len(batches) if joint else n_agents
+        out = dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min"), (sums / nt).tolist()))
+        div = torch.tensor([nt] * 6 + [n_groups] * 2 + [nt] * 2, dtype=torch.float64, device=dev)
+        vals = (acc / div).tolist()
+        out.update(zip(self.DIVERSE_KEYS, vals))
+        if joint:
+            out.update(jade_divm=vals[-2], jfde_divm=vals[-1])
+        out.update(n_agents=n_agents, n_groups=n_groups, K=K, top_m=M, radius=float(radius), metric=metric)
+        return out
+
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
         """The reference's checkpoint dict (train.py:653-663), plus a 'noise' entry ({seed, step}) when self.noise is set."""
