@@ -529,18 +529,20 @@ class GenericTrainer(SocialWaysTrainer):
         self._device_noise(noise)
         return self.test(data, n_gen_samples, False, write_to_file, just_one, collect)
 
-    def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):
-        """evaluate_scenes() at these widths: the draws come from Generator.sample() (the rollouts of test()), their errors
-        from the expressions of test(); the reduction over k and the scene metrics are the library's kernels, which do
-        not depend on the hidden size."""
-        ph = self.G.sample(obsv, K, self.n_next, sb, noise.to(self.device))
-        e = torch.pow((ph[..., :2] - pred.unsqueeze(0)) / ss, 2).sum(dim=3).sqrt()
+    def _pad_z(self, z):      # these paths take z at its own width, whatever that is
+        return z
+
+    def _sample_draws(self, c, K, ss, want_pred):
+        """The evaluate_*() family at these widths: the draws come from Generator.sample() (the rollouts of test()), their
+        errors from the expressions of test(); the reduction over k and the scene metrics are the library's kernels, which
+        do not depend on the hidden size."""
+        ph = self.G.sample(c.obsv, K, self.n_next, c.sb, c.z)
+        e = torch.pow((ph[..., :2] - c.pred.unsqueeze(0)) / ss, 2).sum(dim=3).sqrt()
         err = torch.stack([e.mean(2), e[:, :, -1]], dim=2).contiguous()
-        n = obsv.shape[0]
-        per_agent = torch.empty(n, 4, device=err.device)
-        best = torch.empty(n, dtype=torch.int32, device=err.device)
-        L.call("sw_sample_reduce", L.ptr(err), n, K, L.ptr(per_agent), L.ptr(best), L.stream())
-        return ph.reshape(K * n, self.n_next, 4), per_agent, err, best
+        per_agent = torch.empty(c.n, 4, device=err.device)
+        best = torch.empty(c.n, dtype=torch.int32, device=err.device)
+        L.call("sw_sample_reduce", L.ptr(err), c.n, K, L.ptr(per_agent), L.ptr(best), L.stream())
+        return ph, per_agent, err, best
 
     def step_many(self, batches, sub_batches, ss=1.0, global_B=None, out=None, global_row0=0):
         return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0) for o, p, zv, ov, nz in batches]

@@ -523,11 +523,8 @@ def disc_score(d_w, obsv, pred4, K, want_code=True):
 RANK_MAX_K = 4096      # sw_sample_rank holds an agent's K scores in LDS
 
 
-def sample_rank(score, K, M, err=None, best=None):
-    """order (B, M) int32: per agent its M highest-scored draws of K, best first, equal scores by ascending k - the first M
-    columns of a stable descending sort of score (K, B) over k (sw_sample_rank).  With err (K, B, 2), the row errors of
-    gen_sample, also per_agent (B, 5) = ADE | FDE of the top-scored draw, min over the top M of ADE | of FDE, the rank the
-    scores give draw best[a] (best (B,) int32, the min-ADE draw of gen_sample; 0 without it).  Returns (order, per_agent or None)."""
+def _check_picks(score, K, M, err, best):
+    """The arguments sample_rank and sample_nms share, checked without touching the device -> (B, best made contiguous)."""
     if score.dim() != 2 or score.shape[0] != K or K < 1:
         raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
     B = score.shape[1]
@@ -543,6 +540,15 @@ def sample_rank(score, K, M, err=None, best=None):
         if tuple(best.shape) != (B,) or best.dtype != torch.int32 or best.device != score.device:
             raise ValueError("best must be (B,) = (%d,) int32 on the device of score, got %s %s" % (B, tuple(best.shape), best.dtype))
         best = best.contiguous()
+    return B, best
+
+
+def sample_rank(score, K, M, err=None, best=None):
+    """order (B, M) int32: per agent its M highest-scored draws of K, best first, equal scores by ascending k - the first M
+    columns of a stable descending sort of score (K, B) over k (sw_sample_rank).  With err (K, B, 2), the row errors of
+    gen_sample, also per_agent (B, 5) = ADE | FDE of the top-scored draw, min over the top M of ADE | of FDE, the rank the
+    scores give draw best[a] (best (B,) int32, the min-ADE draw of gen_sample; 0 without it).  Returns (order, per_agent or None)."""
+    B, best = _check_picks(score, K, M, err, best)
     L.require_gpu(score)
     score = score.float().contiguous()
     order = torch.empty(B, M, dtype=torch.int32, device=score.device)
@@ -570,13 +576,7 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
     the mode of every draw; per_row (B, 6) or None without err: ADE | FDE of the first pick, min over the picks of ADE | of
     FDE, the weight | the index of the mode that holds draw best[a]).  err (K, B, 2) and best (B,) int32 as gen_sample
     returns them."""
-    if score.dim() != 2 or score.shape[0] != K or K < 1:
-        raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
-    B = score.shape[1]
-    if not 1 <= M <= K:
-        raise ValueError("M must lie in 1 .. K = %d, got %d" % (K, M))
-    if K > RANK_MAX_K:
-        raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
+    B, best = _check_picks(score, K, M, err, best)
     if metric not in NMS_METRICS:
         raise ValueError("metric must be one of %s, got %r" % (sorted(NMS_METRICS), metric))
     if not float(radius) >= 0.0:
@@ -590,14 +590,6 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
         raise ValueError("pos must be on the device of score")
     if scenes is not None and scenes.B != B:
         raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
-    if err is not None and (tuple(err.shape) != (K, B, 2) or err.device != score.device):
-        raise ValueError("err must be (K, B, 2) = (%d, %d, 2) on the device of score, got %s" % (K, B, tuple(err.shape)))
-    if best is not None:
-        if err is None:
-            raise ValueError("best is only used with err")
-        if tuple(best.shape) != (B,) or best.dtype != torch.int32 or best.device != score.device:
-            raise ValueError("best must be (B,) = (%d,) int32 on the device of score, got %s %s" % (B, tuple(best.shape), best.dtype))
-        best = best.contiguous()
     L.require_gpu(score)
     score, pos = score.float().contiguous(), pos.float().contiguous()
     dev = score.device

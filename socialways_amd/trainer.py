@@ -18,6 +18,7 @@ are all-reduced (sum) before each optimizer step - 3 RCCL all-reduces per traini
 import copy
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -157,6 +158,33 @@ class PackedAdam:
         self.step_t.fill_(float(self.t))
 
 
+class _EvalSums:
+    """What test() and every evaluate_*() return first: the per-agent sums ade_avg | fde_avg | ade_min | fde_min, float64 on the
+    device, added chunk by chunk and divided by data.n_test_samples at the end; and `scenes`, the row ranges evaluated."""
+    KEYS = ("ade_avg", "fde_avg", "ade_min", "fde_min")
+
+    def __init__(self, device):
+        self.sums, self.scenes = torch.zeros(4, dtype=torch.float64, device=device), []
+
+    def add(self, c):
+        self.scenes += c.ab
+        self.sums += c.per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
+
+    def result(self, data):
+        return dict(zip(self.KEYS, (self.sums / data.n_test_samples).tolist()))
+
+
+@torch.no_grad()
+def _scored_draws(tr, obsv_p, n_samples, top_m, sub_batches, noise, row0):
+    """What sample_ranked() and sample_diverse() start with: (K, M, the K draws (K, B, n_next, 4), their scores (K, B)); top_m
+    is checked before anything of the trainer is touched."""
+    K, M = int(n_samples), int(top_m)
+    if not 1 <= M <= K:
+        raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
+    ph = tr.G.sample(obsv_p, K, tr.n_next, sub_batches, noise, row0=row0)
+    return K, M, ph, tr.D.score_samples(obsv_p, ph)[0]
+
+
 class SocialWaysTrainer:
     STEPS_PER_LAUNCH = 4    # train_epoch: consecutive packed batches of one scene layout per graph launch (step_many)
     Z_COLS = 32             # noise columns of the kernels (hidden size 64: train.py:81); smaller models are zero-padded
@@ -184,14 +212,6 @@ class SocialWaysTrainer:
         if dn is not None and not isinstance(dn, DeviceNoise):
             raise TypeError("noise must be a DeviceNoise or None, got %s" % type(dn).__name__)
         return dn
-
-    def _eval_z(self, dn, batches, K, lo, n):
-        """The (K * n, Z_COLS) z of one evaluation chunk, rows lo .. lo + n-1 of the held-out tracks: from the device stream
-        (evaluation domain, row = the ABSOLUTE held-out row, so a scene's draws do not depend on the chunking; one launch
-        that also writes the padding), else the reference's host stream (eval_noise), padded and copied."""
-        if dn is not None:
-            return dn.fill(n, self.noise_len, domain=EVAL, n_draws=K, row0=lo, ld=self.Z_COLS, device=self.device).view(K * n, -1)
-        return self._pad_z(self.eval_noise(batches, K, self.noise_len)).view(K * n, -1).to(self.device)
 
     def _pad_z(self, z):
         return z if z.shape[-1] == self.Z_COLS else torch.nn.functional.pad(z, (0, self.Z_COLS - z.shape[-1]))
@@ -940,57 +960,28 @@ class SocialWaysTrainer:
         identical rollouts, one launch sequence and one host sync per chunk instead of per scene.  The noise is
         drawn scene by scene, K draws of (n, noise_len) each, in the reference's order (train.py:584)."""
         ss, dev, K = data.ss, self.device, n_gen_samples
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
-        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
-        if just_one:
-            batches = batches[:1]
-        i = 0
-        while i < len(batches):
-            j, tot = i + 1, batches[i][1] - batches[i][0]
-            while (j < len(batches) and batches[j][0] == batches[j - 1][1]
-                   and (tot + batches[j][1] - batches[j][0]) * K <= self.TEST_CHUNK):
-                tot += batches[j][1] - batches[j][0]
-                j += 1
-            lo, hi = batches[i][0], batches[j - 1][1]
-            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-            n = hi - lo
+        base = _EvalSums(dev)
+        for first, scenes in self._eval_fold(data, K, just_one):
+            lo, hi = scenes[0][0], scenes[-1][1]
+            c = SimpleNamespace(first=first, ab=scenes, lo=lo, n=hi - lo, obsv=data.obsv[lo:hi], pred=data.pred[lo:hi])
             with torch.no_grad():
-                linear_preds = predict_cv(obsv, self.n_next)
                 if linear and not write_to_file:
-                    preds_k = linear_preds.unsqueeze(0)
-                    errs = torch.pow((linear_preds[:, :, :2] - pred) / ss, 2).sum(dim=2, keepdim=True).sqrt().unsqueeze(0)
+                    preds_k = predict_cv(c.obsv, self.n_next).unsqueeze(0)
                 else:
                     # copy k of scene s sits at rows k * n + (scene rows): K copies of the chunk, each copy its scenes
-                    noise = torch.empty(K, n, self.noise_len)
-                    for a, b in batches[i:j]:
-                        for k in range(K):
-                            noise[k, a - lo:b - lo] = torch.rand(b - a, self.noise_len)      # train.py:584, scene by scene
-                    sb1 = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-                    sb = np.concatenate([sb1 + k * n for k in range(K)])
-                    ph = self.G(obsv.repeat(K, 1, 1), noise.view(K * n, -1).to(dev), self.n_next, sb).view(K, n, self.n_next, 4)
-                    preds_k = ph
-                    errs = torch.pow((ph[:, :, :, :2] - pred.unsqueeze(0)) / ss, 2).sum(dim=3, keepdim=True).sqrt()
+                    noise = self.eval_noise(scenes, K, self.noise_len)
+                    sb1 = np.asarray([[a - lo, b - lo] for a, b in scenes], dtype=np.int64)
+                    sb = np.concatenate([sb1 + k * c.n for k in range(K)])
+                    preds_k = self.G(c.obsv.repeat(K, 1, 1), noise.view(K * c.n, -1).to(dev), self.n_next, sb
+                                     ).view(K, c.n, self.n_next, 4)
+                errs = torch.pow((preds_k[:, :, :, :2] - c.pred.unsqueeze(0)) / ss, 2).sum(dim=3, keepdim=True).sqrt()
                 if write_to_file or collect is not None:
-                    sc = data.scale
-                    for si, (a, b) in enumerate(batches[i:j]):
-                        t = data.times[a] if data.times is not None else i + si
-                        r = slice(a - lo, b - lo)
-                        rec = dict(timestamp=t, obsvs=sc.denormalize(obsv[r, :, :2].cpu().numpy()),
-                                   preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
-                                   preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
-                                   preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
-                        if collect is not None:
-                            collect.append(rec)
-                        if write_to_file:
-                            os.makedirs(write_to_file, exist_ok=True)
-                            np.savez(os.path.join(write_to_file, str(self.epoch) + '-' + str(t) + '.npz'), **rec)
+                    for rec in self._eval_records(data, c, preds_k):
+                        self._eval_emit(rec, collect, write_to_file)
                 e = errs.double()
-                sums += torch.stack([e.mean(2).mean(0).sum(), e[:, :, -1].mean(0).sum(),
-                                     e.mean(2).min(0)[0].sum(), e[:, :, -1].min(0)[0].sum()])
-            i = j
-        n = data.n_test_samples
-        ade_avg, fde_avg, ade_min, fde_min = (sums / n).tolist()
-        return ade_avg, fde_avg, ade_min, fde_min
+                base.sums += torch.stack([e.mean(2).mean(0).sum(), e[:, :, -1].mean(0).sum(),
+                                          e.mean(2).min(0)[0].sum(), e[:, :, -1].min(0)[0].sum()])
+        return tuple(base.result(data).values())
 
     @staticmethod
     def eval_chunks(batches, K, chunk):
@@ -1016,68 +1007,93 @@ class SocialWaysTrainer:
                 noise[k, a - lo:b - lo] = torch.rand(b - a, noise_len)
         return noise
 
-    def _eval_records(self, data, chunk, first, obsv, pred, preds_k):
-        """The prediction records of one chunk of evaluate(): (index in the chunk, the dict test() writes per held-out scene -
-        timestamp, obsvs, preds_our (K, n, n_next, 2), preds_gtt, preds_lnr, all denormalised)."""
-        linear_preds = predict_cv(obsv, self.n_next)
-        sc, lo = data.scale, chunk[0][0]
-        for si, (a, b) in enumerate(chunk):
-            t = data.times[a] if data.times is not None else first + si
-            r = slice(a - lo, b - lo)
-            yield si, dict(timestamp=t, obsvs=sc.denormalize(obsv[r, :, :2].cpu().numpy()),
-                           preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
-                           preds_gtt=sc.denormalize(pred[r, :, :2].cpu().numpy()),
-                           preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
+    # ---- the loop test() and every evaluate_*() share ---------------------------------------------------------------------
+    def _eval_fold(self, data, K, just_one):
+        """(index of its first scene, [(a, b) row range per scene]) of every chunk: the held-out scenes, the first one only
+        with just_one, folded by eval_chunks up to TEST_CHUNK agent copies."""
+        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
+        if just_one:
+            batches = batches[:1]
+        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
+            yield i, batches[i:j]
+
+    def _eval_draws(self, data, K, just_one, dn, base, want_pred=True):
+        """The K draws of the held-out scenes, chunk by chunk: what evaluate() and every evaluate_*() do before their own
+        work.  Yields a namespace per chunk: first (index of its first scene), ab (its scenes' row ranges), lo, n (its rows
+        are lo .. lo + n-1 of the held-out tracks), obsv, pred, sb and scenes (the chunk-local scene ranges and their
+        SceneIndex), z (K, n, Z_COLS) on the device, and from the sampling hook ph (K, n, n_next, 4; None without want_pred),
+        per_agent (n, 4), err (K, n, 2), best (n,) int32.  z comes from `dn` (a DeviceNoise: evaluation domain, row = the
+        ABSOLUTE held-out row, so a scene's draws do not depend on the chunking; one launch that also writes the padding),
+        else from the reference's host stream (eval_noise), padded and copied once.  The chunk's scenes and per-agent sums
+        are added to `base` (an _EvalSums) before it is handed out.  The loop body of the caller runs under this generator's
+        torch.no_grad(), which ends with the generator (if the body raises: when the generator is collected)."""
+        dev = self.device
+        with torch.no_grad():
+            for first, scenes in self._eval_fold(data, K, just_one):
+                lo, hi = scenes[0][0], scenes[-1][1]
+                c = SimpleNamespace(first=first, ab=scenes, lo=lo, n=hi - lo, obsv=data.obsv[lo:hi], pred=data.pred[lo:hi])
+                if dn is not None:
+                    c.z = dn.fill(c.n, self.noise_len, domain=EVAL, n_draws=K, row0=lo, ld=self.Z_COLS, device=dev)[0]
+                else:
+                    c.z = self._pad_z(self.eval_noise(scenes, K, self.noise_len)).to(dev)
+                c.sb = np.asarray([[a - lo, b - lo] for a, b in scenes], dtype=np.int64)
+                c.scenes = ops.SceneIndex.get(c.sb, c.n, c.obsv.device)
+                c.ph, c.per_agent, c.err, c.best = self._sample_draws(c, K, data.ss, want_pred)
+                base.add(c)
+                yield c
+
+    def _sample_draws(self, c, K, ss, want_pred):
+        """The sampling hook of _eval_draws(): K draws of chunk c from c.z -> (ph (K, n, n_next, 4) kept on the device, or None
+        without want_pred; per_agent (n, 4) = mean_k ADE | mean_k FDE | min_k ADE | min_k FDE; err (K, n, 2); best (n,) int32 =
+        the min-ADE draw).  Here: the observations are encoded and pooled ONCE, one launch rolls out the K copies and forms
+        their errors (ops.gen_sample), the mean / min over K is reduced on the device."""
+        G = self.G
+        ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
+                                 c.obsv, c.z.view(K * c.n, -1), c.scenes, self.n_next, G.use_social, K, gt=c.pred,
+                                 inv_ss=1.0 / float(ss), want_pred=want_pred)
+        return ph.view(K, c.n, self.n_next, 4) if ph is not None else None, red[0], red[2], red[1]
+
+    def _eval_records(self, data, c, preds_k, extra={}):
+        """The prediction records of chunk c, one per held-out scene: the dict test() writes - timestamp, obsvs, preds_our
+        (K, n, n_next, 2) from preds_k, preds_gtt, preds_lnr, all denormalised - plus the scene's part of every entry of
+        `extra` = {key: (device tensor, axis)}: axis = the one that runs over the chunk's rows, None = one entry per scene."""
+        linear_preds = predict_cv(c.obsv, self.n_next)
+        sc = data.scale
+        host = {k: (v.cpu().numpy(), ax) for k, (v, ax) in extra.items()}
+        for si, (a, b) in enumerate(c.ab):
+            t = data.times[a] if data.times is not None else c.first + si
+            r = slice(a - c.lo, b - c.lo)
+            rec = dict(timestamp=t, obsvs=sc.denormalize(c.obsv[r, :, :2].cpu().numpy()),
+                       preds_our=sc.denormalize(preds_k[:, r, :, :2].cpu().numpy()),
+                       preds_gtt=sc.denormalize(c.pred[r, :, :2].cpu().numpy()),
+                       preds_lnr=sc.denormalize(linear_preds[r, :, :2].cpu().numpy()))
+            for k, (v, ax) in host.items():
+                rec[k] = v[si if ax is None else (slice(None),) * ax + (r,)].copy()
+            yield rec
+
+    def _eval_emit(self, rec, collect, write_to_file=None):
+        """One record into `collect` and / or the file '<epoch>-<timestamp>.npz' under `write_to_file`."""
+        if collect is not None:
+            collect.append(rec)
+        if write_to_file:
+            os.makedirs(write_to_file, exist_ok=True)
+            np.savez(os.path.join(write_to_file, str(self.epoch) + '-' + str(rec["timestamp"]) + '.npz'), **rec)
 
     def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None, noise=None):
         """The contract of test() (train.py:563-616; without its `linear` branch) on the sampling path: the same four
         return values, prediction files, host noise stream and folding of scenes.  `noise` (default self.noise): a
         DeviceNoise replaces the host stream by the device stream's evaluation domain - draw k of held-out row r is a
         function of (seed, k, r) alone, so two calls agree and TEST_CHUNK / just_one do not change a scene's draws.
-        Per chunk the observations are encoded and pooled ONCE, one launch rolls out the K copies and forms their errors
-        (ops.gen_sample), the mean / min over K is reduced on the device; the K x n trajectories leave the kernel only when a
-        file or `collect` wants them."""
+        The chunks and their draws are _eval_draws()'s; the K x n trajectories leave the kernel only when a file or
+        `collect` wants them."""
         dn = self._device_noise(noise)
-        ss, dev, K = data.ss, self.device, n_gen_samples
-        G = self.G
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
-        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
-        if just_one:
-            batches = batches[:1]
+        base = _EvalSums(self.device)
         want_pred = bool(write_to_file) or collect is not None
-        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
-            lo, hi = batches[i][0], batches[j - 1][1]
-            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-            n = hi - lo
-            with torch.no_grad():
-                z = self._eval_z(dn, batches[i:j], K, lo, n)
-                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-                scenes = ops.SceneIndex.get(sb, n, obsv.device)
-                ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(),
-                                         G.decoder.packed(), obsv, z, scenes, self.n_next, G.use_social, K,
-                                         gt=pred, inv_ss=1.0 / float(ss), want_pred=want_pred)
-                if want_pred:
-                    for _, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
-                        t = rec["timestamp"]
-                        if collect is not None:
-                            collect.append(rec)
-                        if write_to_file:
-                            os.makedirs(write_to_file, exist_ok=True)
-                            np.savez(os.path.join(write_to_file, str(self.epoch) + '-' + str(t) + '.npz'), **rec)
-                sums += red[0].double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
-        ade_avg, fde_avg, ade_min, fde_min = (sums / data.n_test_samples).tolist()
-        return ade_avg, fde_avg, ade_min, fde_min
-
-    def _sample_chunk(self, obsv, pred, noise, scenes, sb, K, ss):
-        """K draws of one chunk for evaluate_scenes(), by the launches of evaluate(): noise (K, n, noise_len) on the host, or
-        (K, n, Z_COLS) already padded on the device -> (pred4 (K * n, n_next, 4) kept on the device, per_agent (n, 4),
-        err (K, n, 2), best (n,) int32 = the min-ADE draw)."""
-        G = self.G
-        z = self._pad_z(noise).view(K * obsv.shape[0], -1).to(self.device)
-        ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
-                                 obsv, z, scenes, self.n_next, G.use_social, K, gt=pred, inv_ss=1.0 / float(ss),
-                                 want_pred=False, keep_pred=True)
-        return ph, red[0], red[2], red[1]
+        for c in self._eval_draws(data, n_gen_samples, just_one, dn, base, want_pred):
+            if want_pred:
+                for rec in self._eval_records(data, c, c.ph):
+                    self._eval_emit(rec, collect, write_to_file)
+        return tuple(base.result(data).values())
 
     def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
         """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
@@ -1099,49 +1115,34 @@ class SocialWaysTrainer:
         With self.noise set (a DeviceNoise) the draws are evaluate()'s from that stream.  This call's argument list is pinned
         (tests/test_scene_host.py), so the stream reaches it through the attribute only, not through a keyword."""
         dn = self._device_noise(None)
-        ss, dev, K = data.ss, self.device, n_gen_samples
-        inv_ss = 1.0 / float(ss)
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        dev, K = self.device, n_gen_samples
+        inv_ss = 1.0 / float(data.ss)
+        base = _EvalSums(dev)
         # sum n * jade | sum n * jfde | then over multi-agent scenes: colliding share | kbest flag | n * agent share | gt flag
         acc = torch.zeros(6, dtype=torch.float64, device=dev)
-        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
-        if just_one:
-            batches = batches[:1]
-        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
-            lo, hi = batches[i][0], batches[j - 1][1]
-            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-            n = hi - lo
-            with torch.no_grad():
-                noise = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
-                    self.eval_noise(batches[i:j], K, self.noise_len)
-                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-                scenes = ops.SceneIndex.get(sb, n, obsv.device)
-                ph, per_agent, err, _ = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
-                per_scene, kbest, clear = ops.scene_metrics(err, ph, obsv, scenes, K, self.n_next, inv_ss, coll_dist)
-                gt_scene, _ = ops.scene_reduce(torch.zeros(1, n, 2, device=dev),
-                                               ops.scene_clearance(pred, obsv[:, -1], scenes, 1, inv_ss), scenes, 1, coll_dist)
-                cnt = (scenes.scene_off[1:] - scenes.scene_off[:-1]).double()
-                multi = (cnt > 1).double()
-                ps = per_scene.double()
-                acc += torch.stack([(cnt * ps[:, 0]).sum(), (cnt * ps[:, 1]).sum(), (multi * ps[:, 2]).sum(),
-                                    (multi * ps[:, 3]).sum(), (multi * cnt * ps[:, 5]).sum(),
-                                    (multi * gt_scene[:, 2].double()).sum()])
-                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
-                if collect is not None:
-                    clear_h, ps_h, kb_h = clear.cpu().numpy(), per_scene.cpu().numpy(), kbest.cpu().numpy()
-                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
-                        a, b = batches[i + si]
-                        rec.update(clear=clear_h[:, a - lo:b - lo].copy(), per_scene=ps_h[si].copy(), kbest=int(kb_h[si]))
-                        collect.append(rec)
-        n_multi = sum(1 for a, b in batches if b - a > 1)
-        agents_multi = sum(b - a for a, b in batches if b - a > 1)
-        ade_avg, fde_avg, ade_min, fde_min = (sums / data.n_test_samples).tolist()
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            per_scene, kbest, clear = ops.scene_metrics(c.err, c.ph, c.obsv, c.scenes, K, self.n_next, inv_ss, coll_dist)
+            gt_scene, _ = ops.scene_reduce(torch.zeros(1, c.n, 2, device=dev),
+                                           ops.scene_clearance(c.pred, c.obsv[:, -1], c.scenes, 1, inv_ss), c.scenes, 1, coll_dist)
+            cnt = (c.scenes.scene_off[1:] - c.scenes.scene_off[:-1]).double()
+            multi = (cnt > 1).double()
+            ps = per_scene.double()
+            acc += torch.stack([(cnt * ps[:, 0]).sum(), (cnt * ps[:, 1]).sum(), (multi * ps[:, 2]).sum(),
+                                (multi * ps[:, 3]).sum(), (multi * cnt * ps[:, 5]).sum(),
+                                (multi * gt_scene[:, 2].double()).sum()])
+            if collect is not None:
+                for rec in self._eval_records(data, c, c.ph, dict(clear=(clear, 1), per_scene=(per_scene, None), kbest=(kbest, None))):
+                    rec["kbest"] = int(rec["kbest"])
+                    collect.append(rec)
+        n_multi = sum(1 for a, b in base.scenes if b - a > 1)
+        agents_multi = sum(b - a for a, b in base.scenes if b - a > 1)
+        out = base.result(data)
         jade, jfde, joint, best, agent, gt = acc.tolist()
-        return dict(ade_avg=ade_avg, fde_avg=fde_avg, ade_min=ade_min, fde_min=fde_min,
-                    jade_min=jade / data.n_test_samples, jfde_min=jfde / data.n_test_samples,
-                    col_joint=joint / n_multi if n_multi else 0.0, col_best=best / n_multi if n_multi else 0.0,
-                    col_agent=agent / agents_multi if n_multi else 0.0, col_gt=gt / n_multi if n_multi else 0.0,
-                    n_scenes=len(batches), n_multi=n_multi)
+        out.update(jade_min=jade / data.n_test_samples, jfde_min=jfde / data.n_test_samples,
+                   col_joint=joint / n_multi if n_multi else 0.0, col_best=best / n_multi if n_multi else 0.0,
+                   col_agent=agent / agents_multi if n_multi else 0.0, col_gt=gt / n_multi if n_multi else 0.0,
+                   n_scenes=len(base.scenes), n_multi=n_multi)
+        return out
 
     def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None, row0=0):
         """The deployment call - K draws, no ground truth, pick a few: the top_m of n_samples futures per agent that the
@@ -1150,12 +1151,8 @@ class SocialWaysTrainer:
         Returns (trajs (M, B, n_next, 4), score (M, B) raw LSGAN score, non-increasing along M, order (B, M) int32: trajs[m, a]
         is draw order[a, m]).  A sampling launch (Generator.sample), a scoring launch (Discriminator.score_samples), a
         ranking launch (ops.sample_rank) and a gather."""
-        K, M = int(n_samples), int(top_m)
-        if not 1 <= M <= K:
-            raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
+        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0)
         with torch.no_grad():
-            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0)
-            score, _ = self.D.score_samples(obsv_p, ph)
             order, _ = ops.sample_rank(score, K, M)
             idx = order.t().long()
             trajs = ph.gather(0, idx[:, :, None, None].expand(M, ph.shape[1], self.n_next, 4))
@@ -1181,41 +1178,23 @@ class SocialWaysTrainer:
         `collect` every record of evaluate() also has `score` (K, n), `order` (n, top_m) and `code_hat` (K, n, codes).
         `noise`: as evaluate() - a DeviceNoise (default self.noise) gives evaluate(noise=...)'s draws."""
         dn = self._device_noise(noise)
-        ss, dev, K, M = data.ss, self.device, int(n_gen_samples), int(top_m)
+        dev, K, M = self.device, int(n_gen_samples), int(top_m)
         if not 1 <= M <= K:
             raise ValueError("top_m must lie in 1 .. n_gen_samples = %d, got %d" % (K, M))
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        base = _EvalSums(dev)
         acc = torch.zeros(len(self.RANKED_KEYS), dtype=torch.float64, device=dev)
-        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
-        if just_one:
-            batches = batches[:1]
-        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
-            lo, hi = batches[i][0], batches[j - 1][1]
-            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-            n = hi - lo
-            with torch.no_grad():
-                noise = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
-                    self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
-                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-                scenes = ops.SceneIndex.get(sb, n, obsv.device)
-                ph, per_agent, err, best = self._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
-                score, code = self.D.score_samples(obsv, ph.view(K, n, self.n_next, 4))
-                order, ranked = ops.sample_rank(score, K, M, err=err, best=best)
-                gt_score, _ = self.D.score_samples(obsv, get_traj_4d(obsv, pred)[1].unsqueeze(0))
-                csq = (code.double() - noise[:, :, :code.shape[-1]].double()).pow(2).mean(dim=2)
-                acc += torch.cat([ranked.double().sum(0), torch.stack([score.double().sum(), gt_score.double().sum(), csq.sum()])])
-                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
-                if collect is not None:
-                    sc_h, or_h, co_h = score.cpu().numpy(), order.cpu().numpy(), code.cpu().numpy()
-                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
-                        a, b = batches[i + si]
-                        rec.update(score=sc_h[:, a - lo:b - lo].copy(), order=or_h[a - lo:b - lo].copy(),
-                                   code_hat=co_h[:, a - lo:b - lo].copy())
-                        collect.append(rec)
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            score, code = self.D.score_samples(c.obsv, c.ph)
+            order, ranked = ops.sample_rank(score, K, M, err=c.err, best=c.best)
+            gt_score, _ = self.D.score_samples(c.obsv, get_traj_4d(c.obsv, c.pred)[1].unsqueeze(0))
+            csq = (code.double() - c.z[:, :, :code.shape[-1]].double()).pow(2).mean(dim=2)
+            acc += torch.cat([ranked.double().sum(0), torch.stack([score.double().sum(), gt_score.double().sum(), csq.sum()])])
+            if collect is not None:
+                collect.extend(self._eval_records(data, c, c.ph, dict(score=(score, 1), order=(order, 0), code_hat=(code, 1))))
         nt = data.n_test_samples
-        out = dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min"), (sums / nt).tolist()))
+        out = base.result(data)
         out.update(zip(self.RANKED_KEYS, (acc / torch.tensor([nt] * 5 + [K * nt, nt, K * nt], dtype=torch.float64, device=dev)).tolist()))
-        out.update(n_agents=sum(b - a for a, b in batches), K=K, top_m=M)
+        out.update(n_agents=sum(b - a for a, b in base.scenes), K=K, top_m=M)
         return out
 
     @staticmethod
@@ -1239,12 +1218,8 @@ class SocialWaysTrainer:
         with joint=True: (S, M), (S, M), (S,), and trajs[m, a] is draw order[scene of a, m] of agent a, score[m, a] that draw's
         own score.  Per agent the scores do not increase along M.  Slots from count on: zeros in trajs, -inf in score, 0 in
         weight, -1 in order.  Sampling, scoring, one suppression launch and a gather."""
-        K, M = int(n_samples), int(top_m)
-        if not 1 <= M <= K:
-            raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
+        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0)
         with torch.no_grad():
-            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0)
-            score, _ = self.D.score_samples(obsv_p, ph)
             B = ph.shape[1]
             scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device) if joint else None
             order, count, weight, _, _ = ops.sample_nms(ph, score, K, M, radius, metric, scenes, inv_ss=scale)
@@ -1286,49 +1261,33 @@ class SocialWaysTrainer:
         if metric not in ops.NMS_METRICS:
             raise ValueError("metric must be one of %s, got %r" % (sorted(ops.NMS_METRICS), metric))
         inv_ss = 1.0 / float(ss)
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)          # ade_avg, fde_avg, ade_min, fde_min
+        base = _EvalSums(dev)
         acc = torch.zeros(len(self.DIVERSE_KEYS) + 2, dtype=torch.float64, device=dev)      # ... | sum n * jade | sum n * jfde
-        batches = [(int(b[0]), int(b[1])) for b in data.test_batches]
-        if just_one:
-            batches = batches[:1]
-        for i, j in self.eval_chunks(batches, K, self.TEST_CHUNK):
-            lo, hi = batches[i][0], batches[j - 1][1]
-            obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-            n = hi - lo
-            with torch.no_grad():
-                z = self._eval_z(dn, batches[i:j], K, lo, n).view(K, n, -1) if dn is not None else \
-                    self.eval_noise(batches[i:j], K, self.noise_len).to(dev)
-                sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-                scenes = ops.SceneIndex.get(sb, n, obsv.device)
-                ph, per_agent, err, best = self._sample_chunk(obsv, pred, z, scenes, sb, K, ss)
-                score, _ = self.D.score_samples(obsv, ph.view(K, n, self.n_next, 4))
-                order, count, weight, assign, per_row = ops.sample_nms(ph, score, K, M, radius, metric, scenes if joint else None,
-                                                                       inv_ss=inv_ss, err=err, best=best)
-                # the first five columns summed in the shape evaluate_ranked() sums its own: the same bits at radius 0
-                part = [torch.cat([per_row[:, :4], per_row[:, 5:6]], dim=1).double().sum(0),
-                        torch.stack([per_row[:, 4].double().sum(), count.double().sum(), weight[:, 0].double().sum()])]
-                if joint:
-                    off = scenes.scene_off.long()
-                    cnt = (off[1:] - off[:-1]).double()
-                    run = torch.cat([torch.zeros(K, 1, 2, dtype=torch.float64, device=dev), err.double().cumsum(1)], dim=1)
-                    mean = ((run[:, off[1:]] - run[:, off[:-1]]) / cnt[None, :, None]).permute(1, 0, 2)      # (S, K, 2)
-                    at = order.long().clamp(min=0)[:, :, None].expand(-1, -1, 2)
-                    picked = torch.where((order >= 0)[:, :, None], mean.gather(1, at), torch.full_like(mean[:, :1], float("inf")))
-                    part.append((cnt[:, None] * picked.min(dim=1)[0]).sum(0))
-                else:
-                    part.append(torch.zeros(2, dtype=torch.float64, device=dev))
-                acc += torch.cat(part)
-                sums += per_agent.double().sum(0)      # per agent: mean_k ADE | mean_k FDE | min_k ADE | min_k FDE
-                if collect is not None:
-                    or_h, cn_h, we_h, as_h = order.cpu().numpy(), count.cpu().numpy(), weight.cpu().numpy(), assign.cpu().numpy()
-                    for si, rec in self._eval_records(data, batches[i:j], i, obsv, pred, ph.view(K, n, self.n_next, 4)):
-                        a, b = batches[i + si]
-                        r = si if joint else slice(a - lo, b - lo)
-                        rec.update(order=or_h[r].copy(), count=cn_h[r].copy(), weight=we_h[r].copy(), assign=as_h[r].copy())
-                        collect.append(rec)
-        nt, n_agents = data.n_test_samples, sum(b - a for a, b in batches)
-        n_groups = len(batches) if joint else n_agents
-        out = dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min"), (sums / nt).tolist()))
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            score, _ = self.D.score_samples(c.obsv, c.ph)
+            order, count, weight, assign, per_row = ops.sample_nms(c.ph, score, K, M, radius, metric, c.scenes if joint else None,
+                                                                   inv_ss=inv_ss, err=c.err, best=c.best)
+            # the first five columns summed in the shape evaluate_ranked() sums its own: the same bits at radius 0
+            part = [torch.cat([per_row[:, :4], per_row[:, 5:6]], dim=1).double().sum(0),
+                    torch.stack([per_row[:, 4].double().sum(), count.double().sum(), weight[:, 0].double().sum()])]
+            if joint:
+                off = c.scenes.scene_off.long()
+                cnt = (off[1:] - off[:-1]).double()
+                run = torch.cat([torch.zeros(K, 1, 2, dtype=torch.float64, device=dev), c.err.double().cumsum(1)], dim=1)
+                mean = ((run[:, off[1:]] - run[:, off[:-1]]) / cnt[None, :, None]).permute(1, 0, 2)      # (S, K, 2)
+                at = order.long().clamp(min=0)[:, :, None].expand(-1, -1, 2)
+                picked = torch.where((order >= 0)[:, :, None], mean.gather(1, at), torch.full_like(mean[:, :1], float("inf")))
+                part.append((cnt[:, None] * picked.min(dim=1)[0]).sum(0))
+            else:
+                part.append(torch.zeros(2, dtype=torch.float64, device=dev))
+            acc += torch.cat(part)
+            if collect is not None:
+                ax = None if joint else 0      # per scene, or the rows of the scene's agents
+                collect.extend(self._eval_records(data, c, c.ph, dict(order=(order, ax), count=(count, ax), weight=(weight, ax),
+                                                                      assign=(assign, ax))))
+        nt, n_agents = data.n_test_samples, sum(b - a for a, b in base.scenes)
+        n_groups = len(base.scenes) if joint else n_agents
+        out = base.result(data)
         div = torch.tensor([nt] * 6 + [n_groups] * 2 + [nt] * 2, dtype=torch.float64, device=dev)
         vals = (acc / div).tolist()
         out.update(zip(self.DIVERSE_KEYS, vals))

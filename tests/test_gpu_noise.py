@@ -208,6 +208,15 @@ def test_evaluate_with_device_noise():
     rk = tr.evaluate_ranked(data, n_gen_samples=K, top_m=5, noise=dn)
     keys = ("ade_avg", "fde_avg", "ade_min", "fde_min")
     assert tuple(rk[k] for k in keys) == want and tr.evaluate_ranked(data, n_gen_samples=K, noise=dn) == rk
+    # ... and so does the diverse form, per agent and per scene; at radius 0 its picks are the ranking's
+    for joint in (False, True):
+        dv = tr.evaluate_diverse(data, n_gen_samples=K, top_m=5, radius=0.5, joint=joint, noise=dn)
+        assert tuple(dv[k] for k in keys) == want
+        assert tr.evaluate_diverse(data, n_gen_samples=K, top_m=5, radius=0.5, joint=joint, noise=dn) == dv
+    d0 = tr.evaluate_diverse(data, n_gen_samples=K, top_m=5, radius=0.0, joint=False, noise=dn)
+    for kd, kr in (("ade_div1", "ade_top1"), ("fde_div1", "fde_top1"), ("ade_divm", "ade_topm"), ("fde_divm", "fde_topm")):
+        assert d0[kd] == rk[kr], (kd, d0[kd], rk[kr])
+    assert torch.equal(torch.get_rng_state(), rng), "the host generator is not consumed"
     # trainer.noise is the default of the keyword
     tr.noise = dn
     sc = tr.evaluate_scenes(data, n_gen_samples=K)

@@ -12,23 +12,16 @@ tools/sample_timing.py and by its method: host clock around calls that end in a 
 
     python tools/nms_timing.py [--repeats 9] [--out profiles/nms_timing.txt]
 """
-import argparse
 import os
 import statistics
 import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(HERE, "tools"))
-import socialways_amd as sw  # noqa: E402
-from socialways_amd import ops  # noqa: E402
-from sample_timing import SHAPES, held_out_set, timed  # noqa: E402
-from scene_timing import alternate, cell  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
+from _timing import METRIC, PER_LAUNCH, RADIUS, TOP_M, cell, first_chunk  # noqa: E402
 
-TOP_M, RADIUS, METRIC = 5, 0.5, "fde"
 NEW = ("ade_div1", "fde_div1", "ade_divm", "fde_divm", "n_modes", "w_first", "w_hit", "rank_hit")
 
 
@@ -68,49 +61,33 @@ def torch_nms(pos, score, M, radius, metric, inv_ss, scene_off=None):
 
 
 def torch_diverse(tr, data, K, M, radius, metric, joint, just_one):
-    """The numbers of evaluate_diverse() with the selection and its read-out formed by torch ops."""
-    ss, dev, Tp = float(data.ss), tr.device, tr.n_next
-    batches = [(int(b[0]), int(b[1])) for b in data.test_batches][:1 if just_one else None]
-    sums = torch.zeros(4, dtype=torch.float64, device=dev)
+    """The numbers of evaluate_diverse() with the selection and its read-out formed by torch ops: the chunks, draws and scores
+    are the call's own (the trainer's chunk generator, Discriminator.score_samples)."""
+    dev = tr.device
+    base = T.sw.trainer._EvalSums(dev)
     acc = torch.zeros(8, dtype=torch.float64, device=dev)
-    for i, j in tr.eval_chunks(batches, K, tr.TEST_CHUNK):
-        lo, hi = batches[i][0], batches[j - 1][1]
-        obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
-        n = hi - lo
-        with torch.no_grad():
-            noise = tr.eval_noise(batches[i:j], K, tr.noise_len).to(dev)
-            sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-            scenes = ops.SceneIndex.get(sb, n, obsv.device)
-            ph, per_agent, err, best = tr._sample_chunk(obsv, pred, noise, scenes, sb, K, ss)
-            score, _ = tr.D.score_samples(obsv, ph.view(K, n, Tp, 4))
-            off = scenes.scene_off if joint else None
-            order, count, weight, assign = torch_nms(ph, score, M, radius, metric, 1.0 / ss, off)
-            rows = torch.arange(n, device=dev)
-            gid = torch.bucketize(rows, off[1:].long(), right=True) if joint else rows
-            ro = order[gid]                                                            # (n, M)
-            e = err.permute(1, 0, 2).gather(1, ro.clamp(min=0)[:, :, None].expand(-1, -1, 2))
-            e = torch.where((ro >= 0)[:, :, None], e, torch.full_like(e, float("inf")))
-            mb = assign[gid, best.long()]
-            acc += torch.cat([e[:, 0].double().sum(0), e.amin(1).double().sum(0),
-                              torch.stack([count.double().sum(), weight[:, 0].double().sum(), weight[gid, mb].double().sum(),
-                                           mb.double().sum()])])
-            sums += per_agent.double().sum(0)
-    nt, n_agents = data.n_test_samples, sum(b - a for a, b in batches)
-    ng = len(batches) if joint else n_agents
-    out = dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min"), (sums / nt).tolist()))
+    for c in tr._eval_draws(data, K, just_one, None, base):
+        score, _ = tr.D.score_samples(c.obsv, c.ph)
+        off = c.scenes.scene_off if joint else None
+        order, count, weight, assign = torch_nms(c.ph, score, M, radius, metric, 1.0 / float(data.ss), off)
+        rows = torch.arange(c.n, device=dev)
+        gid = torch.bucketize(rows, off[1:].long(), right=True) if joint else rows
+        ro = order[gid]                                                            # (n, M)
+        e = c.err.permute(1, 0, 2).gather(1, ro.clamp(min=0)[:, :, None].expand(-1, -1, 2))
+        e = torch.where((ro >= 0)[:, :, None], e, torch.full_like(e, float("inf")))
+        mb = assign[gid, c.best.long()]
+        acc += torch.cat([e[:, 0].double().sum(0), e.amin(1).double().sum(0),
+                          torch.stack([count.double().sum(), weight[:, 0].double().sum(), weight[gid, mb].double().sum(),
+                                       mb.double().sum()])])
+    nt, n_agents = data.n_test_samples, sum(b - a for a, b in base.scenes)
+    ng = len(base.scenes) if joint else n_agents
+    out = base.result(data)
     out.update(zip(NEW, (acc / torch.tensor([nt] * 4 + [ng] * 2 + [nt] * 2, dtype=torch.float64, device=dev)).tolist()))
     return out
 
 
-def first_chunk(tr, data, K, just_one):
-    batches = [(int(b[0]), int(b[1])) for b in data.test_batches][:1 if just_one else None]
-    i, j = next(iter(tr.eval_chunks(batches, K, tr.TEST_CHUNK)))
-    lo, hi = batches[i][0], batches[j - 1][1]
-    sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-    return data.obsv[lo:hi].contiguous(), sb
-
-
 def launch_pair(tr, data, K, just_one, joint, launches):
+    ops = T.sw.ops
     obsv, sb = first_chunk(tr, data, K, just_one)
     B = obsv.shape[0]
     torch.manual_seed(5)
@@ -137,30 +114,20 @@ def launch_pair(tr, data, K, just_one, joint, launches):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--launches", type=int, default=20, help="(b): selections per timed call")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    if a.repeats < 9:
-        ap.error("at least nine repeats")
-    if not torch.cuda.is_available():
-        sys.exit("nms_timing.py measures on an MI355X: no GPU found")
-    torch.manual_seed(0)
-    tr = sw.SocialWaysTrainer(12, use_social=True, device="cuda:0")
+    a = T.parse(__doc__, 9, 9, lambda ap: ap.add_argument("--launches", type=int, default=20, help="(b): selections per timed call"))
+    T.load("nms_timing.py")
+    tr = T.trainer()
     lines = ["(a) host clock around the call, ms; %d alternating repeats after %d warm-up calls of each; top_m %d, radius %.2f, %s; %s"
              % (a.repeats, a.warmup, TOP_M, RADIUS, METRIC, torch.cuda.get_device_name(0)),
              "%-88s %-6s %28s %28s %28s %9s %9s %s" % ("shape", "groups", "evaluate_ranked() median [min, max]", "evaluate_diverse()",
                                                        "same, selection by torch ops", "kernel", "torch", "max(kernel side) < min(torch side)")]
-    for name, n_scenes, agents, K, just_one in SHAPES:
-        data = held_out_set(n_scenes, agents, "cuda:0")
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        data = T.held_out_set(n_scenes, agents)
         for joint in (False, True):
-            calls = {"ranked": lambda: tr.evaluate_ranked(data, n_gen_samples=K, top_m=TOP_M, just_one=just_one),
-                     "diverse": lambda: tr.evaluate_diverse(data, n_gen_samples=K, top_m=TOP_M, radius=RADIUS, metric=METRIC,
-                                                            joint=joint, just_one=just_one),
+            calls = {"ranked": lambda: T.CALLS["evaluate_ranked"](tr, data, K, just_one),
+                     "diverse": lambda: T.CALLS["evaluate_diverse, joint" if joint else "evaluate_diverse"](tr, data, K, just_one),
                      "torch": lambda: torch_diverse(tr, data, K, TOP_M, RADIUS, METRIC, joint, just_one)}
-            ms, last = alternate(calls, timed, a.warmup, a.repeats)
+            ms, last = T.alternate(calls, a.warmup, a.repeats)
             med = {k: statistics.median(v) for k, v in ms.items()}
             lines.append("%-88s %-6s %28s %28s %28s %9.3f %9.3f %s" % (
                 name, "scene" if joint else "agent", cell(ms["ranked"]), cell(ms["diverse"]), cell(ms["torch"]),
@@ -174,21 +141,16 @@ def main():
                  "selection, %d per timed call; %d alternating repeats after %d warm-up calls" % (a.launches, a.repeats, a.warmup))
     lines.append("%-88s %-6s %6s %5s %28s %28s %8s %12s" % ("shape", "groups", "B", "K", "sw_sample_nms median [min, max]", "torch ops",
                                                           "ratio", "equal picks"))
-    for name, n_scenes, agents, K, just_one in SHAPES:
-        data = held_out_set(n_scenes, agents, "cuda:0")
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        data = T.held_out_set(n_scenes, agents)
         for joint in (False, True):
             calls, B, same = launch_pair(tr, data, K, just_one, joint, a.launches)
-            ms, _ = alternate(calls, lambda fn: (timed(fn)[0] / a.launches, None), a.warmup, a.repeats)
-            k, t = ms["kernel"], ms["torch"]
+            ms, _ = T.alternate(calls, a.warmup, a.repeats)
+            k, t = ([x / a.launches for x in ms[side]] for side in ("kernel", "torch"))
             lines.append("%-88s %-6s %6d %5d %28s %28s %8.3f %12.6f" % (
-                name, "scene" if joint else "agent", B, K, "%9.4f [%8.4f, %8.4f]" % (statistics.median(k), min(k), max(k)),
-                "%9.4f [%8.4f, %8.4f]" % (statistics.median(t), min(t), max(t)), statistics.median(k) / statistics.median(t), same))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text)
+                name, "scene" if joint else "agent", B, K, cell(k, fmt=PER_LAUNCH),
+                cell(t, fmt=PER_LAUNCH), statistics.median(k) / statistics.median(t), same))
+    T.write_out(lines, a.out)
 
 
 if __name__ == "__main__":

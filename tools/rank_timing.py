@@ -13,42 +13,31 @@ tools/sample_timing.py and by its method: host clock around calls that end in a 
 
     python tools/rank_timing.py [--repeats 9] [--out profiles/rank_eval_ab.txt]
 """
-import argparse
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(HERE, "tools"))
-import socialways_amd as sw  # noqa: E402
-from socialways_amd import ops  # noqa: E402
-from sample_timing import SHAPES, held_out_set, timed  # noqa: E402
-from scene_timing import alternate, cell  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _timing as T  # noqa: E402
+from _timing import PER_LAUNCH, TOP_M, cell, first_chunk  # noqa: E402
 
-TOP_M = 5
 NEW = ("ade_top1", "fde_top1", "ade_topm", "fde_topm", "best_rank", "score_draws", "score_gt", "code_mse")
 
 
 def torch_ranked(tr, data, K, M, just_one):
     """The numbers of evaluate_ranked() from Generator.sample(), K calls of Discriminator.forward and torch ops."""
     ss, dev, Tp = float(data.ss), tr.device, tr.n_next
-    batches = [(int(b[0]), int(b[1])) for b in data.test_batches][:1 if just_one else None]
     acc = torch.zeros(12, dtype=torch.float64, device=dev)
-    for i, j in tr.eval_chunks(batches, K, tr.TEST_CHUNK):
-        lo, hi = batches[i][0], batches[j - 1][1]
-        obsv, pred = data.obsv[lo:hi], data.pred[lo:hi]
+    for scenes, obsv, pred, sb in T.host_chunks(tr, data, K, just_one):
         with torch.no_grad():
-            noise = tr.eval_noise(batches[i:j], K, tr.noise_len).to(dev)
-            sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
+            noise = tr.eval_noise(scenes, K, tr.noise_len).to(dev)
             ph = tr.G.sample(obsv, K, Tp, sb, noise)
             e = ((ph[..., :2] - pred.unsqueeze(0)) / ss).pow(2).sum(-1).sqrt()                  # (K, n, Tp)
             err = torch.stack([e.mean(2), e[:, :, -1]], dim=2)                                   # (K, n, 2)
-            o4, p4 = sw.get_traj_4d(obsv, pred)
+            o4, p4 = T.sw.get_traj_4d(obsv, pred)
             outs = [tr.D(o4, ph[k]) for k in range(K)]
             score, code = torch.stack([l[:, 0] for l, _ in outs]), torch.stack([c for _, c in outs])
             order = torch.sort(score.t().contiguous(), dim=1, descending=True, stable=True)[1]  # (n, K)
@@ -63,16 +52,9 @@ def torch_ranked(tr, data, K, M, just_one):
     return dict(zip(("ade_avg", "fde_avg", "ade_min", "fde_min") + NEW, v))
 
 
-def first_chunk(tr, data, K, just_one):
-    batches = [(int(b[0]), int(b[1])) for b in data.test_batches][:1 if just_one else None]
-    i, j = next(iter(tr.eval_chunks(batches, K, tr.TEST_CHUNK)))
-    lo, hi = batches[i][0], batches[j - 1][1]
-    sb = np.asarray([[a - lo, b - lo] for a, b in batches[i:j]], dtype=np.int64)
-    return data.obsv[lo:hi].contiguous(), sb
-
-
 def launch_pair(tr, data, K, just_one, launches):
     """(calls, B): `launches` scoring launches, and as many sw_disc_fwd(nb = 1) launches on the replicated rows."""
+    ops = T.sw.ops
     obsv, sb = first_chunk(tr, data, K, just_one)
     B = obsv.shape[0]
     torch.manual_seed(5)
@@ -97,28 +79,19 @@ def launch_pair(tr, data, K, just_one, launches):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--launches", type=int, default=20, help="(b): launches per timed call")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    if a.repeats < 9:
-        ap.error("at least nine repeats")
-    if not torch.cuda.is_available():
-        sys.exit("rank_timing.py measures on an MI355X: no GPU found")
-    torch.manual_seed(0)
-    tr = sw.SocialWaysTrainer(12, use_social=True, device="cuda:0")
+    a = T.parse(__doc__, 9, 9, lambda ap: ap.add_argument("--launches", type=int, default=20, help="(b): launches per timed call"))
+    T.load("rank_timing.py")
+    tr = T.trainer()
     lines = ["(a) host clock around the call, ms; %d alternating repeats after %d warm-up calls of each; top_m %d; %s"
              % (a.repeats, a.warmup, TOP_M, torch.cuda.get_device_name(0)),
              "%-88s %28s %28s %28s %9s %9s %s" % ("shape", "evaluate() median [min, max]", "evaluate_ranked()",
                                                 "sample + K x forward + torch", "new part", "old part", "max(new) < min(old)")]
-    for name, n_scenes, agents, K, just_one in SHAPES:
-        data = held_out_set(n_scenes, agents, "cuda:0")
-        calls = {"evaluate": lambda: tr.evaluate(data, n_gen_samples=K, just_one=just_one),
-                 "ranked": lambda: tr.evaluate_ranked(data, n_gen_samples=K, top_m=TOP_M, just_one=just_one),
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        data = T.held_out_set(n_scenes, agents)
+        calls = {"evaluate": lambda: T.CALLS["evaluate"](tr, data, K, just_one),
+                 "ranked": lambda: T.CALLS["evaluate_ranked"](tr, data, K, just_one),
                  "torch": lambda: torch_ranked(tr, data, K, TOP_M, just_one)}
-        ms, last = alternate(calls, timed, a.warmup, a.repeats)
+        ms, last = T.alternate(calls, a.warmup, a.repeats)
         med = {k: statistics.median(v) for k, v in ms.items()}
         lines.append("%-88s %28s %28s %28s %9.3f %9.3f %s" % (name, cell(ms["evaluate"]), cell(ms["ranked"]), cell(ms["torch"]),
                                                             med["ranked"] - med["evaluate"], med["torch"] - med["evaluate"],
@@ -136,24 +109,18 @@ def main():
                  % (a.launches, a.repeats, a.warmup))
     lines.append("%-88s %6s %5s %28s %28s %8s %s" % ("shape", "B", "K", "sw_disc_score median [min, max]", "sw_disc_fwd, K * B rows",
                                                    "ratio", "score - fwd <= spread of fwd"))
-    for name, n_scenes, agents, K, just_one in SHAPES:
-        data = held_out_set(n_scenes, agents, "cuda:0")
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        data = T.held_out_set(n_scenes, agents)
         calls, B = launch_pair(tr, data, K, just_one, a.launches)
-        ms, _ = alternate(calls, lambda fn: (timed(fn)[0] / a.launches, None), a.warmup, a.repeats)
-        s, f = ms["score"], ms["replicated"]
-        lines.append("%-88s %6d %5d %28s %28s %8.3f %s" % (name, B, K, "%9.4f [%8.4f, %8.4f]" % (statistics.median(s), min(s), max(s)),
-                                                        "%9.4f [%8.4f, %8.4f]" % (statistics.median(f), min(f), max(f)),
+        ms, _ = T.alternate(calls, a.warmup, a.repeats)
+        s, f = ([t / a.launches for t in ms[k]] for k in ("score", "replicated"))
+        lines.append("%-88s %6d %5d %28s %28s %8.3f %s" % (name, B, K, cell(s, fmt=PER_LAUNCH), cell(f, fmt=PER_LAUNCH),
                                                         statistics.median(s) / statistics.median(f),
                                                         statistics.median(s) - statistics.median(f) <= max(f) - min(f)))
     lines.append("")
     lines.append("(c) not measured: the scoring and ranking kernels are new code next to the existing ones (disc_score_kernel in "
                  "sw_disc.hip, sample_rank_kernel in sw_misc.hip); disc_fwd_tile and every shared phase are unchanged.")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text)
+    T.write_out(lines, a.out)
 
 
 if __name__ == "__main__":
