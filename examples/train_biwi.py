@@ -13,6 +13,9 @@
   (one rank per GPU over RCCL; every packed batch is sharded scene-aligned, rank 0 evaluates and saves)
   `SW_ALLREDUCE=direct` exchanges the gradients through the library's own two-hop kernel over hipIpc-mapped peer buffers
   (one launch per optimizer step: exchange + Adam, inside the step's hipGraph) instead of RCCL's ring
+* `--min-past M`: the held-out windows also keep the pedestrians seen for only M .. 7 frames (create_dataset_ragged:
+  right-aligned observations + obs_len), so they are predicted and their neighbours see them; training stays on full
+  windows (there are no ragged backward kernels), the errors are reported per history length (evaluate_history)
 """
 import argparse
 import os
@@ -24,6 +27,20 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import socialways_amd as sw  # noqa: E402
+
+
+def ragged_held_out(obsmat, npz, like, min_past):
+    """The recording's windows with histories of min_past .. n_past frames, written to `npz`; of them the scenes at or after
+    the first held-out timestamp of `like` - the dataset the model trains on, so none of them holds a training window -
+    as an evaluation set in like's coordinates (SceneDataset.held_out)."""
+    obsvs, preds, times, batches, obs_len = sw.biwi_to_npz(obsmat, npz, like.n_past, like.n_next, min_past=min_past)
+    times = np.asarray(times)
+    t_split = like.times[like.n_train_samples]
+    keep = [(a, b) for a, b in batches if times[a] >= t_split]
+    rows = np.concatenate([np.arange(a, b) for a, b in keep])
+    ends = np.cumsum([b - a for a, b in keep])
+    scenes = np.stack([np.concatenate([[0], ends[:-1]]), ends], axis=1)
+    return sw.SceneDataset.held_out(like, obsvs[rows], preds[rows], scenes, times[rows], obs_len[rows])
 
 
 def main(argv=None):
@@ -43,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--diverse", type=float, default=None, metavar="RADIUS",
                     help="also report the diverse top-5 of the K draws: modes kept by suppressing, in the discriminator's score "
                          "order, every draw whose end point lies within RADIUS (world units) of a kept one")
+    ap.add_argument("--min-past", type=int, default=None, metavar="M",
+                    help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
+                         "histories) and report the errors per history length; training stays on full windows")
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -67,6 +87,11 @@ def main(argv=None):
     if world > 1:
         torch.distributed.barrier()
     data = sw.SceneDataset.from_npz(npz, device=dev)
+    ragged = None
+    if args.min_past is not None and rank == 0:
+        ragged = ragged_held_out(obsmat, os.path.join(args.out, "crowd-8-12-ragged.npz"), data, args.min_past)
+        print("ragged held-out set: %d windows in %d scenes, %d of them with fewer than %d frames"
+              % (ragged.n_test_samples, len(ragged.test_batches), int((ragged.obs_len < data.n_past).sum()), data.n_past))
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
@@ -95,6 +120,12 @@ def main(argv=None):
                       "first mode holds %.0f %% of the draws, the min-ADE mode %.0f %%"
                       % (dv["top_m"], args.diverse, dv["ade_div1"], dv["fde_div1"], dv["ade_divm"], dv["fde_divm"], dv["n_modes"],
                          100 * dv["w_first"], 100 * dv["w_hit"]))
+            if ragged is not None:
+                hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
+                print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"
+                      % (hist["ade_avg"], hist["fde_avg"], args.k, hist["ade_min"], hist["fde_min"],
+                         ", ".join("%d frames (%d agents) %.3f / %.3f" % (n, v["count"], v["ade_min"], v["fde_min"])
+                                   for n, v in sorted(hist["by_len"].items()))))
             tr.save(os.path.join(args.out, "socialWays-crowd.pt"), epoch=epoch)
     if world > 1:
         tr.close()              # captured collectives and the direct exchange's buffers go before their process group

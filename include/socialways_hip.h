@@ -78,6 +78,21 @@ int sw_enc_lstm_fwd(const float* x, int x_mode, const float* enc_w, const float*
 int sw_enc_lstm_fwd_aux(const float* x, int x_mode, const float* enc_w, const float* h0, const float* c0, int B, int T,
                         float* hT, float* cT, float* y, float* act, float* x4s, int t0, const float* aux_src,
                         float* aux_dst, long long aux_n, void* stream);
+/* The inference form (zero initial state, nothing saved) for RAGGED observation histories.  `x` stays the dense buffer,
+ * RIGHT-ALIGNED: row a has n_a = obs_len[a] valid frames in columns s_a = T - n_a .. T-1, 2 <= n_a <= T for positions
+ * (x_mode 0), 1 <= n_a <= T for 4-d input (x_mode 1); the columns in front of s_a are padding.  obs_len: int32 [B] on
+ * the device, NULL = every row has T frames.  Row a's state is zero until step s_a, steps s_a .. T-1 run the cell on the
+ * 4-d states get_traj_4d gives for the valid frames alone (x_t = (p_t, p_t - p_{t-1}) for t > s_a, (p_s, p_{s+1} - p_s)
+ * at s_a): hT[a] / cT[a] are, bit for bit, what sw_enc_lstm_fwd returns for the [1, n_a, .] buffer of the valid frames,
+ * with and without registered generator images (sw_gen_images).  The padding is never read: no output bit depends on
+ * it, NaN / Inf included.  An obs_len outside its range is clamped into it on the device (no out-of-bounds read, no
+ * host sync).  The step loop keeps the shape of the dense kernel - every lane computes every step and selects the zero
+ * state in front of its start, no conditional memory operation, one uniform barrier per step - in a kernel of its own:
+ * the kernels sw_enc_lstm_fwd* launch are unchanged.
+ * SW_EARG before any device call: x, enc_w, hT or cT NULL, B < 0, T < 1, x_mode not 0 / 1, T < 2 with x_mode 0.
+ * B == 0: SW_OK without a launch.                                                                                       */
+int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const int* obs_len /*[B] int32 or NULL = all T*/,
+                           int B, int T, float* hT /*[B,64]*/, float* cT /*[B,64]*/, void* stream);
 /* BPTT over rows t0+T-1 .. t0 of `act`; dhT/dcT = gradient w.r.t. the final state (dcT may be
  * NULL); dy optional [B,T,64].  Writes dgates rows [t][B][256]; dh0/dc0 optional outputs.       */
 int sw_enc_lstm_bwd(const float* enc_w, const float* act, const float* c0, const float* dhT,
@@ -393,6 +408,16 @@ int sw_disc_dpred(const float* obsv, int To, int x_mode, const float* pred4 /*[B
  *      SW_ESHAPE: Tp > 64.  B == 0: SW_OK without a launch.  LDS per workgroup: 89 600 B at Tp = 12, 149 504 B at 64.   */
 int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4 /*[K*B,Tp,4]*/, const float* d_w, int B, int K,
                   int Tp, float* score /*[K*B]*/, float* code /*[K*B,2] or NULL*/, void* stream);
+
+/* sw_disc_score with the ragged observation pass of sw_enc_lstm_fwd_ragged: obsv right-aligned, obs_len int32 [B] on the
+ * device (2 <= n <= To for positions, 1 <= n <= To for obsv_4d; clamped on the device; the padding is never read), row a's
+ * observation LSTM starts from the zero state at step To - obs_len[a].  score[k*B + a] / code[k*B + a] are the bits
+ * sw_disc_score gives agent a on the [1, n_a, .] buffer of its valid frames and its draws.  Same grid and k-group rule,
+ * same LDS, same argument checks, same behaviour with and without sw_disc_images; a kernel of its own (sw_disc_score's
+ * is unchanged).  obs_len == NULL: every row has To frames - sw_disc_score's bits.                                       */
+int sw_disc_score_ragged(const float* obsv, int To, int x_mode, const int* obs_len /*[B] int32 or NULL = all To*/,
+                         const float* pred4 /*[K*B,Tp,4]*/, const float* d_w, int B, int K, int Tp, float* score /*[K*B]*/,
+                         float* code /*[K*B,2] or NULL*/, void* stream);
 
 /* ---- LSGAN + InfoGAN losses of train.py:484-494 / 512-523 and their gradients -------------- */
 /* t_a = targets[ia], t_b = targets[ib] (read on the device, so a captured hipGraph sees new values).

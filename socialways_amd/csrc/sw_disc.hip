@@ -584,9 +584,14 @@ __host__ __device__ inline ScoreLds score_lds(int Tp) {
 }
 }  // namespace
 
+// RAGGED: the observation pass starts row b at step To - obs_len[b] (lstm_obs_loop_ragged); everything behind it is the same
+// code.  A template parameter with obs_len as the LAST argument: the dense instance keeps the dense loop, its argument
+// layout and its code.
+template <bool RAGGED>
 __global__ __launch_bounds__(SW_THREADS) void disc_score_kernel(
     const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred4, const float* __restrict__ d_w, int B, int K,
-    int Tp, float* __restrict__ score, float* __restrict__ code, int tiles, int kgroups, const float* __restrict__ dimg) {
+    int Tp, float* __restrict__ score, float* __restrict__ code, int tiles, int kgroups, const float* __restrict__ dimg,
+    const int* __restrict__ obs_len) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* hbuf = smem;                   // [2][16][SW_HLD]
   const ScoreLds S = score_lds(Tp);
@@ -612,8 +617,13 @@ __global__ __launch_bounds__(SW_THREADS) void disc_score_kernel(
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};   // h0 = c0 = 0 (train.py:296-297)
   disc_seed_h(hbuf, false, nullptr, To, B, b);
   sw_barrier();
-  if (x_mode == 0) lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
-  else lstm_obs_loop<1, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
+  if constexpr (RAGGED) {
+    if (x_mode == 0) lstm_obs_loop_ragged<0>(W, hbuf, obsv, To, b, obs_start(obs_len, b, To, 0), c, h);
+    else lstm_obs_loop_ragged<1>(W, hbuf, obsv, To, b, obs_start(obs_len, b, To, 1), c, h);
+  } else {
+    if (x_mode == 0) lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
+    else lstm_obs_loop<1, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
+  }
   // observation fc (waves 0, 1) -> both[0 | 1][:, 0:32]
   disc_obs_fc(smem, F, &hbuf[(To & 1) * 16 * SW_HLD], smem + F.o1, nullptr, live, smem + S.both, 2);
 
@@ -694,8 +704,9 @@ static int disc_score_kgroups(int tiles, int K) {
   return g < 1 ? 1 : g;
 }
 
-extern "C" int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4, const float* d_w, int B, int K, int Tp,
-                             float* score, float* code, void* stream) {
+// sw_disc_score and sw_disc_score_ragged: one set of checks, one grid rule; the dense entry launches the dense kernel
+static int disc_score_launch(bool ragged, const float* obsv, int To, int x_mode, const int* obs_len, const float* pred4,
+                             const float* d_w, int B, int K, int Tp, float* score, float* code, void* stream) {
   if (!obsv || !pred4 || !d_w || !score || K < 1 || B < 0 || To < 1 || Tp < 1 || (x_mode != 0 && x_mode != 1) ||
       (x_mode == 0 && To < 2))
     return SW_EARG;
@@ -703,15 +714,30 @@ extern "C" int sw_disc_score(const float* obsv, int To, int x_mode, const float*
   if (B == 0) return SW_OK;
   const int lds = score_lds(Tp).total * 4;
   if (lds > 163840) return SW_ESHAPE;
-  static int have = 0;
-  if (int rc = sw_set_lds((const void*)disc_score_kernel, lds, have)) return rc;
+  static int have = 0, have_ragged = 0;
+  if (int rc = ragged ? sw_set_lds((const void*)disc_score_kernel<true>, lds, have_ragged)
+                      : sw_set_lds((const void*)disc_score_kernel<false>, lds, have))
+    return rc;
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   const int kgroups = disc_score_kgroups(tiles, K);
   if ((long long)tiles * kgroups > 0x7fffffffLL) return SW_ESHAPE;
-  SW_LAUNCH(disc_score_kernel, dim3((unsigned)(tiles * kgroups)), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode, pred4,
-            d_w, B, K, Tp, score, code, tiles, kgroups, sw_disc_images_for(d_w, Tp).img);
+  const float* dimg = sw_disc_images_for(d_w, Tp).img;
+  if (ragged)
+    SW_LAUNCH(disc_score_kernel<true>, dim3((unsigned)(tiles * kgroups)), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode,
+              pred4, d_w, B, K, Tp, score, code, tiles, kgroups, dimg, obs_len);
+  else
+    SW_LAUNCH(disc_score_kernel<false>, dim3((unsigned)(tiles * kgroups)), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode,
+              pred4, d_w, B, K, Tp, score, code, tiles, kgroups, dimg, (const int*)nullptr);
   SW_CHECK_LAUNCH("disc_score_kernel");
   return SW_OK;
+}
+extern "C" int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4, const float* d_w, int B, int K, int Tp,
+                             float* score, float* code, void* stream) {
+  return disc_score_launch(false, obsv, To, x_mode, nullptr, pred4, d_w, B, K, Tp, score, code, stream);
+}
+extern "C" int sw_disc_score_ragged(const float* obsv, int To, int x_mode, const int* obs_len, const float* pred4, const float* d_w,
+                                    int B, int K, int Tp, float* score, float* code, void* stream) {
+  return disc_score_launch(true, obsv, To, x_mode, obs_len, pred4, d_w, B, K, Tp, score, code, stream);
 }
 
 extern "C" int sw_disc_dpred_supported(int Tp) { return Tp >= 1 && Tp <= 64 && disc_dpred_lds(Tp) <= 163840 ? 1 : 0; }

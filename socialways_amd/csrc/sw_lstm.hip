@@ -320,6 +320,53 @@ extern "C" int sw_enc_lstm_fwd(const float* x, int x_mode, const float* enc_w, c
   return sw_enc_lstm_fwd_aux(x, x_mode, enc_w, h0, c0, B, T, hT, cT, y, act, x4s, t0, nullptr, nullptr, 0, stream);
 }
 
+// The inference form of enc_lstm_fwd_kernel (zero initial state, nothing saved) for ragged observation histories: row b
+// runs its last obs_len[b] steps (lstm_obs_loop_ragged, sw_lstm_dev.h).  A kernel of its own, so that the instantiations
+// above - the training step's among them - keep their code.
+template <int XMODE>
+__global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_ragged_kernel(
+    const float* __restrict__ x, const float* __restrict__ enc_w, const int* __restrict__ obs_len, int B, int T,
+    float* __restrict__ hT, float* __restrict__ cT, const float* __restrict__ gimg) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2 * SW_TILE * SW_HLD];
+  __shared__ __attribute__((aligned(16))) float wx_lds[256 * 4];
+  __shared__ __attribute__((aligned(16))) float bx_lds[256];
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int u0 = wave * 16;
+  const int b = min((int)blockIdx.x * SW_TILE + ln, B - 1);   // padding lanes of the last tile: replicas of agent B-1
+  LstmW W;
+  if (gimg) {
+    lstm_load_img(W, gimg, wave, lane);
+  } else {
+    lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
+    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
+                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
+  }
+  const int s = obs_start(obs_len, b, T, XMODE);
+  f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
+  st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], h);
+  sw_barrier();
+  if (!gimg) lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
+  lstm_obs_loop_ragged<XMODE>(W, hbuf, x, T, b, s, c, h);
+  st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
+  st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
+}
+
+extern "C" int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const int* obs_len, int B, int T,
+                                      float* hT, float* cT, void* stream) {
+  if (!x || !enc_w || !hT || !cT || B < 0 || T < 1 || (x_mode != 0 && x_mode != 1) || (x_mode == 0 && T < 2)) return SW_EARG;
+  if (B == 0) return SW_OK;
+  const float* gimg = sw_gen_images_for(enc_w, nullptr);
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
+  if (x_mode == 0)
+    SW_LAUNCH(enc_lstm_fwd_ragged_kernel<0>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T, hT, cT,
+              gimg);
+  else
+    SW_LAUNCH(enc_lstm_fwd_ragged_kernel<1>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T, hT, cT,
+              gimg);
+  SW_CHECK_LAUNCH("enc_lstm_fwd_ragged_kernel");
+  return SW_OK;
+}
+
 extern "C" int sw_enc_lstm_bwd_aux(const float* enc_w, const float* act, const float* c0, const float* dhT,
                                    const float* dcT, const float* dy, int B, int T, int t0, float* dgates,
                                    float* dh0, float* dc0, const float* aux_src, float* aux_dst, const float* aux_mask,

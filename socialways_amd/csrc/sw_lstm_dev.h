@@ -402,6 +402,58 @@ __device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const
   }
 }
 
+// ---- ragged observation histories (sw_enc_lstm_fwd_ragged, sw_disc_score_ragged) ---------------------------------------
+// Row b of x holds n = obs_len[b] valid frames RIGHT-ALIGNED in its T columns: its LSTM starts from the zero state at step
+// s = T - n, the columns in front of s are padding that is never read.  n is clamped on the device into 2 .. T for positions
+// (the velocity rule needs two points), 1 .. T for 4-d input; obs_len == nullptr: every row starts at 0.
+__device__ __forceinline__ int obs_start(const int* __restrict__ obs_len, int b, int T, int xmode) {
+  const int n = obs_len ? min(max(obs_len[b], xmode == 0 ? 2 : 1), T) : T;
+  return T - n;
+}
+// obs_x4_load for a row that starts at step s: t is clamped to >= s and the first-frame rule v_s := v_{s+1} sits at s
+// (get_traj_4d on the valid frames alone); s = 0 is obs_x4_load.  Branch-free like it.
+__device__ __forceinline__ void obs_x4_load_from(const float* pos, int b, int t, int s, int T, int comp, float& a, float& q) {
+  const float* p = pos + (size_t)b * T * 2;
+  const int c = comp & 1, te = max(t, s), tt = te == s ? s + 1 : te;
+  const bool vel = comp >= 2;
+  a = p[(vel ? tt : te) * 2 + c];
+  q = p[(vel ? tt - 1 : te) * 2 + c];
+}
+// lstm_obs_loop<XMODE, false> from the ZERO state (hbuf[0] zeroed, c = h = 0) with a start step s per lane.  The loop keeps
+// its shape - every lane computes the cell on every step, no conditional memory operation, one uniform barrier per step -
+// and a lane in front of its start SELECTS the zero state instead of the cell's result (the input index is clamped to
+// >= s, so that cell ran on finite values and nothing of the padding was loaded).  From step s on the lane's agent sees
+// exactly the operands of the T - s step run on its valid frames: an agent is one column of the products, so h_T / c
+// carry the bits of lstm_obs_loop on the truncated buffer.  A separate function: the dense loop above keeps its code.
+template <int XMODE>
+__device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int b, int s,
+                                                     f32x4& c, f32x4& h) {
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int u0 = wave * 16;
+  float xa, xq = 0.f;
+  auto load_x = [&](int t) {
+    if constexpr (XMODE == 0) obs_x4_load_from(x, b, t, s, T, lg, xa, xq);
+    else xa = x[((size_t)b * T + max(t, s)) * 4 + lg];
+  };
+  load_x(0);
+  asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE, as in lstm_obs_loop
+  for (int t = 0; t < T; ++t) {
+    const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
+    load_x(min(t + 1, T - 1));
+    f32x4 gate[4];
+    lstm_cell(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], gate, c, h);
+    const bool on = t >= s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      c[r] = on ? c[r] : 0.f;
+      h[r] = on ? h[r] : 0.f;
+    }
+    st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
+    sw_barrier();
+    asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
+  }
+}
+
 // Observation LSTM of the discriminator (train.py:296-299) for the 16-agent tile at a0, leaving the rows its
 // backward needs (see lstm_obs_loop).  It exists as a function so that idle workgroups of ANOTHER launch can run it
 // (the first D pass of a step does not depend on the generator: sw_dec_rollout_fwd_aux).

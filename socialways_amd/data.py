@@ -34,12 +34,25 @@ class Scale(object):
         return out
 
 
+def check_obs_len(obs_len, B, To, lo):
+    """Host data (list / numpy) given as obs_len -> int32 numpy (B,), or ValueError: not integers, not (B,), or a value
+    outside lo .. To (lo = 2 for positions - the velocity rule needs two frames -, 1 for 4-d input)."""
+    a = np.asarray(obs_len)
+    if a.dtype.kind not in "iu":
+        raise ValueError("obs_len must hold integers, got dtype %s" % a.dtype)
+    if a.shape != (B,):
+        raise ValueError("obs_len must be (B,) = (%d,), got %s" % (B, a.shape))
+    if B and (a.min() < lo or a.max() > To):
+        raise ValueError("obs_len must lie in %d .. To = %d, got %d .. %d" % (lo, To, a.min(), a.max()))
+    return a.astype(np.int32)
+
+
 class SceneDataset:
     """train.py:89-124: 4/5 of the scenes train, the rest test; float32 keep-ratio normalisation;
     tracks resident on the device for the whole run.  `batches` may be int16 on disk
     (utils/parse_utils.py:490 overflows above 32767 rows): widened to int64 here."""
 
-    def __init__(self, obsvs, preds, batches, times=None, device="cuda"):
+    def __init__(self, obsvs, preds, batches, times=None, device="cuda", obs_len=None):
         obsvs = np.array(obsvs, dtype=np.float32, copy=True)
         preds = np.array(preds, dtype=np.float32, copy=True)
         self.the_batches = np.asarray(batches).astype(np.int64)
@@ -64,11 +77,37 @@ class SceneDataset:
         self.scale, self.ss = sc, sc.sx
         self.obsv = torch.from_numpy(sc.normalize(obsvs)).to(device)
         self.pred = torch.from_numpy(sc.normalize(preds)).to(device)
+        # ragged histories (create_dataset_ragged): valid frames per row, right-aligned in obsv; int32 on the device, or None
+        self.obs_len = None
+        if obs_len is not None:
+            self.obs_len = torch.from_numpy(check_obs_len(obs_len, obsvs.shape[0], self.n_past, 2)).to(device)
+
+    @classmethod
+    def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None):
+        """Windows that a model trained on `like` is evaluated on: EVERY scene is a test scene (no training part), the
+        coordinates are those of `like` - its scale, not one of these windows' own - and the tensors live on its device.
+        What evaluate*() / evaluate_history() read; batches (S, 2) must cover rows 0 .. N-1."""
+        d = cls.__new__(cls)
+        obsvs = np.array(obsvs, dtype=np.float32, copy=True)
+        preds = np.array(preds, dtype=np.float32, copy=True)
+        d.the_batches = np.asarray(batches).astype(np.int64).reshape(-1, 2)
+        d.times = None if times is None else np.asarray(times)
+        d.train_size, d.train_batches, d.test_batches = 0, d.the_batches[:0], d.the_batches
+        d.n_past, d.n_next = obsvs.shape[1], preds.shape[1]
+        d.n_train_samples, d.n_test_samples = 0, obsvs.shape[0]
+        d.scale, d.ss = like.scale, like.ss
+        d.obsv = torch.from_numpy(like.scale.normalize(obsvs)).to(like.obsv.device)
+        d.pred = torch.from_numpy(like.scale.normalize(preds)).to(like.obsv.device)
+        d.obs_len = None
+        if obs_len is not None:
+            d.obs_len = torch.from_numpy(check_obs_len(obs_len, obsvs.shape[0], d.n_past, 2)).to(like.obsv.device)
+        return d
 
     @classmethod
     def from_npz(cls, path, device="cuda"):
         d = np.load(path)
-        return cls(d["obsvs"], d["preds"], d["batches"], d["times"] if "times" in d.files else None, device)
+        return cls(d["obsvs"], d["preds"], d["batches"], d["times"] if "times" in d.files else None, device,
+                   d["obs_len"] if "obs_len" in d.files else None)
 
     def packed_steps(self, batch_size):
         """Greedy scene packing of train() (train.py:446-456): scenes are appended until the next one
@@ -230,8 +269,17 @@ def create_dataset(p_data, t_data, t_range, n_past=8, n_next=12):
             t0s.append(t)
             xs.append(p_data[i][a:b])
             ys.append(p_data[i][b:c + 1])
+    keep, batches = _scene_runs(t0s)
+    obsvs = np.array([xs[k] for k in keep]).astype(np.float32)
+    preds = np.array([ys[k] for k in keep]).astype(np.float32)
+    return obsvs, preds, t0s, batches
+
+
+def _scene_runs(t0s):
+    """The scenes of create_dataset(): runs of windows sharing t (min_interval = 1, parse_utils.py:481-489) ->
+    (rows kept, in order; batches int64 (S, 2) over the kept rows)."""
     batches, keep, last_t = [], [], -1000
-    for i, t in enumerate(t0s):          # min_interval = 1 (parse_utils.py:481-489)
+    for i, t in enumerate(t0s):
         if t > last_t + 1:
             batches.append([i, i + 1])
             last_t = t
@@ -242,18 +290,55 @@ def create_dataset(p_data, t_data, t_range, n_past=8, n_next=12):
         keep += list(range(a, b))
         out_b.append([last, last + (b - a)])
         last += b - a
+    return keep, np.array(out_b, dtype=np.int64)
+
+
+def create_dataset_ragged(p_data, t_data, t_range, n_past=8, n_next=12, min_past=2):
+    """create_dataset() that also keeps the pedestrians with a SHORT history: one is kept at t if it has samples at t and at
+    t + step*(n_next-1), and its history n is the largest j in min_past .. n_past with a sample at t - step*j exactly j
+    entries before t (none: dropped).  obsvs stay (N, n_past, 2), RIGHT-ALIGNED: row r holds its obs_len[r] samples before
+    t in its last columns, the columns in front repeat the first valid sample (a real, finite position, so the
+    normalisation of SceneDataset is the one of the valid samples).  Windows are ordered and grouped into scenes as in
+    create_dataset(); with min_past == n_past the first four outputs are create_dataset()'s for tracks without gaps (a gap
+    inside the history: create_dataset() only asks for a sample at t - step*n_past, this builder for n_past samples).
+    Returns (obsvs f32, preds f32, times list, batches int64, obs_len int32 (N,))."""
+    n_past, min_past = int(n_past), int(min_past)
+    if not 1 <= min_past <= n_past:
+        raise ValueError("min_past must lie in 1 .. n_past = %d, got %d" % (n_past, min_past))
+    step = t_range.step
+    index = [dict((int(t), k) for k, t in reversed(list(enumerate(td)))) for td in t_data]   # first occurrence wins
+    t0s, xs, ys, ns = [], [], [], []
+    for t in range(t_range.start, t_range.stop, 1):
+        for i, ix in enumerate(index):
+            b, c = ix.get(t), ix.get(t + step * (n_next - 1))
+            if b is None or c is None:
+                continue
+            n = next((j for j in range(n_past, min_past - 1, -1) if ix.get(t - step * j) == b - j and b - j >= 0), 0)
+            if n == 0:
+                continue
+            o = p_data[i][b - n:b]
+            t0s.append(t)
+            xs.append(np.concatenate([np.repeat(o[:1], n_past - n, axis=0), o]))
+            ys.append(p_data[i][b:c + 1])
+            ns.append(n)
+    keep, batches = _scene_runs(t0s)
     obsvs = np.array([xs[k] for k in keep]).astype(np.float32)
     preds = np.array([ys[k] for k in keep]).astype(np.float32)
-    return obsvs, preds, t0s, np.array(out_b, dtype=np.int64)
+    return obsvs, preds, t0s, batches, np.array([ns[k] for k in keep], dtype=np.int32)
 
 
-def biwi_to_npz(obsmat_path, npz_path, n_past=8, n_next=12):
-    """create_dataset.py:1-15: obsmat.txt -> npz {obsvs, preds, times, batches}."""
+def biwi_to_npz(obsmat_path, npz_path, n_past=8, n_next=12, min_past=None):
+    """create_dataset.py:1-15: obsmat.txt -> npz {obsvs, preds, times, batches}.  min_past: the windows of
+    create_dataset_ragged(min_past=...) instead, and `obs_len` with them (also returned, fifth)."""
     p_data, t_data, interval = parse_biwi(obsmat_path)
-    obsvs, preds, times, batches = create_dataset(p_data, t_data, range(int(t_data[0][0]), int(t_data[-1][-1]), interval),
-                                                  n_past, n_next)
-    np.savez(npz_path, obsvs=obsvs, preds=preds, times=times, batches=batches)
-    return obsvs, preds, times, batches
+    t_range = range(int(t_data[0][0]), int(t_data[-1][-1]), interval)
+    if min_past is None:
+        obsvs, preds, times, batches = create_dataset(p_data, t_data, t_range, n_past, n_next)
+        np.savez(npz_path, obsvs=obsvs, preds=preds, times=times, batches=batches)
+        return obsvs, preds, times, batches
+    obsvs, preds, times, batches, obs_len = create_dataset_ragged(p_data, t_data, t_range, n_past, n_next, min_past)
+    np.savez(npz_path, obsvs=obsvs, preds=preds, times=times, batches=batches, obs_len=obs_len)
+    return obsvs, preds, times, batches, obs_len
 
 
 def synth_crowd_frames(n_frames=60, n_ped=24, interval=6, seed=3, max_life=40):

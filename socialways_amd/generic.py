@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d
+from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d, refuse_obs_len
 from .trainer import SocialWaysTrainer
 
 
@@ -314,9 +314,11 @@ class Discriminator(nn.Module):                             # train.py:272-316
         both = torch.cat([obsv_code, pred_code], dim=1)
         return _mlp(self.classifier, both), _mlp(self.latent_decoder, both)
 
-    def score_samples(self, obsv, preds):
+    def score_samples(self, obsv, preds, obs_len=None):
         """The call of the 64-unit Discriminator.score_samples(): obsv (B, To, 2 | 4), preds (K, B, Tp, 4) -> (score (K, B),
-        code_hat (K, B, n_latent_code)).  At these widths it is forward() once per draw (no scoring kernel here).  No gradients."""
+        code_hat (K, B, n_latent_code)).  At these widths it is forward() once per draw (no scoring kernel here).  No gradients.
+        An obs_len is refused (ragged histories belong to the fused 64-unit path)."""
+        refuse_obs_len(obs_len, type(self).__name__)
         check_score_samples(obsv, preds, self.n_next)
         with torch.no_grad():
             o4 = get_traj_4d(obsv, []) if obsv.shape[2] == 2 else obsv
@@ -383,10 +385,11 @@ class Generator(nn.Module):
                 h, c = self.encoder.step(last, h, c)
         return torch.stack(out, dim=1)
 
-    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0):
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0, obs_len=None):
         """n_samples futures per agent, (K, B, n_next, 4) - the call of the 64-unit Generator.sample().  At these widths it is
         forward() on K copies of the batch, each copy with its scenes (no sampling kernels here).  No gradients.  A DeviceNoise
-        is refused (the device noise stream belongs to the fused 64-unit path)."""
+        is refused (the device noise stream belongs to the fused 64-unit path), and so is an obs_len (ragged histories)."""
+        refuse_obs_len(obs_len, type(self).__name__)
         L.require_gpu(obsv_p)
         K, B = int(n_samples), obsv_p.shape[0]
         noise = _sample_noise(noise, K, B, self.noise_len, obsv_p.device)
@@ -535,8 +538,8 @@ class GenericTrainer(SocialWaysTrainer):
     def _sample_draws(self, c, K, ss, want_pred):
         """The evaluate_*() family at these widths: the draws come from Generator.sample() (the rollouts of test()), their
         errors from the expressions of test(); the reduction over k and the scene metrics are the library's kernels, which
-        do not depend on the hidden size."""
-        ph = self.G.sample(c.obsv, K, self.n_next, c.sb, c.z)
+        do not depend on the hidden size.  A ragged dataset (c.obs_len) is refused by Generator.sample()."""
+        ph = self.G.sample(c.obsv, K, self.n_next, c.sb, c.z, obs_len=c.obs_len)
         e = torch.pow((ph[..., :2] - c.pred.unsqueeze(0)) / ss, 2).sum(dim=3).sqrt()
         err = torch.stack([e.mean(2), e[:, :, -1]], dim=2).contiguous()
         per_agent = torch.empty(c.n, 4, device=err.device)

@@ -653,14 +653,16 @@ class Discriminator(_Packed):
         labels, codes, _ = ops.disc_forward(self.packed(), obsv, [pred], save=False)
         return labels[0], codes[0]
 
-    def score_samples(self, obsv, preds):
+    def score_samples(self, obsv, preds, obs_len=None):
         """K futures per agent scored in one launch (ops.disc_score): obsv (B, To, 2) positions or (B, To, 4), preds
         (K, B, Tp, 4) - what Generator.sample() returns -> (score (K, B) raw LSGAN score, higher = more realistic,
         code_hat (K, B, 2)).  What K calls of forward(get_traj_4d(obsv), preds[k]) return, bit for bit, with the observation
-        encoded once.  No gradients."""
+        encoded once.  obs_len (B,) - tensor, numpy array or list: ragged histories as Generator.sample(), agent a is
+        scored on its obs_len[a] valid frames alone (at least 2 positions, or 1 4-d state).  No gradients."""
         check_score_samples(obsv, preds, self.n_next)
+        obs_len = ops.obs_len_arg(obs_len, obsv.shape[0], obsv.shape[1], 2 if obsv.shape[2] == 2 else 1, obsv.device)
         with torch.no_grad():
-            return ops.disc_score(self.packed(), obsv, preds, preds.shape[0])
+            return ops.disc_score(self.packed(), obsv, preds, preds.shape[0], obs_len=obs_len)
 
     def load(self, backup):
         """Restore nn.Linear weights/biases only; the LSTM keeps its update (train.py:311-316)."""
@@ -774,16 +776,23 @@ class Generator(nn.Module):
                                    self.decoder.packed(), obsv_p, noise, scenes, n_next, self.use_social, save=False)
         return pred4
 
-    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0):
+    def sample(self, obsv_p, n_samples, n_next, sub_batches=[], noise=None, row0=0, obs_len=None):
         """n_samples futures per agent: pred_hat_4d (K, B, n_next, 4), sample k of agent a at [k, a] - what K calls of
         forward() on the same observations give, with the observation encoding and the social block computed once
         (ops.gen_sample).  noise (K, B, noise_len), None = torch.rand on the device, or a DeviceNoise: its evaluation
         domain at step 0, draws 0 .. K-1, rows row0 .. row0 + B-1 (one launch that also writes the zero padding; the same
-        agents at the same rows get the same futures whatever else is in the batch's other scenes).  No gradients."""
+        agents at the same rows get the same futures whatever else is in the batch's other scenes).
+        obs_len (B,) - tensor, numpy array or list: ragged histories.  Agent a has obs_len[a] valid frames, 2 .. To,
+        RIGHT-ALIGNED in obsv_p (the columns in front are padding that is never read, whatever it holds); its encoding is
+        the encoder's over those frames alone, from the zero state, and it takes part in the social block of its scene like
+        every other agent (that block and the rollout read the last frames).  Host data out of range, a wrong shape or a
+        non-integer dtype: ValueError; a device tensor is clamped by the kernel.  None: every agent has To frames.
+        No gradients."""
         L.require_gpu(obsv_p)
         if obsv_p.dim() != 3 or obsv_p.shape[2] != 2 or obsv_p.shape[1] < 2:
             raise ValueError("obsv_p must be (B, To >= 2, 2), got %s" % (tuple(obsv_p.shape),))
         K, B = int(n_samples), obsv_p.shape[0]
+        obs_len = ops.obs_len_arg(obs_len, B, obsv_p.shape[1], 2, obsv_p.device)
         if isinstance(noise, DeviceNoise):
             if K < 1:
                 raise ValueError("n_samples must be at least 1")
@@ -795,7 +804,8 @@ class Generator(nn.Module):
         scenes = _scene_index(sub_batches, B, obsv_p.device)
         with torch.no_grad():
             pred4, _ = ops.gen_sample(self.encoder.packed(), self.feature_embedder.packed(), self.attention.packed(),
-                                      self.decoder.packed(), obsv_p, noise.reshape(K * B, 32), scenes, n_next, self.use_social, K)
+                                      self.decoder.packed(), obsv_p, noise.reshape(K * B, 32), scenes, n_next, self.use_social, K,
+                                      obs_len=obs_len)
         return pred4.view(K, B, n_next, 4)
 
 
@@ -840,12 +850,20 @@ def predict(obsv_p, noise, n_next, sub_batches=[], generator=None):
     return g(obsv_p, noise, n_next, sub_batches)
 
 
-def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None, row0=0):
-    """Module-level Generator.sample(): n_samples futures per agent, (K, B, n_next, 4), from `generator` (or the default one)."""
+def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None, row0=0, obs_len=None):
+    """Module-level Generator.sample(): n_samples futures per agent, (K, B, n_next, 4), from `generator` (or the default one);
+    obs_len: ragged histories, as Generator.sample()."""
     g = generator or _default_generator
     if g is None:
         raise RuntimeError("no generator: pass generator= or call set_default_generator()")
-    return g.sample(obsv_p, n_samples, n_next, sub_batches, noise, row0=row0)
+    return g.sample(obsv_p, n_samples, n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
+
+
+def refuse_obs_len(obs_len, who):
+    """The generic-width and wide paths have no ragged kernels: an obs_len there is refused, loudly, before any launch."""
+    if obs_len is not None:
+        raise L.SocialWaysHipError("%s does not take an obs_len: ragged observation histories are implemented for the fused "
+                                   "64-unit path only (hidden_size <= 64, n_latent_codes = 2)" % who)
 
 
 def predict_cv(obsv, n_next):

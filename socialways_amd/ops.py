@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .data import check_obs_len
 
 
 class SceneIndex:
@@ -336,17 +337,45 @@ def gen_backward_k(enc_w, emb_w, att_w, dec_w, ctx, dpred4_k, d_enc, d_emb, d_at
            L.ptr(d_enc), L.ptr(d_dec), 2, L.ptr(wgrad), L.ptr(tmp), pending, L.stream())
 
 
+def obs_len_arg(obs_len, B, To, lo, device):
+    """The obs_len of the model-level calls - None, an integer tensor, a numpy array or a list: valid frames per row of a
+    right-aligned (B, To, .) observation buffer - checked and moved to `device` once -> int32 tensor (B,) or None.
+    ValueError for a wrong shape or a non-integer dtype, and for host data (list, numpy, CPU tensor) outside lo .. To; a
+    device tensor is not read back (the kernels clamp it into the range)."""
+    if obs_len is None:
+        return None
+    if isinstance(obs_len, torch.Tensor) and obs_len.device.type != "cpu":
+        if obs_len.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError("obs_len must hold integers, got dtype %s" % obs_len.dtype)
+        if tuple(obs_len.shape) != (B,):
+            raise ValueError("obs_len must be (B,) = (%d,), got %s" % (B, tuple(obs_len.shape)))
+        return obs_len.to(device=device, dtype=torch.int32).contiguous()
+    host = obs_len.numpy() if isinstance(obs_len, torch.Tensor) else obs_len
+    return torch.from_numpy(check_obs_len(host, B, To, lo)).to(device)
+
+
+def _check_obs_len_tensor(obs_len, B, device):
+    """What gen_sample / disc_score take as obs_len: an int32 tensor (B,) on `device` (obs_len_arg makes one)."""
+    if not isinstance(obs_len, torch.Tensor) or obs_len.dtype != torch.int32 or tuple(obs_len.shape) != (B,) \
+            or obs_len.device != device:
+        raise ValueError("obs_len must be an int32 tensor (B,) = (%d,) on %s" % (B, device))
+    return obs_len.contiguous()
+
+
 _sample_img = {}      # device -> the image buffer the sampling path owns (sw_gen_images)
 
 
 def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, gt=None, inv_ss=1.0,
-               want_pred=True, keep_pred=False):
+               want_pred=True, keep_pred=False, obs_len=None):
     """K sampled futures of predict() for B agents (test(), train.py:563-616): the encoder over the observed steps and the
     social block run ONCE on the B agents, then ONE sampling launch rolls out the K * B rows (row k * B + a = draw k of
     agent a) reading the encoding per agent - nothing is replicated.  noise_k (K * B, 32).
     gt (B, n_next, 2): the per-row errors are formed in the launch and reduced over k on the device.
     keep_pred: pred4 is written and returned although the caller wants no trajectories (want_pred False) - it stays on
     the device for a consumer there (scene_metrics).
+    obs_len (B,) int32 on the device: ragged histories - row a holds obs_len[a] valid frames right-aligned in obsv and its
+    encoding is that of those frames alone (sw_enc_lstm_fwd_ragged in place of the encoder launch; the social block and
+    the rollout read the last frames and are the same launches).  None: the dense encoder launch.
     Returns (pred4 (K * B, n_next, 4) or None when neither want_pred nor keep_pred,
              (per_agent (B, 4) = mean_k ADE | mean_k FDE | min_k ADE | min_k FDE, best (B,) int32, err (K, B, 2)) or None).
     The launches run with the weight images registered, the protocol of the training step: derived into a buffer this path
@@ -367,6 +396,8 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
         if gt.shape != (B, n_next, 2):
             raise ValueError("gt must be (B, n_next, 2)")
     dev = obsv.device
+    if obs_len is not None:
+        obs_len = _check_obs_len_tensor(obs_len, B, dev)
     st = L.stream()
     pred4 = torch.empty(K * B, n_next, 4, device=dev) if want_pred else None
     if B == 0:
@@ -378,8 +409,11 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
     err = torch.empty(K, B, 2, device=dev) if gt is not None else None
     L.call("sw_gen_images", L.ptr(enc_w), L.ptr(dec_w), L.ptr(emb_w), L.ptr(att_w), L.ptr(img), st)
     try:
-        L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
-               None, None, 0, None, None, 0, st)
+        if obs_len is None:
+            L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
+                   None, None, 0, None, None, 0, st)
+        else:
+            L.call("sw_enc_lstm_fwd_ragged", L.ptr(obsv), 0, L.ptr(enc_w), L.ptr(obs_len), B, To, L.ptr(hT), L.ptr(cT), st)
         S = None                                                                 # NULL = zeros (train.py:413)
         if use_social:
             S = torch.empty(B, 64, device=dev)
@@ -493,11 +527,13 @@ def disc_forward(d_w, obsv, preds, save, ws=None, tag="d", save_lstm=True, w_sna
     return labels, codes, ctx
 
 
-def disc_score(d_w, obsv, pred4, K, want_code=True):
+def disc_score(d_w, obsv, pred4, K, want_code=True, obs_len=None):
     """Discriminator.forward on K futures per agent in ONE launch (sw_disc_score): obsv (B, To, 2 | 4) is read per agent -
     its LSTM and fc run once per 16-agent tile -, pred4 (K * B, Tp, 4) or (K, B, Tp, 4) per row (row k * B + a = draw k of
     agent a: what gen_sample returns, scored where it lies).  Returns (score (K, B) raw LSGAN score, code_hat (K, B, 2) or
-    None): the bits of K calls of disc_forward on the draws, with the weight images a caller has registered or without."""
+    None): the bits of K calls of disc_forward on the draws, with the weight images a caller has registered or without.
+    obs_len (B,) int32 on the device: ragged histories, as gen_sample() - row a's observation LSTM runs over its obs_len[a]
+    valid frames alone (sw_disc_score_ragged); None: sw_disc_score."""
     if K < 1:
         raise ValueError("K must be at least 1")
     if obsv.dim() != 3 or obsv.shape[2] not in (2, 4) or (obsv.shape[2] == 2 and obsv.shape[1] < 2) or obsv.shape[1] < 1:
@@ -509,14 +545,20 @@ def disc_score(d_w, obsv, pred4, K, want_code=True):
     if pred4.device != obsv.device:
         raise ValueError("pred4 must be on the device of obsv")
     L.require_gpu(obsv)
+    if obs_len is not None:
+        obs_len = _check_obs_len_tensor(obs_len, B, obsv.device)
     obsv, pred4 = obsv.float().contiguous(), pred4.float().contiguous()
     Tp = pred4.shape[-2]
     score = torch.empty(K, B, device=obsv.device)
     code = torch.empty(K, B, 2, device=obsv.device) if want_code else None
     if B == 0:
         return score, code
-    L.call("sw_disc_score", L.ptr(obsv), To, {2: 0, 4: 1}[obsv.shape[2]], L.ptr(pred4), L.ptr(d_w), B, K, Tp, L.ptr(score),
-           L.ptr(code), L.stream())
+    x_mode = {2: 0, 4: 1}[obsv.shape[2]]
+    if obs_len is None:
+        L.call("sw_disc_score", L.ptr(obsv), To, x_mode, L.ptr(pred4), L.ptr(d_w), B, K, Tp, L.ptr(score), L.ptr(code), L.stream())
+    else:
+        L.call("sw_disc_score_ragged", L.ptr(obsv), To, x_mode, L.ptr(obs_len), L.ptr(pred4), L.ptr(d_w), B, K, Tp, L.ptr(score),
+               L.ptr(code), L.stream())
     return score, code
 
 

@@ -27,7 +27,7 @@ import torch.optim as opt
 from . import _lib as L
 from . import ops
 from .data import shard_scenes
-from .model import Discriminator, Generator, get_traj_4d, predict_cv
+from .model import Discriminator, Generator, get_traj_4d, predict_cv, refuse_obs_len
 from .noise import EVAL, TRAIN, DeviceNoise
 
 
@@ -175,14 +175,25 @@ class _EvalSums:
 
 
 @torch.no_grad()
-def _scored_draws(tr, obsv_p, n_samples, top_m, sub_batches, noise, row0):
+def _scored_draws(tr, obsv_p, n_samples, top_m, sub_batches, noise, row0, obs_len=None):
     """What sample_ranked() and sample_diverse() start with: (K, M, the K draws (K, B, n_next, 4), their scores (K, B)); top_m
-    is checked before anything of the trainer is touched."""
+    is checked before anything of the trainer is touched.  obs_len (ragged histories, Generator.sample()) is checked and
+    moved to the device once and goes to both the sampling and the scoring call."""
     K, M = int(n_samples), int(top_m)
     if not 1 <= M <= K:
         raise ValueError("top_m must lie in 1 .. n_samples = %d, got %d" % (K, M))
-    ph = tr.G.sample(obsv_p, K, tr.n_next, sub_batches, noise, row0=row0)
-    return K, M, ph, tr.D.score_samples(obsv_p, ph)[0]
+    if obs_len is not None:
+        if not isinstance(tr.G, Generator):      # the generic-width and wide paths: no ragged kernels
+            refuse_obs_len(obs_len, type(tr).__name__)
+        obs_len = ops.obs_len_arg(obs_len, obsv_p.shape[0], obsv_p.shape[1], 2, obsv_p.device)
+    ph = tr.G.sample(obsv_p, K, tr.n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
+    return K, M, ph, tr.D.score_samples(obsv_p, ph, obs_len=obs_len)[0]
+
+
+def _refuse_ragged(data, what, why):
+    """Calls without ragged kernels behind them refuse a dataset that carries obs_len, loudly, before any launch."""
+    if getattr(data, "obs_len", None) is not None:
+        raise L.SocialWaysHipError("%s does not take a dataset with obs_len (ragged observation histories): %s" % (what, why))
 
 
 class SocialWaysTrainer:
@@ -846,7 +857,10 @@ class SocialWaysTrainer:
         samples of use_variety_loss="fixed"; row = the row in the GLOBAL packed batch, so a rank fills only its shard and
         the union over ranks is the single-process z.  The z of the batches that share a step_many launch is one fill
         launch in front of the graph launch on the same stream, read by the steps through their z-resident path (no
-        pinned-slot copy).  The label-noise scalars stay the reference's two host draws."""
+        pinned-slot copy).  The label-noise scalars stay the reference's two host draws.
+        A dataset with obs_len (ragged histories) is refused: there are no ragged backward kernels."""
+        _refuse_ragged(data, "train_epoch()", "there are no ragged backward kernels - train on full windows (create_dataset) "
+                       "and evaluate the ragged ones with evaluate*() / evaluate_history()")
         outs, sizes = [], []
         pend, pend_key = [], None        # consecutive packed batches of one layout share a graph launch
         dn = self._device_noise(None) if draw is None else None
@@ -958,7 +972,10 @@ class SocialWaysTrainer:
         of the scene, and consecutive held-out scenes are folded into the same launch (block-diagonal social
         block: a scene's rollout does not depend on its neighbours in the batch) up to TEST_CHUNK agent copies:
         identical rollouts, one launch sequence and one host sync per chunk instead of per scene.  The noise is
-        drawn scene by scene, K draws of (n, noise_len) each, in the reference's order (train.py:584)."""
+        drawn scene by scene, K draws of (n, noise_len) each, in the reference's order (train.py:584).
+        A dataset with obs_len (ragged histories) is refused: this call replicates the dense forward pass."""
+        _refuse_ragged(data, "test()", "it runs the dense forward pass on K copies of every scene - use evaluate() / "
+                       "evaluate_history(), whose sampling path encodes each agent over its valid frames")
         ss, dev, K = data.ss, self.device, n_gen_samples
         base = _EvalSums(dev)
         for first, scenes in self._eval_fold(data, K, just_one):
@@ -1021,17 +1038,22 @@ class SocialWaysTrainer:
         """The K draws of the held-out scenes, chunk by chunk: what evaluate() and every evaluate_*() do before their own
         work.  Yields a namespace per chunk: first (index of its first scene), ab (its scenes' row ranges), lo, n (its rows
         are lo .. lo + n-1 of the held-out tracks), obsv, pred, sb and scenes (the chunk-local scene ranges and their
-        SceneIndex), z (K, n, Z_COLS) on the device, and from the sampling hook ph (K, n, n_next, 4; None without want_pred),
+        SceneIndex), obs_len (the chunk's slice of data.obs_len - ragged histories - or None), z (K, n, Z_COLS) on the device,
+        and from the sampling hook ph (K, n, n_next, 4; None without want_pred),
         per_agent (n, 4), err (K, n, 2), best (n,) int32.  z comes from `dn` (a DeviceNoise: evaluation domain, row = the
         ABSOLUTE held-out row, so a scene's draws do not depend on the chunking; one launch that also writes the padding),
         else from the reference's host stream (eval_noise), padded and copied once.  The chunk's scenes and per-agent sums
         are added to `base` (an _EvalSums) before it is handed out.  The loop body of the caller runs under this generator's
         torch.no_grad(), which ends with the generator (if the body raises: when the generator is collected)."""
+        ol = getattr(data, "obs_len", None)
+        if ol is not None and not isinstance(self.G, Generator):      # the generic-width and wide paths: refused before any chunk is built
+            refuse_obs_len(ol, type(self).__name__)
         dev = self.device
         with torch.no_grad():
             for first, scenes in self._eval_fold(data, K, just_one):
                 lo, hi = scenes[0][0], scenes[-1][1]
                 c = SimpleNamespace(first=first, ab=scenes, lo=lo, n=hi - lo, obsv=data.obsv[lo:hi], pred=data.pred[lo:hi])
+                c.obs_len = ol[lo:hi] if ol is not None else None
                 if dn is not None:
                     c.z = dn.fill(c.n, self.noise_len, domain=EVAL, n_draws=K, row0=lo, ld=self.Z_COLS, device=dev)[0]
                 else:
@@ -1050,14 +1072,21 @@ class SocialWaysTrainer:
         G = self.G
         ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
                                  c.obsv, c.z.view(K * c.n, -1), c.scenes, self.n_next, G.use_social, K, gt=c.pred,
-                                 inv_ss=1.0 / float(ss), want_pred=want_pred)
+                                 inv_ss=1.0 / float(ss), want_pred=want_pred, obs_len=c.obs_len)
         return ph.view(K, c.n, self.n_next, 4) if ph is not None else None, red[0], red[2], red[1]
 
     def _eval_records(self, data, c, preds_k, extra={}):
         """The prediction records of chunk c, one per held-out scene: the dict test() writes - timestamp, obsvs, preds_our
         (K, n, n_next, 2) from preds_k, preds_gtt, preds_lnr, all denormalised - plus the scene's part of every entry of
-        `extra` = {key: (device tensor, axis)}: axis = the one that runs over the chunk's rows, None = one entry per scene."""
+        `extra` = {key: (device tensor, axis)}: axis = the one that runs over the chunk's rows, None = one entry per scene.
+        A ragged chunk (c.obs_len): every record also has obs_len (n,), and preds_lnr is predict_cv of each row's VALID
+        frames - a row of two frames gets the two-frame rule, not a velocity through its padding."""
         linear_preds = predict_cv(c.obsv, self.n_next)
+        obs_len = getattr(c, "obs_len", None)
+        if obs_len is not None:
+            extra = dict(extra, obs_len=(obs_len, 0))
+            if c.obsv.shape[1] > 2:
+                linear_preds = torch.where((obs_len <= 2)[:, None, None], predict_cv(c.obsv[:, -2:], self.n_next), linear_preds)
         sc = data.scale
         host = {k: (v.cpu().numpy(), ax) for k, (v, ax) in extra.items()}
         for si, (a, b) in enumerate(c.ab):
@@ -1094,6 +1123,33 @@ class SocialWaysTrainer:
                 for rec in self._eval_records(data, c, c.ph):
                     self._eval_emit(rec, collect, write_to_file)
         return tuple(base.result(data).values())
+
+    def evaluate_history(self, data, n_gen_samples=20, just_one=False, noise=None):
+        """evaluate() split by history length: what an agent seen for n frames is predicted with.  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          by_len   {n: {count, ade_avg, fde_avg, ade_min, fde_min}} for every history length n present among the agents
+                   evaluated (data.obs_len; a dataset without it: the single bucket n_past), the means over that length's
+                   agents: sum_n count_n * by_len[n][key] / data.n_test_samples is the overall key;
+          n_agents.
+        Chunking, noise and sampling launches are evaluate()'s; the sums are float64 on the device, one host sync at the end."""
+        dn = self._device_noise(noise)
+        dev, To = self.device, data.n_past
+        base = _EvalSums(dev)
+        acc = torch.zeros(To + 1, 5, dtype=torch.float64, device=dev)      # per length: count | the four sums
+        lens = torch.arange(To + 1, device=dev)[:, None]
+        for c in self._eval_draws(data, n_gen_samples, just_one, dn, base, want_pred=False):
+            n = c.obs_len if c.obs_len is not None else torch.full((c.n,), To, dtype=torch.int32, device=dev)
+            rows = torch.cat([torch.ones(c.n, 1, dtype=torch.float64, device=dev), c.per_agent.double()], dim=1)
+            acc += ((n[None, :] == lens).double()[:, :, None] * rows[None]).sum(1)      # (To + 1, n, 5) -> (To + 1, 5)
+        vals = torch.cat([base.sums / data.n_test_samples, acc.flatten()]).tolist()
+        out = dict(zip(_EvalSums.KEYS, vals[:4]))
+        by_len = {}
+        for n in range(To + 1):
+            cnt, *sums = vals[4 + 5 * n:9 + 5 * n]
+            if cnt > 0:
+                by_len[n] = dict(count=int(cnt), **{k: v / cnt for k, v in zip(_EvalSums.KEYS, sums)})
+        out.update(by_len=by_len, n_agents=sum(b - a for a, b in base.scenes))
+        return out
 
     def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
         """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
@@ -1144,14 +1200,16 @@ class SocialWaysTrainer:
                    n_scenes=len(base.scenes), n_multi=n_multi)
         return out
 
-    def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None, row0=0):
+    def sample_ranked(self, obsv_p, n_samples, top_m, sub_batches=[], noise=None, row0=0, obs_len=None):
         """The deployment call - K draws, no ground truth, pick a few: the top_m of n_samples futures per agent that the
         discriminator scores highest, best first.  obsv_p (B, To, 2), noise (K, B, noise_len), None or a DeviceNoise (rows from
-        `row0`) as Generator.sample().
+        `row0`) as Generator.sample().  obs_len (B,) - tensor, numpy array or list: ragged histories, as Generator.sample() -
+        an agent seen for fewer than To frames (at least 2, right-aligned in obsv_p) is sampled and scored on those frames
+        alone and stays in its scene's social block.
         Returns (trajs (M, B, n_next, 4), score (M, B) raw LSGAN score, non-increasing along M, order (B, M) int32: trajs[m, a]
         is draw order[a, m]).  A sampling launch (Generator.sample), a scoring launch (Discriminator.score_samples), a
         ranking launch (ops.sample_rank) and a gather."""
-        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0)
+        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0, obs_len)
         with torch.no_grad():
             order, _ = ops.sample_rank(score, K, M)
             idx = order.t().long()
@@ -1184,9 +1242,9 @@ class SocialWaysTrainer:
         base = _EvalSums(dev)
         acc = torch.zeros(len(self.RANKED_KEYS), dtype=torch.float64, device=dev)
         for c in self._eval_draws(data, K, just_one, dn, base):
-            score, code = self.D.score_samples(c.obsv, c.ph)
+            score, code = self.D.score_samples(c.obsv, c.ph, obs_len=c.obs_len)
             order, ranked = ops.sample_rank(score, K, M, err=c.err, best=c.best)
-            gt_score, _ = self.D.score_samples(c.obsv, get_traj_4d(c.obsv, c.pred)[1].unsqueeze(0))
+            gt_score, _ = self.D.score_samples(c.obsv, get_traj_4d(c.obsv, c.pred)[1].unsqueeze(0), obs_len=c.obs_len)
             csq = (code.double() - c.z[:, :, :code.shape[-1]].double()).pow(2).mean(dim=2)
             acc += torch.cat([ranked.double().sum(0), torch.stack([score.double().sum(), gt_score.double().sum(), csq.sum()])])
             if collect is not None:
@@ -1206,19 +1264,19 @@ class SocialWaysTrainer:
         return torch.where(valid, values.gather(0, at), torch.full((), fill, dtype=values.dtype, device=values.device))
 
     def sample_diverse(self, obsv_p, n_samples, top_m, radius, metric="fde", joint=False, sub_batches=[], noise=None, row0=0,
-                       scale=1.0):
+                       scale=1.0, obs_len=None):
         """sample_ranked() without the near-duplicates: of n_samples futures the highest-scored one is kept, every draw within
         `radius` of it (metric "fde": distance at the last step, "ade": mean distance over the steps, both times `scale` -
         the `scale` of stats.scene_clearance) counts as the same mode, then the highest-scored of the rest, top_m times at
         most (ops.sample_nms).  joint=False: per agent.  joint=True: per scene of sub_batches - draw k of a scene is draw k of
         each of its agents; two joint draws are one mode only if every agent is within the radius, and a joint draw scores
-        as its lowest-scored agent.  obsv_p, noise, row0 as sample_ranked().
+        as its lowest-scored agent.  obsv_p, noise, row0, obs_len as sample_ranked().
         Returns (trajs (M, B, n_next, 4), weight, score (M, B), order, count): order (B, M) int32, weight (B, M) = the share of
         the n_samples draws that fell to each kept mode (rows sum to 1) and count (B,) int32 = the modes found - per scene
         with joint=True: (S, M), (S, M), (S,), and trajs[m, a] is draw order[scene of a, m] of agent a, score[m, a] that draw's
         own score.  Per agent the scores do not increase along M.  Slots from count on: zeros in trajs, -inf in score, 0 in
         weight, -1 in order.  Sampling, scoring, one suppression launch and a gather."""
-        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0)
+        K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0, obs_len)
         with torch.no_grad():
             B = ph.shape[1]
             scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device) if joint else None
@@ -1264,7 +1322,7 @@ class SocialWaysTrainer:
         base = _EvalSums(dev)
         acc = torch.zeros(len(self.DIVERSE_KEYS) + 2, dtype=torch.float64, device=dev)      # ... | sum n * jade | sum n * jfde
         for c in self._eval_draws(data, K, just_one, dn, base):
-            score, _ = self.D.score_samples(c.obsv, c.ph)
+            score, _ = self.D.score_samples(c.obsv, c.ph, obs_len=c.obs_len)
             order, count, weight, assign, per_row = ops.sample_nms(c.ph, score, K, M, radius, metric, c.scenes if joint else None,
                                                                    inv_ss=inv_ss, err=c.err, best=c.best)
             # the first five columns summed in the shape evaluate_ranked() sums its own: the same bits at radius 0
