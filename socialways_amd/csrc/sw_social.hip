@@ -69,6 +69,58 @@ __device__ __forceinline__ void load_pair_w1_img(PairW1& W, const float* __restr
   }
 }
 
+// ---- MFMA A operands a wave reads row-major from global memory (the operand-layout images of a step, where a kernel
+// takes them, are read at the call site) ----
+// fc.2.weight^T: w1T[jt][mt][r] = W1[16mt + 4lg + r][16jt + ln]
+__device__ __forceinline__ void load_w1T(f32x4 w1T[2][4], const float* emb_w, int ln, int lg) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* row1 = emb_w + swp::EMB_W1 + (16 * mt + 4 * lg + r) * 32 + ln;
+      w1T[0][mt][r] = row1[0];
+      w1T[1][mt][r] = row1[16];
+    }
+  }
+}
+// fc.4.weight^T of the wave's 16 units of v_j: w3t[j][r] = W3[m = 16j + 4lg + r][k = 16 wave + ln]
+__device__ __forceinline__ void load_w3t(f32x4 w3t[4], const float* emb_w, int wave, int ln, int lg) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w3t[j][r] = emb_w[swp::EMB_W2 + (16 * j + 4 * lg + r) * 64 + 16 * wave + ln];
+  }
+}
+// attention W^T of the wave's 16 units of dh: wT[kt][r] = W[k = 16kt + 4lg + r][u = 16 wave + ln]
+__device__ __forceinline__ void load_att_wT(f32x4 wT[4], const float* att_w, int wave, int ln, int lg) {
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wT[kt][r] = att_w[swp::ATT_W + (16 * kt + 4 * lg + r) * 64 + 16 * wave + ln];
+  }
+}
+// attention W rows of the wave's 16 units of Wh, and their bias in C layout: wr[j] = W[16 wave + ln][16j + 4lg ..]
+__device__ __forceinline__ void load_att_w(f32x4 wr[4], f32x4& bias, const float* att_w, int wave, int ln, int lg) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) wr[j] = ld4(att_w + swp::ATT_W + (16 * wave + ln) * 64 + 16 * j + 4 * lg);
+  bias = ld4(att_w + swp::ATT_B + 16 * wave + 4 * lg);
+}
+// a 64-float row in C layout: v[mo] = row[16mo + 4lg ..]
+__device__ __forceinline__ void load_row_c(f32x4 v[4], const float* row, int lg) {
+#pragma unroll
+  for (int mo = 0; mo < 4; ++mo) v[mo] = ld4(row + 16 * mo + 4 * lg);
+}
+// single-agent scenes: the agent's 64-float row is zero
+__device__ __forceinline__ void zero_row64(float* row) {
+  if (threadIdx.x < 16) st4(row + 4 * threadIdx.x, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+// (p, v) of agent a from its last two observed points
+__device__ __forceinline__ f32x4 agent_x4(const float* obsv, int To, int a) {
+  const float* p = obsv + ((size_t)a * To + To - 2) * 2;
+  return f32x4{p[2], p[3], p[2] - p[0], p[3] - p[1]};
+}
+
 // [dist, bearing, dca] of the ordered pair (i, j): dp = p_i - p_j, dv = v_i - v_j (train.py:232-234);
 // eps placement as train.py:212,225.  The diagonal gives (0, 0, 0).
 __device__ __forceinline__ void pair_feat(f32x4 si, f32x4 sj, float& f0, float& f1, float& f2) {
@@ -183,10 +235,8 @@ __device__ __forceinline__ void scene_load_h_wh(float* smem, const SocL& Ls, con
   // the attention weights are requested first: they arrive together with the h rows (behind the barrier below they
   // were a global round trip of their own)
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  f32x4 wr[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wr[j] = ld4(att_w + swp::ATT_W + (16 * wave + ln) * 64 + 16 * j + 4 * lg);
-  f32x4 bias = ld4(att_w + swp::ATT_B + 16 * wave + 4 * lg);
+  f32x4 wr[4], bias;
+  load_att_w(wr, bias, att_w, wave, ln, lg);
   for (int i = threadIdx.x; i < n * 16; i += blockDim.x) {
     int a = i >> 4, q = i & 15;
     st4(&hs[a * 68 + 4 * q], ld4(h + (size_t)(s0 + a) * 64 + 4 * q));
@@ -221,11 +271,7 @@ __device__ __forceinline__ void stage_pair_consts(float* smem, const SocL& Ls, c
 __device__ __forceinline__ void scene_prologue(float* smem, const SocL& Ls, const float* obsv, int To, const float* h,
                                                const float* emb_w, const float* att_w, int s0, int n) {
   float* x4 = smem + Ls.x4;
-  for (int a = threadIdx.x; a < n; a += blockDim.x) {
-    const float* p = obsv + ((size_t)(s0 + a) * To + To - 2) * 2;  // last two observed points
-    f32x4 v = {p[2], p[3], p[2] - p[0], p[3] - p[1]};
-    st4(&x4[a * 4], v);
-  }
+  for (int a = threadIdx.x; a < n; a += blockDim.x) st4(&x4[a * 4], agent_x4(obsv, To, s0 + a));
   stage_pair_consts(smem, Ls, emb_w);
   scene_load_h_wh(smem, Ls, h, att_w, s0, n);
 }
@@ -239,12 +285,8 @@ __device__ __forceinline__ void scene_wh_to_v(float* smem, const SocL& Ls, const
   float* wh = smem + Ls.wh;
   const float* b3 = smem + Ls.b12 + 64;
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  f32x4 w3t[4];     // A operand: W3[m = 16j + 4lg + r][k = 16 wave + ln] (wave w owns the units k = 16w .. 16w+15 of v)
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) w3t[j][r] = emb_w[swp::EMB_W2 + (16 * j + 4 * lg + r) * 64 + 16 * wave + ln];
-  }
+  f32x4 w3t[4];     // wave w owns the units k = 16w .. 16w+15 of v
+  load_w3t(w3t, emb_w, wave, ln, lg);
   const int nt = (n + 15) >> 4;
   f32x4 acc[4];
 #pragma unroll
@@ -296,6 +338,119 @@ __device__ __forceinline__ void scene_softmax_pool(float* smem, const SocL& Ls, 
     S_out[(size_t)(s0 + i) * 64 + u] = acc;
   }
 }
+
+// ---- phases the scene, rows and row-block kernels share ------------------------------------------------------------------
+// <h2_ij, v_j> of the 16 pairs of a tile (h2 in C layout, v = row j in C layout): lane partial, then the four lane groups
+__device__ __forceinline__ float pair_sigma(const f32x4 h2[4], const f32x4 v[4]) {
+  float part = 0.f;
+#pragma unroll
+  for (int mo = 0; mo < 4; ++mo) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) part = fmaf(h2[mo][r], v[mo][r], part);
+  }
+  part += __shfl_xor(part, 16);
+  part += __shfl_xor(part, 32);
+  return part;
+}
+// dsigma_ij of a tile -> sd_j, Q_j (pair_block_dw3) and dh2_ij = relu'(h2_ij) dsigma_ij v_j; invalid lanes pass dsv = 0
+__device__ __forceinline__ void pair_dsigma_bwd(float dsv, const f32x4 h2[4], const f32x4 vj[4], float& sd, f32x4 Q[4],
+                                                f32x4 dh2[4]) {
+  sd += dsv;
+#pragma unroll
+  for (int mo = 0; mo < 4; ++mo) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      Q[mo][r] = fmaf(dsv, h2[mo][r], Q[mo][r]);
+      dh2[mo][r] = h2[mo][r] > 0.f ? dsv * vj[mo][r] : 0.f;
+    }
+  }
+}
+// dh1 = relu'(h1) . W1^T dh2 (8 + 8 MFMAs), w1T as load_w1T leaves it
+__device__ __forceinline__ void pair_dh1(const f32x4 w1T[2][4], const f32x4 dh2[4], const f32x4 h1[2], f32x4 dh1[2]) {
+  dh1[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+  dh1[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      dh1[0] = SW_MFMA(w1T[0][mt][r], dh2[mt][r], dh1[0]);
+      dh1[1] = SW_MFMA(w1T[1][mt][r], dh2[mt][r], dh1[1]);
+    }
+  }
+#pragma unroll
+  for (int jt = 0; jt < 2; ++jt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dh1[jt][r] = h1[jt][r] > 0.f ? dh1[jt][r] : 0.f;
+  }
+}
+// dS rows and attention rows of the scene into LDS; WH: also the Wh rows (LDS) out to wh_rows for the deferred dW3 / db3 GEMM
+template <bool WH>
+__device__ __forceinline__ void scene_load_ds_attn(float* smem, const SocL& Ls, const float* dS, const float* attn, int s0,
+                                                   int n, float* wh_rows) {
+  float* dsl = smem + Ls.ds;
+  float* sig = smem + Ls.sig;
+  const float* wh = smem + Ls.wh;
+  for (int i = threadIdx.x; i < n * 16; i += blockDim.x) {
+    int a = i >> 4, q = i & 15;
+    st4(&dsl[a * 68 + 4 * q], ld4(dS + (size_t)(s0 + a) * 64 + 4 * q));
+    if constexpr (WH) st4(wh_rows + (size_t)(s0 + a) * 64 + 4 * q, ld4(&wh[a * 68 + 4 * q]));
+  }
+  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
+    int i = e / n, j = e - i * n;
+    sig[i * Ls.sa + j] = attn[(size_t)(s0 + i) * SW_AMAX + j];
+  }
+}
+// softmax backward, one wave per row: da_ij = <dS_i, h_j>;  dsigma_ij = a_ij (da_ij - sum_j' a_ij' da_ij')
+__device__ __forceinline__ void scene_softmax_bwd(float* smem, const SocL& Ls, int n) {
+  const float* hs = smem + Ls.hs;
+  const float* sig = smem + Ls.sig;
+  const float* dsl = smem + Ls.ds;
+  float* dsg = smem + Ls.dsg;
+  const int sa = Ls.sa;
+  const int lane = sw_lane(), wave = sw_wave();
+  for (int i = wave; i < n; i += 4) {
+    float da = 0.f, a = 0.f;
+    if (lane < n) {
+      a = sig[i * sa + lane];
+      for (int u = 0; u < 64; u += 4) {
+        f32x4 x = ld4(&dsl[i * 68 + u]), y = ld4(&hs[lane * 68 + u]);
+        da = fmaf(x[0], y[0], da); da = fmaf(x[1], y[1], da); da = fmaf(x[2], y[2], da); da = fmaf(x[3], y[3], da);
+      }
+    }
+    float t = a * da;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    if (lane < n) dsg[i * sa + lane] = a * (da - t);
+  }
+}
+// dh_j += sum_i a_ij dS_i  +  W^T dWh_j  on the matrix cores: D[unit u][agent j], wave w owns units 16w .. 16w+15 (wT:
+// load_att_wT); first product over k = the 64 units of dWh, second over k = i (rows beyond n masked to exact zeros)
+__device__ __forceinline__ void scene_dh_rows(const f32x4 wT[4], const float* smem, const SocL& Ls, float* dh, int s0, int n) {
+  const float* sig = smem + Ls.sig;
+  const float* dsl = smem + Ls.ds;
+  const float* dwh = smem + Ls.dwh;
+  const int sa = Ls.sa;
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int npad = (n + 15) & ~15;
+  for (int at = 0; at < npad / 16; ++at) {
+    f32x4 acc = tile_mm_reg<4>(wT, &dwh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
+    f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < npad / 16; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 16 * kt + 4 * lg + r;
+        const float av = i < n ? dsl[i * 68 + 16 * wave + ln] : 0.f;
+        const float bv = i < n ? sig[i * sa + 16 * at + ln] : 0.f;
+        acc2 = SW_MFMA(av, bv, acc2);
+      }
+    }
+    const int j = 16 * at + ln;
+    if (j < n) {
+      float* q = dh + (size_t)(s0 + j) * 64 + 16 * wave + 4 * lg;
+      st4(q, ld4(q) + (acc + acc2));
+    }
+  }
+}
 }  // namespace
 
 __global__ __launch_bounds__(SW_THREADS) void social_pool_fwd_kernel(
@@ -332,7 +487,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_fwd_kernel(
   const int s0 = scene_off[scene], n = scene_off[scene + 1] - s0;
   if (n <= 0 || n > SW_AMAX) return;   // scenes above SW_AMAX agents go through the row-block kernels below
   if (n == 1) {  // train.py:165: single-agent scenes keep S = 0
-    if (threadIdx.x < 16) st4(S_out + (size_t)s0 * 64 + 4 * threadIdx.x, f32x4{0.f, 0.f, 0.f, 0.f});
+    zero_row64(S_out + (size_t)s0 * 64);
     if (attn && threadIdx.x == 0) attn[(size_t)s0 * SW_AMAX] = 0.f;
     return;
   }
@@ -353,15 +508,9 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_fwd_kernel(
     f32x4 h1[2], h2[4];
     pair_l1m(w0a, lg, f0, f1, f2, h1);
     pair_l2(W, b12, lg, h1, h2);
-    float part = 0.f;
-#pragma unroll
-    for (int mo = 0; mo < 4; ++mo) {
-      f32x4 w = ld4(&wh[j * 68 + 16 * mo + 4 * lg]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) part = fmaf(h2[mo][r], w[r], part);
-    }
-    part += __shfl_xor(part, 16);
-    part += __shfl_xor(part, 32);
+    f32x4 vj[4];
+    load_row_c(vj, &wh[j * 68], lg);
+    const float part = pair_sigma(h2, vj);
     if (lg == 0 && pt * 16 + ln < P) sig[i * sa + j] = (i == j) ? -1000.0f : part + wh[j * 68 + 64];  // train.py:170
   }
   sw_barrier();
@@ -638,13 +787,10 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const SocL Ls = soc_lds(a16);
   const int sa = Ls.sa;
-  float* hs = smem + Ls.hs;
   float* wh = smem + Ls.wh;
   float* x4 = smem + Ls.x4;
-  float* sig = smem + Ls.sig;  // attention weights a_ij
   const float* w0b = smem + Ls.w0b;
   const float* b12 = smem + Ls.b12;
-  float* dsl = smem + Ls.ds;
   float* dsg = smem + Ls.dsg;
   float* dwh = smem + Ls.dwh;
   float* w2t = smem + Ls.bwd_total;                   // fc.4.weight^T [64][68]
@@ -659,8 +805,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
   load_pair_w1(W, emb_w, ln, lg);
   // fc.4 itself is only needed for dWh_j = W3 Q_j + b3 sd_j, once per j block: wave w forms the units 16w .. 16w+15
   f32x4 w2own[4];     // A operand: W3[m = 16 wave + ln][k = 16kt + 4lg + r]
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt) w2own[kt] = ld4(emb_w + swp::EMB_W2 + (16 * wave + ln) * 64 + 16 * kt + 4 * lg);
+  load_row_c(w2own, emb_w + swp::EMB_W2 + (16 * wave + ln) * 64, lg);
   const f32x4 b3own = ld4(emb_w + swp::EMB_B2 + 16 * wave + 4 * lg);
   PairGrad G;
   pair_grad_zero(G);
@@ -672,36 +817,15 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
     const int s0 = scene_off[sc], n = scene_off[sc + 1] - s0;
     if (n <= 0 || n > SW_AMAX) continue;
     if (n == 1) {  // S = 0 constant: no gradient anywhere; dWh row is zero
-      if (threadIdx.x < 16) st4(dwh_rows + (size_t)s0 * 64 + 4 * threadIdx.x, f32x4{0.f, 0.f, 0.f, 0.f});
+      zero_row64(dwh_rows + (size_t)s0 * 64);
       continue;
     }
     __syncthreads();   // previous scene's LDS is done with
     scene_prologue(smem, Ls, obsv, To, h, emb_w, att_w, s0, n);
-    for (int i = threadIdx.x; i < n * 16; i += blockDim.x) {
-      int a = i >> 4, q = i & 15;
-      st4(&dsl[a * 68 + 4 * q], ld4(dS + (size_t)(s0 + a) * 64 + 4 * q));
-    }
-    for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-      int i = e / n, j = e - i * n;
-      sig[i * sa + j] = attn[(size_t)(s0 + i) * SW_AMAX + j];
-    }
+    scene_load_ds_attn<false>(smem, Ls, dS, attn, s0, n, nullptr);
     sw_barrier();
     SW_STAMP(0);
-    // da_ij = <dS_i, h_j>;  dsigma_ij = a_ij (da_ij - sum_j' a_ij' da_ij')   (softmax backward)
-    for (int i = wave; i < n; i += 4) {
-      float da = 0.f, a = 0.f;
-      if (lane < n) {
-        a = sig[i * sa + lane];
-        for (int u = 0; u < 64; u += 4) {
-          f32x4 x = ld4(&dsl[i * 68 + u]), y = ld4(&hs[lane * 68 + u]);
-          da = fmaf(x[0], y[0], da); da = fmaf(x[1], y[1], da); da = fmaf(x[2], y[2], da); da = fmaf(x[3], y[3], da);
-        }
-      }
-      float t = a * da;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-      if (lane < n) dsg[i * sa + lane] = a * (da - t);
-    }
+    scene_softmax_bwd(smem, Ls, n);
     sw_barrier();
     SW_STAMP(1);
     // ---- pair tiles: recompute the MLP, back-propagate, accumulate the weight gradients ----------
@@ -718,8 +842,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
       const int jc = min(j, n - 1);
       const f32x4 xj = ld4(&x4[jc * 4]);
       f32x4 whj[4];
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) whj[mo] = ld4(&wh[jc * 68 + 16 * mo + 4 * lg]);
+      load_row_c(whj, &wh[jc * 68], lg);
       // per block: v_j = W3^T Wh_j; per tile dh2 = relu'(h2) dsigma v_j on the VALU, Q_j / sd_j accumulate for dW3 / db3
       f32x4 vj[4], Q[4];
       float sd = 0.f;
@@ -734,15 +857,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
         pair_l2(W, b12, lg, h1, h2);
         const float dsv = valid ? dsg[i * sa + jc] : 0.f;   // invalid lanes contribute exact zeros everywhere below
         f32x4 dh2[4];
-        sd += dsv;
-#pragma unroll
-        for (int mo = 0; mo < 4; ++mo) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            Q[mo][r] = fmaf(dsv, h2[mo][r], Q[mo][r]);
-            dh2[mo][r] = h2[mo][r] > 0.f ? dsv * vj[mo][r] : 0.f;
-          }
-        }
+        pair_dsigma_bwd(dsv, h2, vj, sd, Q, dh2);
         SW_STAMP(2);
         SW_STAMP(3);
         pair_tile_bwd_tail(G, scr, w1t, h1, dh2, f0, f1, f2, ln, lg SW_STAMP_ARG);
@@ -750,8 +865,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
       }
       {
         f32x4 whr[4];     // re-read: keeps 16 registers out of the tile loop
-#pragma unroll
-        for (int mo = 0; mo < 4; ++mo) whr[mo] = ld4(&wh[jc * 68 + 16 * mo + 4 * lg]);
+        load_row_c(whr, &wh[jc * 68], lg);
         pair_block_dw3(G, scr, whr, Q, sd, ln, lg);
       }
       wave_lds_fence();
@@ -787,34 +901,10 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_kernel(
       SW_STAMP(6);
     }
     sw_barrier();
-    // dh_j += sum_i a_ij dS_i  +  W^T dWh_j  on the matrix cores: D[unit u][agent j], wave w owns units 16w .. 16w+15;
-    // first product over k = i (rows beyond n masked to exact zeros), second over k = the 64 units of dWh
     {
-      const int npad = (n + 15) & ~15;
-      f32x4 wT[4];   // A operand of the second product: W[k = 16kt + 4lg + r][u = 16 wave + ln]
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) wT[kt][r] = att_w[swp::ATT_W + (16 * kt + 4 * lg + r) * 64 + 16 * wave + ln];
-      }
-      for (int at = 0; at < npad / 16; ++at) {
-        f32x4 acc = tile_mm_reg<4>(wT, &dwh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
-        f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-        for (int kt = 0; kt < npad / 16; ++kt) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int i = 16 * kt + 4 * lg + r;
-            const float av = i < n ? dsl[i * 68 + 16 * wave + ln] : 0.f;
-            const float bv = i < n ? sig[i * sa + 16 * at + ln] : 0.f;
-            acc2 = SW_MFMA(av, bv, acc2);
-          }
-        }
-        const int j = 16 * at + ln;
-        if (j < n) {
-          float* q = dh + (size_t)(s0 + j) * 64 + 16 * wave + 4 * lg;
-          st4(q, ld4(q) + (acc + acc2));
-        }
-      }
+      f32x4 wT[4];   // loaded here: 16 registers that the pair loop above cannot spare
+      load_att_wT(wT, att_w, wave, ln, lg);
+      scene_dh_rows(wT, smem, Ls, dh, s0, n);
     }
     SW_STAMP(7);
   }
@@ -840,6 +930,20 @@ __host__ __device__ inline PairRows pair_rows(float* base, long long P) {
   r.feat = r.dh1 + 32 * P;
   return r;
 }
+__device__ __forceinline__ void pair_rows_store(const PairRows& pr, size_t row, const f32x4 h2[4], const f32x4 dh2[4],
+                                                const f32x4 h1[2], const f32x4 dh1[2], float f0, float f1, float f2, int lg) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    st4(pr.h2 + row * 64 + 16 * mt + 4 * lg, h2[mt]);
+    st4(pr.dh2 + row * 64 + 16 * mt + 4 * lg, dh2[mt]);
+  }
+#pragma unroll
+  for (int jt = 0; jt < 2; ++jt) {
+    st4(pr.h1 + row * 32 + 16 * jt + 4 * lg, h1[jt]);
+    st4(pr.dh1 + row * 32 + 16 * jt + 4 * lg, dh1[jt]);
+  }
+  if (lg == 0) st4(pr.feat + row * 4, f32x4{f0, f1, f2, 0.f});
+}
 #define SW_PAIR_ROW_FLOATS 196
 #define SW_AGENT_ROW_FLOATS 200      // per agent in the pair workspace: dWh | Wh | Q [64 each] | sd [4] | pad [4]
 
@@ -855,10 +959,8 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   float* hs = smem + Ls.hs;
   float* wh = smem + Ls.wh;
   float* x4 = smem + Ls.x4;
-  float* sig = smem + Ls.sig;  // attention weights a_ij
   const float* w0b = smem + Ls.w0b;
   const float* b12 = smem + Ls.b12;
-  float* dsl = smem + Ls.ds;
   float* dsg = smem + Ls.dsg;
   float* dwh = smem + Ls.dwh;
   float* vv = dwh;             // v_j = W3^T Wh_j [a16][68] during the pair loop (dWh is formed after it)
@@ -866,13 +968,10 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   const int s0 = scene_off[blockIdx.x], n = scene_off[blockIdx.x + 1] - s0;
   if (n <= 0 || n > SW_AMAX) return;
   if (n == 1) {  // S = 0 constant: no gradient anywhere; the agent's rows are zero
-    if (threadIdx.x < 16) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      st4(dwh_rows + (size_t)s0 * 64 + 4 * threadIdx.x, z);
-      st4(wh_rows + (size_t)s0 * 64 + 4 * threadIdx.x, z);
-      st4(q_rows + (size_t)s0 * 64 + 4 * threadIdx.x, z);
-      if (threadIdx.x == 0) st4(sd_rows + (size_t)s0 * 4, z);
-    }
+    zero_row64(dwh_rows + (size_t)s0 * 64);
+    zero_row64(wh_rows + (size_t)s0 * 64);
+    zero_row64(q_rows + (size_t)s0 * 64);
+    if (threadIdx.x == 0) st4(sd_rows + (size_t)s0 * 4, f32x4{0.f, 0.f, 0.f, 0.f});
     return;
   }
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
@@ -899,34 +998,14 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
     for (int kt = 0; kt < 4; ++kt) wT[kt] = ld4(simg + swimg::OP_ATT_T + ((wave * 4 + kt) * 64 + lane) * 4);
   } else {
     load_pair_w1(W, emb_w, ln, lg);
-#pragma unroll
-    for (int mo = 0; mo < 4; ++mo) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float* row1 = emb_w + swp::EMB_W1 + (16 * mo + 4 * lg + r) * 32 + ln;
-        w1T[0][mo][r] = row1[0];
-        w1T[1][mo][r] = row1[16];
-        w3t[mo][r] = emb_w[swp::EMB_W2 + (16 * mo + 4 * lg + r) * 64 + 16 * wave + ln];
-      }
-      w2own[mo] = ld4(emb_w + swp::EMB_W2 + (16 * wave + ln) * 64 + 16 * mo + 4 * lg);
-    }
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) wT[kt][r] = att_w[swp::ATT_W + (16 * kt + 4 * lg + r) * 64 + 16 * wave + ln];
-    }
+    load_w1T(w1T, emb_w, ln, lg);
+    load_w3t(w3t, emb_w, wave, ln, lg);
+    load_row_c(w2own, emb_w + swp::EMB_W2 + (16 * wave + ln) * 64, lg);
+    load_att_wT(wT, att_w, wave, ln, lg);
   }
   const f32x4 b3own = ld4(emb_w + swp::EMB_B2 + 16 * wave + 4 * lg);
   scene_prologue(smem, Ls, obsv, To, h, emb_w, att_w, s0, n);
-  for (int i = threadIdx.x; i < n * 16; i += blockDim.x) {
-    int a = i >> 4, q = i & 15;
-    st4(&dsl[a * 68 + 4 * q], ld4(dS + (size_t)(s0 + a) * 64 + 4 * q));
-    st4(wh_rows + (size_t)(s0 + a) * 64 + 4 * q, ld4(&wh[a * 68 + 4 * q]));     // Wh rows for dW3 / db3 (deferred GEMM)
-  }
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    int i = e / n, j = e - i * n;
-    sig[i * sa + j] = attn[(size_t)(s0 + i) * SW_AMAX + j];
-  }
+  scene_load_ds_attn<true>(smem, Ls, dS, attn, s0, n, wh_rows);
   const int nt = (n + 15) >> 4;
   for (int at = 0; at < nt; ++at) {     // v_j = W3^T Wh_j: wave w the units 16w .. 16w+15
     const f32x4 acc = tile_mm_reg<4>(w3t, &wh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
@@ -934,21 +1013,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   }
   sw_barrier();
   SW_STAMP(0);
-  // da_ij = <dS_i, h_j>;  dsigma_ij = a_ij (da_ij - sum_j' a_ij' da_ij')   (softmax backward)
-  for (int i = wave; i < n; i += 4) {
-    float da = 0.f, a = 0.f;
-    if (lane < n) {
-      a = sig[i * sa + lane];
-      for (int u = 0; u < 64; u += 4) {
-        f32x4 x = ld4(&dsl[i * 68 + u]), y = ld4(&hs[lane * 68 + u]);
-        da = fmaf(x[0], y[0], da); da = fmaf(x[1], y[1], da); da = fmaf(x[2], y[2], da); da = fmaf(x[3], y[3], da);
-      }
-    }
-    float t = a * da;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-    if (lane < n) dsg[i * sa + lane] = a * (da - t);
-  }
+  scene_softmax_bwd(smem, Ls, n);
   sw_barrier();
   SW_STAMP(1);
   // ---- pair tiles: recompute the MLP up to h2, back-propagate, leave rows for the deferred GEMMs --------
@@ -973,35 +1038,8 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
       for (int r = 0; r < 4; ++r) dh2[mt][r] = h2[mt][r] > 0.f ? dsv * v[r] : 0.f;
     }
     f32x4 dh1[2];
-    dh1[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    dh1[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dh1[0] = SW_MFMA(w1T[0][mt][r], dh2[mt][r], dh1[0]);
-        dh1[1] = SW_MFMA(w1T[1][mt][r], dh2[mt][r], dh1[1]);
-      }
-    }
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dh1[jt][r] = h1[jt][r] > 0.f ? dh1[jt][r] : 0.f;
-    }
-    if (valid) {
-      const size_t row = (size_t)(p0 + p);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        st4(pr.h2 + row * 64 + 16 * mt + 4 * lg, h2[mt]);
-        st4(pr.dh2 + row * 64 + 16 * mt + 4 * lg, dh2[mt]);
-      }
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        st4(pr.h1 + row * 32 + 16 * jt + 4 * lg, h1[jt]);
-        st4(pr.dh1 + row * 32 + 16 * jt + 4 * lg, dh1[jt]);
-      }
-      if (lg == 0) st4(pr.feat + row * 4, f32x4{f0, f1, f2, 0.f});
-    }
+    pair_dh1(w1T, dh2, h1, dh1);
+    if (valid) pair_rows_store(pr, (size_t)(p0 + p), h2, dh2, h1, dh1, f0, f1, f2, lg);
   }
   SW_STAMP(2);
   __syncthreads();  // pair rows of this scene are visible to the whole workgroup (same CU)
@@ -1035,28 +1073,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   }
   sw_barrier();
   SW_STAMP(6);
-  // dh_j += sum_i a_ij dS_i  +  W^T dWh_j  on the matrix cores (see social_pool_bwd_kernel)
-  {
-    const int npad = (n + 15) & ~15;
-    for (int at = 0; at < npad / 16; ++at) {
-      f32x4 acc = tile_mm_reg<4>(wT, &dwh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
-      f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-      for (int kt = 0; kt < npad / 16; ++kt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = 16 * kt + 4 * lg + r;
-          const float av = i < n ? dsl[i * 68 + 16 * wave + ln] : 0.f;
-          const float bv = i < n ? sig[i * sa + 16 * at + ln] : 0.f;
-          acc2 = SW_MFMA(av, bv, acc2);
-        }
-      }
-      const int j = 16 * at + ln;
-      if (j < n) {
-        float* q = dh + (size_t)(s0 + j) * 64 + 16 * wave + 4 * lg;
-        st4(q, ld4(q) + (acc + acc2));
-      }
-    }
-  }
+  scene_dh_rows(wT, smem, Ls, dh, s0, n);
   SW_STAMP(7);
 }
 
@@ -1072,10 +1089,6 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
 // ---------------------------------------------------------------------------------------------
 #define SW_BIG_REC 8
 #define SW_BIG_PROW 132   // floats per partial row of the row-block backward: Q_j [64] | sum_i a_ij dS_i [64] | sd_j, pad [4]
-__device__ __forceinline__ f32x4 agent_x4(const float* obsv, int To, int a) {
-  const float* p = obsv + ((size_t)a * To + To - 2) * 2;  // last two observed points -> (p, v)
-  return f32x4{p[2], p[3], p[2] - p[0], p[3] - p[1]};
-}
 
 // Wh = W h + b for the 16 agents of a block (one MFMA tile per wave: units 16w..), and what the attention needs of fc.4:
 // v_j = W3^T Wh_j, c_j = <b3, Wh_j> (scene_wh_to_v has the algebra).  wh / vv [B][64], cc [B].
@@ -1089,14 +1102,9 @@ __global__ __launch_bounds__(SW_THREADS) void social_wh_kernel(const float* __re
   const int s0 = scene_off[rec[0]], n = scene_off[rec[0] + 1] - s0, i0 = rec[1];
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int a = s0 + min(i0 + ln, n - 1);
-  f32x4 wr[4], w3t[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    wr[j] = ld4(att_w + swp::ATT_W + (16 * wave + ln) * 64 + 16 * j + 4 * lg);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) w3t[j][r] = emb_w[swp::EMB_W2 + (16 * j + 4 * lg + r) * 64 + 16 * wave + ln];
-  }
-  f32x4 acc = ld4(att_w + swp::ATT_B + 16 * wave + 4 * lg);
+  f32x4 wr[4], w3t[4], acc;
+  load_w3t(w3t, emb_w, wave, ln, lg);
+  load_att_w(wr, acc, att_w, wave, ln, lg);
   acc = tile_mm_reg<4>(wr, h + (size_t)a * 64 + 4 * lg, acc);
   if (i0 + ln < n) st4(wh + (size_t)a * 64 + 16 * wave + 4 * lg, acc);
   st4(&tile[ln][16 * wave + 4 * lg], acc);
@@ -1139,16 +1147,9 @@ __global__ __launch_bounds__(SW_THREADS) void social_big_fwd_kernel(
       f32x4 h1[2], h2[4];
       pair_l1(w0b, lg, f0, f1, f2, h1);
       pair_l2(W, b12, lg, h1, h2);
-      float part = 0.f;     // sigma_ij = <h2_ij, v_j> + c_j (fc.4 is never run per pair)
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) {
-        f32x4 w = ld4(vv + (size_t)(s0 + jc) * 64 + 16 * mo + 4 * lg);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part = fmaf(h2[mo][r], w[r], part);
-      }
-      part += __shfl_xor(part, 16);
-      part += __shfl_xor(part, 32);
-      part += cc[s0 + jc];
+      f32x4 vj[4];
+      load_row_c(vj, vv + (size_t)(s0 + jc) * 64, lg);
+      const float part = pair_sigma(h2, vj) + cc[s0 + jc];     // sigma_ij = <h2_ij, v_j> + c_j (fc.4 is never run per pair)
       const float sg = !jv ? -INFINITY : (jc == i ? -1000.0f : part);   // train.py:170
       float tmax = sg;
 #pragma unroll
@@ -1250,10 +1251,10 @@ __global__ __launch_bounds__(SW_THREADS) void social_big_bwd_kernel(
     f32x4 vj[4], hj[4], Q[4], dhj_acc[4];     // Q_j = sum_i dsigma_ij h2_ij (-> dW3, dWh_j), see pair_block_dw3
     float sd = 0.f;
     const float cj = cc[s0 + jc];
+    load_row_c(vj, vv + (size_t)(s0 + jc) * 64, lg);
+    load_row_c(hj, h + (size_t)(s0 + jc) * 64, lg);
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo) {
-      vj[mo] = ld4(vv + (size_t)(s0 + jc) * 64 + 16 * mo + 4 * lg);
-      hj[mo] = ld4(h + (size_t)(s0 + jc) * 64 + 16 * mo + 4 * lg);
       Q[mo] = f32x4{0.f, 0.f, 0.f, 0.f};
       dhj_acc[mo] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -1269,41 +1270,24 @@ __global__ __launch_bounds__(SW_THREADS) void social_big_bwd_kernel(
       f32x4 h1[2], h2[4];
       pair_l1(w0b, lg, f0, f1, f2, h1);
       pair_l2_lds(w1s, b12, ln, lg, h1, h2);
-      float part_s = 0.f, da = 0.f;
       f32x4 dsi[4];
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) {
-        dsi[mo] = ld4(dS + (size_t)(s0 + i) * 64 + 16 * mo + 4 * lg);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          part_s = fmaf(h2[mo][r], vj[mo][r], part_s);
-          da = fmaf(dsi[mo][r], hj[mo][r], da);
-        }
-      }
-      part_s += __shfl_xor(part_s, 16);
-      part_s += __shfl_xor(part_s, 32);
-      da += __shfl_xor(da, 16);
-      da += __shfl_xor(da, 32);
-      const float sg = jc == i ? -1000.0f : part_s + cj;                  // train.py:170
+      load_row_c(dsi, dS + (size_t)(s0 + i) * 64, lg);
+      const float da = pair_sigma(dsi, hj);                                // <dS_i, h_j>: the same sum as sigma's
+      const float sg = jc == i ? -1000.0f : pair_sigma(h2, vj) + cj;      // train.py:170
       const float a = jv ? expf(sg - mq) * rlq : 0.f;
       const float dsv = a * (da - Dq);                                     // softmax backward; 0 for invalid lanes
       f32x4 dh2[4];
-      sd += dsv;
+      pair_dsigma_bwd(dsv, h2, vj, sd, Q, dh2);
 #pragma unroll
       for (int mo = 0; mo < 4; ++mo) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          Q[mo][r] = fmaf(dsv, h2[mo][r], Q[mo][r]);
-          dh2[mo][r] = h2[mo][r] > 0.f ? dsv * vj[mo][r] : 0.f;
-          dhj_acc[mo][r] = fmaf(a, dsi[mo][r], dhj_acc[mo][r]);
-        }
+        for (int r = 0; r < 4; ++r) dhj_acc[mo][r] = fmaf(a, dsi[mo][r], dhj_acc[mo][r]);
       }
       pair_tile_bwd_tail(G, scr, w1t, h1, dh2, f0, f1, f2, ln, lg SW_STAMP_ARG);
     }
     {     // dW3 += Wh Q^T, db3 += Wh sd over the block's 16 agents (this wave's rows)
       f32x4 whj[4];
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) whj[mo] = ld4(wh + (size_t)(s0 + jc) * 64 + 16 * mo + 4 * lg);
+      load_row_c(whj, wh + (size_t)(s0 + jc) * 64, lg);
       pair_block_dw3(G, scr, whj, Q, sd, ln, lg);
       wave_lds_fence();
     }
@@ -1431,7 +1415,7 @@ __global__ __launch_bounds__(SW_THREADS) void attention_pool_dense_kernel(
   const int s0 = scene_off[blockIdx.x], n = scene_off[blockIdx.x + 1] - s0;
   if (n <= 0) return;
   if (n == 1) {
-    if (threadIdx.x < 16) st4(S_out + (size_t)s0 * 64 + 4 * threadIdx.x, f32x4{0.f, 0.f, 0.f, 0.f});
+    zero_row64(S_out + (size_t)s0 * 64);
     return;
   }
   scene_load_h_wh(smem, Ls, h, att_w, s0, n);
@@ -1492,19 +1476,10 @@ __global__ __launch_bounds__(SW_THREADS) void embed_features_bwd_kernel(const fl
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   PairW W;
   load_pair_w(W, emb_w, ln, lg);
-  f32x4 w2T[4][4], w1T[2][4];   // fc.4.weight^T, fc.2.weight^T as A operands (see social_pool_bwd_rows_kernel)
+  f32x4 w2T[4][4], w1T[2][4];   // fc.4.weight^T, fc.2.weight^T as A operands: w2T[mt] = the units 16mt .. 16mt+15 (load_w3t)
 #pragma unroll
-  for (int mo = 0; mo < 4; ++mo) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float* row2 = emb_w + swp::EMB_W2 + (16 * mo + 4 * lg + r) * 64 + ln;
-      const float* row1 = emb_w + swp::EMB_W1 + (16 * mo + 4 * lg + r) * 32 + ln;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) w2T[mt][mo][r] = row2[16 * mt];
-      w1T[0][mo][r] = row1[0];
-      w1T[1][mo][r] = row1[16];
-    }
-  }
+  for (int mt = 0; mt < 4; ++mt) load_w3t(w2T[mt], emb_w, mt, ln, lg);
+  load_w1T(w1T, emb_w, ln, lg);
   const long long r0 = ((long long)blockIdx.x * 4 + wave) * 16;
   if (r0 >= R) return;
   const bool valid = r0 + ln < R;
@@ -1528,19 +1503,7 @@ __global__ __launch_bounds__(SW_THREADS) void embed_features_bwd_kernel(const fl
   for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) dh2[mt][r] = h2[mt][r] > 0.f ? dh2[mt][r] : 0.f;
-  dh1[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dh1[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dh1[0] = SW_MFMA(w1T[0][mt][r], dh2[mt][r], dh1[0]);
-      dh1[1] = SW_MFMA(w1T[1][mt][r], dh2[mt][r], dh1[1]);
-    }
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dh1[jt][r] = h1[jt][r] > 0.f ? dh1[jt][r] : 0.f;
+  pair_dh1(w1T, dh2, h1, dh1);
   // fc.0.weight^T dh1: this lane's 8 hidden units, then the four lane groups of the row
   float g0 = 0.f, g1 = 0.f, g2 = 0.f;
 #pragma unroll
@@ -1556,28 +1519,11 @@ __global__ __launch_bounds__(SW_THREADS) void embed_features_bwd_kernel(const fl
   g1 += __shfl_xor(g1, 16); g1 += __shfl_xor(g1, 32);
   g2 += __shfl_xor(g2, 16); g2 += __shfl_xor(g2, 32);
   if (valid) {
-    float* ph2 = rows;
-    float* pdh2 = ph2 + 64 * R;
-    float* ph1 = pdh2 + 64 * R;
-    float* pdh1 = ph1 + 32 * R;
-    float* pf4 = pdh1 + 32 * R;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      st4(ph2 + row * 64 + 16 * mt + 4 * lg, h2[mt]);
-      st4(pdh2 + row * 64 + 16 * mt + 4 * lg, dh2[mt]);
-    }
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) {
-      st4(ph1 + row * 32 + 16 * jt + 4 * lg, h1[jt]);
-      st4(pdh1 + row * 32 + 16 * jt + 4 * lg, dh1[jt]);
-    }
-    if (lg == 0) {
-      st4(pf4 + row * 4, f32x4{f0, f1, f2, 0.f});
-      if (dfeat) {
-        dfeat[row * 3] = g0;
-        dfeat[row * 3 + 1] = g1;
-        dfeat[row * 3 + 2] = g2;
-      }
+    pair_rows_store(pair_rows(rows, R), (size_t)row, h2, dh2, h1, dh1, f0, f1, f2, lg);
+    if (lg == 0 && dfeat) {
+      dfeat[row * 3] = g0;
+      dfeat[row * 3 + 1] = g1;
+      dfeat[row * 3 + 2] = g2;
     }
   }
 }
