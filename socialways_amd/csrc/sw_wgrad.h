@@ -117,6 +117,9 @@ int wg_reduce_launch(WgBatch& b, float* ws, hipStream_t stream);
 // follow in the same stream - the composition back-propagation - may use them)
 int wg_launch_adam(WgBatch& b, float* ws, WgAdam& ad, hipStream_t stream);
 
+// whether wg_add takes N delta columns against K act columns (K = 0: the delta side alone): every block of up to 64
+// columns has to split into whole lane vectors (1 .. 16, even up to 32, multiples of 4 up to 64 delta columns)
+bool wg_shape_ok(int N, int K);
 int wg_add(WgBatch& b, const float* delta, int ldd, const float* act, int lda, int R, int N, int K, float* dW,
            int ldw, float* db, float* db2, int accumulate);
 // same with a tail segment (see WgProblem): K % 16 == 0, K <= 64, K2 + (db ? 1 : 0) <= 16

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgBatch batch, const 
 }
 
 // host side -------------------------------------------------------------------------------------
-static bool wg_shape_ok(int N, int K) {   // every 64-column block of delta / act must split into whole lane vectors
+bool wg_shape_ok(int N, int K) {   // every 64-column block of delta / act must split into whole lane vectors
   for (int n0 = 0; n0 < N; n0 += 64)
     if (!wg_tiles(N - n0 < 64 ? N - n0 : 64, false)) return false;
   return K == 0 || wg_tiles(K, true) != 0;

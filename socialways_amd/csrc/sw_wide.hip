@@ -1659,8 +1659,11 @@ extern "C" int sw_wide_wgrad(const long long* desc, int n, float* wgrad_ws, void
     float* db = (float*)(uintptr_t)d[9];
     const int ldd = (int)d[1], lda = (int)d[3], R = (int)d[4], N = (int)d[5], K = (int)d[6], ldw = (int)d[8];
     if (!delta || !act || !dW || R < 1 || N < 1 || K < 1) return SW_EARG;
-    for (int n0 = 0; n0 < N; n0 += 256) {
-      const int nn = N - n0 < 256 ? N - n0 : 256;
+    for (int n0 = 0, nn; n0 < N; n0 += nn) {
+      nn = N - n0 < 256 ? N - n0 : 256;
+      // a last block the grouped GEMM's lane vectors cannot split (17, 19, .. 63 columns: 17 latent codes) is cut at its
+      // last multiple of 16; the remaining 1 .. 15 columns are the next problem
+      if (!wg_shape_ok(nn, 0) && (nn & 15)) nn -= nn & 15;
       WgBatch trial = b;
       int rc = wg_add(trial, delta + n0, ldd, act, lda, R, nn, K, dW + (size_t)n0 * ldw, ldw, db ? db + n0 : nullptr, nullptr, 0);
       if (rc == SW_ESHAPE && b.np > 0) {        // the batch is full: launch it and start the next one with this problem

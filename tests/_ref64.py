@@ -61,12 +61,12 @@ def _f64():
         torch.set_default_dtype(old)
 
 
-def _close_out(got, ref, what, group, tag):
+def _close_out(got, ref, what, group, tag, at=OUT_AT):
     got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
     scale = max(float(ref.abs().max()), 1e-30)
     _note(group, "out", float((got - ref).abs().max()) / scale)
-    assert_close(got.numpy(), ref.numpy(), OUT_RT, OUT_AT * scale, "%s (%s)" % (what, tag))
+    assert_close(got.numpy(), ref.numpy(), OUT_RT, at * scale, "%s (%s)" % (what, tag))
 
 
 def _close_grad(got, ref, what, group, tag, rel=GRAD_REL):
@@ -277,3 +277,80 @@ def gen_ambiguous(orc, fn, extra_mods=()):
     with torch.no_grad(), _f64(), recording(*gen_mods(orc), *extra_mods) as rec:
         fn()
     return count_ambiguous(rec)
+
+
+# ---- the wide path (hidden sizes above 64): cases and float64 references of test_gpu_wide_reference.py ---------------------
+W_INFO = 0.5
+TARGETS = (0.03, 0.96)
+_MIX = [5, 1, 9, 16, 3, 2]
+# (id, H, n_latent_codes, n_next, To, scene sizes, forms the trainer must take: seq, decloop, heads, generator phases run)
+WIDE_CASES = [
+    ("h64-nl3", 64, 3, 12, 8, _MIX, (True, False, True), True),                 # sequence kernel <1>, per-step decode, nlp padding
+    ("h96", 96, 2, 12, 8, [33, 32, 2], (False, False, True), True),             # per-step LSTM, half-filled 64-unit block, B past 64
+    ("h128-ragged", 128, 2, 12, 8, _MIX, (True, True, True), True),             # sequence <2>, decode loop
+    ("h128-aligned", 128, 2, 12, 8, [16, 16], (True, True, True), True),
+    ("h128-nopairs", 128, 2, 12, 8, [1] * 17, (True, True, True), True),
+    ("h128-amax", 128, 2, 12, 8, [64, 1], (True, True, True), True),
+    ("h128-tp1", 128, 2, 1, 2, [5, 1, 9, 4, 2], (True, True, False), True),     # loop with no re-fed step; K4 = 4: GEMM heads
+    ("h128-tp2", 128, 2, 2, 2, [5, 1, 9, 4, 2], (True, True, False), True),     # one re-fed step; K4 = 8
+    ("h128-nl5-tp16", 128, 5, 16, 8, [33, 32, 2], (True, True, True), True),    # K4 = 64, nlp = 8
+    ("h128-nl17", 128, 17, 12, 8, _MIX, (True, True, False), False),            # nl past the heads' limit: GEMM heads (b, c only)
+    ("h160-tp10", 160, 2, 10, 8, _MIX, (False, False, False), True),            # nub = 3, D3 = 100, K4 = 40: GEMM heads
+    ("h256", 256, 2, 12, 8, [33, 32, 2], (False, False, True), True),           # heads at WH_MAXH, wgrad batch flush
+    ("h288", 288, 2, 12, 2, _MIX, (False, False, False), True),                 # past WH_MAXH
+    ("h128-metric", 128, 2, 12, 8, [8] * 256, (True, True, True), True),        # the one large case
+]
+
+
+def wide_torch_seed(H, nl, Tp):
+    return 3000 + H + 7 * nl + Tp
+
+
+def wide_oracles(H, nl, Tp, use_social=True):
+    """The fp32 oracle drawn from the case's torch seed (the initial weights a WideTrainer draws from the same seed: same
+    construction order) and its float64 copy, D included."""
+    import sw_oracle as O
+    torch.manual_seed(wide_torch_seed(H, nl, Tp))
+    o32 = O.SocialWaysOracle(Tp, hidden_size=H, use_social=use_social, n_latent_codes=nl)
+    return o32, wide_oracle64(o32)
+
+
+def wide_oracle64(src, D=None):
+    """float64 oracle with the weights of `src` (an oracle or a trainer's G: anything with the four generator modules)
+    and of the discriminator D (default src.D)."""
+    import sw_oracle as O
+    H, nl, Tp = src.encoder.hidden_size, (D or src.D).latent_decoder[2].out_features, (D or src.D).n_next
+    with _f64():
+        o64 = O.SocialWaysOracle(Tp, hidden_size=H, use_social=src.use_social, n_latent_codes=nl)
+    for n in G_NAMES:
+        getattr(o64, n).double().load_state_dict({k: v.detach().cpu().double() for k, v in getattr(src, n).state_dict().items()})
+    o64.D.double().load_state_dict({k: v.detach().cpu().double() for k, v in (D or src.D).state_dict().items()})
+    return o64
+
+
+def wide_inputs(B, To, Tp, H):
+    """seed -> (obsv (B, To, 2), real future (B, Tp, 2): one random walk, noise (B, H / 2), cotangent (B, Tp, 4))."""
+    def make(seed):
+        g = torch.Generator().manual_seed(seed)
+        walk = (torch.randn(B, To + Tp, 2, generator=g) * 0.1).cumsum(1)
+        return (walk[:, :To].contiguous(), walk[:, To:].contiguous(), torch.rand(B, H // 2, generator=g),
+                torch.randn(B, Tp, 4, generator=g) * 0.1)
+    return make
+
+
+def wide_ambiguous(o64, inp, sb, Tp):
+    """Kink inputs within MARGIN of 0 in the float64 forward of the generator and of D on the fake and the real future."""
+    import sw_oracle as O
+    o, real, z = inp[0].double(), inp[1].double(), inp[2].double()
+
+    def fn():
+        o4, p4 = O.get_traj_4d(o, real)
+        fake = o64.predict(o, z, Tp, sb)
+        o64.D(o4, fake)
+        o64.D(o4, p4)
+    return gen_ambiguous(o64, fn, [o64.D])
+
+
+def wide_pick(o64, B, To, Tp, H, sb):
+    seed, inp, n_amb = pick_fewest(wide_inputs(B, To, Tp, H), lambda inp: wide_ambiguous(o64, inp, sb, Tp))
+    return seed, inp, n_amb

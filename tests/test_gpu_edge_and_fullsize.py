@@ -567,8 +567,8 @@ def test_wider_networks_train_on_the_generic_path_and_match_the_oracle(H, nl, tm
 
 def test_wide_path_equals_generic_path_and_graph_replay_equals_eager():
     """The wide engine (wide.py: time-step-level kernels, explicit backward) against the layer-by-layer generic path under
-    torch's tape (generic.py) on the same modules: reported sums, rollout, EVERY gradient of the generator, the weights
-    of G and D after each of three steps; then its hipGraph-replayed step against its eager step, bit for bit.  Widths
+    torch's tape (generic.py) on the same modules: reported sums, rollout, EVERY gradient of the generator and - at both of a step's
+    updates - of the discriminator, the weights of G and D after each of three steps; then its hipGraph-replayed step against its eager step, bit for bit.  Widths
     that are not multiples of 32 stay on the generic path."""
     import socialways_amd as sw
     from socialways_amd.generic import GenericTrainer
@@ -584,10 +584,27 @@ def test_wide_path_equals_generic_path_and_graph_replay_equals_eager():
     data = sw.SceneDataset(t["obsvs"], t["preds"], t["batches"], device="cuda:0")
     B, sb = 36, data.the_batches[:6]
     gen = torch.Generator().manual_seed(2)
+    # D's gradients of both updates of a step: the wide engine's packed buffer at the two points where _step_device yields it
+    # (an eager step hands it to _allreduce), the generic path's .grad in front of its optimizer step (_reduce_grads)
+    da, db = [], []
+    a._allreduce = lambda buf: da.append(buf.clone())
+    reduce_b = b._reduce_grads
+
+    def capture_b(optim):
+        if optim is b.D_optimizer:
+            db.append([p.grad.clone() for p in b.D.parameters()])
+        reduce_b(optim)
+    b._reduce_grads = capture_b
     for it in range(3):
         noise = torch.rand(B, H // 2, generator=gen)
+        del da[:], db[:]
         ra = a.step(data.obsv[:B], data.pred[:B], sb, 0.03, 0.94, noise, data.ss)
         rb = b.step(data.obsv[:B], data.pred[:B], sb, 0.03, 0.94, noise, data.ss)
+        assert len(da) == 3 and len(db) == 2 and da[0].numel() == a.dp.gflat.numel() and da[2].numel() == a.gp.gflat.numel()
+        for u in range(2):
+            for (n, _), (o, k, shape), q in zip(a.D.named_parameters(), a.dp.slices, db[u]):
+                assert_close(da[u][o:o + k].view(shape).cpu(), q.cpu(), 1e-4, 1e-4 * max(float(q.abs().max()), 1e-12),
+                             "dD %s, step %d, update %d" % (n, it, u))
         assert_close(ra.cpu(), rb.cpu(), 2e-6, 1e-9, "reported sums, step %d" % it)
         assert_close(a.last_pred_hat.cpu(), b.last_pred_hat.cpu(), 1e-5, 1e-6, "rollout, step %d" % it)
         for (n, p), (_, q) in zip(a.G.named_parameters(), b.G.named_parameters()):

@@ -161,3 +161,16 @@ def test_without_ambiguous_units_it_is_the_plain_comparison():
     with pytest.raises(AssertionError, match="0.weight"):
         R.close_grads_branch_consistent(bad, ref_run, "tiny", "seed 0")
     R._observed.pop("tiny", None)
+
+
+@pytest.mark.parametrize("case", R.WIDE_CASES, ids=[c[0] for c in R.WIDE_CASES])
+def test_wide_cases_have_a_seed_within_the_ambiguity_cap(case):
+    """The seed rule of tests/test_gpu_wide_reference.py, known to hold before a GPU is involved: every row's float64
+    oracle, drawn from the torch seed the GPU test uses, has a seed of SEEDS (pick_fewest) whose generator + discriminator
+    forward keeps at most MAX_AMBIGUOUS kink inputs within MARGIN of 0."""
+    _, H, nl, Tp, To, sizes, _, _ = case
+    B, sb = int(np.sum(sizes)), R.scene_rows(sizes)
+    _, o64 = R.wide_oracles(H, nl, Tp)
+    seed, _, n_amb = R.wide_pick(o64, B, To, Tp, H, sb)
+    print("wide case %-14s seed %3d: %d kink inputs within %.1e of 0" % (case[0], seed, n_amb, R.MARGIN))
+    assert n_amb <= R.MAX_AMBIGUOUS, (case[0], seed, n_amb)
