@@ -14,6 +14,7 @@
 // agents x 64 units (4 accumulators), lanes fetch float4s of their weight / activation rows (k = 16 j + 4 lg + r).
 #include "../../include/socialways_hip.h"
 #include "sw_common.h"
+#include "sw_lstm_dev.h"
 #include "sw_wgrad.h"
 #include <cstddef>
 #include <cstring>
@@ -28,6 +29,83 @@ __device__ __forceinline__ float epi_apply(float v, int epi, float aux) {
     case EPI_DRELU: return aux > 0.f ? v : 0.f;
     case EPI_DLRELU: return aux > 0.f ? v : 0.2f * v;
   }
+  return v;
+}
+
+// ---- phases shared by the kernels below ------------------------------------------------------------------------------------
+// The accumulators of NT 16-column tiles from column n0 on, seeded with the bias (a lane holds columns 4 lg .. 4 lg + 3 of each
+// tile): zero without a bias and beyond column N.
+template <int NT>
+__device__ __forceinline__ void gemm_acc_init(f32x4 (&acc)[NT], const float* __restrict__ bias, int n0, int N, int lg) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = n0 + 16 * t + 4 * lg + q;
+      acc[t][q] = (bias && n < N) ? bias[n] : 0.f;
+    }
+}
+// ... and their way out, for the lane's row `row`: y = epi(acc + cin; aux).  OV: float4 accesses (see wide_gemm_kernel).
+template <bool OV, int NT>
+__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[NT], long long row, int n0, int N, int lg,
+                                              const float* __restrict__ cin, int cin_ld, const float* __restrict__ aux, int aux_ld,
+                                              float* __restrict__ y, int y_ld, int epi) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n = n0 + 16 * t + 4 * lg;
+    if (n >= N) continue;
+    if constexpr (OV) {
+      f32x4 v = acc[t];
+      if (cin) v = v + ld4(cin + row * cin_ld + n);
+      if (epi != EPI_NONE) {
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        if (epi >= EPI_DRELU) a = ld4(aux + row * aux_ld + n);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = epi_apply(v[q], epi, a[q]);
+      }
+      st4(y + row * y_ld + n, v);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (n + q < N) {
+          float v = acc[t][q];
+          if (cin) v += cin[row * cin_ld + n + q];
+          v = epi_apply(v, epi, epi >= EPI_DRELU ? aux[row * aux_ld + n + q] : 0.f);
+          y[row * y_ld + n + q] = v;
+        }
+      }
+    }
+  }
+}
+// The four gate rows (i f g o) of one agent's 16-unit tile, H floats apart: a saved gates / dgates row in memory or in an LDS tile
+__device__ __forceinline__ void st_gates4(float* p, int H, const f32x4 (&g)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) st4(p + q * H, g[q]);
+}
+// A dgates tile in LDS ([16 agents][K + 4]) to the agents' rows of one step (rows = the row of agent 0, K floats each): a wave
+// writes 4 agents' rows, consecutive lanes consecutive float4s; the padding rows of the last tile are replicas of agent B - 1 and
+// go to its row (the same values to the same place).
+template <int K>
+__device__ __forceinline__ void dg_tile_store(const float* tile, float* __restrict__ rows, int a0, int B, int wave, int lane) {
+  static_assert(K % 256 == 0, "whole float4 rounds of a wave");
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int a = 4 * wave + q, bb = min(a0 + a, B - 1);
+#pragma unroll
+    for (int c4 = lane; c4 < K / 4; c4 += 64)
+      st4(rows + (size_t)bb * K + 4 * c4, ld4(tile + a * (K + 4) + 4 * c4));
+  }
+}
+// One float4 of an activation / delta tile, column `col` of the lane's row: into the LDS tile (the next layer's operand) and, the
+// same value, into the saved row
+__device__ __forceinline__ void st_tile_row(float* tile_row, float* __restrict__ saved_row, int col, f32x4 v) {
+  st4(tile_row + col, v);
+  st4(saved_row + col, v);
+}
+// Sum over the 16 lanes of an agent (xor tree 8, 4, 2, 1): every lane ends up with the total
+__device__ __forceinline__ float sum16(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
 
@@ -56,14 +134,7 @@ __global__ __launch_bounds__(256) void wide_gemm_kernel(const float* __restrict_
 #pragma unroll
   for (int t = 0; t < 4; ++t) wr[t] = w + (long long)min(n0 + 16 * t + ln, N - 1) * w_rs;
   f32x4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = n0 + 16 * t + 4 * lg + q;
-      acc[t][q] = (bias && n < N) ? bias[n] : 0.f;
-    }
-  }
+  gemm_acc_init(acc, bias, n0, N, lg);
   // Operands of k-step j (16 columns): one float4 of the lane's activation row and of each of its 4 weight rows.  Three
   // k-steps are in flight: the loads of step j + 2 are issued before the 16 matrix instructions of step j (a wave alone on
   // its SIMD - these grids are a few hundred workgroups - has nothing else to hide the L2 round trip behind).  Loads are
@@ -109,33 +180,7 @@ __global__ __launch_bounds__(256) void wide_gemm_kernel(const float* __restrict_
     load(k0 + 64, xb, wb);
     mma(k0 + 32, xc, wc);
   }
-  if (!rv) return;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int n = n0 + 16 * t + 4 * lg;
-    if (n >= N) continue;
-    if constexpr (OV) {
-      f32x4 v = acc[t];
-      if (cin) v = v + ld4(cin + row * cin_ld + n);
-      if (epi != EPI_NONE) {
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (epi >= EPI_DRELU) a = ld4(aux + row * aux_ld + n);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = epi_apply(v[q], epi, a[q]);
-      }
-      st4(y + row * y_ld + n, v);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (n + q < N) {
-          float v = acc[t][q];
-          if (cin) v += cin[row * cin_ld + n + q];
-          v = epi_apply(v, epi, epi >= EPI_DRELU ? aux[row * aux_ld + n + q] : 0.f);
-          y[row * y_ld + n + q] = v;
-        }
-      }
-    }
-  }
+  if (rv) gemm_epilogue<OV>(acc, row, n0, N, lg, cin, cin_ld, aux, aux_ld, y, y_ld, epi);
 }
 
 
@@ -241,43 +286,11 @@ __global__ __launch_bounds__(256) void wide_gemm_lds_kernel(const float* __restr
   const long long r0 = rb * 16 * AT;
   const int at = wave % AT, ug = wave / AT;
   f32x4 acc[UT];
-#pragma unroll
-  for (int u = 0; u < UT; ++u)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = n0 + 16 * (UT * ug + u) + 4 * lg + q;
-      acc[u][q] = (bias && n < N) ? bias[n] : 0.f;
-    }
+  gemm_acc_init(acc, bias, n0 + 16 * UT * ug, N, lg);
   wide_core<AT, UT>(sm, [&](int i) { return x + min(r0 + i, R - 1) * x_rs; },
                     [&](int i) { return w + (long long)min(n0 + i, N - 1) * w_rs; }, K, acc);
   const long long row = r0 + 16 * at + ln;
-  if (row >= R) return;
-#pragma unroll
-  for (int u = 0; u < UT; ++u) {
-    const int n = n0 + 16 * (UT * ug + u) + 4 * lg;
-    if (n >= N) continue;
-    if constexpr (OV) {
-      f32x4 v = acc[u];
-      if (cin) v = v + ld4(cin + row * cin_ld + n);
-      if (epi != EPI_NONE) {
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (epi >= EPI_DRELU) a = ld4(aux + row * aux_ld + n);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = epi_apply(v[q], epi, a[q]);
-      }
-      st4(y + row * y_ld + n, v);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (n + q < N) {
-          float v = acc[u][q];
-          if (cin) v += cin[row * cin_ld + n + q];
-          v = epi_apply(v, epi, epi >= EPI_DRELU ? aux[row * aux_ld + n + q] : 0.f);
-          y[row * y_ld + n + q] = v;
-        }
-      }
-    }
-  }
+  if (row < R) gemm_epilogue<OV>(acc, row, n0 + 16 * UT * ug, N, lg, cin, cin_ld, aux, aux_ld, y, y_ld, epi);
 }
 
 // Products with a contracted width of at most 8 (the heads' K = 1 / 2 / n_latent back-products, the 3-wide pair features,
@@ -330,23 +343,10 @@ __global__ __launch_bounds__(256) void wide_lstm_fwd_kernel(const float* __restr
     wide_core<4, 4>(sm, [&](int i) { return h_prev + (size_t)min(r0 + i, B - 1) * hp_ld; },
                     [&](int i) { return Whh + ((size_t)(i >> 4) * H + u0 + (i & 15)) * H; }, H, acc);
   if (!rv) return;
-  f32x4 cp = {0.f, 0.f, 0.f, 0.f};
-  if (c_prev) cp = ld4(c_prev + (size_t)row * H + u0 + 4 * lg);
-  f32x4 gi, gf, gg, go, cn, hn;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    gi[q] = sw_sigmoid(acc[0][q]);
-    gf[q] = sw_sigmoid(acc[1][q]);
-    gg[q] = sw_tanh(acc[2][q]);
-    go[q] = sw_sigmoid(acc[3][q]);
-    cn[q] = fmaf(gf[q], cp[q], gi[q] * gg[q]);
-    hn[q] = go[q] * sw_tanh(cn[q]);
-  }
-  float* gr = gates + (size_t)row * 4 * H + u0 + 4 * lg;
-  st4(gr, gi);
-  st4(gr + H, gf);
-  st4(gr + 2 * H, gg);
-  st4(gr + 3 * H, go);
+  f32x4 gate[4], cn = {0.f, 0.f, 0.f, 0.f}, hn;      // cn: c_{t-1} in, c_t out
+  if (c_prev) cn = ld4(c_prev + (size_t)row * H + u0 + 4 * lg);
+  lstm_gates(acc, gate, cn, hn);
+  st_gates4(gates + (size_t)row * 4 * H + u0 + 4 * lg, H, gate);
   st4(c_out + (size_t)row * H + u0 + 4 * lg, cn);
   st4(h_out + (size_t)row * h_ld + u0 + 4 * lg, hn);
   if (h_out2) st4(h_out2 + (size_t)row * h2_ld + u0 + 4 * lg, hn);
@@ -387,27 +387,13 @@ __global__ __launch_bounds__(256) void wide_lstm_bwd_kernel(const float* __restr
     if (dh_ext) dh = dh + ld4(dh_ext + (size_t)row * dhe_ld + u0 + 4 * lg);
     if (dh_ext2) dh = dh + ld4(dh_ext2 + (size_t)row * dhe2_ld + u0 + 4 * lg);
     const float* gr = gates + (size_t)row * 4 * H + u0 + 4 * lg;
-    const f32x4 gi = ld4(gr), gf = ld4(gr + H), gg = ld4(gr + 2 * H), go = ld4(gr + 3 * H), ct = ld4(c + e);
-    f32x4 cp = {0.f, 0.f, 0.f, 0.f}, dc = cp;
+    const f32x4 gate[4] = {ld4(gr), ld4(gr + H), ld4(gr + 2 * H), ld4(gr + 3 * H)}, ct = ld4(c + e);
+    f32x4 cp = {0.f, 0.f, 0.f, 0.f}, dc = cp, dgate[4];      // dc: d c_t in, d c_{t-1} out
     if (c_prev) cp = ld4(c_prev + e);
     if (dc_in) dc = ld4(dc_in + e);
-    f32x4 di, df, dg, dO, dcp;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float tc = sw_tanh(ct[q]);
-      const float dct = fmaf(dh[q] * go[q], 1.0f - tc * tc, dc[q]);
-      di[q] = dct * gg[q] * gi[q] * (1.0f - gi[q]);
-      df[q] = dct * cp[q] * gf[q] * (1.0f - gf[q]);
-      dg[q] = dct * gi[q] * (1.0f - gg[q] * gg[q]);
-      dO[q] = dh[q] * tc * go[q] * (1.0f - go[q]);
-      dcp[q] = dct * gf[q];
-    }
-    float* dq = dgates + (size_t)row * 4 * H + u0 + 4 * lg;
-    st4(dq, di);
-    st4(dq + H, df);
-    st4(dq + 2 * H, dg);
-    st4(dq + 3 * H, dO);
-    st4(dc_out + e, dcp);
+    lstm_cell_bwd(gate, ct, cp, dh, dc, dgate);
+    st_gates4(dgates + (size_t)row * 4 * H + u0 + 4 * lg, H, dgate);
+    st4(dc_out + e, dc);
   }
 }
 
@@ -425,11 +411,8 @@ __global__ __launch_bounds__(256) void wide_out_fwd_kernel(const float* __restri
     vx = fmaf(a, W4[k], vx);
     vy = fmaf(a, W4[D3 + k], vy);
   }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    vx += __shfl_xor(vx, o);
-    vy += __shfl_xor(vy, o);
-  }
+  vx = sum16(vx);
+  vy = sum16(vy);
   if (b >= B || l != 0) return;
   vx += b4[0];
   vy += b4[1];
@@ -463,14 +446,7 @@ __global__ __launch_bounds__(256) void wide_out_bwd_kernel(const float* __restri
         s3 = fmaf(d[q], w3[q], s3);
       }
     }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      s0 += __shfl_xor(s0, o);
-      s1 += __shfl_xor(s1, o);
-      s2 += __shfl_xor(s2, o);
-      s3 += __shfl_xor(s3, o);
-    }
-    g = g + f32x4{s0, s1, s2, s3};
+    g = g + f32x4{sum16(s0), sum16(s1), sum16(s2), sum16(s3)};
   }
   const float dpx = g[0] + dp_run[2 * bc], dpy = g[1] + dp_run[2 * bc + 1];
   const float dvx = g[2] + dpx, dvy = g[3] + dpy;
@@ -617,21 +593,11 @@ __global__ __launch_bounds__(256) void wide_lstm_seq_fwd_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < NU; ++k) {
       const int u0 = 16 * (NU * wave + k);
-      f32x4 gi, gf, gg, go;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        gi[q] = sw_sigmoid(acc[0][k][q]);
-        gf[q] = sw_sigmoid(acc[1][k][q]);
-        gg[q] = sw_tanh(acc[2][k][q]);
-        go[q] = sw_sigmoid(acc[3][k][q]);
-        c[k][q] = fmaf(gf[q], c[k][q], gi[q] * gg[q]);
-        h[k][q] = go[q] * sw_tanh(c[k][q]);
-      }
+      const f32x4 pre[4] = {acc[0][k], acc[1][k], acc[2][k], acc[3][k]};      // tile k's four gates: renaming, no move
+      f32x4 gate[4];
+      lstm_gates(pre, gate, c[k], h[k]);
       st4(&hbuf[(t + 1) & 1][ln * HLD + u0 + 4 * lg], h[k]);
-      st4(grow + u0, gi);
-      st4(grow + H + u0, gf);
-      st4(grow + 2 * H + u0, gg);
-      st4(grow + 3 * H + u0, go);
+      st_gates4(grow + u0, H, gate);
       st4(cs + ((size_t)t * B + b) * H + u0 + 4 * lg, c[k]);
       st4(hs + ((size_t)(t + 1) * B + b) * H + u0 + 4 * lg, h[k]);
     }
@@ -684,12 +650,13 @@ __global__ __launch_bounds__(256) void wide_lstm_seq_bwd_kernel(const float* __r
   __syncthreads();
   for (int t = T - 1; t >= 0; --t) {
     // the saved rows of step t are requested FIRST: their round trip runs under the 256 matrix instructions below
-    f32x4 gi[NU], gf[NU], gg[NU], go[NU], ct[NU], cp[NU];
+    f32x4 gate[NU][4], ct[NU], cp[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) {
       const int u0 = 16 * (NU * wave + k);
       const float* gr = gates + ((size_t)t * B + b) * K + u0 + 4 * lg;
-      gi[k] = ld4(gr); gf[k] = ld4(gr + H); gg[k] = ld4(gr + 2 * H); go[k] = ld4(gr + 3 * H);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) gate[k][g] = ld4(gr + g * H);
       ct[k] = ld4(cs + ((size_t)t * B + b) * H + u0 + 4 * lg);
       cp[k] = ld4(cs + ((size_t)max(t - 1, 0) * B + b) * H + u0 + 4 * lg);      // unconditional; zeroed below for t = 0
     }
@@ -722,31 +689,13 @@ __global__ __launch_bounds__(256) void wide_lstm_seq_bwd_kernel(const float* __r
     for (int k = 0; k < NU; ++k) {
       const int u0 = 16 * (NU * wave + k);
       if (t == 0) cp[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4 di, df, dg, dO;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float tc = sw_tanh(ct[k][q]);
-        const float dct = fmaf(dh[k][q] * go[k][q], 1.0f - tc * tc, dc[k][q]);
-        di[q] = dct * gg[k][q] * gi[k][q] * (1.0f - gi[k][q]);
-        df[q] = dct * cp[k][q] * gf[k][q] * (1.0f - gf[k][q]);
-        dg[q] = dct * gi[k][q] * (1.0f - gg[k][q] * gg[k][q]);
-        dO[q] = dh[k][q] * tc * go[k][q] * (1.0f - go[k][q]);
-        dc[k][q] = dct * gf[k][q];
-      }
-      float* tr = tile + ln * GLD + u0 + 4 * lg;
-      st4(tr, di);
-      st4(tr + H, df);
-      st4(tr + 2 * H, dg);
-      st4(tr + 3 * H, dO);
+      f32x4 dgate[4];
+      lstm_cell_bwd(gate[k], ct[k], cp[k], dh[k], dc[k], dgate);
+      st_gates4(tile + ln * GLD + u0 + 4 * lg, H, dgate);
       dh[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     sw_barrier();      // LDS only: a full __syncthreads() would also drain the 32 KB of dgates rows stored in the previous step
-    // dgates_t rows to memory from the tile: a wave writes 4 agents' rows, consecutive lanes consecutive float4s
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int a = 4 * wave + q, bb = min(a0 + a, B - 1);
-      for (int c4 = lane; c4 < K / 4; c4 += 64) st4(dgates + ((size_t)t * B + bb) * K + 4 * c4, ld4(tile + a * GLD + 4 * c4));
-    }
+    dg_tile_store<K>(tile, dgates + (size_t)t * B * K, a0, B, wave, lane);      // dgates_t rows to memory from the tile
   }
 }
 
@@ -868,8 +817,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_fwd_kernel(WideDecFwd A) {
       for (int t = 0; t < 5; ++t) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[t][q] = sw_lrelu(acc[t][q]);
-        st4(&a1b[ln * L1 + 16 * t1[t] + 4 * lg], acc[t]);
-        st4(g1 + 16 * t1[t], acc[t]);
+        st_tile_row(&a1b[ln * L1 + 4 * lg], g1, 16 * t1[t], acc[t]);
       }
     }
     sw_barrier();
@@ -882,8 +830,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_fwd_kernel(WideDecFwd A) {
       for (int t = 0; t < 3; ++t) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[t][q] = sw_lrelu(acc[t][q]);
-        st4(&a2b[ln * L2 + 16 * t2[t] + 4 * lg], acc[t]);
-        st4(g2 + 16 * t2[t], acc[t]);
+        st_tile_row(&a2b[ln * L2 + 4 * lg], g2, 16 * t2[t], acc[t]);
       }
     }
     sw_barrier();
@@ -893,10 +840,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_fwd_kernel(WideDecFwd A) {
       wide_stream_mm<2, D2 / 16, PD>(w3i, t3, &a2b[ln * L2 + 4 * lg], acc, lane);
       float* g3 = A.a3 + ((size_t)i * B + b) * D3 + 4 * lg;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        st4(&a3b[ln * L3 + 16 * t3[t] + 4 * lg], acc[t]);
-        st4(g3 + 16 * t3[t], acc[t]);
-      }
+      for (int t = 0; t < 2; ++t) st_tile_row(&a3b[ln * L3 + 4 * lg], g3, 16 * t3[t], acc[t]);
     }
     sw_barrier();
     // ---- output layer + integration: every wave for itself (each keeps its own copy of the running position) ----
@@ -937,21 +881,11 @@ __global__ __launch_bounds__(256) void wide_dec_loop_fwd_kernel(WideDecFwd A) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int u0 = 16 * (2 * wave + k);
-        f32x4 gi, gf, gg, go, hn;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          gi[q] = sw_sigmoid(acc[k][q]);
-          gf[q] = sw_sigmoid(acc[2 + k][q]);
-          gg[q] = sw_tanh(acc[4 + k][q]);
-          go[q] = sw_sigmoid(acc[6 + k][q]);
-          c[k][q] = fmaf(gf[q], c[k][q], gi[q] * gg[q]);
-          hn[q] = go[q] * sw_tanh(c[k][q]);
-        }
+        const f32x4 pre[4] = {acc[k], acc[2 + k], acc[4 + k], acc[6 + k]};      // unit tile k's four gates: renaming, no move
+        f32x4 gate[4], hn;
+        lstm_gates(pre, gate, c[k], hn);
         st4(&hb[(i + 1) & 1][ln * HL + u0 + 4 * lg], hn);
-        st4(gr + u0, gi);
-        st4(gr + H + u0, gf);
-        st4(gr + 2 * H + u0, gg);
-        st4(gr + 3 * H + u0, go);
+        st_gates4(gr + u0, H, gate);
         st4(A.cs + trow * H + u0 + 4 * lg, c[k]);
         st4(A.hs + ((size_t)(To + i + 1) * B + b) * H + u0 + 4 * lg, hn);
         st4(A.cat + ((size_t)(i + 1) * B + b) * D1 + u0 + 4 * lg, hn);
@@ -1027,34 +961,14 @@ __global__ __launch_bounds__(256) void wide_dec_loop_bwd_kernel(WideDecBwd A) {
       for (int k = 0; k < 2; ++k) {
         const int u0 = 16 * tu[k];
         const float* gr = A.gates + ((size_t)t * B + b) * K4 + u0 + 4 * lg;
-        const f32x4 gi = ld4(gr), gf = ld4(gr + H), gg = ld4(gr + 2 * H), go = ld4(gr + 3 * H);
+        const f32x4 gate[4] = {ld4(gr), ld4(gr + H), ld4(gr + 2 * H), ld4(gr + 3 * H)};
         const f32x4 ct = ld4(A.cs + ((size_t)t * B + b) * H + u0 + 4 * lg), cp = ld4(A.cs + ((size_t)(t - 1) * B + b) * H + u0 + 4 * lg);
-        f32x4 di, df, dg, dO;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float tc = sw_tanh(ct[q]);
-          const float dct = fmaf(dh[k][q] * go[q], 1.0f - tc * tc, dc[k][q]);
-          di[q] = dct * gg[q] * gi[q] * (1.0f - gi[q]);
-          df[q] = dct * cp[q] * gf[q] * (1.0f - gf[q]);
-          dg[q] = dct * gi[q] * (1.0f - gg[q] * gg[q]);
-          dO[q] = dh[k][q] * tc * go[q] * (1.0f - go[q]);
-          dc[k][q] = dct * gf[q];
-        }
-        float* tr = cur + ln * GL + u0 + 4 * lg;
-        st4(tr, di);
-        st4(tr + H, df);
-        st4(tr + 2 * H, dg);
-        st4(tr + 3 * H, dO);
+        f32x4 dgate[4];
+        lstm_cell_bwd(gate, ct, cp, dh[k], dc[k], dgate);
+        st_gates4(cur + ln * GL + u0 + 4 * lg, H, dgate);
       }
       sw_barrier();
-      // dgates_t rows to memory from the tile (a wave writes 4 agents' rows, consecutive lanes consecutive float4s) ...
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int a = 4 * wave + q, bb = min(a0 + a, B - 1);
-#pragma unroll
-        for (int c4 = 0; c4 < K4 / 4 / 64; ++c4)
-          st4(A.dgates + ((size_t)t * B + bb) * K4 + 4 * (lane + 64 * c4), ld4(cur + a * GL + 4 * (lane + 64 * c4)));
-      }
+      dg_tile_store<K4>(cur, A.dgates + (size_t)t * B * K4, a0, B, wave, lane);      // dgates_t rows to memory from the tile ...
       // ... and dx4 = dgates Wx: this wave's quarter of the 4H columns (8 k-steps of the one WxT row tile)
       {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -1083,8 +997,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_bwd_kernel(WideDecBwd A) {
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = fmaf(dvx, w4[0][j][q], dvy * w4[1][j][q]);
-        st4(&dz3b[ln * L3 + 20 * lg + 4 * j], v);
-        st4(zr + 4 * j, v);
+        st_tile_row(&dz3b[ln * L3 + 20 * lg], zr, 4 * j, v);
       }
     }
     sw_barrier();
@@ -1096,8 +1009,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_bwd_kernel(WideDecBwd A) {
       for (int t = 0; t < 3; ++t) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[t][q] = sw_lrelu_grad(s2[t][q], acc[t][q]);
-        st4(&dz2b[ln * L2 + 16 * t2[t] + 4 * lg], acc[t]);
-        st4(A.dz2 + ((size_t)i * B + b) * D2 + 16 * t2[t] + 4 * lg, acc[t]);
+        st_tile_row(&dz2b[ln * L2 + 4 * lg], A.dz2 + ((size_t)i * B + b) * D2 + 4 * lg, 16 * t2[t], acc[t]);
       }
     }
     sw_barrier();
@@ -1111,8 +1023,7 @@ __global__ __launch_bounds__(256) void wide_dec_loop_bwd_kernel(WideDecBwd A) {
       for (int t = 0; t < 5; ++t) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[t][q] = sw_lrelu_grad(s1[t][q], acc[t][q]);
-        st4(&dz1b[ln * L1 + 16 * t1[t] + 4 * lg], acc[t]);
-        st4(A.dz1 + ((size_t)i * B + b) * D1 + 16 * t1[t] + 4 * lg, acc[t]);
+        st_tile_row(&dz1b[ln * L1 + 4 * lg], A.dz1 + ((size_t)i * B + b) * D1 + 4 * lg, 16 * t1[t], acc[t]);
       }
     }
     sw_barrier();
@@ -1216,14 +1127,12 @@ __global__ __launch_bounds__(256) void wide_disc_heads_fwd_kernel(WideHeads A) {
     f32x4 acc = wh_tile(A.of0, t, H >> 4, hTb + ln * LH + 4 * lg, ld4(A.b_of0 + 16 * t + 4 * lg), lane);
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = sw_lrelu(acc[q]);
-    st4(o1b + ln * L2 + 16 * t + 4 * lg, acc);
-    st4(A.o1 + (size_t)b * H2 + 16 * t + 4 * lg, acc);
+    st_tile_row(o1b + ln * L2, A.o1 + (size_t)b * H2, 16 * t + 4 * lg, acc);
     for (int br = 0; br < nb; ++br) {
       f32x4 aq = wh_tile(A.pe0, t, K4 >> 4, pxb + (br * 16 + ln) * LK + 4 * lg, ld4(A.b_pe0 + 16 * t + 4 * lg), lane);
 #pragma unroll
       for (int q = 0; q < 4; ++q) aq[q] = sw_lrelu(aq[q]);
-      st4(q1b + (br * 16 + ln) * L2 + 16 * t + 4 * lg, aq);
-      st4(A.q1 + ((size_t)br * B + b) * H2 + 16 * t + 4 * lg, aq);
+      st_tile_row(q1b + (br * 16 + ln) * L2, A.q1 + ((size_t)br * B + b) * H2, 16 * t + 4 * lg, aq);
     }
   }
   __syncthreads();
@@ -1232,11 +1141,9 @@ __global__ __launch_bounds__(256) void wide_disc_heads_fwd_kernel(WideHeads A) {
     const f32x4 oc = wh_tile(A.of1, t, H2 >> 4, o1b + ln * L2 + 4 * lg, ld4(A.b_of1 + 16 * t + 4 * lg), lane);
     for (int br = 0; br < nb; ++br) {
       const f32x4 pc = wh_tile(A.pe1, t, H2 >> 4, q1b + (br * 16 + ln) * L2 + 4 * lg, ld4(A.b_pe1 + 16 * t + 4 * lg), lane);
-      st4(bob + (br * 16 + ln) * LH + 16 * t + 4 * lg, oc);
-      st4(bob + (br * 16 + ln) * LH + H2 + 16 * t + 4 * lg, pc);
-      float* g = A.both + ((size_t)br * B + b) * H + 16 * t + 4 * lg;
-      st4(g, oc);
-      st4(g + H2, pc);
+      float* g = A.both + ((size_t)br * B + b) * H;
+      st_tile_row(bob + (br * 16 + ln) * LH, g, 16 * t + 4 * lg, oc);
+      st_tile_row(bob + (br * 16 + ln) * LH, g, H2 + 16 * t + 4 * lg, pc);
     }
   }
   __syncthreads();
@@ -1251,10 +1158,8 @@ __global__ __launch_bounds__(256) void wide_disc_heads_fwd_kernel(WideHeads A) {
         ac[q] = sw_lrelu(ac[q]);
         al[q] = sw_lrelu(al[q]);
       }
-      st4(c1b + (br * 16 + ln) * L2 + 16 * t + 4 * lg, ac);
-      st4(l1b + (br * 16 + ln) * L2 + 16 * t + 4 * lg, al);
-      st4(A.c1 + ((size_t)br * B + b) * H2 + 16 * t + 4 * lg, ac);
-      st4(A.l1 + ((size_t)br * B + b) * H2 + 16 * t + 4 * lg, al);
+      st_tile_row(c1b + (br * 16 + ln) * L2, A.c1 + ((size_t)br * B + b) * H2, 16 * t + 4 * lg, ac);
+      st_tile_row(l1b + (br * 16 + ln) * L2, A.l1 + ((size_t)br * B + b) * H2, 16 * t + 4 * lg, al);
     }
   __syncthreads();
   // ---- label = cl1 c1 + b (1 output), code = la1 l1 + b (nl outputs): dot products, 8 threads per (branch, agent) ----
@@ -1359,8 +1264,7 @@ __global__ __launch_bounds__(256) void wide_disc_heads_bwd_kernel(WideHeads A) {
     for (int br = 0; br < nb; ++br) {
       f32x4 acc = wh_tile(A.cl0, t, H2 >> 4, dc1b + (br * 16 + ln) * L2 + 4 * lg, f32x4{0.f, 0.f, 0.f, 0.f}, lane);
       acc = wh_tile(A.la0, t, H2 >> 4, dl1b + (br * 16 + ln) * L2 + 4 * lg, acc, lane);
-      st4(dbob + (br * 16 + ln) * LH + 16 * t + 4 * lg, acc);
-      st4(A.dboth + ((size_t)br * B + b) * H + 16 * t + 4 * lg, acc);
+      st_tile_row(dbob + (br * 16 + ln) * LH, A.dboth + ((size_t)br * B + b) * H, 16 * t + 4 * lg, acc);
     }
   __syncthreads();
   // ---- dq1 = (pe1^T dpcode) lrelu'(q1); docode = sum over the branches of dboth[:, :H2] ----
@@ -1370,14 +1274,12 @@ __global__ __launch_bounds__(256) void wide_disc_heads_bwd_kernel(WideHeads A) {
       const f32x4 qv = ld4(A.q1 + ((size_t)br * B + b) * H2 + 16 * t + 4 * lg);
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[q] = sw_lrelu_grad(qv[q], acc[q]);
-      st4(dq1b + (br * 16 + ln) * L2 + 16 * t + 4 * lg, acc);
-      st4(A.dq1 + ((size_t)br * B + b) * H2 + 16 * t + 4 * lg, acc);
+      st_tile_row(dq1b + (br * 16 + ln) * L2, A.dq1 + ((size_t)br * B + b) * H2, 16 * t + 4 * lg, acc);
     }
     if (A.need_obs) {
       f32x4 v = ld4(dbob + ln * LH + 16 * t + 4 * lg);
       if (nb > 1) v = v + ld4(dbob + (16 + ln) * LH + 16 * t + 4 * lg);
-      st4(docb + ln * L2 + 16 * t + 4 * lg, v);
-      st4(A.docode + (size_t)b * H2 + 16 * t + 4 * lg, v);
+      st_tile_row(docb + ln * L2, A.docode + (size_t)b * H2, 16 * t + 4 * lg, v);
     }
   }
   __syncthreads();
@@ -1388,8 +1290,7 @@ __global__ __launch_bounds__(256) void wide_disc_heads_bwd_kernel(WideHeads A) {
       const f32x4 ov = ld4(A.o1 + (size_t)b * H2 + 16 * t + 4 * lg);
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[q] = sw_lrelu_grad(ov[q], acc[q]);
-      st4(do1b + ln * L2 + 16 * t + 4 * lg, acc);
-      st4(A.do1 + (size_t)b * H2 + 16 * t + 4 * lg, acc);
+      st_tile_row(do1b + ln * L2, A.do1 + (size_t)b * H2, 16 * t + 4 * lg, acc);
     }
   if (A.want_dpred)
     for (int t = wave; t < (K4 >> 4); t += 4) {
@@ -1507,12 +1408,14 @@ extern "C" int sw_wide_lstm_seq_fwd(const float* x4, const float* Wx, const floa
   if (!x4 || !Wx || !b1 || !whh_img || !gates || !cs || !hs || B < 1 || T < 1 || (h_last2 && (h2_ld < H || (h2_ld & 3)))) return SW_EARG;
   if (!sw_wide_lstm_seq_supported(H)) return SW_ESHAPE;
   const dim3 grid((B + 15) / 16), block(256);
-  if (H == 64)
-    SW_LAUNCH((wide_lstm_seq_fwd_kernel<1>), grid, block, 0, (hipStream_t)stream, x4, Wx, b1, b2, whh_img, B, T, gates, cs, hs, h_last2,
-              h2_ld);
-  else
-    SW_LAUNCH((wide_lstm_seq_fwd_kernel<2>), grid, block, 0, (hipStream_t)stream, x4, Wx, b1, b2, whh_img, B, T, gates, cs, hs, h_last2,
-              h2_ld);
+#define WIDE_SEQ_FWD(NU) \
+  SW_LAUNCH((wide_lstm_seq_fwd_kernel<NU>), grid, block, 0, (hipStream_t)stream, x4, Wx, b1, b2, whh_img, B, T, gates, cs, hs, h_last2, h2_ld)
+  if (H == 64) {
+    WIDE_SEQ_FWD(1);
+  } else {
+    WIDE_SEQ_FWD(2);
+  }
+#undef WIDE_SEQ_FWD
   SW_CHECK_LAUNCH("wide_lstm_seq_fwd_kernel");
   return SW_OK;
 }
@@ -1525,12 +1428,15 @@ extern "C" int sw_wide_lstm_seq_bwd(const float* dh_ext, int dhe_ld, const float
     return SW_EARG;
   if (!sw_wide_lstm_seq_supported(H)) return SW_ESHAPE;
   const dim3 grid((B + 15) / 16), block(256);
-  if (H == 64)
-    SW_LAUNCH((wide_lstm_seq_bwd_kernel<1>), grid, block, 0, (hipStream_t)stream, dh_ext, dhe_ld, dh_ext2, dhe2_ld, dg_init, dc_init,
-              whhT_img, gates, cs, B, T, dgates);
-  else
-    SW_LAUNCH((wide_lstm_seq_bwd_kernel<2>), grid, block, 0, (hipStream_t)stream, dh_ext, dhe_ld, dh_ext2, dhe2_ld, dg_init, dc_init,
-              whhT_img, gates, cs, B, T, dgates);
+#define WIDE_SEQ_BWD(NU)                                                                                                          \
+  SW_LAUNCH((wide_lstm_seq_bwd_kernel<NU>), grid, block, 0, (hipStream_t)stream, dh_ext, dhe_ld, dh_ext2, dhe2_ld, dg_init, dc_init, \
+            whhT_img, gates, cs, B, T, dgates)
+  if (H == 64) {
+    WIDE_SEQ_BWD(1);
+  } else {
+    WIDE_SEQ_BWD(2);
+  }
+#undef WIDE_SEQ_BWD
   SW_CHECK_LAUNCH("wide_lstm_seq_bwd_kernel");
   return SW_OK;
 }
@@ -1608,12 +1514,15 @@ extern "C" int sw_wide_lstm_bwd(const float* dh_ext, int dhe_ld, const float* dh
       (dh_ext && (dhe_ld < H || (dhe_ld & 3))) || (dh_ext2 && (dhe2_ld < H || (dhe2_ld & 3))))
     return SW_EARG;
   const int nub = (H + 63) / 64;
-  if (((B + 31) / 32) * nub >= 512)      // enough workgroups for the chip at 32 agents each
-    SW_LAUNCH((wide_lstm_bwd_kernel<2>), dim3((unsigned)(((B + 31) / 32) * nub)), dim3(256), 0, (hipStream_t)stream, dh_ext, dhe_ld,
-              dh_ext2, dhe2_ld, dg_next, WhhT, gates, c, c_prev, dc_in, B, H, dgates, dc_out);
-  else
-    SW_LAUNCH((wide_lstm_bwd_kernel<1>), dim3((unsigned)(((B + 15) / 16) * nub)), dim3(256), 0, (hipStream_t)stream, dh_ext, dhe_ld,
-              dh_ext2, dhe2_ld, dg_next, WhhT, gates, c, c_prev, dc_in, B, H, dgates, dc_out);
+#define WIDE_LSTM_BWD(AT)                                                                                                        \
+  SW_LAUNCH((wide_lstm_bwd_kernel<AT>), dim3((unsigned)(((B + 16 * AT - 1) / (16 * AT)) * nub)), dim3(256), 0, (hipStream_t)stream, \
+            dh_ext, dhe_ld, dh_ext2, dhe2_ld, dg_next, WhhT, gates, c, c_prev, dc_in, B, H, dgates, dc_out)
+  if (((B + 31) / 32) * nub >= 512) {      // enough workgroups for the chip at 32 agents each
+    WIDE_LSTM_BWD(2);
+  } else {
+    WIDE_LSTM_BWD(1);
+  }
+#undef WIDE_LSTM_BWD
   SW_CHECK_LAUNCH("wide_lstm_bwd_kernel");
   return SW_OK;
 }

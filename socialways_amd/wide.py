@@ -315,6 +315,21 @@ class WideTrainer(GenericTrainer):
                 arr[10 * i + j] = 0 if v is None else (int(v) if isinstance(v, (int, np.integer)) else v.data_ptr())
         L.call("sw_wide_wgrad", ctypes.cast(arr, ctypes.c_void_p), len(problems), L.ptr(w["wgrad"]), L.stream())
 
+    def _lstm_step_fwd(self, t, B, x4, hs, cs, gates, Wx, b1, b2, whh, h2=None, h2_ld=0):
+        """Step t of an LSTM as one launch (sw_wide_lstm_fwd): h_{t-1} = hs[t] and c_{t-1} from step 1 on, h_t also to h2."""
+        H = self.H
+        L.call("sw_wide_lstm_fwd", L.ptr(x4[t]), 4, L.ptr(hs[t]) if t > 0 else None, H, L.ptr(cs[t - 1]) if t > 0 else None,
+               L.ptr(Wx), L.ptr(b1), L.ptr(b2), L.ptr(whh), B, H, L.ptr(gates[t]), L.ptr(cs[t]), L.ptr(hs[t + 1]), H, _p(h2), h2_ld,
+               L.stream())
+
+    def _lstm_step_bwd(self, t, T, B, whhT, gates, cs, dg, dc, dh_ext, dhe_ld, dh_ext2=None, dhe2_ld=0):
+        """Backward of step t of a T-step LSTM as one launch (sw_wide_lstm_bwd).  Behind the last step nothing follows: from
+        step T - 2 down dgates of step t + 1 feed dh through W_hh^T and dc, rewritten by every step, comes in as d c_t."""
+        more = t + 1 < T
+        L.call("sw_wide_lstm_bwd", _p(dh_ext), dhe_ld, _p(dh_ext2), dhe2_ld, L.ptr(dg[t + 1]) if more else None, L.ptr(whhT),
+               L.ptr(gates[t]), L.ptr(cs[t]), L.ptr(cs[t - 1]) if t > 0 else None, L.ptr(dc) if more else None, B, self.H,
+               L.ptr(dg[t]), L.ptr(dc), L.stream())
+
     def _gen_forward(self, w, sc, B, To):
         """predict() (train.py:392-432): observation encoding, social pooling, Tp decode steps with the re-fed encoder."""
         H, Tp, st = self.H, self.n_next, L.stream()
@@ -334,19 +349,14 @@ class WideTrainer(GenericTrainer):
             L.call("sw_wide_opimage", L.ptr(self._wxT16), L.ptr(self._wxT_tab), 1, 16 * 4 * H // 4, L.ptr(self._wxT_img), st)
         x4, hs, cs, gates, cat = w["x4"], w["hs"], w["cs"], w["gates"], w["cat"]
         x4[:To].copy_(w["o4"].transpose(0, 1))
-
-        def lstm(t, h2=None, h2_ld=0):
-            L.call("sw_wide_lstm_fwd", L.ptr(x4[t]), 4, L.ptr(hs[t]) if t > 0 else None, H, L.ptr(cs[t - 1]) if t > 0 else None,
-                   L.ptr(w["Wx"]), L.ptr(w["bxc"]), L.ptr(enc.lstm.bias_hh_l0), L.ptr(whh), B, H, L.ptr(gates[t]),
-                   L.ptr(cs[t]), L.ptr(hs[t + 1]), H, _p(h2), h2_ld, st)
-
+        step = (B, x4, hs, cs, gates, w["Wx"], w["bxc"], enc.lstm.bias_hh_l0, whh)
         if self.seq:
             self._images(self._gI_args)
             L.call("sw_wide_lstm_seq_fwd", L.ptr(x4), L.ptr(w["Wx"]), L.ptr(w["bxc"]), L.ptr(enc.lstm.bias_hh_l0), L.ptr(self.gI["whh"]),
                    B, H, To, L.ptr(gates), L.ptr(cs), L.ptr(hs), L.ptr(cat[0]), D1, st)
         else:
             for t in range(To):
-                lstm(t, cat[0] if t == To - 1 else None, D1)
+                self._lstm_step_fwd(t, *step, cat[0] if t == To - 1 else None, D1)
         hT = hs[To]
         if G.use_social and sc.P > 0:
             if sc.NB:
@@ -381,7 +391,7 @@ class WideTrainer(GenericTrainer):
             L.call("sw_wide_out_fwd", L.ptr(w["a3"][i]), D3, L.ptr(dec[5].weight), L.ptr(dec[5].bias), L.ptr(w["pcur"]), B,
                    _off(w["pred4"], 4 * i), 4 * Tp, L.ptr(x4[To + i]), st)
             if i + 1 < Tp:                      # the step after the last decode is dead compute (train.py:430)
-                lstm(To + i, cat[i + 1], D1)
+                self._lstm_step_fwd(To + i, *step, cat[i + 1], D1)
         return w["pred4"]
 
     def _gen_backward(self, w, sc, B, To, dpred4):
@@ -398,27 +408,18 @@ class WideTrainer(GenericTrainer):
         gT = self.gT
         gates, cs, hs, dg = w["gates"], w["cs"], w["hs"], w["dgates"]
         w["dprun"].zero_()
-        have_dc = False
-
-        def lstm_bwd(t, dh_ext, dhe_ld, dh_ext2=None, dhe2_ld=0):
-            nonlocal have_dc
-            L.call("sw_wide_lstm_bwd", _p(dh_ext), dhe_ld, _p(dh_ext2), dhe2_ld, L.ptr(dg[t + 1]) if t + 1 < Ta else None,
-                   L.ptr(gT["whh"]), L.ptr(gates[t]), L.ptr(cs[t]), L.ptr(cs[t - 1]) if t > 0 else None,
-                   L.ptr(w["dc"]) if have_dc else None, B, H, L.ptr(dg[t]), L.ptr(w["dc"]), st)
-            have_dc = True
-
+        step = (Ta, B, gT["whh"], gates, cs, dg, w["dc"])
         if self.decloop:
             gI = self.gI
             L.call("sw_wide_dec_loop_bwd", L.ptr(gI["whhT"]), L.ptr(gI["w3T"]), L.ptr(gI["w2T"]), L.ptr(gI["w1hT"]), L.ptr(self._wxT_img),
                    L.ptr(dec[5].weight), L.ptr(dpred4), L.ptr(w["a1"]), L.ptr(w["a2"]), L.ptr(gates), L.ptr(cs), L.ptr(dg), L.ptr(w["dv"]),
                    L.ptr(w["dz3"]), L.ptr(w["dz2"]), L.ptr(w["dz1"]), L.ptr(w["dhcat"]), L.ptr(w["dc"]), B, H, To, Tp, st)
-            have_dc = Tp > 1
         for i in range(-1 if self.decloop else Tp - 1, -1, -1):
             t_in = To + i                      # the LSTM step that consumed x4 = (p_i, v_i)
             dgt = None
             if i + 1 < Tp:
                 # h of step t_in feeds decode step i + 1 (dhcat) and LSTM step t_in + 1 (dgates of t_in + 1)
-                lstm_bwd(t_in, w["dhcat"], H)
+                self._lstm_step_bwd(t_in, *step, w["dhcat"], H)
                 dgt = dg[t_in]
             # dx4 = dgates Wx, the position / velocity chain and dz3 = dv W4 (fc4: linear, no activation) in one launch
             L.call("sw_wide_out_bwd", _off(dpred4, 4 * i), 4 * Tp, _p(dgt), L.ptr(w["WxT"]), 4 * H, L.ptr(w["dprun"]), B,
@@ -453,13 +454,13 @@ class WideTrainer(GenericTrainer):
         # observation steps: h_{To-1} feeds decode step 0 (dhcat), LSTM step To (dgates of To) and the social block
         if self.seq:
             L.call("sw_wide_lstm_seq_bwd", L.ptr(w["dhcat"]), H, _p(dh2), dh2_ld, L.ptr(dg[To]) if To < Ta else None,
-                   L.ptr(w["dc"]) if have_dc else None, L.ptr(self.gI["whhT"]), L.ptr(gates), L.ptr(cs), B, H, To, L.ptr(dg), st)
+                   L.ptr(w["dc"]) if To < Ta else None, L.ptr(self.gI["whhT"]), L.ptr(gates), L.ptr(cs), B, H, To, L.ptr(dg), st)
         else:
             for t in range(To - 1, -1, -1):
                 if t == To - 1:
-                    lstm_bwd(t, w["dhcat"], H, dh2, dh2_ld)
+                    self._lstm_step_bwd(t, *step, w["dhcat"], H, dh2, dh2_ld)
                 else:
-                    lstm_bwd(t, None, 0)
+                    self._lstm_step_bwd(t, *step, None, 0)
         # weight gradients: LSTM (W_hh against h_{t-1}: hs[t], zero slab first; the composed input matrix against x4)
         problems += [(dg, 4 * H, hs, H, Ta * B, 4 * H, H, gp.g(whh), H, gp.g(enc.lstm.bias_hh_l0)),
                      (dg, 4 * H, w["x4"], 4, Ta * B, 4 * H, 4, w["dWx"], 4, w["dbx"]),
@@ -490,9 +491,7 @@ class WideTrainer(GenericTrainer):
             L.call("sw_wide_lstm_seq_fwd", L.ptr(x4), L.ptr(lstm.weight_ih_l0), L.ptr(lstm.bias_ih_l0), L.ptr(lstm.bias_hh_l0),
                    L.ptr(self.dI["whh"]), B, H, To, L.ptr(gates), L.ptr(cs), L.ptr(hs), None, 0, st)
         for t in range(0 if self.seq else To):
-            L.call("sw_wide_lstm_fwd", L.ptr(x4[t]), 4, L.ptr(hs[t]) if t > 0 else None, H, L.ptr(cs[t - 1]) if t > 0 else None,
-                   L.ptr(lstm.weight_ih_l0), L.ptr(lstm.bias_ih_l0), L.ptr(lstm.bias_hh_l0), L.ptr(lstm.weight_hh_l0), B, H,
-                   L.ptr(gates[t]), L.ptr(cs[t]), L.ptr(hs[t + 1]), H, None, 0, st)
+            self._lstm_step_fwd(t, B, x4, hs, cs, gates, lstm.weight_ih_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, lstm.weight_hh_l0)
         of, pe, cl, la = D.obsv_encoder_fc, D.pred_encoder, D.classifier, D.latent_decoder
         R = nb * B
         if self.heads:
@@ -570,10 +569,7 @@ class WideTrainer(GenericTrainer):
             L.call("sw_wide_lstm_seq_bwd", L.ptr(w["d_dhT"]), H, None, 0, None, None, L.ptr(self.dI["whhT"]), L.ptr(gates), L.ptr(cs),
                    B, H, To, L.ptr(dg), st)
         for t in range(-1 if self.seq else To - 1, -1, -1):
-            L.call("sw_wide_lstm_bwd", L.ptr(w["d_dhT"]) if t == To - 1 else None, H, None, 0,
-                   L.ptr(dg[t + 1]) if t + 1 < To else None, L.ptr(dT["whh"]), L.ptr(gates[t]), L.ptr(cs[t]),
-                   L.ptr(cs[t - 1]) if t > 0 else None, L.ptr(w["d_dc"]) if t + 1 < To else None, B, H, L.ptr(dg[t]),
-                   L.ptr(w["d_dc"]), st)
+            self._lstm_step_bwd(t, To, B, dT["whh"], gates, cs, dg, w["d_dc"], w["d_dhT"] if t == To - 1 else None, H)
         g = dp.g
         R = 2 * B
         self._wgrad(w, [
