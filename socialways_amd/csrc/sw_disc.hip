@@ -325,7 +325,9 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     for (int t = 0; t < 8; ++t) {
       const float xb = xa - (lg >= 2 ? xq : 0.f);
       obs_x4_load(obsv, b, t + 1 < 8 ? t + 1 : 7, 8, lg, xa, xq);
-      lstm_cell(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], sg[t], c, h);
+      const float* hrow = &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg];
+      if (t == 0) lstm_cell<false>(W, xb, hrow, sg[t], c, h);     // from h = 0: no recurrent products (unrolled: no branch)
+      else lstm_cell(W, xb, hrow, sg[t], c, h);
       sc[t] = c;
       st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
       st4g(hrow_g, h);

@@ -75,11 +75,11 @@ __global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_kernel(
   asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE: the loop header must see no pending load on any path in
   float* yrow = Y ? y + (size_t)b * T * 64 + u0 + 4 * lg : nullptr;
   float* xrow = X4S ? x4s + ((size_t)t0 * B + b) * 4 + lg : nullptr;
-  for (int t = 0; t < T; ++t) {
+  auto step = [&](int t, auto hp) {
     const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
     load_x(min(t + 1, T - 1));
     f32x4 gate[4];
-    lstm_cell(W, xb, &hbuf[t & 1][ln * HS + HO + 4 * lg], gate, c, h);
+    lstm_cell<decltype(hp)::value>(W, xb, &hbuf[t & 1][ln * HS + HO + 4 * lg], gate, c, h);
     if constexpr (ACT) lstm_put_act_tile(hbuf[(t + 1) & 1], gate, c, h, ln, lg, u0);
     else st4(&hbuf[(t + 1) & 1][ln * HS + u0 + 4 * lg], h);
     if constexpr (Y) {
@@ -93,7 +93,13 @@ __global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_kernel(
     sw_barrier();
     if constexpr (ACT) lstm_store_act_tile(hbuf[(t + 1) & 1], act + (size_t)(t0 + t) * B * 384, a0, B, wave, lane);
     asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
-  }
+  };
+  // Step 0 is peeled.  Without h0 it starts from h = 0 and issues only Wx x + b: no recurrent products, no read of the
+  // zeroed h tile.  h0 is a kernel argument (a uniform branch), and both sides issue the same global loads and stores in
+  // the same order, so the loop header sees one count of operations in flight whichever way it was reached.
+  if (h0) step(0, std::true_type{});
+  else step(0, std::false_type{});
+  for (int t = 1; t < T; ++t) step(t, std::true_type{});
   st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
   st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
 }
@@ -146,21 +152,23 @@ __global__ __launch_bounds__(512) void enc_lstm_fwd8_kernel(
   obs_x4_load(x, b, 0, T, lg, xa, xq);
   asm volatile("" : "+v"(xa), "+v"(xq));
   float* xrow = x4s + ((size_t)t0 * B + b) * 4 + lg;
-  for (int t = 0; t < T; ++t) {
+  auto step = [&](int t, auto hp) {
     const float xb = xa - (lg >= 2 ? xq : 0.f);
     obs_x4_load(x, b, min(t + 1, T - 1), T, lg, xa, xq);
-    const float* hrow = &hbuf[t & 1][ln * SW_ALD + 320 + 4 * lg];
-    f32x4 bq[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bq[j] = ld4(hrow + 16 * j);
     f32x4 acc0 = SW_MFMA(wx[0], xb, bias[0]), acc1 = SW_MFMA(wx[1], xb, bias[1]);
+    if constexpr (decltype(hp)::value) {     // (false: the step starts from h = 0 - neither the h tile nor W_hh is touched)
+      const float* hrow = &hbuf[t & 1][ln * SW_ALD + 320 + 4 * lg];
+      f32x4 bq[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j) bq[j] = ld4(hrow + 16 * j);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc0 = SW_MFMA(whh[0][j][r], bq[j][r], acc0);
-        acc1 = SW_MFMA(whh[1][j][r], bq[j][r], acc1);
-      }
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc0 = SW_MFMA(whh[0][j][r], bq[j][r], acc0);
+          acc1 = SW_MFMA(whh[1][j][r], bq[j][r], acc1);
+        }
+    }
     float2 gi, gf, gg, go;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
@@ -191,7 +199,10 @@ __global__ __launch_bounds__(512) void enc_lstm_fwd8_kernel(
       }
     }
     asm volatile("" : "+v"(xa), "+v"(xq));
-  }
+  };
+  if (h0) step(0, std::true_type{});       // step 0 peeled, as in enc_lstm_fwd_kernel
+  else step(0, std::false_type{});
+  for (int t = 1; t < T; ++t) step(t, std::true_type{});
   *reinterpret_cast<float2*>(hT + (size_t)b * 64 + ub) = h;
   *reinterpret_cast<float2*>(cT + (size_t)b * 64 + ub) = c;
 }

@@ -8,6 +8,7 @@
 // the composition W_ih * W_embed (no non-linearity sits between embed and the LSTM,
 // train.py:266-268), for the discriminator W_ih itself.
 #pragma once
+#include <type_traits>
 #include "sw_common.h"
 
 #define SW_HLD 68    // LDS row stride of a 64-wide h tile
@@ -97,26 +98,31 @@ __device__ __forceinline__ void lstm_load_img(LstmW& W, const float* __restrict_
 
 // The products of one cell step for NB 16-agent tiles: acc[k][g] = Wx x_k + b + W_hh h_k (pre-activation rows of gate g),
 // every W_hh operand issued against the NB h tiles in turn.  xb[k] = x4[agent ln][component lg] of tile k;
-// hrow[k] = &h_lds_k[ln*ld + 4*lg] (previous h).
-template <int NB>
+// hrow[k] = &h_lds_k[ln*ld + 4*lg] (previous h).  HP = false: the step starts from h = 0 - W_hh h adds exact zeros, so
+// neither the 64 recurrent products nor the read of the (zeroed) h tile are issued: acc = Wx x + b.
+template <int NB, bool HP = true>
 __device__ __forceinline__ void lstm_products(const LstmW& W, const float (&xb)[NB], const float* const (&hrow)[NB],
                                               f32x4 (&acc)[NB][4]) {
   f32x4 b[NB][4];
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
+    if constexpr (HP) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) b[k][j] = ld4(hrow[k] + 16 * j);   // one LDS round trip for the whole step
+      for (int j = 0; j < 4; ++j) b[k][j] = ld4(hrow[k] + 16 * j);   // one LDS round trip for the whole step
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[k][g] = SW_MFMA(W.wx[g], xb[k], W.bias[g]);
   }
+  if constexpr (HP) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < 4; ++j) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < 4; ++r) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < 4; ++g) {
 #pragma unroll
-        for (int k = 0; k < NB; ++k) acc[k][g] = SW_MFMA(W.whh[g][j][r], b[k][j][r], acc[k][g]);
+          for (int k = 0; k < NB; ++k) acc[k][g] = SW_MFMA(W.whh[g][j][r], b[k][j][r], acc[k][g]);
+        }
       }
     }
   }
@@ -151,11 +157,12 @@ __device__ __forceinline__ void lstm_cell(const LstmW& W, const float (&xb)[NB],
 #pragma unroll
   for (int k = 0; k < NB; ++k) lstm_gates(acc[k], gate[k], c[k], h[k]);
 }
-// ... of one tile: xb = x4[agent ln][component lg]; hrow = &h_lds[ln*SW_HLD + 4*lg] (previous h).
+// ... of one tile: xb = x4[agent ln][component lg]; hrow = &h_lds[ln*SW_HLD + 4*lg] (previous h; HP = false: h = 0, not read).
+template <bool HP = true>
 __device__ __forceinline__ void lstm_cell(const LstmW& W, float xb, const float* hrow, f32x4 gate[4],
                                           f32x4& c, f32x4& h) {
   f32x4 acc[1][4];
-  lstm_products<1>(W, {xb}, {hrow}, acc);
+  lstm_products<1, HP>(W, {xb}, {hrow}, acc);
   lstm_gates(acc[0], gate, c, h);
 }
 
@@ -363,11 +370,12 @@ __device__ __forceinline__ float obs_x4(const float* pos, int b, int t, int T, i
   return a - (comp >= 2 ? q : 0.f);
 }
 
-// The time loop of an LSTM over a 4-d input sequence (h0 = c0 given in hbuf[0] / c) for the 16-agent tile of agent
-// row b (clamped), W loaded.  XMODE 0: x = positions [B][T][2]; 1: x = [B][T][4].  SAVE: per step t and agent b,
-// act + (t B + b) 384 = gates i|f|g|o [256], c [64], h [64] and the step's input at x4s + (t B + b) 4.  No
-// conditional memory operation inside (see enc_lstm_fwd_kernel); padding lanes of the last tile are replicas of
-// agent B-1.  On return h_T sits in hbuf[T & 1].
+// The time loop of an LSTM over a 4-d input sequence FROM THE ZERO STATE (c = h = 0 on entry; every caller is the
+// discriminator's observation pass, train.py:296-297) for the 16-agent tile of agent row b (clamped), W loaded.  XMODE 0:
+// x = positions [B][T][2]; 1: x = [B][T][4].  SAVE: per step t and agent b, act + (t B + b) 384 = gates i|f|g|o [256],
+// c [64], h [64] and the step's input at x4s + (t B + b) 4.  Step 0 is peeled and issues only Wx x + b (lstm_products
+// with HP = false): hbuf[0] is not read.  No conditional memory operation inside (see enc_lstm_fwd_kernel); padding
+// lanes of the last tile are replicas of agent B-1.  On return h_T sits in hbuf[T & 1].
 template <int XMODE, bool SAVE>
 __device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int B, int b,
                                               f32x4& c, f32x4& h, float* __restrict__ act, float* __restrict__ x4s) {
@@ -382,11 +390,11 @@ __device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const
   asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE: the loop header must see no pending load on any path in
   float* arow = SAVE ? act + (size_t)b * 384 + u0 + 4 * lg : nullptr;
   float* xrow = SAVE ? x4s + (size_t)b * 4 + lg : nullptr;
-  for (int t = 0; t < T; ++t) {
+  auto step = [&](int t, auto hp) {
     const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
     load_x(min(t + 1, T - 1));   // the input of step t+1 is fetched while step t computes
     f32x4 gate[4];
-    lstm_cell(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], gate, c, h);
+    lstm_cell<decltype(hp)::value>(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], gate, c, h);
     st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
     if constexpr (SAVE) {
 #pragma unroll
@@ -399,7 +407,9 @@ __device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const
     }
     sw_barrier();
     asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
-  }
+  };
+  step(0, std::false_type{});
+  for (int t = 1; t < T; ++t) step(t, std::true_type{});
 }
 
 // ---- ragged observation histories (sw_enc_lstm_fwd_ragged, sw_disc_score_ragged) ---------------------------------------

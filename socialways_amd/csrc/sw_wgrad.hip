@@ -26,9 +26,9 @@
 // SIMDs hold 4 such waves.  Each delta element is read once per column block, each act element once
 // per 64-row output block: L2 traffic, not HBM (the rows were written microseconds earlier).
 // Branch-free streaming body, specialised on the tile counts (NI output-row tiles x KT column tiles of
-// this wave's 64x64 block): loads are unconditional from clamped addresses and masked by a 0/1
-// factor, so the hot loop is NI+KT loads, a few multiplies and NI*KT MFMAs - no exec-mask branches,
-// no accumulator shuffling through control flow.
+// this wave's 64x64 block): loads are unconditional buffer loads bounded by the wave's row slice
+// (rows outside it read zero), so the hot loop is one load and one offset add per operand and NI*KT
+// MFMAs - no clamps, no masks, no exec-mask branches, no accumulator shuffling through control flow.
 // workgroups that carry jobs: the job count padded to whole rounds of 8 XCDs x chunks of 4 (see the kernel)
 __host__ __device__ inline int wg_grid_jobs(int total_jobs) { return (total_jobs + 31) & ~31; }
 #ifdef SW_WG_STAMP      // timing experiment (tools/build_variant.sh): start / end of every workgroup of the last launch
@@ -161,10 +161,19 @@ bool wg_shape_ok(int N, int K) {   // every 64-column block of delta / act must 
   return K == 0 || wg_tiles(K, true) != 0;
 }
 
+// The kernel addresses a wave's row slice by 32-bit BYTE offsets from the slice's first row (buffer loads, sw_wgrad_dev.h).
+// A slice has at most R / 4 + 4 rows (4 waves per workgroup, at least one workgroup per output block, rounded up to a
+// 4-row group); the prefetch runs up to 8 groups past its end, and the `act` offsets of rows below row0 start up to
+// row0 rows in front of the descriptor and must wrap OUT of range.  All of that stays below 2^31 bytes.
+static bool wg_span_ok(int R, int ld, int row0) {
+  const long long rows = (long long)R / 4 + 4 + 8 * 4 * SW_WG_DEPTH + row0;
+  return rows * ld * 4 < (1LL << 31);
+}
+
 int wg_add(WgBatch& b, const float* delta, int ldd, const float* act, int lda, int R, int N, int K, float* dW,
            int ldw, float* db, float* db2, int accumulate) {
   if (N > 256 || (ldd & 3) || (lda & 3)) return SW_ESHAPE;
-  if ((long long)R * ldd >= (1LL << 31) || (long long)R * lda >= (1LL << 31)) return SW_ESHAPE;   // 32-bit element offsets in the kernel
+  if (!wg_span_ok(R, ldd, 0) || !wg_span_ok(R, lda, 0)) return SW_ESHAPE;
   // column blocks of <= 64 REAL act columns; the ones column (bias gradient) rides with the last block on the VALU
   // (it used to open a block of its own whenever K was a multiple of 64: every delta row read again for a row sum)
   if (K < 1) return SW_ESHAPE;
@@ -200,7 +209,7 @@ int wg_add_tail(WgBatch& b, const float* delta, int ldd, const float* act, int l
                 int accumulate) {
   if (N > 256 || (ldd & 3) || (lda & 3) || (lda2 & 3) || K != 64 || K2 != 4 || b.np >= SW_WG_MAXP)   // the tail runs on the
     return SW_ESHAPE;                                                                                  // VALU: 4 columns, float4 rows
-  if ((long long)R * ldd >= (1LL << 31) || (long long)R * lda >= (1LL << 31) || (long long)R * lda2 >= (1LL << 31)) return SW_ESHAPE;
+  if (row0 < 0 || !wg_span_ok(R, ldd, 0) || !wg_span_ok(R, lda, row0) || !wg_span_ok(R, lda2, 0)) return SW_ESHAPE;
   WgProblem& P = b.p[b.np++];
   P.delta = delta; P.ldd = ldd; P.act = act; P.lda = lda; P.R = R; P.N = N; P.K = K; P.ones = db ? 1 : 0;
   P.dW = dW; P.ldw = ldw; P.db = db; P.db2 = db ? db2 : nullptr; P.accumulate = accumulate; P.pre = 0;
@@ -230,7 +239,10 @@ int wg_add_pre(WgBatch& b, int N, int K, float* dW, int ldw, float* db, int nsli
 // ceil(N/64) output blocks.  C0 and the VALU term are fitted on per-workgroup start / end stamps of the launches at the
 // metric shape (-DSW_WG_STAMP): the LSTM problem measures 848 cycles per group and wave = 512 +
 // 80 + 256.  With C0 = 0 the narrow problems (K = 32 blocks, the 2048-row S / z blocks of fc1.0) were undersplit and their
-// jobs ended the generator's launch 8 us after the average job.
+// jobs ended the generator's launch 8 us after the average job.  (Fitted on the kernel with flat, clamped and masked operand
+// loads.  With the bounded buffer loads of sw_wgrad_dev.h the LSTM problem's jobs - 45 groups per wave - went from 33.1 to
+// 30.7 us, the longest job of the launch from 36.5 to 33.1 us (profiles/wgrad_bounded_ab.txt); the constants are kept as they
+// are: a refit moves the split, and with it which rows meet in which partial - the last bits of every gradient.)
 #ifndef SW_WG_GROUP_C0
 #define SW_WG_GROUP_C0 256.0
 #endif

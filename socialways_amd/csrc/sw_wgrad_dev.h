@@ -16,22 +16,35 @@
 
 #define SW_WG_RLD 69   // LDS row stride of a wave's 64 x (<= 69) block: 64 act columns + tail segment + ones
 
-// NV consecutive floats as ONE vector load (dword / dwordx2 / dwordx3 / dwordx4)
+// Bounded operand loads: a wave reads its row slice through one buffer descriptor per operand.  The descriptor's range
+// ends on the slice's last row boundary, so a row beyond it - prefetch overrun, the padding of the last 4-row group - comes
+// back as zeros from the hardware's range check, and a row in front of the base (byte offset wrapped past 2^32) does too:
+// no row clamp, no 64-bit address, no 0/1 mask factor.
+typedef __amdgpu_buffer_rsrc_t wg_rsrc;
+// `base` and `bytes` must be wave-uniform TO THE COMPILER (formed from kernel arguments and readfirstlane values): a
+// descriptor it cannot prove uniform gets every load wrapped in a serialising loop over the lanes' values
+__device__ __forceinline__ wg_rsrc wg_make_rsrc(const float* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
+}
+// NV consecutive floats at byte offset `off` as ONE vector load (dword / dwordx2 / dwordx3 / dwordx4)
+// (each component goes through a scalar of its own: __builtin_bit_cast applied to a vector ELEMENT reads component 0)
 template <int NV>
-__device__ __forceinline__ void wg_ldv(float (&v)[NV], const float* p) {
+__device__ __forceinline__ void wg_ldv(float (&v)[NV], wg_rsrc rs, unsigned off) {
+  unsigned u[NV];
   if constexpr (NV == 4) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+    u[0] = q[0]; u[1] = q[1]; u[2] = q[2]; u[3] = q[3];
   } else if constexpr (NV == 3) {
-    struct __attribute__((packed, aligned(4))) P3 { float a, b, c; };
-    const P3 q = *reinterpret_cast<const P3*>(p);
-    v[0] = q.a; v[1] = q.b; v[2] = q.c;
+    const auto q = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)off, 0, 0);
+    u[0] = q[0]; u[1] = q[1]; u[2] = q[2];
   } else if constexpr (NV == 2) {
-    const float2 q = *reinterpret_cast<const float2*>(p);
-    v[0] = q.x; v[1] = q.y;
+    const auto q = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, 0);
+    u[0] = q[0]; u[1] = q[1];
   } else {
-    v[0] = p[0];
+    u[0] = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0);
   }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = __uint_as_float(u[i]);
 }
 
 // Tiles per lane vector: the smallest t with 16 t >= n and n % t == 0 (every lane's vector is then wholly live or wholly
@@ -55,12 +68,15 @@ __host__ __device__ inline int wg_tiles(int n, bool allow3) {
 // order of every output element - its rows, 4 per MFMA, in slice order - is unchanged: bit-identical results.
 //   NA = min(4, tiles of 16 delta columns in this block), KR = tiles of real act columns (1..4),
 //   XT = 1: one more k-tile holding the tail segment (act2, K2 columns) and / or the ones column at lanes ln = 0..
-// Branch-free streaming body: loads are unconditional from clamped addresses and masked by 0/1 factors; the pipeline
-// registers hold RAW loaded values (arithmetic attached to a load would sit in front of the loop's back edge and
-// drain the pipeline once per DEPTH groups).
+// Branch-free streaming body: loads are unconditional and bounded by the operand's descriptor (rows outside the slice read
+// zero); the pipeline registers hold RAW loaded values (arithmetic attached to a load would sit in front of the loop's back
+// edge and drain the pipeline once per DEPTH groups).
+// rbeg / rend must be wave-uniform to the compiler (wg_job passes them through readfirstlane).  Rows below row0 have no
+// `act` operand: its descriptor starts at row max(rbeg, row0) - `abase` itself may lie IN FRONT of the allocation (the LSTM
+// problem passes h_{t-1} as "the act row one time step earlier") and is never dereferenced below that row.
 template <int NA, int KR, int K2, int ONES, int DSCALE = 1>
 __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const float* __restrict__ abase, int ldd, int lda,
-                                       int rbeg, int rend, int rmax, int acol, int bcol, int lg, int ln,
+                                       int rbeg, int rend, int acol, int bcol, int lg, int ln,
                                        float* __restrict__ mine,
                                        const float* __restrict__ abase2, int lda2, int row0, int xoff) {
   constexpr int KT = KR, XC = K2 + ONES;
@@ -84,62 +100,60 @@ __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const fl
   constexpr int DEPTH = (K2 > 0 ? SW_WG_DEPTH_TAIL : SW_WG_DEPTH) * DSCALE;
   float a[DEPTH][NA], b[DEPTH][KT];
   f32x4 xq[DEPTH];
-  auto load = [&](int r0, float (&av)[NA], float (&bv)[KT], f32x4& xv) {
-    const int rc = min(r0 + lg, rmax);
-    // 32-bit element offsets (the host rejects a problem whose rows x stride reach 2^31): one multiply-add per load
-    // instead of a 64-bit multiply-add + shift-add
-    wg_ldv<NA>(av, dbase + (unsigned)(rc * ldd + acol));
+  // One descriptor per operand: the slice's rows [rbeg, rend) - for `act` [max(rbeg, row0), rend) -, ending on a row
+  // boundary (a lane's vector lies inside its row: no load straddles the end).  Byte offsets are 32-bit (the host rejects
+  // a problem whose slices could span 2^31 bytes); a lane's offset advances by one add per group.
+  const int abeg = K2 > 0 ? max(rbeg, row0) : rbeg, aend = max(abeg, rend);
+  const wg_rsrc drs = wg_make_rsrc(dbase + (size_t)rbeg * ldd, (unsigned)(rend - rbeg) * (unsigned)ldd * 4u);
+  const wg_rsrc ars = wg_make_rsrc(abase + (size_t)abeg * lda, (unsigned)(aend - abeg) * (unsigned)lda * 4u);
+  const wg_rsrc xrs = wg_make_rsrc(abase2 + (size_t)rbeg * lda2, (unsigned)(rend - rbeg) * (unsigned)lda2 * 4u);
+  // rows below row0 start at a NEGATIVE row of the act descriptor: the unsigned offset wraps out of range -> zeros
+  unsigned doff = (unsigned)(lg * ldd + acol) * 4u, aoff = (unsigned)((rbeg - abeg + lg) * lda + bcol) * 4u;
+  unsigned xoff2 = (unsigned)(lg * lda2) * 4u;
+  const unsigned dstep = 16u * (unsigned)ldd, astep = 16u * (unsigned)lda, xstep = 16u * (unsigned)lda2;
+  auto load = [&](float (&av)[NA], float (&bv)[KT], f32x4& xv) {     // the next 4-row group of the slice
+    wg_ldv<NA>(av, drs, doff);
+    doff += dstep;
+    wg_ldv<KR>(bv, ars, aoff);
+    aoff += astep;
     if constexpr (K2 > 0) {
-      wg_ldv<KR>(bv, abase + (unsigned)(max(rc, row0) * lda + bcol));   // rows below row0 have no `act` operand
-      xv = ld4(abase2 + (unsigned)(rc * lda2));                          // the row's tail columns (same address for 16 lanes)
-    } else {
-      wg_ldv<KR>(bv, abase + (unsigned)(rc * lda + bcol));              // (row0 = 0 without a tail segment)
+      float x4[4];
+      wg_ldv<4>(x4, xrs, xoff2);                                      // the row's tail columns (same address for 16 lanes)
+      xv = f32x4{x4[0], x4[1], x4[2], x4[3]};
+      xoff2 += xstep;
     }
   };
 #pragma unroll
-  for (int q = 0; q < DEPTH - 1; ++q) load(rbeg + 4 * q, a[q], b[q], xq[q]);
-  // Row masks only (rows >= rend belong to the next slice; rows below row0 have no act operand - a zero delta row
-  // already kills its products).  There are no COLUMN masks: a lane beyond the block's live delta / act columns
-  // (clamped to the last live ones) only feeds output rows / columns that are never written out - an MFMA output
-  // element mixes nothing but its own row and column.  (Peeling the unmasked interior into a branch of its own was
+  for (int q = 0; q < DEPTH - 1; ++q) load(a[q], b[q], xq[q]);
+  // No masks at all.  Rows outside [rbeg, rend) load zeros (a zero delta row kills its products, its tail columns and its
+  // ones column), rows below row0 a zero act row.  There are no COLUMN masks either: a lane beyond the block's live delta /
+  // act columns (clamped to the last live ones) only feeds output rows / columns that are never written out - an MFMA
+  // output element mixes nothing but its own row and column.  (Peeling the interior into a branch of its own was
   // measured 1.8 x slower: memory operations under a branch cost the exact vmcnt bookkeeping, see DESIGN.md.)
   for (int r = rbeg; r < rend; r += 4 * DEPTH) {
 #pragma unroll
     for (int q = 0; q < DEPTH; ++q) {
-      load(r + 4 * (q + DEPTH - 1), a[(q + DEPTH - 1) % DEPTH], b[(q + DEPTH - 1) % DEPTH], xq[(q + DEPTH - 1) % DEPTH]);
+      load(a[(q + DEPTH - 1) % DEPTH], b[(q + DEPTH - 1) % DEPTH], xq[(q + DEPTH - 1) % DEPTH]);
       asm volatile("" ::: "memory");   // the loads are issued HERE (DEPTH - 1 groups ahead), not sunk to their uses
 #pragma unroll
       for (int i = 0; i < NA; ++i) asm volatile("" : "+v"(a[q][i]));   // ... and group q is first touched here
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) asm volatile("" : "+v"(b[q][kt]));
       if constexpr (K2 > 0) asm volatile("" : "+v"(xq[q]));
-      const int rr = r + 4 * q + lg;
-      const float rs = rr < rend ? 1.0f : 0.0f;
-      float av[NA], bv[KT];
-#pragma unroll
-      for (int i = 0; i < NA; ++i) av[i] = a[q][i] * rs;
-      if constexpr (K2 > 0) {       // only problems with a tail segment have rows without an `act` operand (row0 > 0)
-        const float rs0 = rr >= row0 ? 1.0f : 0.0f;
-#pragma unroll
-        for (int kt = 0; kt < KR; ++kt) bv[kt] = b[q][kt] * rs0;
-      } else {
-#pragma unroll
-        for (int kt = 0; kt < KR; ++kt) bv[kt] = b[q][kt];
-      }
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
-          acc[i][kt] = SW_MFMA(av[i], bv[kt], acc[i][kt]);
+          acc[i][kt] = SW_MFMA(a[q][i], b[q][kt], acc[i][kt]);
         }
       }
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         if constexpr (K2 > 0) {
 #pragma unroll
-          for (int c = 0; c < K2; ++c) xacc[i][c] = fmaf(av[i], xq[q][c], xacc[i][c]);
+          for (int c = 0; c < K2; ++c) xacc[i][c] = fmaf(a[q][i], xq[q][c], xacc[i][c]);
         }
-        if constexpr (ONES) xacc[i][K2] += av[i];
+        if constexpr (ONES) xacc[i][K2] += a[q][i];
       }
     }
   }
@@ -191,8 +205,9 @@ __device__ __forceinline__ void wg_job(const WgBatch& batch, float* __restrict__
   const int KR = K > 0 ? wg_tiles(K, true) : 1;         // real act tiles (a block with only the ones column: one masked tile)
   const int nsub = P.nsplit * 4;
   const int rows_per = (((P.R + nsub - 1) / nsub) + 3) & ~3;
-  const int rbeg = min(P.R, s * rows_per);
-  const int rend = min(P.R, rbeg + rows_per);
+  // the slice bounds feed the buffer descriptors: wave-uniform, and through readfirstlane the compiler knows it
+  const int rbeg = __builtin_amdgcn_readfirstlane(min(P.R, s * rows_per));
+  const int rend = __builtin_amdgcn_readfirstlane(min(P.R, rbeg + rows_per));
   // the lane's NA delta columns n0 + NA ln + i and KR act columns KR ln + kt; bases clamped into the row, dead
   // components masked
   const int acol = n0 + max(0, min(NA * ln, Nb - NA));
@@ -201,7 +216,7 @@ __device__ __forceinline__ void wg_job(const WgBatch& batch, float* __restrict__
   // extra columns on the VALU: a tail segment of exactly 4 columns (K2; only next to K = 64) and / or the ones column
 #define WG_CASE(na, kr, k2, on)                                                                                     \
   case ((na * 8 + kr) * 2 + (k2 ? 1 : 0)) * 2 + on:                                                                 \
-    wg_run<na, kr, k2, on, DSCALE>(P.delta, P.act, P.ldd, P.lda, rbeg, rend, P.R - 1, acol, bcol, lg, ln,              \
+    wg_run<na, kr, k2, on, DSCALE>(P.delta, P.act, P.ldd, P.lda, rbeg, rend, acol, bcol, lg, ln,                      \
                                    mine, P.act2 ? P.act2 : P.delta, P.act2 ? P.lda2 : P.ldd, P.row0, K);            \
     break;
 #define WG_CASES(na)                                                                                                \
