@@ -14,8 +14,11 @@
   `SW_ALLREDUCE=direct` exchanges the gradients through the library's own two-hop kernel over hipIpc-mapped peer buffers
   (one launch per optimizer step: exchange + Adam, inside the step's hipGraph) instead of RCCL's ring
 * `--min-past M`: the held-out windows also keep the pedestrians seen for only M .. 7 frames (create_dataset_ragged:
-  right-aligned observations + obs_len), so they are predicted and their neighbours see them; training stays on full
-  windows (there are no ragged backward kernels), the errors are reported per history length (evaluate_history)
+  right-aligned observations + obs_len), so they are predicted and their neighbours see them; the errors are reported per
+  history length (evaluate_history).  Training stays on full windows unless
+* `--train-ragged` (with `--min-past M`): the ragged windows in front of the held-out part are what the model trains on
+  (train_epoch_ragged: one eager step per packed batch on the unfused route, no graph capture - slower per step than
+  train_epoch)
 """
 import argparse
 import os
@@ -29,18 +32,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import socialways_amd as sw  # noqa: E402
 
 
-def ragged_held_out(obsmat, npz, like, min_past):
-    """The recording's windows with histories of min_past .. n_past frames, written to `npz`; of them the scenes at or after
-    the first held-out timestamp of `like` - the dataset the model trains on, so none of them holds a training window -
-    as an evaluation set in like's coordinates (SceneDataset.held_out)."""
-    obsvs, preds, times, batches, obs_len = sw.biwi_to_npz(obsmat, npz, like.n_past, like.n_next, min_past=min_past)
-    times = np.asarray(times)
+def ragged_windows(npz, like, train):
+    """Of the recording's windows with histories of min_past .. n_past frames (`npz`, written by biwi_to_npz(min_past=...)) the
+    scenes at or after the first held-out timestamp of `like` - the dataset of full windows, so none of them holds a
+    training window - as an evaluation set in like's coordinates (SceneDataset.held_out), or with `train` the scenes in
+    front of that timestamp as a training set in the same coordinates."""
+    d = np.load(npz)
+    obsvs, preds, times, batches, obs_len = d["obsvs"], d["preds"], np.asarray(d["times"]), d["batches"], d["obs_len"]
     t_split = like.times[like.n_train_samples]
-    keep = [(a, b) for a, b in batches if times[a] >= t_split]
+    keep = [(a, b) for a, b in batches if (times[a] < t_split) == bool(train)]
     rows = np.concatenate([np.arange(a, b) for a, b in keep])
     ends = np.cumsum([b - a for a, b in keep])
     scenes = np.stack([np.concatenate([[0], ends[:-1]]), ends], axis=1)
-    return sw.SceneDataset.held_out(like, obsvs[rows], preds[rows], scenes, times[rows], obs_len[rows])
+    return sw.SceneDataset.held_out(like, obsvs[rows], preds[rows], scenes, times[rows], obs_len[rows], train=train)
 
 
 def main(argv=None):
@@ -62,8 +66,16 @@ def main(argv=None):
                          "order, every draw whose end point lies within RADIUS (world units) of a kept one")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
-                         "histories) and report the errors per history length; training stays on full windows")
+                         "histories) and report the errors per history length; training stays on full windows unless "
+                         "--train-ragged is given")
+    ap.add_argument("--train-ragged", action="store_true",
+                    help="with --min-past M: train on the ragged windows in front of the held-out part (train_epoch_ragged: "
+                         "eager steps on the unfused route) instead of the full windows only")
     args = ap.parse_args(argv)
+    if args.train_ragged and args.min_past is None:
+        ap.error("--train-ragged needs --min-past M")
+    if args.train_ragged and args.hidden_size != 64:
+        ap.error("--train-ragged: ragged histories are implemented for the fused 64-unit path (--hidden-size 64)")
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -86,12 +98,23 @@ def main(argv=None):
                                                                     int(np.max(batches[:, 1] - batches[:, 0]))))
     if world > 1:
         torch.distributed.barrier()
-    data = sw.SceneDataset.from_npz(npz, device=dev)
-    ragged = None
+    ragged_npz = os.path.join(args.out, "crowd-8-12-ragged.npz")
     if args.min_past is not None and rank == 0:
-        ragged = ragged_held_out(obsmat, os.path.join(args.out, "crowd-8-12-ragged.npz"), data, args.min_past)
+        sw.biwi_to_npz(obsmat, ragged_npz, 8, 12, min_past=args.min_past)
+    if world > 1:
+        torch.distributed.barrier()
+    data = sw.SceneDataset.from_npz(npz, device=dev)
+    ragged = train_set = None
+    if args.min_past is not None and rank == 0:
+        ragged = ragged_windows(ragged_npz, data, train=False)
         print("ragged held-out set: %d windows in %d scenes, %d of them with fewer than %d frames"
               % (ragged.n_test_samples, len(ragged.test_batches), int((ragged.obs_len < data.n_past).sum()), data.n_past))
+    if args.train_ragged:                 # every rank: the packed batches are sharded scene-aligned as in train_epoch()
+        train_set = ragged_windows(ragged_npz, data, train=True)
+        if rank == 0:
+            print("ragged training set: %d windows in %d scenes, %d of them with fewer than %d frames (full windows: %d)"
+                  % (train_set.n_train_samples, len(train_set.train_batches), int((train_set.obs_len < data.n_past).sum()),
+                     data.n_past, data.n_train_samples))
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
@@ -100,7 +123,10 @@ def main(argv=None):
         tr.noise = sw.DeviceNoise(args.device_noise)
     for epoch in range(1, args.epochs + 1):
         t0 = time.perf_counter()
-        ade, fde, losses, sizes = tr.train_epoch(data, args.batch_size)
+        if train_set is not None:
+            ade, fde, losses, sizes = tr.train_epoch_ragged(train_set, args.batch_size)
+        else:
+            ade, fde, losses, sizes = tr.train_epoch(data, args.batch_size)
         if rank == 0:
             print("Epc=%4d, Train ADE,FDE = (%.3f, %.3f) | time = %.2f | %d packed batches | D/G losses %.4f %.4f"
                   % (epoch, ade, fde, time.perf_counter() - t0, len(sizes), losses[:, 0].mean() + losses[:, 2].mean(),

@@ -93,6 +93,24 @@ int sw_enc_lstm_fwd_aux(const float* x, int x_mode, const float* enc_w, const fl
  * B == 0: SW_OK without a launch.                                                                                       */
 int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const int* obs_len /*[B] int32 or NULL = all T*/,
                            int B, int T, float* hT /*[B,64]*/, float* cT /*[B,64]*/, void* stream);
+/* The TRAINING form of sw_enc_lstm_fwd_ragged: the same ragged pass (x right-aligned, obs_len int32 [B] on the device or
+ * NULL = every row has T frames, clamped on the device into 2 .. T for positions / 1 .. T for 4-d input, zero initial state,
+ * the padding never read) that also leaves the rows the backward needs, in the layout of sw_enc_lstm_fwd(..., act, x4s,
+ * t0 = 0): act = [T][B][384] rows (i f g o | c | h), x4s = [T][B][4].  For row a with s_a = T - obs_len[a]:
+ *   steps t >= s_a: act[t][a], x4s[t][a], hT[a], cT[a] are, bit for bit, what sw_enc_lstm_fwd saves / returns at step
+ *                   t - s_a of the [1, n_a, .] buffer of the valid frames, with and without registered generator images;
+ *   steps t <  s_a: act[t][a] and x4s[t][a] are all-zero bits - SELECTED zeros, never values computed from the padding.
+ * With these rows the dense backward gives the ragged gradients as it is: sw_enc_lstm_bwd* forms zero dgates rows in
+ * front of s_a (i = g = o = 0, c_t = c_{t-1} = 0) and takes c_{s-1} = h_{s-1} = 0 as the initial state at s_a, and the
+ * weight-gradient sums (sw_gen_wgrad*) get zero dgates against zero inputs there.  The step loop keeps the shape of the
+ * dense kernel (every lane computes every step, unconditional stores of selected values, one barrier per step, the saved
+ * row assembled in the LDS row tile) in a kernel of its own: the kernels sw_enc_lstm_fwd* launch are unchanged.  No
+ * auxiliary copy: the caller moves z itself.
+ * SW_EARG before any device call: x, enc_w, hT, cT, act or x4s NULL, B < 0, T < 1, x_mode not 0 / 1, T < 2 with x_mode 0.
+ * B == 0: SW_OK without a launch.                                                                                       */
+int sw_enc_lstm_fwd_ragged_save(const float* x, int x_mode, const float* enc_w, const int* obs_len /*[B] int32 or NULL = all T*/,
+                                int B, int T, float* hT /*[B,64]*/, float* cT /*[B,64]*/, float* act /*[T,B,384]*/,
+                                float* x4s /*[T,B,4]*/, void* stream);
 /* BPTT over rows t0+T-1 .. t0 of `act`; dhT/dcT = gradient w.r.t. the final state (dcT may be
  * NULL); dy optional [B,T,64].  Writes dgates rows [t][B][256]; dh0/dc0 optional outputs.       */
 int sw_enc_lstm_bwd(const float* enc_w, const float* act, const float* c0, const float* dhT,
@@ -418,6 +436,28 @@ int sw_disc_score(const float* obsv, int To, int x_mode, const float* pred4 /*[K
 int sw_disc_score_ragged(const float* obsv, int To, int x_mode, const int* obs_len /*[B] int32 or NULL = all To*/,
                          const float* pred4 /*[K*B,Tp,4]*/, const float* d_w, int B, int K, int Tp, float* score /*[K*B]*/,
                          float* code /*[K*B,2] or NULL*/, void* stream);
+
+/* ---- the discriminator's training passes over RAGGED observation histories ---------------------------------------------
+ * sw_disc_fwd / sw_disc_dpred with obs_len [B] (int32 on the device, NULL = every row has To frames; clamped on the device
+ * into 2 .. To for positions, 1 .. To for obsv_4d) between x_mode and pred4: obsv is right-aligned, row a's observation
+ * LSTM runs from the zero state over its obs_len[a] valid frames alone and the padding is never read.  label / code /
+ * dpred4 / the saved head activations of agent a carry the bits of the dense entry on the [1, n_a, .] buffer of its valid
+ * frames (an agent is one column of every product).  The LSTM rows of the save buffer (save_lstm = 1) follow
+ * sw_enc_lstm_fwd_ragged_save: the dense entry's bits from step To - n_a on, all-zero rows and inputs in front of it, so
+ * sw_disc_bwd* run on the buffer unchanged and give the ragged gradients.  Same grid rule, LDS, argument checks and
+ * behaviour with and without sw_disc_images as the dense entries; a kernel of its own (disc_fwd_kernel is unchanged).
+ * sw_disc_fwd_ragged takes save_lstm 0 or 1 only: 2 is SW_EARG, there is no precomputed observation pass for ragged rows.
+ * sw_disc_dpred_ragged needs sw_disc_dpred_supported(Tp) like sw_disc_dpred (SW_ESHAPE otherwise).
+ * B == 0: SW_OK without a launch.                                                                                          */
+int sw_disc_fwd_ragged(const float* obsv, int To, int x_mode, const int* obs_len /*[B] int32 or NULL = all To*/,
+                       const float* const* pred4 /*nb x [B,Tp,4]*/, int nb, const float* d_w, int B, int Tp,
+                       float* const* label /*nb x [B,1]*/, float* const* code /*nb x [B,2]*/, float* dsave /*or NULL*/,
+                       int save_lstm /*0 or 1*/, float* w_snapshot /*or NULL*/, void* stream);
+int sw_disc_dpred_ragged(const float* obsv, int To, int x_mode, const int* obs_len /*[B] int32 or NULL = all To*/,
+                         const float* pred4 /*[B,Tp,4]*/, const float* d_w, int B, int Tp, const float* targets, int t_idx,
+                         const float* z /*[B,32]*/, float g_label, float g_code, float* dpred4 /*[B,Tp,4]*/,
+                         float* label /*[B,1] or NULL*/, float* code /*[B,2] or NULL*/, float* loss_part /*or NULL*/,
+                         void* stream);
 
 /* ---- LSGAN + InfoGAN losses of train.py:484-494 / 512-523 and their gradients -------------- */
 /* t_a = targets[ia], t_b = targets[ib] (read on the device, so a captured hipGraph sees new values).

@@ -37,6 +37,19 @@ __global__ __launch_bounds__(SW_THREADS, 2) void disc_fwd_kernel(
                 save_lstm, split, w_snap, fuse, gl, dpred_out, dimg);
 }
 
+// The forward pass over RAGGED observation histories (sw_disc_fwd_ragged, sw_disc_dpred_ragged): disc_fwd_tile with the
+// ragged observation loop.  A kernel of its own with obs_len as the last argument; disc_fwd_kernel keeps its code.
+__global__ __launch_bounds__(SW_THREADS, 2) void disc_fwd_ragged_kernel(
+    const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred_a,
+    const float* __restrict__ pred_b, int nb, const float* __restrict__ d_w, int B, int Tp, float* __restrict__ label_a, float* __restrict__ label_b,
+    float* __restrict__ code_a, float* __restrict__ code_b, float* __restrict__ dsave, int save_lstm, int split,
+    float* __restrict__ w_snap, int fuse, DiscLoss gl, float* __restrict__ dpred_out, const float* __restrict__ dimg,
+    const int* __restrict__ obs_len) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  disc_fwd_tile<true>(smem, blockIdx.x, gridDim.x, obsv, To, x_mode, pred_a, pred_b, nb, d_w, B, Tp, label_a, label_b, code_a, code_b,
+                      dsave, save_lstm, split, w_snap, fuse, gl, dpred_out, dimg, obs_len);
+}
+
 // ---------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------
@@ -512,21 +525,35 @@ static int g_disc_fwd_lds = 0;   // dynamic-LDS limit of disc_fwd_kernel (plain 
 size_t sw_dsave_floats(int B, int To, int Tp, int nb) { return dsave_layout(B, To, Tp, nb).total; }
 size_t sw_ddelta_floats(int B, int To, int Tp, int nb) { return ddelta_layout(B, To, Tp, nb).total; }
 
-extern "C" int sw_disc_fwd(const float* obsv, int To, int x_mode, const float* const* pred4, int nb,
+static int g_disc_fwd_ragged_lds = 0;   // ... of disc_fwd_ragged_kernel
+
+// sw_disc_fwd and sw_disc_fwd_ragged: one set of checks, one grid rule; the dense entry launches the dense kernel
+static int disc_fwd_launch(bool ragged, const float* obsv, int To, int x_mode, const int* obs_len, const float* const* pred4, int nb,
                            const float* d_w, int B, int Tp, float* const* label, float* const* code, float* dsave,
                            int save_lstm, float* w_snapshot, void* stream) {
   if (!obsv || !pred4 || !d_w || !label || !code || nb < 1 || nb > SW_DISC_MAXB || B < 0 || To < 1 || Tp < 1 ||
       (x_mode != 0 && x_mode != 1) || (x_mode == 0 && To < 2) || save_lstm < 0 || save_lstm > 2 || (save_lstm == 2 && !dsave))
     return SW_EARG;
+  if (ragged && save_lstm == 2) return SW_EARG;   // no precomputed observation pass for ragged rows
   for (int k = 0; k < nb; ++k)
     if (!pred4[k] || !label[k] || !code[k]) return SW_EARG;
   if (Tp > 64) return SW_ESHAPE;
   if (B == 0) return SW_OK;
   int lds = head_lds(Tp, 2 * 16 * SW_HLD + 1280).total * 4;
   if (lds > 163840) return SW_ESHAPE;
-  if (int rc = sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds)) return rc;
+  if (int rc = ragged ? sw_set_lds((const void*)disc_fwd_ragged_kernel, lds, g_disc_fwd_ragged_lds)
+                      : sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds))
+    return rc;
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   const int split = (nb == 2 && 2 * tiles <= SW_SPLIT_MAX_WGS) ? 1 : 0;   // idle CUs: one workgroup per (tile, branch)
+  if (ragged) {
+    SW_LAUNCH(disc_fwd_ragged_kernel, dim3(split ? 2 * tiles : tiles), dim3(SW_THREADS), lds, (hipStream_t)stream,
+                       obsv, To, x_mode, pred4[0], nb > 1 ? pred4[1] : nullptr, nb, d_w, B, Tp, label[0],
+                       nb > 1 ? label[1] : nullptr, code[0], nb > 1 ? code[1] : nullptr, dsave, save_lstm, split, w_snapshot, 0, DiscLoss{}, nullptr,
+                       sw_disc_images_for(d_w, Tp).img, obs_len);
+    SW_CHECK_LAUNCH("disc_fwd_ragged_kernel");
+    return SW_OK;
+  }
   SW_LAUNCH(disc_fwd_kernel, dim3(split ? 2 * tiles : tiles), dim3(SW_THREADS), lds, (hipStream_t)stream,
                      obsv, To, x_mode, pred4[0], nb > 1 ? pred4[1] : nullptr, nb, d_w, B, Tp, label[0],
                      nb > 1 ? label[1] : nullptr, code[0], nb > 1 ? code[1] : nullptr, dsave, save_lstm, split, w_snapshot, 0, DiscLoss{}, nullptr,
@@ -534,12 +561,23 @@ extern "C" int sw_disc_fwd(const float* obsv, int To, int x_mode, const float* c
   SW_CHECK_LAUNCH("disc_fwd_kernel");
   return SW_OK;
 }
+extern "C" int sw_disc_fwd(const float* obsv, int To, int x_mode, const float* const* pred4, int nb,
+                           const float* d_w, int B, int Tp, float* const* label, float* const* code, float* dsave,
+                           int save_lstm, float* w_snapshot, void* stream) {
+  return disc_fwd_launch(false, obsv, To, x_mode, nullptr, pred4, nb, d_w, B, Tp, label, code, dsave, save_lstm, w_snapshot, stream);
+}
+extern "C" int sw_disc_fwd_ragged(const float* obsv, int To, int x_mode, const int* obs_len, const float* const* pred4, int nb,
+                                  const float* d_w, int B, int Tp, float* const* label, float* const* code, float* dsave,
+                                  int save_lstm, float* w_snapshot, void* stream) {
+  return disc_fwd_launch(true, obsv, To, x_mode, obs_len, pred4, nb, d_w, B, Tp, label, code, dsave, save_lstm, w_snapshot, stream);
+}
 
 // Generator phase in ONE launch: forward of D on (obsv, pred_hat) and the backward of its prediction heads down to
 // d(g_loss)/d(pred_hat) (train.py:510-523, 538): no saves, no second prologue, activations stay in LDS.
-extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float* pred4, const float* d_w, int B, int Tp,
-                             const float* targets, int t_idx, const float* z, float g_label, float g_code,
-                             float* dpred4, float* label, float* code, float* loss_part, void* stream) {
+// sw_disc_dpred and sw_disc_dpred_ragged: one set of checks; the dense entry launches the dense kernel
+static int disc_dpred_launch(bool ragged, const float* obsv, int To, int x_mode, const int* obs_len, const float* pred4,
+                             const float* d_w, int B, int Tp, const float* targets, int t_idx, const float* z, float g_label,
+                             float g_code, float* dpred4, float* label, float* code, float* loss_part, void* stream) {
   if (!obsv || !pred4 || !d_w || !targets || !z || !dpred4 || B < 0 || To < 1 || Tp < 1 || t_idx < 0 ||
       (x_mode != 0 && x_mode != 1) || (x_mode == 0 && To < 2))
     return SW_EARG;
@@ -547,14 +585,35 @@ extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float*
   if (B == 0) return SW_OK;
   const int lds = disc_dpred_lds(Tp);
   if (lds > 163840) return SW_ESHAPE;
-  if (int rc = sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds)) return rc;
+  if (int rc = ragged ? sw_set_lds((const void*)disc_fwd_ragged_kernel, lds, g_disc_fwd_ragged_lds)
+                      : sw_set_lds((const void*)disc_fwd_kernel, lds, g_disc_fwd_lds))
+    return rc;
   DiscLoss gl{targets, z, t_idx, t_idx, g_label, g_code, 1, loss_part};
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
+  if (ragged) {
+    SW_LAUNCH(disc_fwd_ragged_kernel, dim3(tiles), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode, pred4,
+                       (const float*)nullptr, 1, d_w, B, Tp, label, (float*)nullptr, code, (float*)nullptr, (float*)nullptr, 0, 0,
+                       (float*)nullptr, 1, gl, dpred4, sw_disc_images_for(d_w, Tp).img, obs_len);
+    SW_CHECK_LAUNCH("disc_fwd_ragged_kernel");
+    return SW_OK;
+  }
   SW_LAUNCH(disc_fwd_kernel, dim3(tiles), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv, To, x_mode, pred4,
                      (const float*)nullptr, 1, d_w, B, Tp, label, (float*)nullptr, code, (float*)nullptr, (float*)nullptr, 0, 0,
                      (float*)nullptr, 1, gl, dpred4, sw_disc_images_for(d_w, Tp).img);
   SW_CHECK_LAUNCH("disc_fwd_kernel");
   return SW_OK;
+}
+extern "C" int sw_disc_dpred(const float* obsv, int To, int x_mode, const float* pred4, const float* d_w, int B, int Tp,
+                             const float* targets, int t_idx, const float* z, float g_label, float g_code,
+                             float* dpred4, float* label, float* code, float* loss_part, void* stream) {
+  return disc_dpred_launch(false, obsv, To, x_mode, nullptr, pred4, d_w, B, Tp, targets, t_idx, z, g_label, g_code, dpred4, label, code,
+                           loss_part, stream);
+}
+extern "C" int sw_disc_dpred_ragged(const float* obsv, int To, int x_mode, const int* obs_len, const float* pred4, const float* d_w,
+                                    int B, int Tp, const float* targets, int t_idx, const float* z, float g_label, float g_code,
+                                    float* dpred4, float* label, float* code, float* loss_part, void* stream) {
+  return disc_dpred_launch(true, obsv, To, x_mode, obs_len, pred4, d_w, B, Tp, targets, t_idx, z, g_label, g_code, dpred4, label, code,
+                           loss_part, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -351,11 +351,16 @@ __device__ __forceinline__ f32x4 disc_obs_bwd_tail(const float* of1T, const floa
 // `fuse` (generator phase, one branch) also the backward of the prediction heads down to d(loss)/d(pred).  A device function
 // so that another launch can run the generator-phase pass of a tile in front of its own work (dec_rollout_bwd_kernel<true>,
 // sw_decoder.hip: the pass is tile-local and its only consumer is that tile's decode BPTT).
+// RAGGED (sw_disc_fwd_ragged, sw_disc_dpred_ragged): the observation pass starts row b at step To - obs_len[b] and saves
+// the selected rows (lstm_obs_loop_ragged, sw_lstm_dev.h); everything behind it is the same code.  A template parameter with
+// obs_len as the LAST argument, as disc_score_kernel: the dense instances keep the dense loop and their code.
+template <bool RAGGED = false>
 __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, const unsigned nbx,
     const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred_a,
     const float* __restrict__ pred_b, int nb, const float* __restrict__ d_w, int B, int Tp, float* __restrict__ label_a, float* __restrict__ label_b,
     float* __restrict__ code_a, float* __restrict__ code_b, float* __restrict__ dsave, int save_lstm, int split,
-    float* __restrict__ w_snap, int fuse, DiscLoss gl, float* __restrict__ dpred_out, const float* __restrict__ dimg) {
+    float* __restrict__ w_snap, int fuse, DiscLoss gl, float* __restrict__ dpred_out, const float* __restrict__ dimg,
+    const int* __restrict__ obs_len = nullptr) {
   // LSTM part
   float* hbuf = smem;                        // [2][16][68]
   const HeadLds L = head_lds(Tp, 2 * 16 * SW_HLD + 1280);   // (the 1280 floats in between: Wx | bx of disc_obs_lstm_tile)
@@ -410,7 +415,17 @@ __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, co
     const bool sv = dsave && save_lstm && save_obs;
     float* act = sv ? dsave + ds.act : nullptr;
     float* x4s = sv ? dsave + ds.x4s : nullptr;
-    if (x_mode == 0) {
+    if constexpr (RAGGED) {
+      if (x_mode == 0) {
+        const int s = obs_start(obs_len, b, To, 0);
+        if (sv) lstm_obs_loop_ragged<0, SAVE_ROWS>(W, hbuf, obsv, To, b, s, c, h, act, x4s, B);
+        else lstm_obs_loop_ragged<0>(W, hbuf, obsv, To, b, s, c, h);
+      } else {
+        const int s = obs_start(obs_len, b, To, 1);
+        if (sv) lstm_obs_loop_ragged<1, SAVE_ROWS>(W, hbuf, obsv, To, b, s, c, h, act, x4s, B);
+        else lstm_obs_loop_ragged<1>(W, hbuf, obsv, To, b, s, c, h);
+      }
+    } else if (x_mode == 0) {
       if (sv) lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
       else lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
     } else {

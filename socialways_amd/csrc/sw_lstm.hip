@@ -378,6 +378,57 @@ extern "C" int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* e
   return SW_OK;
 }
 
+// The training form of the ragged encoder (zero initial state, saved rows + inputs out): enc_lstm_fwd_kernel<., true, false,
+// true> at t0 = 0 with the ragged loop's SAVE_TILE form (sw_lstm_dev.h) - the saved row of a step is assembled in the LDS
+// row tile and leaves behind the step's barrier, zeros in front of a row's start.  A kernel of its own: the dense kernels
+// above keep their code.  No z pull by spare workgroups: the ragged step copies z itself.
+template <int XMODE>
+__global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_ragged_save_kernel(
+    const float* __restrict__ x, const float* __restrict__ enc_w, const int* __restrict__ obs_len, int B, int T,
+    float* __restrict__ hT, float* __restrict__ cT, float* __restrict__ act, float* __restrict__ x4s,
+    const float* __restrict__ gimg) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2 * SW_TILE * SW_ALD];
+  __shared__ __attribute__((aligned(16))) float wx_lds[256 * 4];
+  __shared__ __attribute__((aligned(16))) float bx_lds[256];
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int u0 = wave * 16;
+  const int a0 = (int)blockIdx.x * SW_TILE;
+  const int b = min(a0 + ln, B - 1);   // padding lanes of the last tile: replicas of agent B-1
+  LstmW W;
+  if (gimg) {
+    lstm_load_img(W, gimg, wave, lane);
+  } else {
+    lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
+    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
+                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
+  }
+  const int s = obs_start(obs_len, b, T, XMODE);
+  f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
+  st4(&hbuf[ln * SW_ALD + 320 + u0 + 4 * lg], h);
+  sw_barrier();
+  if (!gimg) lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
+  lstm_obs_loop_ragged<XMODE, SAVE_TILE>(W, hbuf, x, T, b, s, c, h, act, x4s, B, a0);
+  st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
+  st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
+}
+
+extern "C" int sw_enc_lstm_fwd_ragged_save(const float* x, int x_mode, const float* enc_w, const int* obs_len, int B, int T,
+                                           float* hT, float* cT, float* act, float* x4s, void* stream) {
+  if (!x || !enc_w || !hT || !cT || !act || !x4s || B < 0 || T < 1 || (x_mode != 0 && x_mode != 1) || (x_mode == 0 && T < 2))
+    return SW_EARG;
+  if (B == 0) return SW_OK;
+  const float* gimg = sw_gen_images_for(enc_w, nullptr);
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
+  if (x_mode == 0)
+    SW_LAUNCH(enc_lstm_fwd_ragged_save_kernel<0>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T,
+              hT, cT, act, x4s, gimg);
+  else
+    SW_LAUNCH(enc_lstm_fwd_ragged_save_kernel<1>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T,
+              hT, cT, act, x4s, gimg);
+  SW_CHECK_LAUNCH("enc_lstm_fwd_ragged_save_kernel");
+  return SW_OK;
+}
+
 extern "C" int sw_enc_lstm_bwd_aux(const float* enc_w, const float* act, const float* c0, const float* dhT,
                                    const float* dcT, const float* dy, int B, int T, int t0, float* dgates,
                                    float* dh0, float* dc0, const float* aux_src, float* aux_dst, const float* aux_mask,

@@ -435,11 +435,25 @@ __device__ __forceinline__ void obs_x4_load_from(const float* pos, int b, int t,
 // >= s, so that cell ran on finite values and nothing of the padding was loaded).  From step s on the lane's agent sees
 // exactly the operands of the T - s step run on its valid frames: an agent is one column of the products, so h_T / c
 // carry the bits of lstm_obs_loop on the truncated buffer.  A separate function: the dense loop above keeps its code.
-template <int XMODE>
+//
+// SAVE (the training forms: sw_enc_lstm_fwd_ragged_save, sw_disc_fwd_ragged) stores per step the SELECTED row in the layout
+// of the dense kernels - the cell's gates | c | h and the step's 4-d input from the lane's start on, ZEROS in front of it -
+// so that the dense BPTT and weight-gradient kernels give the ragged gradients as they are: with i = g = o = 0 and
+// c_t = c_{t-1} = 0 lstm_cell_bwd yields zero dgates and dc_{t-1} = 0 whatever arrives from step s, and the weight
+// gradients sum zero dgates against zero inputs.  Selected, never computed from the padding: 0 * NaN would poison the GEMM.
+// The stores stay unconditional (the value is selected, not the store).
+//   SAVE_ROWS: straight from the registers, as lstm_obs_loop<., true> (act / x4s = row 0 of step 0, B = rows per step)
+//   SAVE_TILE: through the LDS row tile, as enc_lstm_fwd_kernel<., true, ., true>: hbuf is then [2][16][SW_ALD], whose h
+//              columns (320 ..) are the next step's operand, and the rows leave behind the step's barrier (a0 = the tile's
+//              first agent)
+enum { SAVE_NONE = 0, SAVE_ROWS = 1, SAVE_TILE = 2 };
+template <int XMODE, int SAVE = SAVE_NONE>
 __device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int b, int s,
-                                                     f32x4& c, f32x4& h) {
+                                                     f32x4& c, f32x4& h, float* __restrict__ act = nullptr,
+                                                     float* __restrict__ x4s = nullptr, int B = 0, int a0 = 0) {
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int u0 = wave * 16;
+  constexpr int HS = SAVE == SAVE_TILE ? SW_ALD : SW_HLD, HO = SAVE == SAVE_TILE ? 320 : 0;
   float xa, xq = 0.f;
   auto load_x = [&](int t) {
     if constexpr (XMODE == 0) obs_x4_load_from(x, b, t, s, T, lg, xa, xq);
@@ -447,19 +461,38 @@ __device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf
   };
   load_x(0);
   asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE, as in lstm_obs_loop
+  float* arow = SAVE == SAVE_ROWS ? act + (size_t)b * 384 + u0 + 4 * lg : nullptr;
+  float* xrow = SAVE != SAVE_NONE ? x4s + (size_t)b * 4 + lg : nullptr;
   for (int t = 0; t < T; ++t) {
     const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
     load_x(min(t + 1, T - 1));
     f32x4 gate[4];
-    lstm_cell(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], gate, c, h);
+    lstm_cell(W, xb, &hbuf[(t & 1) * 16 * HS + ln * HS + HO + 4 * lg], gate, c, h);
     const bool on = t >= s;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       c[r] = on ? c[r] : 0.f;
       h[r] = on ? h[r] : 0.f;
     }
-    st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
+    if constexpr (SAVE != SAVE_NONE) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gate[g][r] = on ? gate[g][r] : 0.f;
+      *xrow = on ? xb : 0.f;   // all four waves hold the same x_t and all store it
+      xrow += (size_t)B * 4;
+    }
+    if constexpr (SAVE == SAVE_TILE) lstm_put_act_tile(hbuf + ((t + 1) & 1) * 16 * HS, gate, c, h, ln, lg, u0);
+    else st4(&hbuf[((t + 1) & 1) * 16 * HS + ln * HS + u0 + 4 * lg], h);
+    if constexpr (SAVE == SAVE_ROWS) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) st4g(arow + g * 64, gate[g]);
+      st4g(arow + 256, c);
+      st4g(arow + 320, h);
+      arow += (size_t)B * 384;
+    }
     sw_barrier();
+    if constexpr (SAVE == SAVE_TILE) lstm_store_act_tile(hbuf + ((t + 1) & 1) * 16 * HS, act + (size_t)t * B * 384, a0, B, wave, lane);
     asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
   }
 }

@@ -83,10 +83,12 @@ class SceneDataset:
             self.obs_len = torch.from_numpy(check_obs_len(obs_len, obsvs.shape[0], self.n_past, 2)).to(device)
 
     @classmethod
-    def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None):
+    def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None, train=False):
         """Windows that a model trained on `like` is evaluated on: EVERY scene is a test scene (no training part), the
         coordinates are those of `like` - its scale, not one of these windows' own - and the tensors live on its device.
-        What evaluate*() / evaluate_history() read; batches (S, 2) must cover rows 0 .. N-1."""
+        What evaluate*() / evaluate_history() read; batches (S, 2) must cover rows 0 .. N-1.
+        train=True: the other way round - every scene is a TRAINING scene (no test part) in like's coordinates: what
+        train_epoch_ragged() reads when the ragged windows in front of like's held-out part join its training."""
         d = cls.__new__(cls)
         obsvs = np.array(obsvs, dtype=np.float32, copy=True)
         preds = np.array(preds, dtype=np.float32, copy=True)
@@ -101,6 +103,9 @@ class SceneDataset:
         d.obs_len = None
         if obs_len is not None:
             d.obs_len = torch.from_numpy(check_obs_len(obs_len, obsvs.shape[0], d.n_past, 2)).to(like.obsv.device)
+        if train:
+            d.train_size, d.train_batches, d.test_batches = len(d.the_batches), d.the_batches, d.the_batches[:0]
+            d.n_train_samples, d.n_test_samples = obsvs.shape[0], 0
         return d
 
     @classmethod

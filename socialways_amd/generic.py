@@ -449,6 +449,12 @@ class GenericTrainer(SocialWaysTrainer):
     def use_social(self):
         return self.G.use_social
 
+    def train_epoch_ragged(self, data, batch_size, draw=None):
+        """Refused: training on ragged observation histories belongs to the fused 64-unit path (no device is touched)."""
+        raise L.SocialWaysHipError("%s has no train_epoch_ragged(): training on a dataset with obs_len (ragged observation "
+                                   "histories) is implemented for the fused 64-unit path (SocialWaysTrainer) only"
+                                   % type(self).__name__)
+
     def step(self, obsv, pred, sub_batches, zeros_val, ones_val, noise, ss=1.0, global_B=None, out=None, global_row0=0,
              variety_noise=None):
         """One packed batch (train.py:458-554).  Returns the (U+3, 3) float64 sums of SocialWaysTrainer.step()."""

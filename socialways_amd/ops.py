@@ -122,15 +122,45 @@ class GenCtx:
     __slots__ = ("obsv", "noise", "scenes", "hT", "cT", "S", "attn", "gsave", "B", "To", "Tp", "use_social", "wh", "ml")
 
 
+def _ragged_arg(obs_len, B, device, noise_src=None, d_obs=None):
+    """The obs_len of the training-side calls: None or an int32 tensor (B,) on `device` (obs_len_arg makes one).  Ragged rows
+    have no z pull in the encoder launch and no precomputed D observation pass."""
+    if obs_len is None:
+        return None
+    if noise_src is not None:
+        raise ValueError("obs_len: the ragged encoder launch pulls no z - noise_src must be None (the caller copies z)")
+    if d_obs is not None:
+        raise ValueError("obs_len: there is no precomputed observation pass for ragged rows - d_obs must be None")
+    return _check_obs_len_tensor(obs_len, B, device)
+
+
+def _enc_save(obsv, enc_w, B, To, hT, cT, gsave, x4s_ptr, obs_len, aux, st):
+    """The encoder launch of a training forward pass: the dense kernel (aux = (src, dst, n): its z pull) or, with obs_len,
+    the saving ragged kernel - the same rows in the same places, zeros in front of a row's start."""
+    if obs_len is None:
+        L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
+               L.ptr(gsave), x4s_ptr, 0, aux[0], aux[1], aux[2], st)
+    elif gsave is None:
+        L.call("sw_enc_lstm_fwd_ragged", L.ptr(obsv), 0, L.ptr(enc_w), L.ptr(obs_len), B, To, L.ptr(hT), L.ptr(cT), st)
+    else:
+        L.call("sw_enc_lstm_fwd_ragged_save", L.ptr(obsv), 0, L.ptr(enc_w), L.ptr(obs_len), B, To, L.ptr(hT), L.ptr(cT),
+               L.ptr(gsave), x4s_ptr, st)
+
+
 def gen_forward(enc_w, emb_w, att_w, dec_w, obsv, noise, scenes, n_next, use_social, save, ws=None, tag="g", ade=None,
-                noise_src=None, d_obs=None):
+                noise_src=None, d_obs=None, obs_len=None):
     """predict(): encode obs (train.py:397-404), social pooling (408-413), decode loop (415-432).
     Returns pred_hat_4d (B, n_next, 4) and, if `save`, the context backward needs.
     ade = (gt (B,n_next,2), 1/ss, out (ceil(B/16),3)): the decode kernel also leaves the per-tile ADE/FDE
     partial sums of train.py:546-551 in `out`.
     noise_src: address `noise` is filled from (pinned host memory) by idle workgroups of the encoder launch.
     d_obs = (packed D weights, dsave buffer): idle workgroups of the decode launch run the discriminator's
-    observation LSTM for the next disc_forward(..., save_lstm=2) on the same obsv (see d_obs_buffer)."""
+    observation LSTM for the next disc_forward(..., save_lstm=2) on the same obsv (see d_obs_buffer).
+    obs_len (B,) int32 on the device: ragged histories - row a holds obs_len[a] valid frames right-aligned in obsv and trains
+    as if its encoder ran on those frames alone from the zero state (sw_enc_lstm_fwd_ragged_save in place of the encoder
+    launch: zero saved rows in front of a row's start, so gen_backward is unchanged; the social block and the rollout read
+    the last two frames and are the same launches).  noise_src and d_obs must be None then.  None: the dense launch."""
+    obs_len = _ragged_arg(obs_len, obsv.shape[0], obsv.device, noise_src, d_obs)
     L.require_gpu(obsv)
     obsv = obsv.contiguous()
     noise = noise.contiguous()
@@ -154,9 +184,8 @@ def gen_forward(enc_w, emb_w, att_w, dec_w, obsv, noise, scenes, n_next, use_soc
     # pull over this launch and the social block's moved the cost, 168 + 148 -> 135 + 185 us: the CUs that host the pulling
     # workgroups serve their tiles / scenes late.  A caller that wants it gone hands z over in device memory.)
     z_in_enc, z_in_soc, n_enc = noise_src, None, noise.numel() if noise_src else 0
-    L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
-           L.ptr(gsave), (gsave.data_ptr() + 4 * x4s_off) if save else None, 0,
-           z_in_enc, L.ptr(noise) if z_in_enc else None, n_enc, st)
+    _enc_save(obsv, enc_w, B, To, hT, cT, gsave, (gsave.data_ptr() + 4 * x4s_off) if save else None, obs_len,
+              (z_in_enc, L.ptr(noise) if z_in_enc else None, n_enc), st)
     attn = wh = ml = None
     if use_social:
         S = torch.empty(B, 64, device=dev)
@@ -250,11 +279,13 @@ class GenCtxK:
     __slots__ = ("one", "K", "obsv_k", "noise_k", "S_k", "gsave_k")
 
 
-def gen_forward_k(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, ws, tag="gv"):
+def gen_forward_k(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, ws, tag="gv", obs_len=None):
     """K rollouts of predict() on the SAME observations with K noise draws (the best-of-K variety term, train.py:527-536
     with its intended semantics): EncoderLstm over the observed steps and the social pooling do not depend on z, so they run
     ONCE on the B agents; only the decode loop runs on the K*B copies (copy k = rows [k*B, (k+1)*B)).
+    obs_len (B,) int32 on the device: ragged histories, as gen_forward() - the one encoder launch is the saving ragged one.
     Returns pred_hat_4d (K*B, n_next, 4) and the context for gen_backward_k."""
+    obs_len = _ragged_arg(obs_len, obsv.shape[0], obsv.device)
     L.require_gpu(obsv)
     obsv = obsv.contiguous()
     noise_k = noise_k.contiguous()
@@ -268,8 +299,7 @@ def gen_forward_k(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use
     gsave_1 = ws.get(tag + ".gsave1", L.workspace_floats(L.WS_GSAVE, B, To, n_next))
     gsave_k = ws.get(tag + ".gsave", L.workspace_floats(L.WS_GSAVE, KB, To, n_next))
     Ta = To + n_next - 1
-    L.call("sw_enc_lstm_fwd_aux", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None,
-           L.ptr(gsave_1), gsave_1.data_ptr() + 4 * Ta * B * 384, 0, None, None, 0, st)
+    _enc_save(obsv, enc_w, B, To, hT, cT, gsave_1, gsave_1.data_ptr() + 4 * Ta * B * 384, obs_len, (None, None, 0), st)
     attn = wh = ml = None
     if use_social:
         S = torch.empty(B, 64, device=dev)
@@ -497,10 +527,17 @@ def d_obs_buffer(ws, B, To, Tp, nb=2, tag="d"):
     return ws.get(tag + ".dsave", L.workspace_floats(L.WS_DSAVE, B, To, Tp, nb))
 
 
-def disc_forward(d_w, obsv, preds, save, ws=None, tag="d", save_lstm=True, w_snapshot=None):
+def disc_forward(d_w, obsv, preds, save, ws=None, tag="d", save_lstm=True, w_snapshot=None, obs_len=None):
     """Discriminator.forward for 1 or 2 future branches sharing the observation encoding.
     Returns ([label_k (B,1)], [code_k (B,2)], ctx).  save_lstm=2: the LSTM rows are already in the save buffer
-    (gen_forward(d_obs=...))."""
+    (gen_forward(d_obs=...)).
+    obs_len (B,) int32 on the device: ragged histories - row a's observation LSTM runs over its obs_len[a] valid frames alone
+    (sw_disc_fwd_ragged: zero saved rows in front of a row's start, so disc_backward* are unchanged); save_lstm=2 is
+    refused then.  None: sw_disc_fwd."""
+    if obs_len is not None:
+        obs_len = _check_obs_len_tensor(obs_len, obsv.shape[0], obsv.device)
+        if int(save_lstm) == 2:
+            raise ValueError("obs_len: there is no precomputed observation pass for ragged rows - save_lstm=2 is refused")
     L.require_gpu(obsv)
     obsv = obsv.contiguous()
     preds = [p.contiguous() for p in preds]
@@ -518,8 +555,12 @@ def disc_forward(d_w, obsv, preds, save, ws=None, tag="d", save_lstm=True, w_sna
     pp, _k1 = L.ptr_array(preds)
     lp, _k2 = L.ptr_array(labels)
     cp, _k3 = L.ptr_array(codes)
-    L.call("sw_disc_fwd", L.ptr(obsv), To, x_mode, pp, nb, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave), int(save_lstm),
-           L.ptr(w_snapshot), L.stream())
+    if obs_len is None:
+        L.call("sw_disc_fwd", L.ptr(obsv), To, x_mode, pp, nb, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave), int(save_lstm),
+               L.ptr(w_snapshot), L.stream())
+    else:
+        L.call("sw_disc_fwd_ragged", L.ptr(obsv), To, x_mode, L.ptr(obs_len), pp, nb, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave),
+               int(save_lstm), L.ptr(w_snapshot), L.stream())
     if not save:
         return labels, codes, None
     ctx = DiscCtx()
@@ -674,16 +715,23 @@ def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None,
     return dpreds
 
 
-def disc_dpred(d_w, obsv, pred_hat, targets, t_idx, z, g_label, g_code, loss_part=None):
+def disc_dpred(d_w, obsv, pred_hat, targets, t_idx, z, g_label, g_code, loss_part=None, obs_len=None):
     """Generator phase: D(obsv, pred_hat) forward + the backward of its prediction heads in one launch;
-    returns d(g_loss)/d(pred_hat) (B,Tp,4)."""
+    returns d(g_loss)/d(pred_hat) (B,Tp,4).  obs_len (B,) int32 on the device: ragged histories, as disc_forward()
+    (sw_disc_dpred_ragged); None: sw_disc_dpred."""
+    if obs_len is not None:
+        obs_len = _check_obs_len_tensor(obs_len, obsv.shape[0], obsv.device)
     L.require_gpu(obsv)
     obsv, pred_hat = obsv.contiguous(), pred_hat.contiguous()
     B, To, Tp = obsv.shape[0], obsv.shape[1], pred_hat.shape[1]
     x_mode = {2: 0, 4: 1}[obsv.shape[2]]
     dpred = torch.empty(B, Tp, 4, device=obsv.device)
-    L.call("sw_disc_dpred", L.ptr(obsv), To, x_mode, L.ptr(pred_hat), L.ptr(d_w), B, Tp, L.ptr(targets), int(t_idx), L.ptr(z),
-           g_label, g_code, L.ptr(dpred), None, None, L.ptr(loss_part), L.stream())
+    if obs_len is None:
+        L.call("sw_disc_dpred", L.ptr(obsv), To, x_mode, L.ptr(pred_hat), L.ptr(d_w), B, Tp, L.ptr(targets), int(t_idx), L.ptr(z),
+               g_label, g_code, L.ptr(dpred), None, None, L.ptr(loss_part), L.stream())
+    else:
+        L.call("sw_disc_dpred_ragged", L.ptr(obsv), To, x_mode, L.ptr(obs_len), L.ptr(pred_hat), L.ptr(d_w), B, Tp, L.ptr(targets),
+               int(t_idx), L.ptr(z), g_label, g_code, L.ptr(dpred), None, None, L.ptr(loss_part), L.stream())
     return dpred
 
 

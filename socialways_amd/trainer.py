@@ -482,7 +482,7 @@ class SocialWaysTrainer:
             self.release_graphs()
 
     def step(self, obsv, pred, sub_batches, zeros_val, ones_val, noise, ss=1.0, global_B=None, out=None, global_row0=0,
-             variety_noise=None):
+             variety_noise=None, obs_len=None):
         """One packed batch (train.py:458-554) on this rank's rows.  obsv (B,To,2), pred (B,Tp,2) and
         noise (B,32) are tensors (noise normally lives on the host, like train.py:473); `global_B` = agents
         of the whole packed batch over all ranks.
@@ -493,9 +493,20 @@ class SocialWaysTrainer:
         the raw (U+3, tiles, 3) partials without that extra reduction (bench loop).
         With `use_graph` the whole step - ~35 kernels incl. the input staging and the Adam updates - is
         captured once per batch layout into a hipGraph and replayed: per step the host only fills a pinned
-        slot (pointers of the track slices, z, the two label-noise scalars) and launches the graph."""
+        slot (pointers of the track slices, z, the two label-noise scalars) and launches the graph.
+        obs_len (B,) - tensor, numpy array or list: ragged histories.  Row a holds obs_len[a] valid frames, 2 .. To,
+        right-aligned in obsv and trains exactly as if its two observation LSTMs (encoder, discriminator) ran on those
+        frames alone from the zero state; the padding is never read.  Such a step runs eagerly, never through a captured
+        graph, on the unfused route: no precomputed D observation pass, D updates as disc_forward + disc_backward_gan
+        (with the fused Adam), the generator phase as disc_dpred (or, where Tp > 24, disc_forward + disc_backward_gan),
+        never inside the decode BPTT launch; the backward launches, losses and all-reduce points are the dense step's."""
         self._resolve_collectives()
         B = obsv.shape[0]
+        self._obs_len = None        # read by _step_body of this step only
+        if obs_len is not None:
+            if obsv.shape[2] != 2:
+                raise ValueError("step(obs_len=...) takes positions (B, To, 2)")
+            obs_len = ops.obs_len_arg(obs_len, B, obsv.shape[1], 2, self.device)
         Bg = float(global_B if global_B is not None else B)
         dev = self.device
         self._row0 = int(global_row0)       # first row of this rank's shard in the packed batch (variety term only)
@@ -510,7 +521,7 @@ class SocialWaysTrainer:
         part = None
         if not self._graphs and self.ws.retired:      # eager-only runs: nothing captured can reference an outgrown workspace
             self.ws.release_retired()                 # (stream-ordered allocator: kernels already queued on it stay valid)
-        if self.use_graph and self.use_variety_loss != "fixed":    # the folded K-sample step runs eagerly
+        if self.use_graph and self.use_variety_loss != "fixed" and obs_len is None:    # the folded K-sample and the ragged step run eagerly
             # one graph set per packed-batch layout; datasets with ragged scenes produce many layouts, so the
             # number of captured layouts is capped and the rest of the steps run eagerly
             scenes = ops.SceneIndex.get(sub_batches, B, dev)
@@ -524,7 +535,11 @@ class SocialWaysTrainer:
             noise = self._pad_z(noise.to(dev, non_blocking=True)).contiguous()
             # label-noise scalars of train.py:471-472 live in device memory: [zeros_val, ones_val]
             targets = torch.tensor([float(zeros_val), float(ones_val)], dtype=torch.float32).to(dev, non_blocking=True)
-            self._step_impl(obsv.contiguous(), pred.contiguous(), None, scenes, targets, noise, float(ss), Bg, part)
+            self._obs_len = obs_len
+            try:
+                self._step_impl(obsv.contiguous(), pred.contiguous(), None, scenes, targets, noise, float(ss), Bg, part)
+            finally:
+                self._obs_len = None
         if out is False:           # caller reads the static partials before the next step overwrites them
             return part
         return part.sum(1, dtype=torch.float64)
@@ -712,6 +727,7 @@ class SocialWaysTrainer:
         g_label = 1.0 / Bg
         g_code = (self.loss_info_w if self.use_info_loss else 0.0) / (2.0 * Bg)
         noise_src, self._noise_src = self._noise_src, None      # set by the staging of this step (graph / warm-up path)
+        ol = getattr(self, "_obs_len", None)                    # ragged histories (step(obs_len=...)): the unfused route
         if pred4 is None:          # real future as 4-d (train.py:470); the observation stays 2-d: kernels form (p, v) on the fly
             pred4 = torch.empty(B, Tp, 4, device=dev)
             o4_scratch = ws.get("o4", B * obsv.shape[1] * 4)
@@ -724,7 +740,7 @@ class SocialWaysTrainer:
             # is the prediction every other loss term and the ADE/FDE sums see
             # (the encoder over the observed steps and the social pooling do not depend on z: once for all K copies)
             pred_hat_k, gctx = ops.gen_forward_k(enc._flat, emb._flat, att._flat, dec._flat, obsv,
-                                                 torch.cat([noise, self._vnoise]), scenes, Tp, G.use_social, KV, ws=ws)
+                                                 torch.cat([noise, self._vnoise]), scenes, Tp, G.use_social, KV, ws=ws, obs_len=ol)
             pred_hat = pred_hat_k[:B]
             out[U + 2].zero_()
             L.call("sw_ade_fde", L.ptr(pred_hat), L.ptr(pred), B, Tp, 1.0 / float(ss), L.ptr(out[U + 2]),
@@ -733,10 +749,11 @@ class SocialWaysTrainer:
         else:
             # the decode kernel also leaves the ADE/FDE partial sums of the prediction (train.py:546-551)
             # ... and, while it leaves CUs idle, the observation LSTM of the first D pass (independent of the generator)
-            d_pre = ops.d_obs_buffer(ws, B, obsv.shape[1], Tp) if obsv.shape[2] == 2 else None
+            d_pre = ops.d_obs_buffer(ws, B, obsv.shape[1], Tp) if obsv.shape[2] == 2 and ol is None else None
             pred_hat, gctx = ops.gen_forward(enc._flat, emb._flat, att._flat, dec._flat, obsv, noise, scenes, Tp,
                                              G.use_social, save=True, ws=ws, ade=(pred, 1.0 / float(ss), out[U + 2]),
-                                             noise_src=noise_src, d_obs=(D._flat, d_pre) if d_pre is not None else None)
+                                             noise_src=noise_src, d_obs=(D._flat, d_pre) if d_pre is not None else None,
+                                             obs_len=ol)
         d_gflat = D.grad_views()
         backup = None
         # ---- discriminator updates (train.py:476-499) ------------------------------------------------
@@ -749,7 +766,7 @@ class SocialWaysTrainer:
             fuse = (self._fuse_d_adam and isinstance(self.D_optimizer, PackedAdam) and self.D_optimizer.fusable
                     and not (self.world > 1 or self._force_dist))
             adam = self.D_optimizer.fused_args(None if steps is None else steps[u]) if fuse else None
-            if obsv.shape[2] == 2 and ops.disc_update_supported(D._flat, B, obsv.shape[1], Tp):
+            if ol is None and obsv.shape[2] == 2 and ops.disc_update_supported(D._flat, B, obsv.shape[1], Tp):
                 # shapes that leave CUs idle: forward + loss gradients + backward of the pass in ONE launch (sw_disc_update)
                 ops.disc_update(D._flat, obsv, [pred_hat, pred4], targets, (0, 1), noise, g_label, g_code, d_gflat, ws,
                                 obs_pre=(u == 0 and d_pre is not None), w_snapshot=backup if u == 1 else None,
@@ -757,7 +774,7 @@ class SocialWaysTrainer:
             else:
                 labels, codes, dctx = ops.disc_forward(D._flat, obsv, [pred_hat, pred4], save=True, ws=ws,
                                                        save_lstm=2 if (u == 0 and d_pre is not None) else 1,
-                                                       w_snapshot=backup if u == 1 else None)
+                                                       w_snapshot=backup if u == 1 else None, obs_len=ol)
                 ops.disc_backward_gan(D._flat, dctx, labels, codes, targets, (0, 1), noise, g_label, g_code, d_gflat, (), ws=ws,
                                       loss_part=out[u], adam=adam)
             if self._exchange_adam(self.D_optimizer, d_gflat):
@@ -778,13 +795,13 @@ class SocialWaysTrainer:
         dfuse = None
         one_pass = ops.disc_dpred_supported(Tp)
         if (ops.DFUSE and one_pass and KV == 1 and not self.use_l2_loss and self.use_variety_loss is False
-                and obsv.shape[2] == 2):
+                and obsv.shape[2] == 2 and ol is None):
             dfuse = (D._flat, pred_hat, targets, 1, noise, g_label, g_code, out[U + 1])
         dpred = None
         if dfuse is None and one_pass:
-            dpred = ops.disc_dpred(D._flat, obsv, pred_hat, targets, 1, noise, g_label, g_code, loss_part=out[U + 1])
+            dpred = ops.disc_dpred(D._flat, obsv, pred_hat, targets, 1, noise, g_label, g_code, loss_part=out[U + 1], obs_len=ol)
         elif dfuse is None:
-            labels, codes, dctx = ops.disc_forward(D._flat, obsv, [pred_hat], save=True, ws=ws, save_lstm=0)
+            labels, codes, dctx = ops.disc_forward(D._flat, obsv, [pred_hat], save=True, ws=ws, save_lstm=0, obs_len=ol)
             dpred = ops.disc_backward_gan(D._flat, dctx, labels, codes, targets, (1,), noise, g_label, g_code, None, (True,),
                                           ws=ws, loss_part=out[U + 1])[0]
         if self.use_l2_loss:                                                 # train.py:525-526
@@ -858,9 +875,25 @@ class SocialWaysTrainer:
         the union over ranks is the single-process z.  The z of the batches that share a step_many launch is one fill
         launch in front of the graph launch on the same stream, read by the steps through their z-resident path (no
         pinned-slot copy).  The label-noise scalars stay the reference's two host draws.
-        A dataset with obs_len (ragged histories) is refused: there are no ragged backward kernels."""
-        _refuse_ragged(data, "train_epoch()", "there are no ragged backward kernels - train on full windows (create_dataset) "
-                       "and evaluate the ragged ones with evaluate*() / evaluate_history()")
+        A dataset with obs_len (ragged histories) is refused: its steps run eagerly through train_epoch_ragged()."""
+        _refuse_ragged(data, "train_epoch()", "its graph-captured steps have no ragged form - train on the ragged windows with "
+                       "train_epoch_ragged(), or on full windows (create_dataset) and evaluate the ragged ones with "
+                       "evaluate*() / evaluate_history()")
+        return self._train_epoch(data, batch_size, draw, None)
+
+    def train_epoch_ragged(self, data, batch_size, draw=None):
+        """train_epoch() for a dataset that carries obs_len (create_dataset_ragged / SceneDataset(obs_len=...)): the same
+        packed batches, RNG draws (host stream or `self.noise`), scene sharding, return value and epoch counter, one eager
+        step(..., obs_len=data.obs_len[rows]) per packed batch (see step(): the unfused route, no graph capture).
+        A dataset without obs_len is refused: train_epoch() is its call."""
+        ol = getattr(data, "obs_len", None)
+        if ol is None:
+            raise L.SocialWaysHipError("train_epoch_ragged() needs a dataset with obs_len (create_dataset_ragged, "
+                                       "SceneDataset(obs_len=...)): train a dataset of full windows with train_epoch()")
+        return self._train_epoch(data, batch_size, draw, ol)
+
+    def _train_epoch(self, data, batch_size, draw, obs_len):
+        """The epoch loop of train_epoch() (obs_len None) and train_epoch_ragged() (obs_len = data.obs_len)."""
         outs, sizes = [], []
         pend, pend_key = [], None        # consecutive packed batches of one layout share a graph launch
         dn = self._device_noise(None) if draw is None else None
@@ -910,15 +943,17 @@ class SocialWaysTrainer:
                 r0, r1 = int(sb[lo, 0]), int(sb[hi - 1, 1])
                 sbl = sb[lo:hi] - r0
             item = (data.obsv[a + r0:a + r1], data.pred[a + r0:a + r1], zv, ov, noise[r0:r1] if noise is not None else None)
-            if fixed:                 # the folded K-sample step is not graph-captured: one step() per packed batch
-                flush()
+            if fixed or obs_len is not None:     # the folded K-sample step and the ragged step are not graph-captured:
+                flush()                          # one step() per packed batch
+                z0, vnl = item[4], None
                 if dn is not None:    # draws 0 .. variety_k-1 of this rank's rows in one launch, padded to the kernels' width
-                    z = dn.fill(r1 - r0, self.noise_len, domain=TRAIN, step=step_i, n_draws=self.variety_k, row0=r0,
-                                ld=self.Z_COLS, device=self.device)[0]
-                    z0, vnl = z[0], z[1:].reshape(-1, self.Z_COLS)
-                else:
-                    z0, vnl = item[4], vn[:, r0:r1].reshape(-1, self.noise_len)
-                outs.append(self.step(*item[:2], sbl, zv, ov, z0, data.ss, global_B=bs, global_row0=r0, variety_noise=vnl))
+                    z = dn.fill(r1 - r0, self.noise_len, domain=TRAIN, step=step_i, n_draws=self.variety_k if fixed else 1,
+                                row0=r0, ld=self.Z_COLS, device=self.device)[0]
+                    z0, vnl = z[0], z[1:].reshape(-1, self.Z_COLS) if fixed else None
+                elif fixed:
+                    vnl = vn[:, r0:r1].reshape(-1, self.noise_len)
+                outs.append(self.step(*item[:2], sbl, zv, ov, z0, data.ss, global_B=bs, global_row0=r0, variety_noise=vnl,
+                                      obs_len=obs_len[a + r0:a + r1] if obs_len is not None else None))
                 continue
             # consecutive packed batches with the same local layout share one graph launch (step_many)
             key = (bs, r0, np.asarray(sbl).tobytes())

@@ -10,7 +10,17 @@ and by the method of tools/rank_timing.py: host clock around calls that end in a
       sw_enc_lstm_fwd, sw_disc_score_ragged vs sw_disc_score - what the select per step costs.  One timed call = `--launches`
       launches back to back and a synchronisation; ms per launch.  The results are compared bit for bit first.
 
-    python tools/ragged_timing.py [--repeats 9] [--out profiles/ragged_timing.txt]
+  (c) training on ragged histories, on the rows and futures of the same chunks as ONE packed batch: SocialWaysTrainer.step()
+      eager and dense, against step(obs_len=all To), against step(obs_len=uniform 2 .. 8), against the graph-captured dense
+      step.  The first gap is the price of the ragged step's unfused route (no sw_disc_update, no D observation pass in the
+      decode launch, no D pass inside the decode BPTT), the second what the lengths themselves cost, the third what a ragged
+      sw_disc_update and a captured ragged step could win back.  Every side has a trainer of its own from the same seed and
+      takes the same z and label noise; a timed call ends in the host read of the step's sums.  And, as in (b),
+      sw_enc_lstm_fwd_ragged_save against sw_enc_lstm_fwd with saves at full length: what the selects on the saved row cost.
+      Written to --train-out.
+
+    python tools/ragged_timing.py [--repeats 9] [--legs abc] [--out profiles/ragged_timing.txt]
+                                  [--train-out profiles/ragged_train_timing.txt]
 """
 import os
 import statistics
@@ -68,10 +78,90 @@ def launch_pairs(tr, obsv, sb, K, launches):
     return {"enc": enc, "enc_ragged": enc_ragged, "score": score, "score_ragged": score_ragged}
 
 
+def step_sides(obsv, pred, sb, full, mixed):
+    """{name: fn} of the four training steps of (c); every side owns a trainer drawn from the same seed."""
+    sw = T.sw
+    B = obsv.shape[0]
+    z = torch.rand(B, 32, device=obsv.device, generator=torch.Generator(device="cuda").manual_seed(11))
+
+    def side(use_graph, obs_len):
+        torch.manual_seed(0)
+        tr = sw.SocialWaysTrainer(12, use_social=True, device="cuda:0", use_graph=use_graph)
+
+        def call():
+            out = tr.step(obsv, pred, sb, 0.04, 0.93, z, 1.0, obs_len=obs_len)
+            return float(out.sum())      # the host synchronisation
+        return call
+    return {"eager": side(False, None), "full": side(False, full), "mixed": side(False, mixed), "graph": side(True, None)}
+
+
+def enc_save_pair(tr, obsv, launches):
+    """sw_enc_lstm_fwd with saves against sw_enc_lstm_fwd_ragged_save at full length, `launches` launches and a synchronisation."""
+    L = T.sw._lib
+    B, To = obsv.shape[0], obsv.shape[1]
+    enc_w, st = tr.G.encoder.packed(), L.stream()
+    full = torch.full((B,), To, dtype=torch.int32, device=obsv.device)
+    bufs = [[torch.empty(B, 64, device=obsv.device), torch.empty(B, 64, device=obsv.device),
+             torch.empty(To, B, 384, device=obsv.device), torch.empty(To, B, 4, device=obsv.device)] for _ in range(2)]
+
+    def enc():
+        hT, cT, act, x4s = bufs[0]
+        for _ in range(launches):
+            L.call("sw_enc_lstm_fwd", L.ptr(obsv), 0, L.ptr(enc_w), None, None, B, To, L.ptr(hT), L.ptr(cT), None, L.ptr(act),
+                   L.ptr(x4s), 0, st)
+        torch.cuda.synchronize()
+
+    def enc_ragged():
+        hT, cT, act, x4s = bufs[1]
+        for _ in range(launches):
+            L.call("sw_enc_lstm_fwd_ragged_save", L.ptr(obsv), 0, L.ptr(enc_w), L.ptr(full), B, To, L.ptr(hT), L.ptr(cT),
+                   L.ptr(act), L.ptr(x4s), st)
+        torch.cuda.synchronize()
+    enc(), enc_ragged()
+    assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(*bufs))
+    return {"enc": enc, "enc_ragged": enc_ragged}
+
+
+def train_leg(a, tr):
+    lines = ["(c) SocialWaysTrainer.step() on the first evaluation chunk as one packed batch: eager dense, step(obs_len=all To), "
+             "step(obs_len=uniform 2 .. 8), graph-captured dense; host clock around the call, ms; %d alternating repeats after %d "
+             "warm-up calls of each; %s" % (a.repeats, max(a.warmup, 4), torch.cuda.get_device_name(0)),
+             "%-88s %6s %28s %28s %8s %28s %8s %28s %8s" % ("shape", "B", "eager dense median [min, max]", "obs_len = all To",
+                                                          "/eager", "obs_len uniform 2 .. 8", "/full", "graph dense", "/full")]
+    enc_lines = ["", "sw_enc_lstm_fwd_ragged_save at full length (obs_len all To) vs sw_enc_lstm_fwd with saves, same bits; ms per "
+                 "launch, %d launches per timed call; %d alternating repeats after %d warm-up calls" % (a.launches, a.repeats, a.warmup),
+                 "%-88s %6s %28s %28s %8s" % ("shape", "B", "sw_enc_lstm_fwd median [min, max]", "sw_enc_lstm_fwd_ragged_save", "ratio")]
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        _, obsv, pred, sb = next(T.host_chunks(tr, T.held_out_set(n_scenes, agents), K, just_one))
+        obsv, pred = obsv.contiguous(), pred.contiguous()
+        B, To = obsv.shape[0], obsv.shape[1]
+        gen = torch.Generator(device="cuda").manual_seed(7)
+        mixed = torch.randint(2, To + 1, (B,), device="cuda", generator=gen, dtype=torch.int32)
+        full = torch.full((B,), To, dtype=torch.int32, device="cuda")
+        ms, _ = T.alternate(step_sides(obsv, pred, sb, full, mixed), max(a.warmup, 4), a.repeats)      # the graph is captured on the third call
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        lines.append("%-88s %6d %28s %28s %8.3f %28s %8.3f %28s %8.3f"
+                     % (name, B, cell(ms["eager"]), cell(ms["full"]), med["full"] / med["eager"], cell(ms["mixed"]),
+                        med["mixed"] / med["full"], cell(ms["graph"]), med["graph"] / med["full"]))
+        ms, _ = T.alternate(enc_save_pair(tr, obsv, a.launches), a.warmup, a.repeats)
+        per = {k: [t / a.launches for t in v] for k, v in ms.items()}
+        enc_lines.append("%-88s %6d %28s %28s %8.3f" % (name, B, cell(per["enc"], fmt=PER_LAUNCH), cell(per["enc_ragged"], fmt=PER_LAUNCH),
+                                                      statistics.median(per["enc_ragged"]) / statistics.median(per["enc"])))
+    T.write_out(lines + enc_lines, a.train_out)
+
+
 def main():
-    a = T.parse(__doc__, 9, 9, lambda ap: ap.add_argument("--launches", type=int, default=20, help="(b): launches per timed call"))
+    def more(ap):
+        ap.add_argument("--launches", type=int, default=20, help="(b), (c): launches per timed call")
+        ap.add_argument("--legs", default="abc", help="the legs to run, any of a, b, c")
+        ap.add_argument("--train-out", default=None, help="(c): where its table is written")
+    a = T.parse(__doc__, 9, 9, more)
     T.load("ragged_timing.py")
     tr = T.trainer()
+    if "c" in a.legs:
+        train_leg(a, tr)
+    if not set("ab") & set(a.legs):
+        return
     chunks = []
     for name, n_scenes, agents, K, just_one in T.SHAPES:
         obsv, sb = first_chunk(tr, T.held_out_set(n_scenes, agents), K, just_one)
@@ -106,7 +196,7 @@ def main():
                         med["enc_ragged"] / med["enc"], cell(per["score"], fmt=PER_LAUNCH), cell(per["score_ragged"], fmt=PER_LAUNCH),
                         med["score_ragged"] / med["score"]))
     lines.append("")
-    lines.append("(c) not measured: skipping the steps in front of a tile's earliest start - the loop runs To steps for every tile.")
+    lines.append("not measured: skipping the steps in front of a tile's earliest start - the loop runs To steps for every tile.")
     T.write_out(lines, a.out)
 
 
