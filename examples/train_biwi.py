@@ -19,6 +19,8 @@
 * `--train-ragged` (with `--min-past M`): the ragged windows in front of the held-out part are what the model trains on
   (train_epoch_ragged: one eager step per packed batch on the unfused route, no graph capture - slower per step than
   train_epoch)
+* `--ragged-fused` (with `--train-ragged`): SocialWaysTrainer(ragged_fused=True) - the ragged D updates in one launch each and
+  the ragged steps graph-captured per layout like the dense ones (same weights and losses bit for bit)
 """
 import argparse
 import os
@@ -71,7 +73,11 @@ def main(argv=None):
     ap.add_argument("--train-ragged", action="store_true",
                     help="with --min-past M: train on the ragged windows in front of the held-out part (train_epoch_ragged: "
                          "eager steps on the unfused route) instead of the full windows only")
+    ap.add_argument("--ragged-fused", action="store_true",
+                    help="with --train-ragged: the fused ragged step (ragged_fused=True: one-launch D updates, graph-captured steps)")
     args = ap.parse_args(argv)
+    if args.ragged_fused and not args.train_ragged:
+        ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
         ap.error("--train-ragged needs --min-past M")
     if args.train_ragged and args.hidden_size != 64:
@@ -118,7 +124,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
-                              process_group=pg)
+                              process_group=pg, **(dict(ragged_fused=True) if args.ragged_fused else {}))
     if args.device_noise is not None:     # the same seed on every rank: the union of the shards is the single-process z
         tr.noise = sw.DeviceNoise(args.device_noise)
     for epoch in range(1, args.epochs + 1):

@@ -394,6 +394,16 @@ int sw_disc_update(const float* obsv /*[B,To,2]*/, int To, const float* const* p
                    const float* targets, int t0, int t1, const float* z, float g_label, float g_code, float* ddelta,
                    float* d_d_w, float* wgrad_ws, float* loss_part /*or NULL*/, float* adam_w /*or NULL*/, float* adam_m,
                    float* adam_v, const float* adam_step, double lr, double beta1, double beta2, double eps, void* stream);
+/*      sw_disc_update_ragged = sw_disc_update over RAGGED observation histories: what sw_disc_fwd_ragged(nb = 2, x_mode 0,
+ *      save_lstm 1) followed by sw_disc_bwd_gan[_adam] computes, into the same buffers, bit for bit.  Row b holds
+ *      clamp(obs_len[b], 2, To) valid frames right-aligned in obsv; the padding is never read.  sw_disc_update's arguments
+ *      without obs_pre (ragged rows have no precomputed observation pass), obs_len (B int32, device) behind To; a NULL
+ *      obs_len is SW_EARG, a shape outside sw_disc_update_supported() SW_ESHAPE.                                       */
+int sw_disc_update_ragged(const float* obsv /*[B,To,2]*/, int To, const int* obs_len /*[B]*/, const float* const* pred4, const float* d_w,
+                          int B, int Tp, float* const* label, float* const* code, float* dsave, float* w_snapshot /*or NULL*/,
+                          const float* targets, int t0, int t1, const float* z, float g_label, float g_code, float* ddelta,
+                          float* d_d_w, float* wgrad_ws, float* loss_part /*or NULL*/, float* adam_w /*or NULL*/, float* adam_m,
+                          float* adam_v, const float* adam_step, double lr, double beta1, double beta2, double eps, void* stream);
 
 /* ---- generator phase in one launch (train.py:510-523, 538): D forward on (obsv, pred_hat) fused with the backward of
  *      its prediction heads: dpred4 = d(g_loss)/d(pred_hat) with g_loss = mse(label, targets[t_idx]) +
@@ -533,6 +543,18 @@ int sw_stage_step_zdev(const float* slot, int B, int To, int Tp, float* obsv_dst
                        float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates, const float* enc_w,
                        const float* dec_w, const float* emb_w, const float* att_w, float* img, const float* d_w, float* d_img,
                        const int* d_tab, int z_device, void* stream);
+
+/*      sw_stage_step_ragged = sw_stage_step_zdev for a captured step over RAGGED observation histories, with a slot layout
+ *      of its own: words [0..7] as above, [8,9] the device pointer of z when z_device = 1, [10,11] the device pointer of this
+ *      step's obs_len (B int32, contiguous), z values from word SW_STAGE_HEADER_RAGGED on when z_device = 0.  It writes what
+ *      sw_stage_step_zdev writes and obs_len_dst[i] = clamp(obs_len[i], 2, To), the static buffer the graph's ragged kernels
+ *      read.  z_dst and obs_len_dst are required (SW_EARG): the ragged encoder launch pulls no z, so this launch fills z
+ *      in both z modes.                                                                                                   */
+#define SW_STAGE_HEADER_RAGGED 12
+int sw_stage_step_ragged(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst, float* pred4_dst,
+                         float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates, const float* enc_w,
+                         const float* dec_w, const float* emb_w, const float* att_w, float* img, const float* d_w, float* d_img,
+                         const int* d_tab, int z_device, int* obs_len_dst /*[B]*/, void* stream);
 
 /* ---- derived weight images of the DISCRIMINATOR (Discriminator.forward, train.py:294-309, as the kernels consume it):
  *      MFMA A-operand images of lstm.weight_hh and its transpose, and the eight head matrices transposed and zero-padded

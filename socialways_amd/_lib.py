@@ -74,6 +74,9 @@ PROTOTYPES = {
     "sw_disc_dpred_supported": (_i, [_i]),
     "sw_disc_update": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
+    "sw_disc_update_ragged": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   _vp]),
     "sw_disc_dpred": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "sw_disc_score": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sw_disc_score_ragged": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -88,6 +91,8 @@ PROTOTYPES = {
     "sw_gen_images": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sw_stage_step_img": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sw_stage_step_zdev": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sw_stage_step_ragged": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                  _vp]),
     "sw_disc_image_floats": (_i, [_i]),
     "sw_disc_image_table": (_i, [_i, _vp]),
     "sw_disc_images": (_i, [_vp, _vp, _vp, _i, _vp]),

@@ -396,12 +396,14 @@ __device__ __forceinline__ void disc_images_scatter(const float* __restrict__ d_
 void sw_ktime_begin(const char* name, hipStream_t st);
 void sw_ktime_end(hipStream_t st);
 extern bool g_sw_ktime_on;
-#define SW_LAUNCH(kernel, grid, block, lds, stream, ...)                           \
+// SW_LAUNCH_AS: under a name of the caller's choice (the instances of a kernel template are timed as one kernel).
+#define SW_LAUNCH_AS(name, kernel, grid, block, lds, stream, ...)                   \
   do {                                                                              \
-    if (g_sw_ktime_on) sw_ktime_begin(#kernel, (stream));                           \
+    if (g_sw_ktime_on) sw_ktime_begin(name, (stream));                              \
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);              \
     if (g_sw_ktime_on) sw_ktime_end((stream));                                      \
   } while (0)
+#define SW_LAUNCH(kernel, grid, block, lds, stream, ...) SW_LAUNCH_AS(#kernel, kernel, grid, block, lds, stream, __VA_ARGS__)
 
 // host-side error plumbing ---------------------------------------------------------------------
 void sw_set_error(const char* what, hipError_t e);

@@ -283,11 +283,18 @@ __host__ __device__ inline UpdLds upd_lds(int Tp) {
 }
 }  // namespace
 
+// RAGGED (sw_disc_update_ragged): the observation pass starts row b at step s = To - obs_len[b] (clamped, obs_start) and
+// keeps the zero state in front of it by a SELECT on the cell's result - the values lstm_obs_loop_ragged<0, SAVE_ROWS> leaves
+// (sw_lstm_dev.h), its products per step included: the recurrent product stays on step 0.  Zero gates with zero c_t, c_{t-1}
+// give zero gate gradients and dc_{t-1} = 0, so everything behind the observation pass - heads, loss gradients, BPTT - is
+// the dense code.  A template parameter with obs_len as the LAST argument, as disc_score_kernel: the dense instance keeps
+// the dense loop and its code.  There is no precomputed observation pass for ragged rows (obs_pre = 0).
+template <bool RAGGED>
 __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     const float* __restrict__ obsv, int To, const float* __restrict__ pred_a, const float* __restrict__ pred_b,
     const float* __restrict__ d_w, int B, int Tp, float* __restrict__ label_a, float* __restrict__ label_b,
     float* __restrict__ code_a, float* __restrict__ code_b, float* __restrict__ dsave, int obs_pre, float* __restrict__ w_snap,
-    DiscLoss gl, float* __restrict__ ddelta, const float* __restrict__ dimg) {
+    DiscLoss gl, float* __restrict__ ddelta, const float* __restrict__ dimg, const int* __restrict__ obs_len) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const UpdLds U = upd_lds(Tp);
   const HeadLds& F = U.F;
@@ -328,7 +335,44 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
   // gradient) and the step's input go to memory: a sixth of the saved bytes, no row loads in the BPTT.
   const bool reg8 = !obs_pre && To == 8;
   f32x4 sg[8][4], sc[8];
-  if (reg8) {
+  int s0 = 0;             // RAGGED: the step this lane's row starts at (requested here: it arrives under the staging above)
+  if constexpr (RAGGED) {
+    __builtin_assume(obs_len != nullptr);
+    s0 = obs_start(obs_len, b, To, 0);
+  }
+  if (RAGGED && reg8) {
+    // the unrolled loop below for a start step per lane: every lane computes every step (W_hh h on step 0 too: exact
+    // zeros, the products of lstm_obs_loop_ragged) and selects the zero state in front of its start, so sg[t] / sc[t] and
+    // the h row / input that go to dsave hold SELECTED zeros there.  The stores stay unconditional.
+    float xa, xq;
+    obs_x4_load_from(obsv, b, 0, s0, 8, lg, xa, xq);
+    asm volatile("" : "+v"(xa), "+v"(xq));
+    float* hrow_g = dsave + ds.act + (size_t)b * 384 + 320 + u0 + 4 * lg;
+    float* xrow = dsave + ds.x4s + (size_t)b * 4 + lg;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const float xb = xa - (lg >= 2 ? xq : 0.f);
+      obs_x4_load_from(obsv, b, t + 1 < 8 ? t + 1 : 7, s0, 8, lg, xa, xq);
+      const float* hrow = &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg];
+      lstm_cell(W, xb, hrow, sg[t], c, h);
+      const bool on = t >= s0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        c[r] = on ? c[r] : 0.f;
+        h[r] = on ? h[r] : 0.f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) sg[t][g][r] = on ? sg[t][g][r] : 0.f;
+      }
+      sc[t] = c;
+      st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
+      st4g(hrow_g, h);
+      *xrow = on ? xb : 0.f;
+      hrow_g += (size_t)B * 384;
+      xrow += (size_t)B * 4;
+      sw_barrier();
+      asm volatile("" : "+v"(xa), "+v"(xq));
+    }
+  } else if (reg8) {
     float xa, xq;
     obs_x4_load(obsv, b, 0, 8, lg, xa, xq);
     asm volatile("" : "+v"(xa), "+v"(xq));
@@ -351,7 +395,8 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
       asm volatile("" : "+v"(xa), "+v"(xq));
     }
   } else if (!obs_pre) {
-    lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, dsave + ds.act, dsave + ds.x4s);
+    if constexpr (RAGGED) lstm_obs_loop_ragged<0, SAVE_ROWS, 1>(W, hbuf, obsv, To, b, s0, c, h, dsave + ds.act, dsave + ds.x4s, B);
+    else lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, dsave + ds.act, dsave + ds.x4s);
   }
   const float* hlast = &hbuf[(To & 1) * 16 * SW_HLD];
 
@@ -879,31 +924,62 @@ extern "C" int sw_disc_update_supported(const float* d_w, int B, int To, int Tp)
 // adam_w = d_w): what sw_disc_fwd(nb = 2, x_mode 0, save_lstm 1 | 2) followed by sw_disc_bwd_gan[_adam] computes, to the
 // same buffers.  obs_pre = 1: the observation-LSTM rows are already in dsave (sw_dec_rollout_fwd_aux).  Requires
 // sw_disc_update_supported() (SW_ESHAPE otherwise).
-extern "C" int sw_disc_update(const float* obsv, int To, const float* const* pred4, const float* d_w, int B, int Tp,
-                              float* const* label, float* const* code, float* dsave, int obs_pre, float* w_snapshot,
+// sw_disc_update and sw_disc_update_ragged: one set of checks, one grid rule; the dense entry launches the dense instance
+static int disc_update_launch(bool ragged, const float* obsv, int To, const int* obs_len, const float* const* pred4, const float* d_w,
+                              int B, int Tp, float* const* label, float* const* code, float* dsave, int obs_pre, float* w_snapshot,
                               const float* targets, int t0, int t1, const float* z, float g_label, float g_code, float* ddelta,
                               float* d_d_w, float* wgrad_ws, float* loss_part, float* adam_w, float* adam_m, float* adam_v,
                               const float* adam_step, double lr, double beta1, double beta2, double eps, void* stream) {
   if (!obsv || !pred4 || !pred4[0] || !pred4[1] || !d_w || !label || !label[0] || !label[1] || !code || !code[0] || !code[1] ||
       !dsave || !targets || !z || !ddelta || !d_d_w || !wgrad_ws || t0 < 0 || t1 < 0 || To < 2)
     return SW_EARG;
+  if (ragged && !obs_len) return SW_EARG;
   if (adam_w && (!adam_m || !adam_v || !adam_step || adam_w != d_w)) return SW_EARG;
   if (B == 0) return SW_OK;
   if (!sw_disc_update_supported(d_w, B, To, Tp)) return SW_ESHAPE;
   const int lds = upd_lds(Tp).total * 4;
-  static int have = 0;
-  if (int rc = sw_set_lds((const void*)disc_update_kernel, lds, have)) return rc;
+  static int have = 0, have_ragged = 0;
+  if (int rc = ragged ? sw_set_lds((const void*)disc_update_kernel<true>, lds, have_ragged)
+                      : sw_set_lds((const void*)disc_update_kernel<false>, lds, have))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const DiscImages di = sw_disc_images_for(d_w, Tp);
   DiscLoss gl{targets, z, t0, t1, g_label, g_code, 1, loss_part};
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   WgBatch wb;
   if (int rc = disc_wgrad_problems(wb, dsave, ddelta, 2, B, To, Tp, d_d_w)) return rc;
-  SW_LAUNCH(disc_update_kernel, dim3(tiles), dim3(SW_THREADS), lds, st, obsv, To, pred4[0], pred4[1], d_w, B, Tp, label[0],
-            label[1], code[0], code[1], dsave, obs_pre ? 1 : 0, w_snapshot, gl, ddelta, di.img);
+  // (both instances are timed as "disc_update_kernel": SW_LAUNCH_AS)
+  if (ragged)
+    SW_LAUNCH_AS("disc_update_kernel", disc_update_kernel<true>, dim3(tiles), dim3(SW_THREADS), lds, st, obsv, To, pred4[0], pred4[1],
+                 d_w, B, Tp, label[0], label[1], code[0], code[1], dsave, 0, w_snapshot, gl, ddelta, di.img, obs_len);
+  else
+    SW_LAUNCH_AS("disc_update_kernel", disc_update_kernel<false>, dim3(tiles), dim3(SW_THREADS), lds, st, obsv, To, pred4[0], pred4[1],
+                 d_w, B, Tp, label[0], label[1], code[0], code[1], dsave, obs_pre ? 1 : 0, w_snapshot, gl, ddelta, di.img,
+                 (const int*)nullptr);
   SW_CHECK_LAUNCH("disc_update_kernel");
   WgAdam ad = disc_adam(adam_w, adam_m, adam_v, adam_step, d_d_w, lr, beta1, beta2, eps, Tp);
   return wg_launch_adam(wb, wgrad_ws, ad, st);
+}
+extern "C" int sw_disc_update(const float* obsv, int To, const float* const* pred4, const float* d_w, int B, int Tp,
+                              float* const* label, float* const* code, float* dsave, int obs_pre, float* w_snapshot,
+                              const float* targets, int t0, int t1, const float* z, float g_label, float g_code, float* ddelta,
+                              float* d_d_w, float* wgrad_ws, float* loss_part, float* adam_w, float* adam_m, float* adam_v,
+                              const float* adam_step, double lr, double beta1, double beta2, double eps, void* stream) {
+  return disc_update_launch(false, obsv, To, nullptr, pred4, d_w, B, Tp, label, code, dsave, obs_pre, w_snapshot, targets, t0, t1, z,
+                            g_label, g_code, ddelta, d_d_w, wgrad_ws, loss_part, adam_w, adam_m, adam_v, adam_step, lr, beta1, beta2,
+                            eps, stream);
+}
+// ... over RAGGED observation histories: what sw_disc_fwd_ragged(nb = 2, x_mode 0, save_lstm 1) followed by
+// sw_disc_bwd_gan[_adam] computes, to the same buffers, bit for bit.  Row b holds clamp(obs_len[b], 2, To) valid frames
+// right-aligned in obsv.  sw_disc_update's arguments without obs_pre: ragged rows have no precomputed observation pass.
+extern "C" int sw_disc_update_ragged(const float* obsv, int To, const int* obs_len, const float* const* pred4, const float* d_w, int B,
+                                     int Tp, float* const* label, float* const* code, float* dsave, float* w_snapshot,
+                                     const float* targets, int t0, int t1, const float* z, float g_label, float g_code,
+                                     float* ddelta, float* d_d_w, float* wgrad_ws, float* loss_part, float* adam_w, float* adam_m,
+                                     float* adam_v, const float* adam_step, double lr, double beta1, double beta2, double eps,
+                                     void* stream) {
+  return disc_update_launch(true, obsv, To, obs_len, pred4, d_w, B, Tp, label, code, dsave, 0, w_snapshot, targets, t0, t1, z, g_label,
+                            g_code, ddelta, d_d_w, wgrad_ws, loss_part, adam_w, adam_m, adam_v, adam_step, lr, beta1, beta2, eps, stream);
 }
 
 extern "C" int sw_disc_bwd(const float* d_w, const float* dsave, const float* const* dlabel,

@@ -446,8 +446,11 @@ __device__ __forceinline__ void obs_x4_load_from(const float* pos, int b, int t,
 //   SAVE_TILE: through the LDS row tile, as enc_lstm_fwd_kernel<., true, ., true>: hbuf is then [2][16][SW_ALD], whose h
 //              columns (320 ..) are the next step's operand, and the rows leave behind the step's barrier (a0 = the tile's
 //              first agent)
+//   USER: no meaning inside.  A second kernel that inlines ONE instantiation moves instructions in the first (seen on
+//         disc_fwd_ragged_kernel's address arithmetic when disc_update_kernel<true> took <0, SAVE_ROWS> as well); a later
+//         user names an instantiation of its own and the earlier kernels keep their code.
 enum { SAVE_NONE = 0, SAVE_ROWS = 1, SAVE_TILE = 2 };
-template <int XMODE, int SAVE = SAVE_NONE>
+template <int XMODE, int SAVE = SAVE_NONE, int USER = 0>
 __device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int b, int s,
                                                      f32x4& c, f32x4& h, float* __restrict__ act = nullptr,
                                                      float* __restrict__ x4s = nullptr, int B = 0, int a0 = 0) {

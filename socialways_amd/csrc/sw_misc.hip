@@ -1000,6 +1000,72 @@ extern "C" int sw_stage_step_zdev(const float* slot, int B, int To, int Tp, floa
   if (d_img) sw_disc_images_register(d_w, d_img, d_tab, Tp);
   return SW_OK;
 }
+// ---- ... of a captured step over RAGGED observation histories (sw_stage_step_ragged) -----------------
+// A sibling of stage_step_kernel with a slot layout of its own (SW_STAGE_HEADER_RAGGED = 12 words in front of z):
+//   [0..7] as above   [8,9] device pointer of z when z_device = 1   [10,11] device pointer of this step's obs_len (B int32)
+//   [12 ..] z (B*32) when z_device = 0 - 48 bytes in: the 16-byte alignment of the ld4 reads holds
+// It writes what stage_step_kernel writes with z_dst given (the ragged encoder launch pulls no z: this launch fills z in
+// both z modes) and obs_len_dst[i] = clamp(obs_len[i], 2, To), the static int32 buffer the graph's ragged kernels read.
+__global__ __launch_bounds__(256) void stage_step_ragged_kernel(const float* __restrict__ slot, int B, int To, int Tp,
+                                                                 float* __restrict__ obsv_dst, float* __restrict__ pred_dst,
+                                                                 float* __restrict__ pred4_dst, float* __restrict__ targets_dst,
+                                                                 float* __restrict__ z_dst, float* __restrict__ steps_dst,
+                                                                 int n_d_updates, const float* __restrict__ enc_w,
+                                                                 const float* __restrict__ dec_w, const float* __restrict__ emb_w,
+                                                                 const float* __restrict__ att_w, float* __restrict__ img,
+                                                                 int img_blocks, const float* __restrict__ d_w,
+                                                                 float* __restrict__ d_img, const int* __restrict__ d_tab, int d_n,
+                                                                 int dimg_blocks, int z_device, int* __restrict__ obs_len_dst) {
+  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks) {
+    gen_images_block(enc_w, dec_w, emb_w, att_w, img, (int)blockIdx.x - ((int)gridDim.x - img_blocks));
+    return;
+  }
+  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks - dimg_blocks) {
+    disc_images_scatter(d_w, d_img, d_tab, d_n, (int)blockIdx.x - ((int)gridDim.x - img_blocks - dimg_blocks), dimg_blocks);
+    return;
+  }
+  const unsigned long long* ptrs = reinterpret_cast<const unsigned long long*>(slot);
+  const float* obsv = reinterpret_cast<const float*>(ptrs[0]);
+  const float* pred = reinterpret_cast<const float*>(ptrs[1]);
+  const int* obs_len = reinterpret_cast<const int*>(ptrs[5]);
+  const int gid = blockIdx.x * 256 + threadIdx.x, gsz = ((int)gridDim.x - img_blocks - dimg_blocks) * 256;
+  const float* zs = z_device ? reinterpret_cast<const float*>(ptrs[4]) : slot + SW_STAGE_HEADER_RAGGED;
+  for (int i = gid; i < B * SW_Z / 4; i += gsz) st4(z_dst + 4 * (size_t)i, ld4(zs + 4 * (size_t)i));
+  for (int i = gid; i < B; i += gsz) obs_len_dst[i] = min(max(obs_len[i], 2), To);
+  if (gid < 2) targets_dst[gid] = slot[4 + gid];
+  if (steps_dst && gid <= n_d_updates) steps_dst[gid] = gid < n_d_updates ? slot[6] + 1.0f + (float)gid : slot[7] + 1.0f;
+  for (int i = gid; i < B * To; i += gsz)
+    *reinterpret_cast<float2*>(obsv_dst + 2 * (size_t)i) = *reinterpret_cast<const float2*>(obsv + 2 * (size_t)i);
+  for (int k = gid; k < B * Tp; k += gsz) {
+    const int b = k / Tp, t = k - b * Tp;
+    const float2 p = *reinterpret_cast<const float2*>(pred + 2 * (size_t)k);
+    const float2 q = *reinterpret_cast<const float2*>(t == 0 ? obsv + ((size_t)b * To + To - 1) * 2 : pred + 2 * (size_t)k - 2);
+    *reinterpret_cast<float2*>(pred_dst + 2 * (size_t)k) = p;
+    st4(pred4_dst + 4 * (size_t)k, f32x4{p.x, p.y, p.x - q.x, p.y - q.y});
+  }
+}
+extern "C" int sw_stage_step_ragged(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst,
+                                    float* pred4_dst, float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates,
+                                    const float* enc_w, const float* dec_w, const float* emb_w, const float* att_w, float* img,
+                                    const float* d_w, float* d_img, const int* d_tab, int z_device, int* obs_len_dst,
+                                    void* stream) {
+  if (!obs_len_dst || !z_dst) return SW_EARG;
+  if (!slot || !obsv_dst || !pred_dst || !pred4_dst || !targets_dst || B < 1 || To < 2 || Tp < 1 ||
+      n_d_updates < 0 || n_d_updates > 254)
+    return SW_EARG;
+  if (img && (!enc_w || !dec_w || ((emb_w != nullptr) != (att_w != nullptr)))) return SW_EARG;
+  if (d_img && (!d_w || !d_tab || Tp > 64)) return SW_EARG;
+  int blocks = (B * SW_Z / 4 + 255) / 256;      // the grid rule of sw_stage_step_zdev with z_dst
+  if (blocks > 1024) blocks = 1024;
+  const int ib = img ? SW_IMG_BLOCKS : 0, db = d_img ? SW_DIMG_BLOCKS : 0;
+  SW_LAUNCH(stage_step_ragged_kernel, dim3(blocks + ib + db), dim3(256), 0, (hipStream_t)stream, slot, B, To, Tp, obsv_dst,
+            pred_dst, pred4_dst, targets_dst, z_dst, steps_dst, n_d_updates, enc_w, dec_w, emb_w, att_w, img, ib,
+            d_w, d_img, d_tab, d_img ? swp::disc(Tp).n : 0, db, z_device ? 1 : 0, obs_len_dst);
+  SW_CHECK_LAUNCH("stage_step_ragged_kernel");
+  if (img) gen_images_register(enc_w, dec_w, emb_w, att_w, img);
+  if (d_img) sw_disc_images_register(d_w, d_img, d_tab, Tp);
+  return SW_OK;
+}
 extern "C" int sw_stage_step_img(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst,
                                  float* pred4_dst, float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates,
                                  const float* enc_w, const float* dec_w, const float* emb_w, const float* att_w, float* img,

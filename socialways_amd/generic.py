@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d, refuse_obs_len
+from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d, refuse_obs_len, refuse_ragged_fused
 from .trainer import SocialWaysTrainer
 
 
@@ -413,9 +413,10 @@ class GenericTrainer(SocialWaysTrainer):
                  use_variety_loss=False, loss_l2_w=0.5, **perf_only):
         # options of the fused trainer that change speed, not results, are accepted and have no effect here; anything else
         # is a mistake worth hearing about
-        unknown = set(perf_only) - {"variety_k", "use_graph", "fused_adam"}
+        unknown = set(perf_only) - {"variety_k", "use_graph", "fused_adam", "ragged_fused"}
         if unknown:
             raise TypeError("unexpected keyword arguments: %s" % sorted(unknown))
+        refuse_ragged_fused(perf_only.get("ragged_fused", False), type(self).__name__)
         if use_variety_loss not in (False, True):
             raise L.SocialWaysHipError("generic-width path: use_variety_loss=%r (the folded best-of-K form) is not implemented; "
                                        "True = the reference's term as written" % (use_variety_loss,))

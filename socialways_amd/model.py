@@ -859,6 +859,13 @@ def sample(obsv_p, n_samples, n_next, sub_batches=[], noise=None, generator=None
     return g.sample(obsv_p, n_samples, n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
 
 
+def refuse_ragged_fused(ragged_fused, who):
+    """... and so is the switch that fuses the ragged training step (SocialWaysTrainer(ragged_fused=True)); False is accepted."""
+    if ragged_fused:
+        raise L.SocialWaysHipError("%s does not take ragged_fused=True: training on ragged observation histories (obs_len) is "
+                                   "implemented for the fused 64-unit path only (hidden_size <= 64, n_latent_codes = 2)" % who)
+
+
 def refuse_obs_len(obs_len, who):
     """The generic-width and wide paths have no ragged kernels: an obs_len there is refused, loudly, before any launch."""
     if obs_len is not None:

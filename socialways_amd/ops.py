@@ -776,9 +776,16 @@ def disc_update_supported(d_w, B, To, Tp):
 
 
 def disc_update(d_w, obsv, preds, targets, t_idx, z, g_label, g_code, d_d_w, ws, tag="d", obs_pre=False, w_snapshot=None,
-                loss_part=None, adam=None):
+                loss_part=None, adam=None, obs_len=None):
     """disc_forward(obsv, [fake, real]) + disc_backward_gan(...) of one D update (train.py:476-495) as one launch
-    (sw_disc_update) + the weight-gradient GEMM (+ the Adam update).  Returns (labels, codes)."""
+    (sw_disc_update) + the weight-gradient GEMM (+ the Adam update).  Returns (labels, codes).
+    obs_len (B,) int32 on the device: ragged histories, as disc_forward() - sw_disc_update_ragged, the bits of
+    disc_forward(obs_len=) + disc_backward_gan(); there is no precomputed observation pass for ragged rows, so obs_pre is
+    refused then.  None: sw_disc_update."""
+    if obs_len is not None:
+        obs_len = _check_obs_len_tensor(obs_len, obsv.shape[0], obsv.device)
+        if obs_pre:
+            raise ValueError("obs_len: there is no precomputed observation pass for ragged rows - obs_pre=True is refused")
     L.require_gpu(obsv)
     obsv = obsv.contiguous()
     preds = [p.contiguous() for p in preds]
@@ -796,8 +803,11 @@ def disc_update(d_w, obsv, preds, targets, t_idx, z, g_label, g_code, d_d_w, ws,
     lr = b1 = b2 = eps = 0.0
     if adam is not None:
         m, v, step, lr, b1, b2, eps = adam
-    L.call("sw_disc_update", L.ptr(obsv), To, pp, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave), int(bool(obs_pre)), L.ptr(w_snapshot),
-           L.ptr(targets), int(t_idx[0]), int(t_idx[1]), L.ptr(z), g_label, g_code, L.ptr(ddelta), L.ptr(d_d_w), L.ptr(wgrad),
-           L.ptr(loss_part), L.ptr(d_w) if adam is not None else None, L.ptr(m), L.ptr(v), L.ptr(step), float(lr), float(b1),
-           float(b2), float(eps), L.stream())
+    tail = (L.ptr(w_snapshot), L.ptr(targets), int(t_idx[0]), int(t_idx[1]), L.ptr(z), g_label, g_code, L.ptr(ddelta), L.ptr(d_d_w),
+            L.ptr(wgrad), L.ptr(loss_part), L.ptr(d_w) if adam is not None else None, L.ptr(m), L.ptr(v), L.ptr(step), float(lr),
+            float(b1), float(b2), float(eps), L.stream())
+    if obs_len is None:
+        L.call("sw_disc_update", L.ptr(obsv), To, pp, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave), int(bool(obs_pre)), *tail)
+    else:
+        L.call("sw_disc_update_ragged", L.ptr(obsv), To, L.ptr(obs_len), pp, L.ptr(d_w), B, Tp, lp, cp, L.ptr(dsave), *tail)
     return labels, codes

@@ -202,6 +202,7 @@ class SocialWaysTrainer:
     _direct = None          # the direct gradient exchange (SW_ALLREDUCE=direct / auto; the fused trainer only) and what the
     exchange_probe = None   # auto mode's probe measured - class-level defaults: the wider trainers have their own __init__
     noise = None            # a DeviceNoise: z of train_epoch() / evaluate*() from the device stream; None = the reference's host streams
+    ragged_fused = False    # step(obs_len=...): D updates in one launch (sw_disc_update_ragged) and, with use_graph, captured steps
 
     def __new__(cls, n_next=None, hidden_size=64, *args, **kw):
         """Widths above the fused kernels' 64 units and latent-code counts other than 2 (train.py:42-44, 65) train on
@@ -229,8 +230,13 @@ class SocialWaysTrainer:
 
     def __init__(self, n_next, hidden_size=64, lr_g=1e-4, lr_d=1e-3, n_unrolling_steps=1, use_social=True,
                  use_info_loss=True, loss_info_w=0.5, n_latent_codes=2, device="cuda", process_group=None,
-                 fused_adam=True, use_graph=None, use_l2_loss=False, use_variety_loss=False, loss_l2_w=0.5, variety_k=20):
+                 fused_adam=True, use_graph=None, use_l2_loss=False, use_variety_loss=False, loss_l2_w=0.5, variety_k=20,
+                 ragged_fused=False):
         self.device = L.indexed_device(device)
+        # Ragged steps (step(obs_len=...), train_epoch_ragged()) on the fused route: each D update one launch
+        # (ops.disc_update(obs_len=...)) and, with use_graph, the step captured per layout like the dense one, obs_len staged
+        # through the pinned slot.  Off (the default): every ragged step makes the eager launches it always made.
+        self.ragged_fused = bool(ragged_fused)
         self.n_next = n_next
         self.noise_len = hidden_size // 2
         self.n_unrolling_steps = n_unrolling_steps
@@ -466,14 +472,14 @@ class SocialWaysTrainer:
         return all(nz.is_cuda and nz.dtype == torch.float32 and nz.is_contiguous() and nz.device == self.device
                    and tuple(nz.shape) == (b[0].shape[0], self.Z_COLS) for b in batches for nz in (b[4],))
 
-    def _graph_key(self, scenes, To, ss, Bg, K, zdev=False):
+    def _graph_key(self, scenes, To, ss, Bg, K, zdev=False, ragged=False):
         """Everything a captured step bakes in besides the buffer addresses: the scene layout, the loss switches and
         weights, the unrolling depth and the optimizer hyper-parameters (host-side scalars of the recorded launches)."""
         og, od = self.predictor_optimizer.param_groups[0], self.D_optimizer.param_groups[0]
         return (scenes.key, To, float(ss), float(Bg), self._row0, K, self.n_unrolling_steps, self.use_info_loss,
                 self.loss_info_w, self.use_l2_loss, self.use_variety_loss, self.loss_l2_w, self.variety_k,
                 og["lr"], tuple(og["betas"]), og["eps"], og.get("weight_decay", 0), od["lr"], tuple(od["betas"]), od["eps"],
-                od.get("weight_decay", 0), bool(zdev))
+                od.get("weight_decay", 0), bool(ragged), bool(zdev))
 
     def _graphs_current(self):
         """A workspace outgrown since the last capture means captured graphs hold retired addresses: they stay valid
@@ -496,10 +502,15 @@ class SocialWaysTrainer:
         slot (pointers of the track slices, z, the two label-noise scalars) and launches the graph.
         obs_len (B,) - tensor, numpy array or list: ragged histories.  Row a holds obs_len[a] valid frames, 2 .. To,
         right-aligned in obsv and trains exactly as if its two observation LSTMs (encoder, discriminator) ran on those
-        frames alone from the zero state; the padding is never read.  Such a step runs eagerly, never through a captured
-        graph, on the unfused route: no precomputed D observation pass, D updates as disc_forward + disc_backward_gan
+        frames alone from the zero state; the padding is never read.  By default such a step runs eagerly, never through a
+        captured graph, on the unfused route: no precomputed D observation pass, D updates as disc_forward + disc_backward_gan
         (with the fused Adam), the generator phase as disc_dpred (or, where Tp > 24, disc_forward + disc_backward_gan),
-        never inside the decode BPTT launch; the backward launches, losses and all-reduce points are the dense step's."""
+        never inside the decode BPTT launch; the backward launches, losses and all-reduce points are the dense step's.
+        With `ragged_fused` every D update is one launch wherever the dense step's is (ops.disc_update(obs_len=...): the same
+        bits) and, with `use_graph` (not the "fixed" variety step), the step is captured per layout like the dense one - a
+        graph of its own beside the layout's dense graph, obs_len travelling by address through the pinned slot
+        (sw_stage_step_ragged), an obs_len given as a device tensor never read by the host.  Still out: the D observation
+        pass inside the decode forward launch and the generator-phase D pass inside the decode BPTT launch."""
         self._resolve_collectives()
         B = obsv.shape[0]
         self._obs_len = None        # read by _step_body of this step only
@@ -521,14 +532,17 @@ class SocialWaysTrainer:
         part = None
         if not self._graphs and self.ws.retired:      # eager-only runs: nothing captured can reference an outgrown workspace
             self.ws.release_retired()                 # (stream-ordered allocator: kernels already queued on it stay valid)
-        if self.use_graph and self.use_variety_loss != "fixed" and obs_len is None:    # the folded K-sample and the ragged step run eagerly
+        # the folded K-sample step runs eagerly, and so does the ragged step without `ragged_fused`
+        if self.use_graph and self.use_variety_loss != "fixed" and (obs_len is None or self.ragged_fused):
             # one graph set per packed-batch layout; datasets with ragged scenes produce many layouts, so the
             # number of captured layouts is capped and the rest of the steps run eagerly
             scenes = ops.SceneIndex.get(sub_batches, B, dev)
             self._graphs_current()
             zdev = self._z_resident([(obsv, pred, zeros_val, ones_val, noise)])
-            if self._graph_key(scenes, obsv.shape[1], ss, Bg, 1, zdev) in self._graphs or len(self._graphs) < self.max_graphs:
-                part = self._step_graph([(obsv, pred, zeros_val, ones_val, noise)], sub_batches, float(ss), Bg)[0]
+            key = self._graph_key(scenes, obsv.shape[1], ss, Bg, 1, zdev, obs_len is not None)
+            if key in self._graphs or len(self._graphs) < self.max_graphs:
+                part = self._step_graph([(obsv, pred, zeros_val, ones_val, noise)], sub_batches, float(ss), Bg,
+                                        None if obs_len is None else [obs_len])[0]
         if part is None:
             part = torch.zeros(self.n_unrolling_steps + 3, (B + 15) // 16, 3, device=dev)     # one triple per 16-agent tile
             scenes = ops.SceneIndex.get(sub_batches, B, dev)
@@ -544,34 +558,61 @@ class SocialWaysTrainer:
             return part
         return part.sum(1, dtype=torch.float64)
 
-    def step_many(self, batches, sub_batches, ss=1.0, global_B=None, out=None, global_row0=0):
+    def step_many(self, batches, sub_batches, ss=1.0, global_B=None, out=None, global_row0=0, **ragged):
         """K consecutive training steps on K packed batches of the SAME scene layout in ONE graph launch:
         `batches` = [(obsv, pred, zeros_val, ones_val, noise), ...].  Exactly the K `step()` calls in order (same
         kernels, same results); what it saves is the gap between two graph launches (~13 us, the system-scope
-        fence at the end of a hipGraph) on K-1 of the K steps.  Returns the list of the K step results."""
+        fence at the end of a hipGraph) on K-1 of the K steps.  Returns the list of the K step results.
+        obs_len: a list of the K batches' obs_len (ragged histories, see step()) or None.  With `ragged_fused` and
+        `use_graph` the K ragged steps are one graph launch; otherwise they are K step(obs_len=...) calls.  It is the one
+        keyword `**ragged` takes: the named parameters are the dense call's, as tests/test_ragged_train_host.py pins them."""
+        obs_len = ragged.pop("obs_len", None)
+        if ragged:
+            raise TypeError("step_many() got an unexpected keyword argument %r" % sorted(ragged)[0])
+        if obs_len is not None:       # checked before anything of the trainer is touched
+            obs_len = list(obs_len)
+            if len(obs_len) != len(batches):
+                raise ValueError("step_many(obs_len=...) takes one obs_len per batch: %d for %d batches" % (len(obs_len), len(batches)))
+            n_none = sum(ol is None for ol in obs_len)
+            if 0 < n_none < len(obs_len):
+                raise ValueError("step_many(obs_len=...) takes an obs_len for every batch or None, not a mix of both")
+            if n_none:
+                obs_len = None
         self._resolve_collectives()
-        if not self.use_graph or len(batches) == 1 or self.use_variety_loss:
-            return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0) for o, p, zv, ov, nz in batches]
-        B = batches[0][0].shape[0]
+        ols = obs_len if obs_len is not None else [None] * len(batches)
+
+        def steps():
+            return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0, obs_len=ol)
+                    for (o, p, zv, ov, nz), ol in zip(batches, ols)]
+        if not self.use_graph or len(batches) == 1 or self.use_variety_loss or (obs_len is not None and not self.ragged_fused):
+            return steps()
+        B, To = batches[0][0].shape[0], batches[0][0].shape[1]
+        if obs_len is not None:
+            if any(b[0].shape[2] != 2 for b in batches):
+                raise ValueError("step_many(obs_len=...) takes positions (B, To, 2)")
+            obs_len = [ops.obs_len_arg(ol, B, To, 2, self.device) for ol in obs_len]
         Bg = float(global_B if global_B is not None else B)
         self._row0 = int(global_row0)
         scenes = ops.SceneIndex.get(sub_batches, B, self.device)
         self._graphs_current()
-        key = self._graph_key(scenes, batches[0][0].shape[1], ss, Bg, len(batches), self._z_resident(batches))
+        key = self._graph_key(scenes, To, ss, Bg, len(batches), self._z_resident(batches), obs_len is not None)
         if key not in self._graphs and len(self._graphs) >= self.max_graphs:
-            return [self.step(o, p, sub_batches, zv, ov, nz, ss, global_B, out, global_row0) for o, p, zv, ov, nz in batches]
-        parts = self._step_graph(batches, sub_batches, float(ss), Bg)
+            return steps()
+        self._obs_len = None
+        parts = self._step_graph(batches, sub_batches, float(ss), Bg, obs_len)
         return parts if out is False else [q.sum(1, dtype=torch.float64) for q in parts]
 
-    def _step_graph(self, batches, sub_batches, ss, Bg):
+    def _step_graph(self, batches, sub_batches, ss, Bg, obs_lens=None):
+        """obs_lens: the K batches' obs_len as int32 device tensors (the captured ragged step, `ragged_fused`) or None."""
         K = len(batches)
         B, To, Tp = batches[0][0].shape[0], batches[0][0].shape[1], self.n_next
         dev = self.device
         scenes = ops.SceneIndex.get(sub_batches, B, dev)
         zdev = self._z_resident(batches)
-        key = self._graph_key(scenes, To, ss, Bg, K, zdev)
+        ragged = obs_lens is not None
+        key = self._graph_key(scenes, To, ss, Bg, K, zdev, ragged)
         st = self._graphs.get(key)
-        HDR = 8                                                   # SW_STAGE_HEADER words in front of z
+        HDR = 12 if ragged else 8                                 # SW_STAGE_HEADER[_RAGGED] words in front of z
         if st is None:
             st = self._graphs[key] = dict(
                 n=0, graph=None, flip=0, scenes=scenes, obsv=torch.empty(B, To, 2, device=dev),
@@ -581,7 +622,9 @@ class SocialWaysTrainer:
                 outs=[torch.zeros(self.n_unrolling_steps + 3, (B + 15) // 16, 3, device=dev) for _ in range(K)],
                 slots=[[torch.zeros(HDR + B * self.Z_COLS, dtype=torch.float32).pin_memory() for _ in range(K)]
                        for _ in range(2)],
-                done=[torch.cuda.Event(), torch.cuda.Event()], keep=[None, None])
+                done=[torch.cuda.Event(), torch.cuda.Event()], keep=[None, None],
+                # the ragged graph's static obs_len (clamped by the staging launch), read by its ragged kernels
+                obs_len=torch.full((B,), To, dtype=torch.int32, device=dev) if ragged else None)
         # Inputs of a step travel through a pinned host slot that the step's first graph node (sw_stage_step)
         # reads itself: the device pointers of this batch's track slices, the two label-noise scalars, the Adam
         # counters and z.  A hipMemcpyAsync enqueued behind graph launches would block the host until the stream
@@ -596,12 +639,15 @@ class SocialWaysTrainer:
             hn = st["slots"][k][j].numpy()
             hn[:4].view(np.uint64)[:] = (obsv.data_ptr(), pred.data_ptr())
             hn[4], hn[5] = float(zeros_val), float(ones_val)
+            if ragged:        # this step's obs_len travels by address, like the tracks
+                hn[10:12].view(np.uint64)[:] = obs_lens[j].data_ptr()
+                keep.append(obs_lens[j])
             if packed:        # updates applied so far: the staging kernel turns them into this step's Adam step indices
                 hn[6], hn[7] = float(self.D_optimizer.t), float(self.predictor_optimizer.t)
                 self.D_optimizer.t += self.n_unrolling_steps + 1
                 self.predictor_optimizer.t += 1
             if zdev:          # z already in HBM: only its address travels
-                hn[HDR:HDR + 2].view(np.uint64)[:] = noise.data_ptr()
+                hn[8:10].view(np.uint64)[:] = noise.data_ptr()    # words [8, 9] in both slot layouts
                 keep.append(noise)
                 continue
             # (a hidden size below 64 draws fewer z columns: the kernels' remaining columns stay zero, like their weights)
@@ -610,6 +656,16 @@ class SocialWaysTrainer:
 
         def stage(kk, j):
             slot = st["slots"][kk][j]
+            if ragged:        # the ragged encoder launch pulls no z: the staging launch fills it in both z modes
+                L.call("sw_stage_step_ragged", slot.data_ptr(), B, To, Tp, L.ptr(st["obsv"]), L.ptr(st["pred"]),
+                       L.ptr(st["pred4"]), L.ptr(st["targets"]), L.ptr(st["noise"]), L.ptr(st["steps"]),
+                       self.n_unrolling_steps + 1,
+                       L.ptr(self.G.encoder._flat), L.ptr(self.G.decoder._flat), L.ptr(self.G.feature_embedder._flat),
+                       L.ptr(self.G.attention._flat), L.ptr(self._gimg),
+                       L.ptr(self.D._flat) if self._dimg is not None else None, L.ptr(self._dimg), L.ptr(self._dtab), int(zdev),
+                       L.ptr(st["obs_len"]), L.stream())
+                self._noise_src = None
+                return
             L.call("sw_stage_step_zdev", slot.data_ptr(), B, To, Tp, L.ptr(st["obsv"]), L.ptr(st["pred"]),
                    L.ptr(st["pred4"]), L.ptr(st["targets"]), L.ptr(st["noise"]) if zdev else None, L.ptr(st["steps"]),
                    self.n_unrolling_steps + 1,
@@ -624,9 +680,16 @@ class SocialWaysTrainer:
             return (st["obsv"], st["pred"], st["pred4"], scenes, st["targets"], st["noise"], ss, Bg, st["outs"][j],
                     st["steps"] if packed else None)
 
+        def one_step(j, pre=None):   # its segments; a ragged graph's kernels read its static obs_len (_step_body)
+            self._obs_len = st["obs_len"]
+            try:
+                yield from self._step_gen(*args(j), pre=pre)
+            finally:
+                self._obs_len = None
+
         def body(kk):          # the K steps of one executable, back to back
             for j in range(K):
-                yield from self._step_gen(*args(j), pre=lambda j=j: stage(kk, j))
+                yield from one_step(j, pre=lambda j=j: stage(kk, j))
         if st["graph"] is not None:
             st["flip"] = k
             for g, buf in st["graph"][k]:
@@ -637,7 +700,8 @@ class SocialWaysTrainer:
             st["n"] += 1
             for j in range(K):
                 stage(0, j)
-                self._step_impl(*args(j))
+                for buf in one_step(j):
+                    self._allreduce(buf)
         else:
             # Capture.  Single GPU: one graph for the K steps.  Data parallel: the same with the RCCL
             # all-reduces recorded in it when the group can do that (see __init__), else one graph per
@@ -727,7 +791,7 @@ class SocialWaysTrainer:
         g_label = 1.0 / Bg
         g_code = (self.loss_info_w if self.use_info_loss else 0.0) / (2.0 * Bg)
         noise_src, self._noise_src = self._noise_src, None      # set by the staging of this step (graph / warm-up path)
-        ol = getattr(self, "_obs_len", None)                    # ragged histories (step(obs_len=...)): the unfused route
+        ol = getattr(self, "_obs_len", None)                    # ragged histories (step(obs_len=...))
         if pred4 is None:          # real future as 4-d (train.py:470); the observation stays 2-d: kernels form (p, v) on the fly
             pred4 = torch.empty(B, Tp, 4, device=dev)
             o4_scratch = ws.get("o4", B * obsv.shape[1] * 4)
@@ -766,11 +830,13 @@ class SocialWaysTrainer:
             fuse = (self._fuse_d_adam and isinstance(self.D_optimizer, PackedAdam) and self.D_optimizer.fusable
                     and not (self.world > 1 or self._force_dist))
             adam = self.D_optimizer.fused_args(None if steps is None else steps[u]) if fuse else None
-            if ol is None and obsv.shape[2] == 2 and ops.disc_update_supported(D._flat, B, obsv.shape[1], Tp):
-                # shapes that leave CUs idle: forward + loss gradients + backward of the pass in ONE launch (sw_disc_update)
+            if ((ol is None or self.ragged_fused) and obsv.shape[2] == 2
+                    and ops.disc_update_supported(D._flat, B, obsv.shape[1], Tp)):
+                # shapes that leave CUs idle: forward + loss gradients + backward of the pass in ONE launch (sw_disc_update;
+                # ragged histories with `ragged_fused`: sw_disc_update_ragged)
                 ops.disc_update(D._flat, obsv, [pred_hat, pred4], targets, (0, 1), noise, g_label, g_code, d_gflat, ws,
                                 obs_pre=(u == 0 and d_pre is not None), w_snapshot=backup if u == 1 else None,
-                                loss_part=out[u], adam=adam)
+                                loss_part=out[u], adam=adam, obs_len=ol)
             else:
                 labels, codes, dctx = ops.disc_forward(D._flat, obsv, [pred_hat, pred4], save=True, ws=ws,
                                                        save_lstm=2 if (u == 0 and d_pre is not None) else 1,
@@ -885,6 +951,9 @@ class SocialWaysTrainer:
         """train_epoch() for a dataset that carries obs_len (create_dataset_ragged / SceneDataset(obs_len=...)): the same
         packed batches, RNG draws (host stream or `self.noise`), scene sharding, return value and epoch counter, one eager
         step(..., obs_len=data.obs_len[rows]) per packed batch (see step(): the unfused route, no graph capture).
+        With `ragged_fused` and `use_graph` (not the "fixed" variety step) the loop is train_epoch()'s: consecutive packed
+        batches of one local layout share a step_many(obs_len=[...]) launch of up to STEPS_PER_LAUNCH captured ragged steps,
+        with `self.noise` one fill launch in front of it - the same weights and return values bit for bit.
         A dataset without obs_len is refused: train_epoch() is its call."""
         ol = getattr(data, "obs_len", None)
         if ol is None:
@@ -913,7 +982,8 @@ class SocialWaysTrainer:
                     z = dn.fill(items[0][0].shape[0], self.noise_len, domain=TRAIN, step=pend[0][4], n_steps=len(pend), row0=r0,
                                 ld=self.Z_COLS, device=self.device)
                     items = [it[:4] + (z[j, 0],) for j, it in enumerate(items)]
-                outs.extend(self.step_many(items, pend[0][1], data.ss, global_B=pend[0][2], global_row0=pend[0][3]))
+                kw = dict(obs_len=[p[5] for p in pend]) if obs_len is not None else {}     # (the wider trainers' step_many has none)
+                outs.extend(self.step_many(items, pend[0][1], data.ss, global_B=pend[0][2], global_row0=pend[0][3], **kw))
                 pend, pend_key = [], None
         for a, b, sb in data.packed_steps(batch_size):
             bs = b - a
@@ -943,7 +1013,8 @@ class SocialWaysTrainer:
                 r0, r1 = int(sb[lo, 0]), int(sb[hi - 1, 1])
                 sbl = sb[lo:hi] - r0
             item = (data.obsv[a + r0:a + r1], data.pred[a + r0:a + r1], zv, ov, noise[r0:r1] if noise is not None else None)
-            if fixed or obs_len is not None:     # the folded K-sample step and the ragged step are not graph-captured:
+            # the folded K-sample step and, without `ragged_fused` + `use_graph`, the ragged step are not graph-captured:
+            if fixed or (obs_len is not None and not (self.ragged_fused and self.use_graph)):
                 flush()                          # one step() per packed batch
                 z0, vnl = item[4], None
                 if dn is not None:    # draws 0 .. variety_k-1 of this rank's rows in one launch, padded to the kernels' width
@@ -960,7 +1031,7 @@ class SocialWaysTrainer:
             if key != pend_key or len(pend) == self.STEPS_PER_LAUNCH:
                 flush()
                 pend_key = key
-            pend.append((item, sbl, bs, r0, step_i))
+            pend.append((item, sbl, bs, r0, step_i, obs_len[a + r0:a + r1] if obs_len is not None else None))
         flush()
         allo = torch.stack(outs)
         self._allreduce(allo)

@@ -19,11 +19,23 @@ and by the method of tools/rank_timing.py: host clock around calls that end in a
       sw_enc_lstm_fwd_ragged_save against sw_enc_lstm_fwd with saves at full length: what the selects on the saved row cost.
       Written to --train-out.
 
+  (d) the fused ragged step (SocialWaysTrainer(ragged_fused=True)), on the packed batches of (c) with obs_len uniform in
+      2 .. 8: (i) the PARENT commit's step(obs_len=) - a tree of the parent with its library built, --parent-tree -, (ii) this
+      build with the switch off, (iii) ragged_fused=True single steps, (iv) ragged_fused=True through step_many of 4 (ms per
+      step), and the captured dense step as the floor.  Two trees cannot share a process: every side runs in child processes
+      of its tree, --rounds of each, one at a time and alternating, --repeats / --rounds timed calls per child after its
+      warm-up.  And sw_disc_update_ragged at full length against sw_disc_update (same bits) and against sw_disc_fwd_ragged +
+      sw_disc_bwd_gan_adam, us per launch.  Written to --fused-out.
+
     python tools/ragged_timing.py [--repeats 9] [--legs abc] [--out profiles/ragged_timing.txt]
                                   [--train-out profiles/ragged_train_timing.txt]
+    python tools/ragged_timing.py --legs d --parent-tree ab_old [--rounds 3] [--fused-out profiles/ragged_fused_timing.txt]
 """
+import argparse
+import json
 import os
 import statistics
+import subprocess
 import sys
 
 import torch
@@ -150,14 +162,142 @@ def train_leg(a, tr):
     T.write_out(lines + enc_lines, a.train_out)
 
 
+def packed_batches(tr):
+    """(c)'s packed batches: per shape (name, obsv, pred, sb, lengths uniform in 2 .. 8)."""
+    for name, n_scenes, agents, K, just_one in T.SHAPES:
+        _, obsv, pred, sb = next(T.host_chunks(tr, T.held_out_set(n_scenes, agents), K, just_one))
+        gen = torch.Generator(device="cuda").manual_seed(7)
+        mixed = torch.randint(2, obsv.shape[1] + 1, (obsv.shape[0],), device="cuda", generator=gen, dtype=torch.int32)
+        yield name, obsv.contiguous(), pred.contiguous(), sb, mixed
+
+
+FUSED_SIDES = ("off", "fused", "many4", "dense")     # this build's sides of (d); the parent tree runs "off" alone
+
+
+def fused_child(a):
+    """One tree's sides of (d) on the three packed batches -> one JSON line {shape: {side: [ms per step]}}."""
+    sw = T.load("ragged_timing.py", a.tree)
+    out = {}
+    for name, obsv, pred, sb, mixed in packed_batches(T.trainer()):
+        z = torch.rand(obsv.shape[0], 32, device=obsv.device, generator=torch.Generator(device="cuda").manual_seed(11))
+
+        def side(k):
+            torch.manual_seed(0)
+            tr = sw.SocialWaysTrainer(12, use_social=True, device="cuda:0", **(dict(ragged_fused=True) if k in ("fused", "many4") else {}))
+
+            def call():
+                if k == "many4":
+                    outs = tr.step_many([(obsv, pred, 0.04, 0.93, z)] * 4, sb, 1.0, obs_len=[mixed] * 4)
+                    return float(sum(o.sum() for o in outs))
+                out = tr.step(obsv, pred, sb, 0.04, 0.93, z, 1.0, **({} if k == "dense" else dict(obs_len=mixed)))
+                return float(out.sum())      # the host synchronisation
+            return call
+        ms, _ = T.alternate({k: side(k) for k in a.sides.split(",")}, max(a.warmup, 4), a.repeats)      # captured on the third call
+        out[name] = {k: [t / (4 if k == "many4" else 1) for t in v] for k, v in ms.items()}
+    print("TIMING_CHILD " + json.dumps(out))
+
+
+def update_kernels(tr, obsv, pred, launches):
+    """{name: fn}: sw_disc_update, sw_disc_update_ragged at full length, and the two ragged launches it replaces; `launches`
+    update passes (with the fused Adam) and a synchronisation each.  The bits are compared first."""
+    L, ops, sw = T.sw._lib, T.sw.ops, T.sw
+    B, To, Tp = obsv.shape[0], obsv.shape[1], pred.shape[1]
+    dev = obsv.device
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    preds = [sw.get_traj_4d(obsv, pred)[1].contiguous(), (torch.randn(B, Tp, 4, device=dev, generator=gen) * 0.1).contiguous()]
+    z = torch.rand(B, 32, device=dev, generator=gen)
+    full = torch.full((B,), To, dtype=torch.int32, device=dev)
+    targets = torch.tensor([0.04, 0.93], device=dev)
+    D, w0 = tr.D, tr.D._flat.clone()
+    ws = ops.Workspaces(dev)
+    state = [torch.zeros_like(D._flat) for _ in range(3)]      # g, m, v
+    step = torch.ones((), device=dev)
+
+    def passes(kind, n):
+        D._flat.copy_(w0)
+        for t in state:
+            t.zero_()
+        L.call("sw_disc_images", L.ptr(D._flat), L.ptr(tr._dimg), L.ptr(tr._dtab), Tp, L.stream())
+        g, m, v = state
+        adam = (m, v, step, 1e-3, 0.9, 0.999, 1e-8)
+        try:
+            for _ in range(n):
+                if kind == "two":
+                    labels, codes, ctx = ops.disc_forward(D._flat, obsv, preds, save=True, ws=ws, save_lstm=1, obs_len=full)
+                    ops.disc_backward_gan(D._flat, ctx, labels, codes, targets, (0, 1), z, 1.0 / B, 0.25 / B, g, (), ws=ws, adam=adam)
+                else:
+                    ops.disc_update(D._flat, obsv, preds, targets, (0, 1), z, 1.0 / B, 0.25 / B, g, ws, adam=adam,
+                                    **(dict(obs_len=full) if kind == "ragged" else {}))
+            torch.cuda.synchronize()
+        finally:
+            L.call("sw_disc_images", None, None, None, 0, None)
+        return [D._flat.clone(), g.clone(), m.clone(), v.clone()]
+    ref = passes("dense", 2)
+    for kind in ("ragged", "two"):
+        assert all(torch.equal(x, y) for x, y in zip(ref, passes(kind, 2))), kind
+    calls = {k: (lambda k=k: passes(k, launches)) for k in ("dense", "ragged", "two")}
+    return calls, lambda: D._flat.copy_(w0)
+
+
+def fused_leg(a, tr):
+    if not a.parent_tree or a.rounds < 1 or a.repeats % a.rounds:
+        sys.exit("leg d needs --parent-tree (a tree of the parent commit with its library built) and --repeats a multiple of --rounds")
+    res = {}
+    for _ in range(a.rounds):      # one child at a time, alternating between the trees
+        for tree, sides in ((os.path.abspath(a.parent_tree), "off"), (T.HERE, ",".join(FUSED_SIDES))):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--fused-child", "--tree", tree, "--sides", sides, "--repeats",
+                                str(a.repeats // a.rounds), "--warmup", str(a.warmup)], capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                sys.exit("child on %s failed (%d): %s" % (tree, p.returncode, p.stderr[-2000:]))
+            got = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("TIMING_CHILD ")][-1][13:])
+            for shape, ms in got.items():
+                for k, v in ms.items():
+                    res.setdefault(shape, {}).setdefault("parent" if tree != T.HERE else k, []).extend(v)
+    cols = (("parent", "(i) parent step(obs_len)"), ("off", "(ii) switch off"), ("fused", "(iii) ragged_fused"),
+            ("many4", "(iv) step_many of 4, per step"), ("dense", "captured dense step"))
+    lines = ["(d) the ragged training step on the packed batches of (c), obs_len uniform in 2 .. 8: the parent commit's build, this build "
+             "with the switch off, ragged_fused=True single steps and through step_many of 4, and the captured dense step; host clock "
+             "around calls that end in a host read, ms per step; %d child processes of each tree, alternating, %d timed calls per child "
+             "after %d warm-up calls; %s" % (a.rounds, a.repeats // a.rounds, max(a.warmup, 4), torch.cuda.get_device_name(0)),
+             "%-88s %6s " % ("shape", "B") + " ".join("%30s" % c for _, c in cols) + "  (ii) inside (i)   (iii) max < (i) min   (iv) max < (i) min"]
+    for name, obsv, pred, sb, mixed in packed_batches(tr):
+        r = res[name]
+        lines.append("%-88s %6d " % (name, obsv.shape[0]) + " ".join("%30s" % cell(r[k]) for k, _ in cols)
+                     + "  %-17s %-21s %s" % (min(r["parent"]) <= statistics.median(r["off"]) <= max(r["parent"]),
+                                             max(r["fused"]) < min(r["parent"]), max(r["many4"]) < min(r["parent"])))
+    lines += ["", "sw_disc_update_ragged at full length (obs_len all To) vs sw_disc_update (same bits) and vs sw_disc_fwd_ragged + "
+              "sw_disc_bwd_gan_adam, each with the weight-gradient GEMM and the fused Adam; us per update pass, %d passes per timed call; "
+              "%d alternating repeats after %d warm-up calls" % (a.launches, a.repeats, a.warmup),
+              "%-88s %6s %30s %30s %8s %30s %8s" % ("shape", "B", "sw_disc_update median [min, max]", "sw_disc_update_ragged", "/dense",
+                                                  "the two ragged launches", "/ragged")]
+    for name, obsv, pred, sb, mixed in packed_batches(tr):
+        calls, restore = update_kernels(tr, obsv, pred, a.launches)
+        ms, _ = T.alternate(calls, a.warmup, a.repeats)
+        restore()
+        per = {k: [1e3 * t / a.launches for t in v] for k, v in ms.items()}
+        med = {k: statistics.median(v) for k, v in per.items()}
+        lines.append("%-88s %6d %30s %30s %8.3f %30s %8.3f" % (name, obsv.shape[0], cell(per["dense"]), cell(per["ragged"]),
+                                                            med["ragged"] / med["dense"], cell(per["two"]), med["two"] / med["ragged"]))
+    T.write_out(lines, a.fused_out)
+
+
 def main():
     def more(ap):
-        ap.add_argument("--launches", type=int, default=20, help="(b), (c): launches per timed call")
-        ap.add_argument("--legs", default="abc", help="the legs to run, any of a, b, c")
+        ap.add_argument("--launches", type=int, default=20, help="(b), (c), (d): launches per timed call")
+        ap.add_argument("--legs", default="abc", help="the legs to run, any of a, b, c, d")
         ap.add_argument("--train-out", default=None, help="(c): where its table is written")
-    a = T.parse(__doc__, 9, 9, more)
+        ap.add_argument("--fused-out", default=None, help="(d): where its tables are written")
+        T.parent_tree_args(ap)
+        ap.add_argument("--fused-child", action="store_true", help=argparse.SUPPRESS)
+        ap.add_argument("--tree", default=T.HERE, help=argparse.SUPPRESS)
+        ap.add_argument("--sides", default="off", help=argparse.SUPPRESS)
+    a = T.parse(__doc__, 9, 1 if "--fused-child" in sys.argv else 9, more)
+    if a.fused_child:
+        return fused_child(a)
     T.load("ragged_timing.py")
     tr = T.trainer()
+    if "d" in a.legs:
+        fused_leg(a, tr)
     if "c" in a.legs:
         train_leg(a, tr)
     if not set("ab") & set(a.legs):
