@@ -21,6 +21,10 @@
   train_epoch)
 * `--ragged-fused` (with `--train-ragged`): SocialWaysTrainer(ragged_fused=True) - the ragged D updates in one launch each and
   the ragged steps graph-captured per layout like the dense ones (same weights and losses bit for bit)
+* `--min-next M`: the held-out windows also keep the pedestrians whose track ends M .. 11 frames after t (ragged futures:
+  create_dataset_ragged(min_next=M), left-aligned futures + pred_len), so they are predicted, scored against the frames
+  they were seen for and stay in their neighbours' scenes; the errors are reported per future length (evaluate_horizon).
+  Combines with `--min-past`.  Training windows are always built without it: a truncated future is no discriminator input.
 """
 import argparse
 import os
@@ -35,7 +39,8 @@ import socialways_amd as sw  # noqa: E402
 
 
 def ragged_windows(npz, like, train):
-    """Of the recording's windows with histories of min_past .. n_past frames (`npz`, written by biwi_to_npz(min_past=...)) the
+    """Of the recording's windows with histories of min_past .. n_past frames (`npz`, written by biwi_to_npz(min_past=...), or
+    by biwi_to_npz_ragged(min_next=...) with futures of min_next .. n_next frames and `pred_len` as well) the
     scenes at or after the first held-out timestamp of `like` - the dataset of full windows, so none of them holds a
     training window - as an evaluation set in like's coordinates (SceneDataset.held_out), or with `train` the scenes in
     front of that timestamp as a training set in the same coordinates."""
@@ -46,7 +51,8 @@ def ragged_windows(npz, like, train):
     rows = np.concatenate([np.arange(a, b) for a, b in keep])
     ends = np.cumsum([b - a for a, b in keep])
     scenes = np.stack([np.concatenate([[0], ends[:-1]]), ends], axis=1)
-    return sw.SceneDataset.held_out(like, obsvs[rows], preds[rows], scenes, times[rows], obs_len[rows], train=train)
+    out = sw.SceneDataset.held_out(like, obsvs[rows], preds[rows], scenes, times[rows], obs_len[rows], train=train)
+    return out.set_pred_len(d["pred_len"][rows]) if "pred_len" in d.files and not train else out
 
 
 def main(argv=None):
@@ -70,6 +76,10 @@ def main(argv=None):
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
                          "--train-ragged is given")
+    ap.add_argument("--min-next", type=int, default=None, metavar="M",
+                    help="also evaluate on held-out windows that keep the pedestrians whose track ends M .. 11 frames after t "
+                         "(ragged futures) and report the errors per future length; combines with --min-past; training windows "
+                         "are always full")
     ap.add_argument("--train-ragged", action="store_true",
                     help="with --min-past M: train on the ragged windows in front of the held-out part (train_epoch_ragged: "
                          "eager steps on the unfused route) instead of the full windows only")
@@ -80,6 +90,8 @@ def main(argv=None):
         ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
         ap.error("--train-ragged needs --min-past M")
+    if args.min_next is not None and args.hidden_size != 64:
+        ap.error("--min-next: ragged futures are implemented for the fused 64-unit path (--hidden-size 64)")
     if args.train_ragged and args.hidden_size != 64:
         ap.error("--train-ragged: ragged histories are implemented for the fused 64-unit path (--hidden-size 64)")
 
@@ -107,10 +119,18 @@ def main(argv=None):
     ragged_npz = os.path.join(args.out, "crowd-8-12-ragged.npz")
     if args.min_past is not None and rank == 0:
         sw.biwi_to_npz(obsmat, ragged_npz, 8, 12, min_past=args.min_past)
+    next_npz = os.path.join(args.out, "crowd-8-12-next.npz")
+    if args.min_next is not None and rank == 0:      # evaluation windows only: min_past 8 (full histories) unless --min-past
+        sw.biwi_to_npz_ragged(obsmat, next_npz, 8, 12, min_past=args.min_past if args.min_past is not None else 8,
+                              min_next=args.min_next)
     if world > 1:
         torch.distributed.barrier()
     data = sw.SceneDataset.from_npz(npz, device=dev)
-    ragged = train_set = None
+    ragged = train_set = short = None
+    if args.min_next is not None and rank == 0:
+        short = ragged_windows(next_npz, data, train=False)
+        print("ragged-future held-out set: %d windows in %d scenes, %d of them with fewer than %d future frames"
+              % (short.n_test_samples, len(short.test_batches), int((short.pred_len < data.n_next).sum()), data.n_next))
     if args.min_past is not None and rank == 0:
         ragged = ragged_windows(ragged_npz, data, train=False)
         print("ragged held-out set: %d windows in %d scenes, %d of them with fewer than %d frames"
@@ -158,6 +178,12 @@ def main(argv=None):
                       % (hist["ade_avg"], hist["fde_avg"], args.k, hist["ade_min"], hist["fde_min"],
                          ", ".join("%d frames (%d agents) %.3f / %.3f" % (n, v["count"], v["ade_min"], v["fde_min"])
                                    for n, v in sorted(hist["by_len"].items()))))
+            if short is not None:
+                hz = tr.evaluate_horizon(short, n_gen_samples=args.k)
+                print("Ragged-future held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by future length: %s"
+                      % (hz["ade_avg"], hz["fde_avg"], args.k, hz["ade_min"], hz["fde_min"],
+                         ", ".join("%d frames (%d agents) %.3f / %.3f" % (n, v["count"], v["ade_min"], v["fde_min"])
+                                   for n, v in sorted(hz["by_next"].items()))))
             tr.save(os.path.join(args.out, "socialWays-crowd.pt"), epoch=epoch)
     if world > 1:
         tr.close()              # captured collectives and the direct exchange's buffers go before their process group

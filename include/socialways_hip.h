@@ -238,6 +238,21 @@ int sw_dec_sample_fwd(const float* obsv /*[B,To,2]*/, int To, const float* z /*[
                       const float* S_pool /*[B,64] or NULL = zeros*/, const float* hT, const float* cT /*[B,64]*/,
                       const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4, const float* gt /*[B,Tp,2]*/,
                       float inv_ss, float* err, void* stream);
+/* sw_dec_sample_fwd with RAGGED FUTURES: gt stays the dense [B,Tp,2] buffer, left-aligned; pred_len [B] int32 (read per
+ * agent at a = r % B, like gt) gives the valid frames of row a, 1 .. Tp, the columns behind them are padding that no output
+ * depends on (NaN included: selects, not products).  With e_t = |(p_hat_t - gt_t) * inv_ss| and n = pred_len[a]:
+ *   err [K*B][2] = { (e_0 + .. + e_{n-1}) / (float)n, e_{n-1} }, summed over t ascending in fp32 as the dense launch sums:
+ *                  a row of length n carries the bits of sw_dec_sample_fwd called with Tp = n on the first n frames of gt.
+ * The rollout is untouched: every row runs all Tp steps and pred4 is the dense launch's bit for bit.  Errors are formed in
+ * the launch (pred4 == NULL: no trajectory leaves the kernel).  The kernel clamps n into 1 .. Tp, so a bad device-side
+ * length neither divides by zero nor reads past the row.  pred_len == NULL, or err == NULL (nothing for the lengths to
+ * say): sw_dec_sample_fwd itself.  Checked before the device is touched: everything sw_dec_sample_fwd checks, with the
+ * same codes.  Both tile forms; one owner per output, fixed order: two calls give the same bits.                     */
+int sw_dec_sample_fwd_plen(const float* obsv /*[B,To,2]*/, int To, const float* z /*[K*B,32]*/,
+                           const float* S_pool /*[B,64] or NULL = zeros*/, const float* hT, const float* cT /*[B,64]*/,
+                           const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
+                           const float* gt /*[B,Tp,2]*/, const int* pred_len /*[B] int32 or NULL*/, float inv_ss, float* err,
+                           void* stream);
 /* Best-of-K reduction of err [K][B][2] (sw_dec_sample_fwd): per_agent [B][4] = { mean_k ADE, mean_k FDE, min_k ADE,
  * min_k FDE }, best [B] (int32, or NULL) = the k of the smallest ADE, the lowest k on ties.  Sums run over k ascending
  * in fp32 (s = s + e_k, then s / K): deterministic.  Sums over agents are the caller's (test() keeps them in float64). */
@@ -271,6 +286,17 @@ int sw_sample_rank(const float* score /*[K,B]*/, const float* err /*[K,B,2] or N
  * clear[k][a] has one owner (no atomics): deterministic.                                                           */
 int sw_scene_clearance(const float* pos, int pstride, const float* start /*or NULL*/, int sstride, const int* scene_off,
                        int S, int B, int K, int Tp, float inv_ss, float* clear /*[K,B]*/, void* stream);
+/* sw_scene_clearance with a LENGTH per agent: len [B] int32, the valid future frames of agent a, 1 .. Tp (clamped into
+ * that range by the kernel), in every draw k; pos stays [K,B,Tp,pstride], left-aligned, and what lies behind a row's length
+ * is padding no output depends on (NaN included).  A collision needs both agents present: in the clearance of pair (a, b)
+ * the segment that ENDS at future frame t counts only if t < min(len[a], len[b]); segments run from t = 0 with a start
+ * point, else from t = 1.  An agent for which no segment counts against any partner has clearance +inf, like a
+ * single-agent scene.  r0 of a pair advances through every segment; only the minimum is gated.  All lengths n: the bits of
+ * sw_scene_clearance on the paths cut to n frames.  len == NULL (= all Tp): sw_scene_clearance itself.  Checked before the
+ * device is touched: everything sw_scene_clearance checks.  One owner per clear[k][a], no atomics: deterministic.    */
+int sw_scene_clearance_len(const float* pos, int pstride, const float* start /*or NULL*/, int sstride, const int* scene_off,
+                           const int* len /*[B] int32 or NULL*/, int S, int B, int K, int Tp, float inv_ss,
+                           float* clear /*[K,B]*/, void* stream);
 /* sw_scene_reduce: with sade[k][s] / sfde[k][s] = the mean over the scene's agents of err[k][a][0] / [1] and
  * sclear[k][s] = the minimum over them of clear[k][a],
  *   per_scene [S,6] = { min_k sade, min_k sfde, share of k with sclear < coll_dist, 1 if draw kbest collides else 0,

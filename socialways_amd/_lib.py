@@ -42,9 +42,11 @@ PROTOTYPES = {
     "sw_dec_rollout_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "sw_dec_rollout_fwd_aux": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "sw_dec_sample_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    "sw_dec_sample_fwd_plen": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "sw_sample_reduce": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "sw_sample_rank": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sw_scene_clearance": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "sw_scene_clearance_len": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "sw_scene_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sw_sample_nms": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sw_dec_rollout_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -100,15 +100,21 @@ __device__ __forceinline__ f32x4 fwd_l2_part(const f32x4 (&w2p)[3], const f32x4 
 // equals the plain form's on replicated inputs bit for bit.  ADE then means per-ROW errors: ade_part is err [B][2] =
 // { mean over t of the scaled displacement error, the error at the last step }, the per-lane sums the tile epilogue would
 // have folded.  PRED = false (metrics only) drops the pred4 stores at compile time.  No riders, no saved rows, no h_end.
-template <bool SAVE, bool ADE, int NB, bool SAMPLE = false, bool PRED = true>
+//
+// PLEN (sampling form with errors only): ragged FUTURES - gt row a holds pred_len[a] valid frames, left-aligned; the rest is
+// padding.  The rollout is untouched (all Tp steps, the same pred4); a row's error sums stop at its n = clamp(pred_len, 1,
+// Tp): err = { (e_0 + .. + e_{n-1}) / n, e_{n-1} }, the sums in the dense order, so a row of length n equals the dense
+// launch with Tp = n on the truncated gt bit for bit.  Selects, not products: NaN padding does not reach an output.
+template <bool SAVE, bool ADE, int NB, bool SAMPLE = false, bool PRED = true, bool PLEN = false>
 __device__ __forceinline__ void dec_rollout_fwd_tiles(
     float* smem, const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
     const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
     const float* __restrict__ dec_w, int B, int Tp, float* __restrict__ pred4, float* __restrict__ h_end,
     float* __restrict__ c_end, float* __restrict__ gsave, const float* __restrict__ gt, float inv_ss,
     float* __restrict__ ade_part, const float* __restrict__ dobs_w, float* __restrict__ dobs_act,
-    float* __restrict__ dobs_x4s, const float* __restrict__ gimg, int BA) {
+    float* __restrict__ dobs_x4s, const float* __restrict__ gimg, int BA, const int* __restrict__ pred_len = nullptr) {
   static_assert(!SAMPLE || (!SAVE && (ADE || PRED)), "sampling form: nothing saved, and something wanted");
+  static_assert(!PLEN || (SAMPLE && ADE), "future lengths: the sampling form's row errors only");
   if constexpr (NB == 1 && !SAMPLE) {
     // Workgroups beyond the agent tiles (only launched while the rollout leaves CUs idle): the observation LSTM of
     // the discriminator's first pass of this step - it does not depend on the generator - with the rows disc_bwd needs
@@ -144,6 +150,11 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
     b[k] = min(a0[k] + ln, B - 1);
     ag[k] = SAMPLE ? b[k] % BA : b[k];
     live[k] = (a0[k] + ln) < B;
+  }
+  [[maybe_unused]] int nlen[NB];   // PLEN: valid future frames of the row's agent (every lane loads: ag is clamped)
+  if constexpr (PLEN) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) nlen[k] = min(max(pred_len[ag[k]], 1), Tp);
   }
   const GSave gs = gsave_layout(B, To, Tp);
   // this wave's share of the layers (see above)
@@ -350,6 +361,10 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
   asm volatile("" : "+v"(b43i[0]), "+v"(b43i[1]));
 #pragma unroll
   for (int k = 0; k < NB; ++k) asm volatile("" : "+v"(px[k]), "+v"(py[k]), "+v"(c[k]), "+v"(h[k]));
+  if constexpr (PLEN) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) asm volatile("" : "+v"(nlen[k]));
+  }
   using T_ = std::true_type;
   using F_ = std::false_type;
   auto step = [&](int i, auto last_) {
@@ -497,9 +512,16 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
           const float q = dx * dx + dy * dy;
           const float e = sqrtf(q);
           if (ade_lane[k]) {      // arithmetic only: no memory operation under this branch
-            e_sum[k] += e;
-            e_sq[k] += q;
-            if (LAST) e_last[k] = e;
+            if constexpr (PLEN) {   // a row's sums stop at its length; its last valid step is rarely the peeled one
+              const bool in = i < nlen[k];
+              e_sum[k] = in ? e_sum[k] + e : e_sum[k];
+              e_sq[k] = in ? e_sq[k] + q : e_sq[k];
+              e_last[k] = i == nlen[k] - 1 ? e : e_last[k];
+            } else {
+              e_sum[k] += e;
+              e_sq[k] += q;
+              if (LAST) e_last[k] = e;
+            }
           }
         }
         {   // every lane of agent ln holds the same (p, v): all of them store it (no lane-dependent store)
@@ -547,7 +569,8 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
     }
     if constexpr (SAMPLE) {
       if (ade_lane[k]) {      // per row, not per tile: the lane that summed the row's errors stores them
-        ade_part[(size_t)b[k] * 2 + 0] = e_sum[k] / (float)Tp;
+        if constexpr (PLEN) ade_part[(size_t)b[k] * 2 + 0] = e_sum[k] / (float)nlen[k];
+        else ade_part[(size_t)b[k] * 2 + 0] = e_sum[k] / (float)Tp;
         ade_part[(size_t)b[k] * 2 + 1] = e_last[k];
       }
     } else if (ADE && wave == 0) {   // fixed shuffle tree over the tile's 16 agents -> one partial triple per 16-agent tile
@@ -602,6 +625,19 @@ __global__ __launch_bounds__(SW_THREADS) void dec_sample_fwd_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   dec_rollout_fwd_tiles<false, ERR, NB, true, PRED>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, R, Tp, pred4, nullptr, nullptr,
                                                     nullptr, gt, inv_ss, err, nullptr, nullptr, nullptr, gimg, BA);
+}
+
+// ... with ragged futures: err against the first pred_len[a] frames of gt (PLEN above); errors are always formed.
+template <bool PRED, int NB>
+__global__ __launch_bounds__(SW_THREADS) void dec_sample_fwd_plen_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ z, const float* __restrict__ S_pool,
+    const float* __restrict__ hT, const float* __restrict__ cT, const float* __restrict__ enc_w,
+    const float* __restrict__ dec_w, int R, int BA, int Tp, float* __restrict__ pred4, const float* __restrict__ gt,
+    const int* __restrict__ pred_len, float inv_ss, float* __restrict__ err, const float* __restrict__ gimg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  dec_rollout_fwd_tiles<false, true, NB, true, PRED, true>(smem, obsv, To, z, S_pool, hT, cT, enc_w, dec_w, R, Tp, pred4, nullptr,
+                                                           nullptr, nullptr, gt, inv_ss, err, nullptr, nullptr, nullptr, gimg, BA,
+                                                           pred_len);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1063,9 +1099,10 @@ extern "C" int sw_dec_rollout_fwd(const float* obsv, int To, const float* z, con
 // K rollouts of B encoded agents in one launch (sampling / evaluation): row k B + a reads z at the row and everything
 // else at agent a.  The tile forms are chosen as in sw_dec_rollout_fwd_aux (two tiles per workgroup above 256 tiles,
 // with registered images; SW_DEC_FWD2=0 / 1 forces either).
-extern "C" int sw_dec_sample_fwd(const float* obsv, int To, const float* z, const float* S_pool, const float* hT,
-                                 const float* cT, const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
-                                 const float* gt, float inv_ss, float* err, void* stream) {
+// pred_len (sw_dec_sample_fwd_plen) selects the length-aware kernels; NULL: the dense ones, as before.
+static int dec_sample_fwd_impl(const float* obsv, int To, const float* z, const float* S_pool, const float* hT,
+                               const float* cT, const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
+                               const float* gt, const int* pred_len, float inv_ss, float* err, void* stream) {
   if (!obsv || !z || !hT || !cT || !enc_w || !dec_w || B < 0 || K < 1 || To < 2 || Tp < 1) return SW_EARG;
   if ((!pred4 && !err) || (err && !gt)) return SW_EARG;
   if ((long long)K * B > 0x7fffffffLL - 2 * SW_TILE) return SW_ESHAPE;     // row and tile indices are ints
@@ -1083,15 +1120,39 @@ extern "C" int sw_dec_sample_fwd(const float* obsv, int To, const float* z, cons
     SW_CHECK_LAUNCH("dec_sample_fwd_kernel");
     return SW_OK;
   };
+  auto launch_plen = [&](auto nb_, auto pred_) -> int {
+    constexpr int NB = decltype(nb_)::value;
+    constexpr bool PR = decltype(pred_)::value;
+    constexpr int lds = NB * FwdLds::total * 4;
+    static int have = 0;
+    if (int rc = sw_set_lds((const void*)dec_sample_fwd_plen_kernel<PR, NB>, lds, have)) return rc;
+    SW_LAUNCH((dec_sample_fwd_plen_kernel<PR, NB>), dim3((tiles + NB - 1) / NB), dim3(SW_THREADS), lds, (hipStream_t)stream, obsv,
+              To, z, S_pool, hT, cT, enc_w, dec_w, R, B, Tp, pred4, gt, pred_len, inv_ss, err, gimg);
+    SW_CHECK_LAUNCH("dec_sample_fwd_plen_kernel");
+    return SW_OK;
+  };
   auto dispatch = [&](auto nb_) -> int {
     using T_ = std::true_type;
     using F_ = std::false_type;
-    if (!err) return launch(nb_, F_{}, T_{});
+    if (!err) return launch(nb_, F_{}, T_{});      // no errors wanted: the lengths have nothing to say
+    if (pred_len) return pred4 ? launch_plen(nb_, T_{}) : launch_plen(nb_, F_{});
     return pred4 ? launch(nb_, T_{}, T_{}) : launch(nb_, T_{}, F_{});
   };
   static const int fwd2_env = getenv("SW_DEC_FWD2") ? atoi(getenv("SW_DEC_FWD2")) : -1;
   if (gimg && (fwd2_env >= 0 ? fwd2_env != 0 : tiles > 256)) return dispatch(std::integral_constant<int, 2>{});
   return dispatch(std::integral_constant<int, 1>{});
+}
+
+extern "C" int sw_dec_sample_fwd(const float* obsv, int To, const float* z, const float* S_pool, const float* hT,
+                                 const float* cT, const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
+                                 const float* gt, float inv_ss, float* err, void* stream) {
+  return dec_sample_fwd_impl(obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, K, Tp, pred4, gt, nullptr, inv_ss, err, stream);
+}
+
+extern "C" int sw_dec_sample_fwd_plen(const float* obsv, int To, const float* z, const float* S_pool, const float* hT,
+                                      const float* cT, const float* enc_w, const float* dec_w, int B, int K, int Tp, float* pred4,
+                                      const float* gt, const int* pred_len, float inv_ss, float* err, void* stream) {
+  return dec_sample_fwd_impl(obsv, To, z, S_pool, hT, cT, enc_w, dec_w, B, K, Tp, pred4, gt, pred_len, inv_ss, err, stream);
 }
 
 extern "C" int sw_dec_rollout_bwd_aux(const float* dpred4, const float* enc_w, const float* dec_w,

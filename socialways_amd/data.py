@@ -47,6 +47,19 @@ def check_obs_len(obs_len, B, To, lo):
     return a.astype(np.int32)
 
 
+def check_pred_len(pred_len, B, Tp):
+    """The twin of check_obs_len for ragged FUTURES: host data (list / numpy) given as pred_len -> int32 numpy (B,), or
+    ValueError: not integers, not (B,), or a value outside 1 .. Tp (valid frames per row of a left-aligned (B, Tp, .) future)."""
+    a = np.asarray(pred_len)
+    if a.dtype.kind not in "iu":
+        raise ValueError("pred_len must hold integers, got dtype %s" % a.dtype)
+    if a.shape != (B,):
+        raise ValueError("pred_len must be (B,) = (%d,), got %s" % (B, a.shape))
+    if B and (a.min() < 1 or a.max() > Tp):
+        raise ValueError("pred_len must lie in 1 .. Tp = %d, got %d .. %d" % (Tp, a.min(), a.max()))
+    return a.astype(np.int32)
+
+
 class SceneDataset:
     """train.py:89-124: 4/5 of the scenes train, the rest test; float32 keep-ratio normalisation;
     tracks resident on the device for the whole run.  `batches` may be int16 on disk
@@ -82,6 +95,20 @@ class SceneDataset:
         if obs_len is not None:
             self.obs_len = torch.from_numpy(check_obs_len(obs_len, obsvs.shape[0], self.n_past, 2)).to(device)
 
+    # ragged futures (create_dataset_ragged(min_next=...)): valid frames per row, left-aligned in pred; int32 on the device,
+    # or None.  Evaluation only: set through set_pred_len(), read by evaluate*(); the training calls refuse such a dataset.
+    pred_len = None
+
+    def set_pred_len(self, pred_len):
+        """Attach the future lengths (N,) of create_dataset_ragged(min_next=...) - list, numpy array or tensor, 1 .. n_next -
+        checked on the host and uploaded as int32; None detaches them.  Works on held_out() datasets too.  Returns self."""
+        if pred_len is None:
+            self.pred_len = None
+            return self
+        host = pred_len.cpu().numpy() if isinstance(pred_len, torch.Tensor) else pred_len
+        self.pred_len = torch.from_numpy(check_pred_len(host, self.pred.shape[0], self.n_next)).to(self.pred.device)
+        return self
+
     @classmethod
     def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None, train=False):
         """Windows that a model trained on `like` is evaluated on: EVERY scene is a test scene (no training part), the
@@ -111,8 +138,9 @@ class SceneDataset:
     @classmethod
     def from_npz(cls, path, device="cuda"):
         d = np.load(path)
-        return cls(d["obsvs"], d["preds"], d["batches"], d["times"] if "times" in d.files else None, device,
-                   d["obs_len"] if "obs_len" in d.files else None)
+        out = cls(d["obsvs"], d["preds"], d["batches"], d["times"] if "times" in d.files else None, device,
+                  d["obs_len"] if "obs_len" in d.files else None)
+        return out.set_pred_len(d["pred_len"]) if "pred_len" in d.files else out
 
     def packed_steps(self, batch_size):
         """Greedy scene packing of train() (train.py:446-456): scenes are appended until the next one
@@ -298,7 +326,7 @@ def _scene_runs(t0s):
     return keep, np.array(out_b, dtype=np.int64)
 
 
-def create_dataset_ragged(p_data, t_data, t_range, n_past=8, n_next=12, min_past=2):
+def create_dataset_ragged(p_data, t_data, t_range, n_past=8, n_next=12, min_past=2, min_next=None):
     """create_dataset() that also keeps the pedestrians with a SHORT history: one is kept at t if it has samples at t and at
     t + step*(n_next-1), and its history n is the largest j in min_past .. n_past with a sample at t - step*j exactly j
     entries before t (none: dropped).  obsvs stay (N, n_past, 2), RIGHT-ALIGNED: row r holds its obs_len[r] samples before
@@ -306,17 +334,34 @@ def create_dataset_ragged(p_data, t_data, t_range, n_past=8, n_next=12, min_past
     normalisation of SceneDataset is the one of the valid samples).  Windows are ordered and grouped into scenes as in
     create_dataset(); with min_past == n_past the first four outputs are create_dataset()'s for tracks without gaps (a gap
     inside the history: create_dataset() only asks for a sample at t - step*n_past, this builder for n_past samples).
-    Returns (obsvs f32, preds f32, times list, batches int64, obs_len int32 (N,))."""
+    Returns (obsvs f32, preds f32, times list, batches int64, obs_len int32 (N,)).
+    min_next (1 .. n_next; None = the above): pedestrians with a SHORT FUTURE are kept as well - evaluation windows.  One is
+    kept at t if it has a sample at t and a history as above; its future m is the largest j in min_next .. n_next with the
+    sample at t + step*(j-1) exactly j-1 entries after the one at t (no gap inside the future; none: dropped).  preds stay
+    (N, n_next, 2), LEFT-ALIGNED, the columns behind the m valid ones repeating the last valid sample (finite, a real
+    position), and a sixth output pred_len int32 (N,) holds m.  With min_next == n_next the first five outputs are those of
+    min_next=None for tracks without gaps."""
     n_past, min_past = int(n_past), int(min_past)
     if not 1 <= min_past <= n_past:
         raise ValueError("min_past must lie in 1 .. n_past = %d, got %d" % (n_past, min_past))
+    if min_next is not None:
+        if int(min_next) != min_next or not 1 <= int(min_next) <= int(n_next):
+            raise ValueError("min_next must be an integer in 1 .. n_next = %d, got %r" % (n_next, min_next))
+        min_next = int(min_next)
     step = t_range.step
     index = [dict((int(t), k) for k, t in reversed(list(enumerate(td)))) for td in t_data]   # first occurrence wins
-    t0s, xs, ys, ns = [], [], [], []
+    t0s, xs, ys, ns, ms = [], [], [], [], []
     for t in range(t_range.start, t_range.stop, 1):
         for i, ix in enumerate(index):
-            b, c = ix.get(t), ix.get(t + step * (n_next - 1))
-            if b is None or c is None:
+            b = ix.get(t)
+            if b is None:
+                continue
+            if min_next is None:
+                c, m = ix.get(t + step * (n_next - 1)), n_next
+            else:
+                m = next((j for j in range(n_next, min_next - 1, -1) if ix.get(t + step * (j - 1)) == b + j - 1), 0)
+                c = b + m - 1 if m else None
+            if c is None:
                 continue
             n = next((j for j in range(n_past, min_past - 1, -1) if ix.get(t - step * j) == b - j and b - j >= 0), 0)
             if n == 0:
@@ -324,12 +369,17 @@ def create_dataset_ragged(p_data, t_data, t_range, n_past=8, n_next=12, min_past
             o = p_data[i][b - n:b]
             t0s.append(t)
             xs.append(np.concatenate([np.repeat(o[:1], n_past - n, axis=0), o]))
-            ys.append(p_data[i][b:c + 1])
+            y = p_data[i][b:c + 1]
+            ys.append(y if min_next is None else np.concatenate([y, np.repeat(y[-1:], n_next - m, axis=0)]))
             ns.append(n)
+            ms.append(m)
     keep, batches = _scene_runs(t0s)
     obsvs = np.array([xs[k] for k in keep]).astype(np.float32)
     preds = np.array([ys[k] for k in keep]).astype(np.float32)
-    return obsvs, preds, t0s, batches, np.array([ns[k] for k in keep], dtype=np.int32)
+    obs_len = np.array([ns[k] for k in keep], dtype=np.int32)
+    if min_next is None:
+        return obsvs, preds, t0s, batches, obs_len
+    return obsvs, preds, t0s, batches, obs_len, np.array([ms[k] for k in keep], dtype=np.int32)
 
 
 def biwi_to_npz(obsmat_path, npz_path, n_past=8, n_next=12, min_past=None):
@@ -344,6 +394,17 @@ def biwi_to_npz(obsmat_path, npz_path, n_past=8, n_next=12, min_past=None):
     obsvs, preds, times, batches, obs_len = create_dataset_ragged(p_data, t_data, t_range, n_past, n_next, min_past)
     np.savez(npz_path, obsvs=obsvs, preds=preds, times=times, batches=batches, obs_len=obs_len)
     return obsvs, preds, times, batches, obs_len
+
+
+def biwi_to_npz_ragged(obsmat_path, npz_path, n_past=8, n_next=12, min_past=2, min_next=1):
+    """biwi_to_npz for evaluation windows with short histories AND short futures: obsmat.txt -> npz {obsvs, preds, times,
+    batches, obs_len, pred_len} of create_dataset_ragged(min_past=, min_next=); the six arrays are returned as well."""
+    p_data, t_data, interval = parse_biwi(obsmat_path)
+    t_range = range(int(t_data[0][0]), int(t_data[-1][-1]), interval)
+    obsvs, preds, times, batches, obs_len, pred_len = create_dataset_ragged(p_data, t_data, t_range, n_past, n_next, min_past,
+                                                                            min_next)
+    np.savez(npz_path, obsvs=obsvs, preds=preds, times=times, batches=batches, obs_len=obs_len, pred_len=pred_len)
+    return obsvs, preds, times, batches, obs_len, pred_len
 
 
 def synth_crowd_frames(n_frames=60, n_ped=24, interval=6, seed=3, max_life=40):

@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .model import _sample_noise, _scene_index, _wgrad_ws, check_score_samples, get_traj_4d, refuse_obs_len, refuse_ragged_fused
-from .trainer import SocialWaysTrainer
+from .trainer import _PRED_LEN_TRAIN, SocialWaysTrainer, _refuse_pred_len
 
 
 def _c(t):
@@ -452,6 +452,7 @@ class GenericTrainer(SocialWaysTrainer):
 
     def train_epoch_ragged(self, data, batch_size, draw=None):
         """Refused: training on ragged observation histories belongs to the fused 64-unit path (no device is touched)."""
+        _refuse_pred_len(data, "train_epoch_ragged()", _PRED_LEN_TRAIN)
         raise L.SocialWaysHipError("%s has no train_epoch_ragged(): training on a dataset with obs_len (ragged observation "
                                    "histories) is implemented for the fused 64-unit path (SocialWaysTrainer) only"
                                    % type(self).__name__)

@@ -392,17 +392,29 @@ def _check_obs_len_tensor(obs_len, B, device):
     return obs_len.contiguous()
 
 
+def _check_pred_len_tensor(pred_len, B, device, name="pred_len"):
+    """What gen_sample / scene_clearance take as future lengths: an int32 tensor (B,) on `device` (SceneDataset.set_pred_len
+    makes one; the kernels clamp it into 1 .. Tp)."""
+    if not isinstance(pred_len, torch.Tensor) or pred_len.dtype != torch.int32 or tuple(pred_len.shape) != (B,) \
+            or pred_len.device != device:
+        raise ValueError("%s must be an int32 tensor (B,) = (%d,) on %s" % (name, B, device))
+    return pred_len.contiguous()
+
+
 _sample_img = {}      # device -> the image buffer the sampling path owns (sw_gen_images)
 
 
 def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_social, K, gt=None, inv_ss=1.0,
-               want_pred=True, keep_pred=False, obs_len=None):
+               want_pred=True, keep_pred=False, pred_len=None, obs_len=None):
     """K sampled futures of predict() for B agents (test(), train.py:563-616): the encoder over the observed steps and the
     social block run ONCE on the B agents, then ONE sampling launch rolls out the K * B rows (row k * B + a = draw k of
     agent a) reading the encoding per agent - nothing is replicated.  noise_k (K * B, 32).
     gt (B, n_next, 2): the per-row errors are formed in the launch and reduced over k on the device.
     keep_pred: pred4 is written and returned although the caller wants no trajectories (want_pred False) - it stays on
     the device for a consumer there (scene_metrics).
+    pred_len (B,) int32 on the device: ragged futures - row a of gt holds pred_len[a] valid frames, left-aligned, and its
+    errors are the mean over those frames and the error at the last of them (sw_dec_sample_fwd_plen; the rollout and pred4
+    are the dense launch's, the padding of gt reaches no output).  Needs gt.  None: the dense sampling launch.
     obs_len (B,) int32 on the device: ragged histories - row a holds obs_len[a] valid frames right-aligned in obsv and its
     encoding is that of those frames alone (sw_enc_lstm_fwd_ragged in place of the encoder launch; the social block and
     the rollout read the last frames and are the same launches).  None: the dense encoder launch.
@@ -426,6 +438,10 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
         if gt.shape != (B, n_next, 2):
             raise ValueError("gt must be (B, n_next, 2)")
     dev = obsv.device
+    if pred_len is not None:
+        if gt is None:
+            raise ValueError("pred_len describes gt: it needs one")
+        pred_len = _check_pred_len_tensor(pred_len, B, dev)
     if obs_len is not None:
         obs_len = _check_obs_len_tensor(obs_len, B, dev)
     st = L.stream()
@@ -451,8 +467,12 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
             L.call("sw_social_pool_fwd_aux", L.ptr(obsv), To, L.ptr(hT), L.ptr(scenes.scene_off), scenes.S, B, scenes.amax,
                    L.ptr(emb_w), L.ptr(att_w), L.ptr(S), None, L.ptr(scenes.big_blocks), scenes.NB, L.ptr(wh), None,
                    None, None, 0, st)
-        L.call("sw_dec_sample_fwd", L.ptr(obsv), To, L.ptr(noise_k), L.ptr(S), L.ptr(hT), L.ptr(cT), L.ptr(enc_w),
-               L.ptr(dec_w), B, K, n_next, L.ptr(pred4), L.ptr(gt), float(inv_ss), L.ptr(err), st)
+        if pred_len is None:
+            L.call("sw_dec_sample_fwd", L.ptr(obsv), To, L.ptr(noise_k), L.ptr(S), L.ptr(hT), L.ptr(cT), L.ptr(enc_w),
+                   L.ptr(dec_w), B, K, n_next, L.ptr(pred4), L.ptr(gt), float(inv_ss), L.ptr(err), st)
+        else:
+            L.call("sw_dec_sample_fwd_plen", L.ptr(obsv), To, L.ptr(noise_k), L.ptr(S), L.ptr(hT), L.ptr(cT), L.ptr(enc_w),
+                   L.ptr(dec_w), B, K, n_next, L.ptr(pred4), L.ptr(gt), L.ptr(pred_len), float(inv_ss), L.ptr(err), st)
     finally:
         L.call("sw_gen_images", None, None, None, None, None, None)
     if err is None:
@@ -463,10 +483,13 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
     return pred4, (per_agent, best, err)
 
 
-def scene_clearance(pos, start, scenes, K, inv_ss=1.0):
+def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     """clear (K, B): per draw and agent the closest approach to another agent of its scene, times inv_ss; +inf in
     single-agent scenes (sw_scene_clearance).  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or
-    None: the point in front of the Tp positions (any row stride: a view such as obsv[:, -1] is read in place)."""
+    None: the point in front of the Tp positions (any row stride: a view such as obsv[:, -1] is read in place).
+    lens (B,) int32 on the device: ragged futures - agent a is present for its first lens[a] frames (in every draw), and the
+    segment of a pair that ends at frame t counts only if both are present at t; +inf where nothing counts
+    (sw_scene_clearance_len).  None: the dense launch."""
     L.require_gpu(pos)
     pos = pos.contiguous()
     Tp, pstride, B = pos.shape[-2], pos.shape[-1], scenes.B
@@ -480,8 +503,13 @@ def scene_clearance(pos, start, scenes, K, inv_ss=1.0):
             start = start[:, :2].float().contiguous()
         sstride = start.stride(0)
     clear = torch.empty(K, B, device=pos.device)
-    L.call("sw_scene_clearance", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, K,
-           Tp, float(inv_ss), L.ptr(clear), L.stream())
+    if lens is None:
+        L.call("sw_scene_clearance", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, K,
+               Tp, float(inv_ss), L.ptr(clear), L.stream())
+    else:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+        L.call("sw_scene_clearance_len", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off),
+               L.ptr(lens), scenes.S, B, K, Tp, float(inv_ss), L.ptr(clear), L.stream())
     return clear
 
 
@@ -505,9 +533,16 @@ def scene_metrics(err, pred4, obsv, scenes, K, n_next, inv_ss, coll_dist):
     launches: the clearance of every (draw, agent) along pred4 (K * B, n_next, 4), each path starting at the agent's last
     observed position, and the reduction per scene.  err (K, B, 2) = the row errors of gen_sample.
     Returns (per_scene (S, 6), kbest (S,) int32, clear (K, B)) - the columns of scene_reduce."""
+    return scene_metrics_len(err, pred4, obsv, scenes, K, n_next, inv_ss, coll_dist)
+
+
+def scene_metrics_len(err, pred4, obsv, scenes, K, n_next, inv_ss, coll_dist, lens=None):
+    """scene_metrics() with future lengths (its own argument list is pinned): lens (B,) int32 on the device - the clearance
+    counts a pair's segment only while both agents are present (scene_clearance(lens=...)), and err is expected to be
+    gen_sample(pred_len=...)'s.  lens None: the dense launches."""
     if pred4.shape[-2] != n_next:
         raise ValueError("pred4 must hold n_next = %d steps" % n_next)
-    clear = scene_clearance(pred4, obsv[:, -1], scenes, K, inv_ss)
+    clear = scene_clearance(pred4, obsv[:, -1], scenes, K, inv_ss, lens=lens)
     per_scene, kbest = scene_reduce(err, clear, scenes, K, coll_dist)
     return per_scene, kbest, clear
 

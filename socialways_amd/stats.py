@@ -14,6 +14,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .data import check_pred_len
 
 
 def _dev(x, device):
@@ -122,6 +123,31 @@ def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
             raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
     scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
     clear = ops.scene_clearance(t4, start, scenes, K, float(scale))
+    return clear if t.dim() == 4 else clear[0]
+
+
+def scene_clearance_len(trajs, sub_batches, lens, start=None, scale=1.0, device="cuda"):
+    """scene_clearance() for futures of different lengths (`sw_scene_clearance_len`): lens (B,) - list, numpy array or
+    tensor of integers 1 .. T - gives the frames agent a is present for, left-aligned in trajs (what lies behind them is
+    padding and reaches no output).  A collision needs both agents present: the segment of a pair that ends at frame t counts
+    only if t < min(lens[a], lens[b]).  An agent for which no segment counts has clearance +inf.  Everything else as
+    scene_clearance()."""
+    t = _dev(trajs, device)
+    L.require_gpu(t)
+    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
+        raise ValueError("trajs must be (K, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    t4 = t if t.dim() == 4 else t.unsqueeze(0)
+    K, B, T = t4.shape[0], t4.shape[1], t4.shape[2]
+    if K < 1:
+        raise ValueError("no draws")
+    host = lens.cpu().numpy() if isinstance(lens, torch.Tensor) else lens
+    lens = torch.from_numpy(check_pred_len(host, B, T)).to(t.device)
+    if start is not None:
+        start = _dev(start, device)
+        if tuple(start.shape) != (B, 2):
+            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    clear = ops.scene_clearance(t4, start, scenes, K, float(scale), lens=lens)
     return clear if t.dim() == 4 else clear[0]
 
 

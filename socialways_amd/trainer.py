@@ -196,6 +196,18 @@ def _refuse_ragged(data, what, why):
         raise L.SocialWaysHipError("%s does not take a dataset with obs_len (ragged observation histories): %s" % (what, why))
 
 
+def _refuse_pred_len(data, what, why):
+    """Ragged futures are an evaluation feature: every call whose losses or errors would read the padding of a short future
+    as truth refuses a dataset that carries pred_len, loudly, before any launch."""
+    if getattr(data, "pred_len", None) is not None:
+        raise L.SocialWaysHipError("%s does not take a dataset with pred_len (ragged futures): %s" % (what, why))
+
+
+_PRED_LEN_TRAIN = ("a truncated future has no discriminator input (D encodes the flattened n_next frames) and the losses would "
+                   "read the padding as truth - train on full windows (create_dataset / create_dataset_ragged without "
+                   "min_next) and evaluate the short futures with evaluate*() / evaluate_horizon()")
+
+
 class SocialWaysTrainer:
     STEPS_PER_LAUNCH = 4    # train_epoch: consecutive packed batches of one scene layout per graph launch (step_many)
     Z_COLS = 32             # noise columns of the kernels (hidden size 64: train.py:81); smaller models are zero-padded
@@ -942,6 +954,7 @@ class SocialWaysTrainer:
         launch in front of the graph launch on the same stream, read by the steps through their z-resident path (no
         pinned-slot copy).  The label-noise scalars stay the reference's two host draws.
         A dataset with obs_len (ragged histories) is refused: its steps run eagerly through train_epoch_ragged()."""
+        _refuse_pred_len(data, "train_epoch()", _PRED_LEN_TRAIN)
         _refuse_ragged(data, "train_epoch()", "its graph-captured steps have no ragged form - train on the ragged windows with "
                        "train_epoch_ragged(), or on full windows (create_dataset) and evaluate the ragged ones with "
                        "evaluate*() / evaluate_history()")
@@ -954,7 +967,8 @@ class SocialWaysTrainer:
         With `ragged_fused` and `use_graph` (not the "fixed" variety step) the loop is train_epoch()'s: consecutive packed
         batches of one local layout share a step_many(obs_len=[...]) launch of up to STEPS_PER_LAUNCH captured ragged steps,
         with `self.noise` one fill launch in front of it - the same weights and return values bit for bit.
-        A dataset without obs_len is refused: train_epoch() is its call."""
+        A dataset without obs_len is refused: train_epoch() is its call; so is one with pred_len (ragged futures)."""
+        _refuse_pred_len(data, "train_epoch_ragged()", _PRED_LEN_TRAIN)
         ol = getattr(data, "obs_len", None)
         if ol is None:
             raise L.SocialWaysHipError("train_epoch_ragged() needs a dataset with obs_len (create_dataset_ragged, "
@@ -1080,6 +1094,8 @@ class SocialWaysTrainer:
         identical rollouts, one launch sequence and one host sync per chunk instead of per scene.  The noise is
         drawn scene by scene, K draws of (n, noise_len) each, in the reference's order (train.py:584).
         A dataset with obs_len (ragged histories) is refused: this call replicates the dense forward pass."""
+        _refuse_pred_len(data, "test()", "its errors run over all n_next frames of the dense forward pass - use evaluate() / "
+                         "evaluate_horizon(), whose sampling launch scores each agent on its valid frames")
         _refuse_ragged(data, "test()", "it runs the dense forward pass on K copies of every scene - use evaluate() / "
                        "evaluate_history(), whose sampling path encodes each agent over its valid frames")
         ss, dev, K = data.ss, self.device, n_gen_samples
@@ -1144,7 +1160,8 @@ class SocialWaysTrainer:
         """The K draws of the held-out scenes, chunk by chunk: what evaluate() and every evaluate_*() do before their own
         work.  Yields a namespace per chunk: first (index of its first scene), ab (its scenes' row ranges), lo, n (its rows
         are lo .. lo + n-1 of the held-out tracks), obsv, pred, sb and scenes (the chunk-local scene ranges and their
-        SceneIndex), obs_len (the chunk's slice of data.obs_len - ragged histories - or None), z (K, n, Z_COLS) on the device,
+        SceneIndex), obs_len (the chunk's slice of data.obs_len - ragged histories - or None), pred_len (the slice of
+        data.pred_len - ragged futures: per_agent and err are then over each row's valid frames - or None), z (K, n, Z_COLS) on the device,
         and from the sampling hook ph (K, n, n_next, 4; None without want_pred),
         per_agent (n, 4), err (K, n, 2), best (n,) int32.  z comes from `dn` (a DeviceNoise: evaluation domain, row = the
         ABSOLUTE held-out row, so a scene's draws do not depend on the chunking; one launch that also writes the padding),
@@ -1154,12 +1171,17 @@ class SocialWaysTrainer:
         ol = getattr(data, "obs_len", None)
         if ol is not None and not isinstance(self.G, Generator):      # the generic-width and wide paths: refused before any chunk is built
             refuse_obs_len(ol, type(self).__name__)
+        pl = getattr(data, "pred_len", None)
+        if not isinstance(self.G, Generator):
+            _refuse_pred_len(data, "%s.evaluate*()" % type(self).__name__, "ragged futures are implemented for the fused 64-unit "
+                             "path only (hidden_size <= 64, n_latent_codes = 2)")
         dev = self.device
         with torch.no_grad():
             for first, scenes in self._eval_fold(data, K, just_one):
                 lo, hi = scenes[0][0], scenes[-1][1]
                 c = SimpleNamespace(first=first, ab=scenes, lo=lo, n=hi - lo, obsv=data.obsv[lo:hi], pred=data.pred[lo:hi])
                 c.obs_len = ol[lo:hi] if ol is not None else None
+                c.pred_len = pl[lo:hi] if pl is not None else None
                 if dn is not None:
                     c.z = dn.fill(c.n, self.noise_len, domain=EVAL, n_draws=K, row0=lo, ld=self.Z_COLS, device=dev)[0]
                 else:
@@ -1178,7 +1200,7 @@ class SocialWaysTrainer:
         G = self.G
         ph, red = ops.gen_sample(G.encoder.packed(), G.feature_embedder.packed(), G.attention.packed(), G.decoder.packed(),
                                  c.obsv, c.z.view(K * c.n, -1), c.scenes, self.n_next, G.use_social, K, gt=c.pred,
-                                 inv_ss=1.0 / float(ss), want_pred=want_pred, obs_len=c.obs_len)
+                                 inv_ss=1.0 / float(ss), want_pred=want_pred, pred_len=c.pred_len, obs_len=c.obs_len)
         return ph.view(K, c.n, self.n_next, 4) if ph is not None else None, red[0], red[2], red[1]
 
     def _eval_records(self, data, c, preds_k, extra={}):
@@ -1186,8 +1208,11 @@ class SocialWaysTrainer:
         (K, n, n_next, 2) from preds_k, preds_gtt, preds_lnr, all denormalised - plus the scene's part of every entry of
         `extra` = {key: (device tensor, axis)}: axis = the one that runs over the chunk's rows, None = one entry per scene.
         A ragged chunk (c.obs_len): every record also has obs_len (n,), and preds_lnr is predict_cv of each row's VALID
-        frames - a row of two frames gets the two-frame rule, not a velocity through its padding."""
+        frames - a row of two frames gets the two-frame rule, not a velocity through its padding.
+        A chunk with ragged futures (c.pred_len): every record also has pred_len (n,); preds_gtt keeps its padding."""
         linear_preds = predict_cv(c.obsv, self.n_next)
+        if getattr(c, "pred_len", None) is not None:
+            extra = dict(extra, pred_len=(c.pred_len, 0))
         obs_len = getattr(c, "obs_len", None)
         if obs_len is not None:
             extra = dict(extra, obs_len=(obs_len, 0))
@@ -1257,6 +1282,35 @@ class SocialWaysTrainer:
         out.update(by_len=by_len, n_agents=sum(b - a for a, b in base.scenes))
         return out
 
+    def evaluate_horizon(self, data, n_gen_samples=20, just_one=False, noise=None):
+        """evaluate() split by FUTURE length, the twin of evaluate_history(): what an agent that stays for m more frames is
+        predicted with.  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          by_next  {m: {count, ade_avg, fde_avg, ade_min, fde_min}} for every future length m present among the agents
+                   evaluated (data.pred_len; a dataset without it: the single bucket n_next), the means over that length's
+                   agents: sum_m count_m * by_next[m][key] / data.n_test_samples is the overall key;
+          n_agents.
+        Chunking, noise and sampling launches are evaluate()'s; the sums are float64 on the device, one host sync at the end."""
+        dn = self._device_noise(noise)
+        dev, Tp = self.device, data.n_next
+        base = _EvalSums(dev)
+        acc = torch.zeros(Tp + 1, 5, dtype=torch.float64, device=dev)      # per length: count | the four sums
+        lens = torch.arange(Tp + 1, device=dev)[:, None]
+        for c in self._eval_draws(data, n_gen_samples, just_one, dn, base, want_pred=False):
+            m = c.pred_len if c.pred_len is not None else torch.full((c.n,), Tp, dtype=torch.int32, device=dev)
+            rows = torch.cat([torch.ones(c.n, 1, dtype=torch.float64, device=dev), c.per_agent.double()], dim=1)
+            # a select per bucket, not a product with a 0 / 1 mask: a row whose error is not finite stays in its own bucket
+            acc += torch.where((m[None, :] == lens)[:, :, None], rows[None], torch.zeros((), dtype=torch.float64, device=dev)).sum(1)
+        vals = torch.cat([base.sums / data.n_test_samples, acc.flatten()]).tolist()
+        out = dict(zip(_EvalSums.KEYS, vals[:4]))
+        by_next = {}
+        for m in range(Tp + 1):
+            cnt, *sums = vals[4 + 5 * m:9 + 5 * m]
+            if cnt > 0:
+                by_next[m] = dict(count=int(cnt), **{k: v / cnt for k, v in zip(_EvalSums.KEYS, sums)})
+        out.update(by_next=by_next, n_agents=sum(b - a for a, b in base.scenes))
+        return out
+
     def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
         """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
         its agents - the joint future that copy k of the scene rolls out.  Returns a dict:
@@ -1275,7 +1329,10 @@ class SocialWaysTrainer:
         the draws where they are and the same two on the ground truth; sums are float64 on the device, one host sync at the end.  With `collect` every
         record of evaluate() also has `clear` (K, n), `per_scene` (6,) and `kbest` (columns: ops.scene_reduce).
         With self.noise set (a DeviceNoise) the draws are evaluate()'s from that stream.  This call's argument list is pinned
-        (tests/test_scene_host.py), so the stream reaches it through the attribute only, not through a keyword."""
+        (tests/test_scene_host.py), so the stream reaches it through the attribute only, not through a keyword.
+        A dataset with pred_len (ragged futures): the errors are over each agent's valid frames and a collision needs both
+        agents present - the segment of a pair that ends at frame t counts only while t < both lengths, for the K draws
+        and for col_gt alike (ops.scene_clearance(lens=...)): a draw is not charged for crossing a place nobody was seen at."""
         dn = self._device_noise(None)
         dev, K = self.device, n_gen_samples
         inv_ss = 1.0 / float(data.ss)
@@ -1283,9 +1340,11 @@ class SocialWaysTrainer:
         # sum n * jade | sum n * jfde | then over multi-agent scenes: colliding share | kbest flag | n * agent share | gt flag
         acc = torch.zeros(6, dtype=torch.float64, device=dev)
         for c in self._eval_draws(data, K, just_one, dn, base):
-            per_scene, kbest, clear = ops.scene_metrics(c.err, c.ph, c.obsv, c.scenes, K, self.n_next, inv_ss, coll_dist)
+            per_scene, kbest, clear = ops.scene_metrics_len(c.err, c.ph, c.obsv, c.scenes, K, self.n_next, inv_ss, coll_dist,
+                                                            lens=c.pred_len)      # no lengths: scene_metrics()'s launches
             gt_scene, _ = ops.scene_reduce(torch.zeros(1, c.n, 2, device=dev),
-                                           ops.scene_clearance(c.pred, c.obsv[:, -1], c.scenes, 1, inv_ss), c.scenes, 1, coll_dist)
+                                           ops.scene_clearance(c.pred, c.obsv[:, -1], c.scenes, 1, inv_ss, lens=c.pred_len),
+                                           c.scenes, 1, coll_dist)
             cnt = (c.scenes.scene_off[1:] - c.scenes.scene_off[:-1]).double()
             multi = (cnt > 1).double()
             ps = per_scene.double()
@@ -1340,25 +1399,40 @@ class SocialWaysTrainer:
         Per-agent sums are divided by data.n_test_samples like evaluate()'s, per-(draw, agent) sums by K times that; float64
         sums on the device, one host sync at the end.  Chunking, host noise and sampling launches are evaluate()'s.  With
         `collect` every record of evaluate() also has `score` (K, n), `order` (n, top_m) and `code_hat` (K, n, codes).
-        `noise`: as evaluate() - a DeviceNoise (default self.noise) gives evaluate(noise=...)'s draws."""
+        `noise`: as evaluate() - a DeviceNoise (default self.noise) gives evaluate(noise=...)'s draws.
+        A dataset with pred_len (ragged futures): the errors are over each agent's valid frames; D scores the draws, which are
+        full length, as ever; a truncated future is no D input, so score_gt is the mean over the agents with a FULL future,
+        divided by their count n_full (0.0 when there is none), and the dict gains n_full."""
         dn = self._device_noise(noise)
         dev, K, M = self.device, int(n_gen_samples), int(top_m)
         if not 1 <= M <= K:
             raise ValueError("top_m must lie in 1 .. n_gen_samples = %d, got %d" % (K, M))
         base = _EvalSums(dev)
         acc = torch.zeros(len(self.RANKED_KEYS), dtype=torch.float64, device=dev)
+        ragged_next = getattr(data, "pred_len", None) is not None
+        n_full = torch.zeros(1, dtype=torch.float64, device=dev)      # rows with a full future (ragged futures only)
         for c in self._eval_draws(data, K, just_one, dn, base):
             score, code = self.D.score_samples(c.obsv, c.ph, obs_len=c.obs_len)
             order, ranked = ops.sample_rank(score, K, M, err=c.err, best=c.best)
             gt_score, _ = self.D.score_samples(c.obsv, get_traj_4d(c.obsv, c.pred)[1].unsqueeze(0), obs_len=c.obs_len)
+            if c.pred_len is not None:      # a select: what D made of a padded future is dropped, whatever it is
+                full = (c.pred_len == self.n_next).view(1, -1)
+                gt_score = torch.where(full, gt_score, torch.zeros_like(gt_score))
+                n_full += full.sum()
             csq = (code.double() - c.z[:, :, :code.shape[-1]].double()).pow(2).mean(dim=2)
             acc += torch.cat([ranked.double().sum(0), torch.stack([score.double().sum(), gt_score.double().sum(), csq.sum()])])
             if collect is not None:
                 collect.extend(self._eval_records(data, c, c.ph, dict(score=(score, 1), order=(order, 0), code_hat=(code, 1))))
         nt = data.n_test_samples
         out = base.result(data)
-        out.update(zip(self.RANKED_KEYS, (acc / torch.tensor([nt] * 5 + [K * nt, nt, K * nt], dtype=torch.float64, device=dev)).tolist()))
+        div = torch.tensor([nt] * 5 + [K * nt, nt, K * nt], dtype=torch.float64, device=dev)
+        if ragged_next:      # score_gt over the full rows, divided on the device (no full row: 0 / 1); n_full rides along
+            div[6:7] = n_full.clamp(min=1.0)
+        vals = torch.cat([acc / div, n_full]).tolist()
+        out.update(zip(self.RANKED_KEYS, vals))
         out.update(n_agents=sum(b - a for a, b in base.scenes), K=K, top_m=M)
+        if ragged_next:
+            out.update(n_full=int(vals[-1]))
         return out
 
     @staticmethod
