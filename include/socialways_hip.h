@@ -202,6 +202,20 @@ int sw_social_pool_bwd(const float* obsv, int To, const float* h, const int* sce
                                                handle for the next sw_gen_wgrad on the same workspace*/,
                        void* stream);
 
+/* sw_social_pool_bwd's per-pair-rows form followed by sw_enc_lstm_bwd_aux (dy, c0, dh0, dc0 NULL, t0 = 0) in ONE launch of a
+ * workgroup per scene that keeps dh_T + its social gradient on chip: the same dgates rows, pair rows, agent rows and deferred
+ * weight-gradient problems as the two launches; dhT is read, not updated.  For layouts in which every scene has at most 16
+ * agents (Amax <= 16, no big_blocks), S <= sw_scene_wg_max_scenes(), and on which the two launches take the rows form
+ * (0 < P < sw_social_rows_max_pairs() * S); SW_ESHAPE otherwise (the caller then issues the two launches).  scene_off must
+ * tile [0, B).  aux_*: the masked copy of sw_enc_lstm_bwd_aux.                                                          */
+int sw_scene_wg_max_scenes(void);
+int sw_social_rows_max_pairs(void);
+int sw_social_enc_bwd(const float* obsv, int To, const float* h, const int* scene_off, const long long* pair_off, int S, int B,
+                      int Amax, long long P, const float* emb_w, const float* att_w, const float* attn, const float* dS,
+                      const float* dhT, const float* dcT, float* d_emb_w, float* d_att_w, float* pair_ws, float* wgrad_ws,
+                      const float* enc_w, const float* act, float* dgates, const float* aux_src, float* aux_dst,
+                      const float* aux_mask, long long aux_n, sw_wgrad_batch* defer, void* stream);
+
 /* ---- predict() decode loop (train.py:415-432): DecoderFC + position integration + the
  *      re-fed EncoderLstm step, Tp times, one persistent kernel (one workgroup per 16-agent tile; with the
  *      step's weight images registered and more than 256 tiles: per two tiles, the same body issuing every

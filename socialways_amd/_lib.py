@@ -34,6 +34,10 @@ PROTOTYPES = {
     "sw_enc_lstm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sw_social_pool_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sw_social_pool_fwd_aux": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "sw_scene_wg_max_scenes": (_i, []),
+    "sw_social_rows_max_pairs": (_i, []),
+    "sw_social_enc_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _ll, _vp, _vp]),
     "sw_social_features": (_i, [_vp, _i, _vp, _vp]),
     "sw_embed_features": (_i, [_vp, _ll, _vp, _vp, _vp]),
     "sw_attention_pool_dense": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -280,6 +280,13 @@ struct LstmBptt {
   float* trash;         // see lstm_store_dgates_tile
   int a0, B;
 };
+__device__ __forceinline__ int lstm_bptt_bound(const LstmBptt& S) { return S.B; }   // rows a0 .. bound-1 are the tile's
+// ... of a tile that holds ONE SCENE inside the batch (the scene-per-workgroup launch): B stays the time-major stride, the
+// rows end at `bound`, so that a scene never stores into its neighbour's rows
+struct LstmBpttScene : LstmBptt {
+  int bound;
+};
+__device__ __forceinline__ int lstm_bptt_bound(const LstmBpttScene& S) { return S.bound; }
 struct SwNop {
   template <class... A> __device__ void operator()(A&&...) const {}
 };
@@ -302,8 +309,8 @@ __device__ __forceinline__ void lstm_bptt_load(const LstmBptt& S, int t, f32x4 (
 // One step t on the rows in gate / ct / cprev, dh and dc carried.  PF: the rows of step t-1 (HP: with a row in front) are
 // requested right behind the last use of step t's, into the same registers (rolling prefetch, DESIGN section 3 "one
 // register set"); NX: dh_{t-1} is formed.  stamp(k): the phase stamps 12-14 of disc_bwd (SW_PHASE_STAMPS).
-template <bool PF, bool HP, bool NX, class Stamp = SwNop>
-__device__ __forceinline__ void lstm_bptt_step(const LstmWT& W, const LstmBptt& S, int t, f32x4 (&gate)[4], f32x4& ct,
+template <bool PF, bool HP, bool NX, class Stamp = SwNop, class St = LstmBptt>
+__device__ __forceinline__ void lstm_bptt_step(const LstmWT& W, const St& S, int t, f32x4 (&gate)[4], f32x4& ct,
                                                f32x4& cprev, f32x4& dh, f32x4& dc, Stamp stamp = {}) {
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   f32x4 dgate[4];
@@ -318,7 +325,7 @@ __device__ __forceinline__ void lstm_bptt_step(const LstmWT& W, const LstmBptt& 
   for (int g = 0; g < 4; ++g) st4(dgl + g * 64, dgate[g]);
   stamp(12);
   sw_barrier();
-  lstm_store_dgates_tile(tile, S.dg + (size_t)t * S.B * 256, S.trash, S.a0, S.B, wave, lane);
+  lstm_store_dgates_tile(tile, S.dg + (size_t)t * S.B * 256, S.trash, S.a0, lstm_bptt_bound(S), wave, lane);
   stamp(13);
   if constexpr (NX) dh = lstm_dh_prev(W, tile + ln * SW_GLD + 4 * lg);
   // the prefetched rows are not touched before the matrix products above have been issued
@@ -330,8 +337,8 @@ __device__ __forceinline__ void lstm_bptt_step(const LstmWT& W, const LstmBptt& 
 // for in front of the loop: a loop header with an unknown count of pending operations gets s_waitcnt vmcnt(0), which every
 // step then pays as the round trip of the dgates rows it has just stored.  stamp(k): called at points 10-14 (the phase
 // stamps of disc_bwd; disc_update puts its barrier at 10, behind the request of the first rows).
-template <bool DH0, class Pre = SwNop, class Stamp = SwNop>
-__device__ __forceinline__ void lstm_bptt_rows(LstmWT& W, const LstmBptt& S, int T, f32x4& dh, f32x4& dc, Pre pre = {},
+template <bool DH0, class Pre = SwNop, class Stamp = SwNop, class St = LstmBptt>
+__device__ __forceinline__ void lstm_bptt_rows(LstmWT& W, const St& S, int T, f32x4& dh, f32x4& dc, Pre pre = {},
                                                Stamp stamp = {}) {
   f32x4 gate[4], ct, cprev;
   if (T > 1) lstm_bptt_load<true>(S, T - 1, gate, ct, cprev);

@@ -17,6 +17,7 @@
 // returns f_ij.  Pair embeddings never touch HBM in the forward pass.
 #include "../../include/socialways_hip.h"
 #include "sw_common.h"
+#include "sw_lstm_dev.h"
 #include "sw_wgrad.h"
 
 #define SW_AMAX 64  // max agents per scene handled by one workgroup (attn row stride)
@@ -425,29 +426,34 @@ __device__ __forceinline__ void scene_softmax_bwd(float* smem, const SocL& Ls, i
 }
 // dh_j += sum_i a_ij dS_i  +  W^T dWh_j  on the matrix cores: D[unit u][agent j], wave w owns units 16w .. 16w+15 (wT:
 // load_att_wT); first product over k = the 64 units of dWh, second over k = i (rows beyond n masked to exact zeros)
-__device__ __forceinline__ void scene_dh_rows(const f32x4 wT[4], const float* smem, const SocL& Ls, float* dh, int s0, int n) {
+__device__ __forceinline__ f32x4 scene_dh_tile(const f32x4 wT[4], const float* smem, const SocL& Ls, int n, int at, int npad,
+                                               int wave, int ln, int lg) {
   const float* sig = smem + Ls.sig;
   const float* dsl = smem + Ls.ds;
   const float* dwh = smem + Ls.dwh;
   const int sa = Ls.sa;
+  f32x4 acc = tile_mm_reg<4>(wT, &dwh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
+  f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+  for (int kt = 0; kt < npad / 16; ++kt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 16 * kt + 4 * lg + r;
+      const float av = i < n ? dsl[i * 68 + 16 * wave + ln] : 0.f;
+      const float bv = i < n ? sig[i * sa + 16 * at + ln] : 0.f;
+      acc2 = SW_MFMA(av, bv, acc2);
+    }
+  }
+  return acc + acc2;
+}
+__device__ __forceinline__ void scene_dh_rows(const f32x4 wT[4], const float* smem, const SocL& Ls, float* dh, int s0, int n) {
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int npad = (n + 15) & ~15;
   for (int at = 0; at < npad / 16; ++at) {
-    f32x4 acc = tile_mm_reg<4>(wT, &dwh[(16 * at + ln) * 68 + 4 * lg], f32x4{0.f, 0.f, 0.f, 0.f});
-    f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < npad / 16; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * kt + 4 * lg + r;
-        const float av = i < n ? dsl[i * 68 + 16 * wave + ln] : 0.f;
-        const float bv = i < n ? sig[i * sa + 16 * at + ln] : 0.f;
-        acc2 = SW_MFMA(av, bv, acc2);
-      }
-    }
+    const f32x4 d = scene_dh_tile(wT, smem, Ls, n, at, npad, wave, ln, lg);
     const int j = 16 * at + ln;
     if (j < n) {
       float* q = dh + (size_t)(s0 + j) * 64 + 16 * wave + 4 * lg;
-      st4(q, ld4(q) + (acc + acc2));
+      st4(q, ld4(q) + d);
     }
   }
 }
@@ -947,13 +953,17 @@ __device__ __forceinline__ void pair_rows_store(const PairRows& pr, size_t row, 
 #define SW_PAIR_ROW_FLOATS 196
 #define SW_AGENT_ROW_FLOATS 200      // per agent in the pair workspace: dWh | Wh | Q [64 each] | sd [4] | pad [4]
 
-__global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
-    const float* __restrict__ obsv, int To, const float* __restrict__ h, const int* __restrict__ scene_off,
-    const long long* __restrict__ pair_off, const float* __restrict__ emb_w, const float* __restrict__ att_w,
-    const float* __restrict__ attn, const float* __restrict__ dS, float* __restrict__ dh,
+// The body of social_pool_bwd_rows_kernel for the scene `scene`.  KEEP (the scene-per-workgroup launch sw_social_enc_bwd,
+// scenes of at most 16 agents): the last phase's sum_i a_ij dS_i + W^T dWh_j of the lane's agent `ln` and units
+// 16 wave + 4 lg .. is RETURNED instead of added to the dh rows in memory (dh is not touched; zero for n == 1).
+template <bool KEEP>
+__device__ __forceinline__ f32x4 social_bwd_rows_scene(
+    float* smem, int scene, const float* __restrict__ obsv, int To, const float* __restrict__ h,
+    const int* __restrict__ scene_off, const long long* __restrict__ pair_off, const float* __restrict__ emb_w,
+    const float* __restrict__ att_w, const float* __restrict__ attn, const float* __restrict__ dS, float* __restrict__ dh,
     float* __restrict__ dwh_rows, float* __restrict__ wh_rows, float* __restrict__ q_rows, float* __restrict__ sd_rows,
-    PairRows pr, int a16, const float* __restrict__ simg) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+    const PairRows& pr, int a16, const float* __restrict__ simg) {
+  const f32x4 none = {0.f, 0.f, 0.f, 0.f};
   const SocL Ls = soc_lds(a16);
   const int sa = Ls.sa;
   float* hs = smem + Ls.hs;
@@ -965,17 +975,17 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   float* dwh = smem + Ls.dwh;
   float* vv = dwh;             // v_j = W3^T Wh_j [a16][68] during the pair loop (dWh is formed after it)
   float* qq = hs;              // Q_j | sd_j [a16][68] behind the pair loop (h is last read by the softmax backward)
-  const int s0 = scene_off[blockIdx.x], n = scene_off[blockIdx.x + 1] - s0;
-  if (n <= 0 || n > SW_AMAX) return;
+  const int s0 = scene_off[scene], n = scene_off[scene + 1] - s0;
+  if (n <= 0 || n > SW_AMAX) return none;
   if (n == 1) {  // S = 0 constant: no gradient anywhere; the agent's rows are zero
     zero_row64(dwh_rows + (size_t)s0 * 64);
     zero_row64(wh_rows + (size_t)s0 * 64);
     zero_row64(q_rows + (size_t)s0 * 64);
     if (threadIdx.x == 0) st4(sd_rows + (size_t)s0 * 4, f32x4{0.f, 0.f, 0.f, 0.f});
-    return;
+    return none;
   }
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  const long long p0 = pair_off[blockIdx.x];
+  const long long p0 = pair_off[scene];
 #ifdef SW_PHASE_STAMPS
   long long _tprev = clock64();
 #endif
@@ -1073,8 +1083,88 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
   }
   sw_barrier();
   SW_STAMP(6);
-  scene_dh_rows(wT, smem, Ls, dh, s0, n);
-  SW_STAMP(7);
+  if constexpr (KEEP) {
+    return scene_dh_tile(wT, smem, Ls, n, 0, 16, wave, ln, lg);
+  } else {
+    scene_dh_rows(wT, smem, Ls, dh, s0, n);
+    SW_STAMP(7);
+    return none;
+  }
+}
+
+__global__ __launch_bounds__(SW_THREADS) void social_pool_bwd_rows_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ h, const int* __restrict__ scene_off,
+    const long long* __restrict__ pair_off, const float* __restrict__ emb_w, const float* __restrict__ att_w,
+    const float* __restrict__ attn, const float* __restrict__ dS, float* __restrict__ dh,
+    float* __restrict__ dwh_rows, float* __restrict__ wh_rows, float* __restrict__ q_rows, float* __restrict__ sd_rows,
+    PairRows pr, int a16, const float* __restrict__ simg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  social_bwd_rows_scene<false>(smem, (int)blockIdx.x, obsv, To, h, scene_off, pair_off, emb_w, att_w, attn, dS, dh, dwh_rows,
+                               wh_rows, q_rows, sd_rows, pr, a16, simg);
+}
+
+// ---- scene-per-workgroup backward: the social backward carries the observation BPTT (sw_social_enc_bwd) --------------------
+// social_pool_bwd_rows and enc_lstm_bwd are two launches because the social block works on scenes and the BPTT on 16-agent
+// tiles: the first ends in a read-modify-write of dh_T in memory, the second starts by fetching that row and W_hh^T.  With
+// every scene at most SW_SCENE_WG_MAX_AGENTS agents and at most SW_SCENE_WG_MAX_SCENES scenes (a CU per scene), one
+// workgroup runs the rows body of its scene, keeps dh_T + (sum_i a_ij dS_i + W^T dWh_j) in registers - the same expression -
+// and runs the BPTT of enc_lstm_bwd_kernel<false> on the scene's agents as columns 0 .. n-1 of a tile (the other columns:
+// replicas of the last agent, stored over its rows; an agent is one column of the products, so the bits are the tiles'),
+// with W_hh^T requested at kernel start.  Nothing waits on another workgroup.
+// The masked D.load(backup) copy that rides in enc_lstm_bwd: by workgroups of its own behind the scenes while scenes and
+// copiers together leave a CU to each (gridDim.x > nscene); with more scenes every CU hosts one, and the copy - device memory,
+// under one element per thread then - is spread over the scene workgroups' first instructions.
+#define SW_SCENE_WG_MAX_AGENTS 16
+#define SW_SCENE_WG_MAX_SCENES 256   // one CU per scene workgroup
+#define SW_SCENE_WG_CUS 256
+// floats of the backward's social carve for a 16-agent scene: soc_lds(16).bwd_total, which sw_social_enc_bwd checks before it
+// launches (soc_lds stays a plain inline function: as a constexpr one it moved instructions in five kernels of this file)
+#define SW_SCENE_BWD_LDS (4 * 16 * 68 + 16 * 4 + 2 * 16 * 16 + 128 + 128)
+static_assert((SW_SCENE_BWD_LDS + 2 * SW_TILE * SW_GLD + SW_TILE * SW_HLD) * 4 <= 64 * 1024, "static LDS of social_enc_bwd_kernel");
+__global__ __launch_bounds__(SW_THREADS) void social_enc_bwd_kernel(
+    const float* __restrict__ obsv, int To, const float* __restrict__ h, const int* __restrict__ scene_off,
+    const long long* __restrict__ pair_off, int nscene, const float* __restrict__ emb_w, const float* __restrict__ att_w,
+    const float* __restrict__ attn, const float* __restrict__ dS, const float* __restrict__ dhT, const float* __restrict__ dcT,
+    float* __restrict__ dwh_rows, float* __restrict__ wh_rows, float* __restrict__ q_rows, float* __restrict__ sd_rows,
+    PairRows pr, const float* __restrict__ simg, const float* __restrict__ whh, const float* __restrict__ gimg,
+    const float* __restrict__ act, int B, float* __restrict__ dgates, const float* __restrict__ aux_src,
+    float* __restrict__ aux_dst, const float* __restrict__ aux_mask, long long aux_n) {
+  const int copiers = (int)gridDim.x - nscene;
+  if ((int)blockIdx.x >= nscene) {          // a copy workgroup
+    const long long stride = (long long)copiers * SW_THREADS;
+    for (long long i = (long long)((int)blockIdx.x - nscene) * SW_THREADS + threadIdx.x; i < aux_n; i += stride)
+      if (aux_mask[i] > 0.f) aux_dst[i] = aux_src[i];
+    return;
+  }
+  __shared__ __attribute__((aligned(16))) float smem[SW_SCENE_BWD_LDS];
+  __shared__ __attribute__((aligned(16))) float dgbuf[2][SW_TILE * SW_GLD];
+  __shared__ __attribute__((aligned(16))) float dhx[SW_TILE * SW_HLD];
+  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
+  const int u0 = wave * 16;
+  const int scene = (int)blockIdx.x;
+  const int s0 = scene_off[scene], n = scene_off[scene + 1] - s0;
+  if (copiers == 0) {                  // no idle CU: every scene workgroup copies its share first
+    const long long stride = (long long)nscene * SW_THREADS;
+    for (long long i = (long long)blockIdx.x * SW_THREADS + threadIdx.x; i < aux_n; i += stride)
+      if (aux_mask[i] > 0.f) aux_dst[i] = aux_src[i];
+  }
+  if (n <= 0 || n > SW_SCENE_WG_MAX_AGENTS || s0 < 0 || s0 + n > B) return;   // not a layout of this launch
+  LstmWT W;
+  lstm_load_whhT(W, gimg, swimg::OP_WHHT, whh, wave, lane);
+  const int b = s0 + min(ln, n - 1);
+  const f32x4 dh_in = ld4(dhT + (size_t)b * 64 + u0 + 4 * lg);
+  f32x4 dc = ld4(dcT + (size_t)b * 64 + u0 + 4 * lg);
+  const f32x4 dsoc = social_bwd_rows_scene<true>(smem, scene, obsv, To, h, scene_off, pair_off, emb_w, att_w, attn, dS, nullptr,
+                                                 dwh_rows, wh_rows, q_rows, sd_rows, pr, SW_SCENE_WG_MAX_AGENTS, simg);
+  // scene_dh_rows' expression; single-agent scenes have no social gradient and keep dh_T as it is.  The replica columns
+  // take the last agent's row through LDS: the products above give them nothing
+  f32x4 dh = n > 1 ? dh_in + dsoc : dh_in;
+  if (ln < n) st4(&dhx[ln * SW_HLD + u0 + 4 * lg], dh);
+  sw_barrier();
+  dh = ld4(&dhx[min(ln, n - 1) * SW_HLD + u0 + 4 * lg]);
+  const float* act_b = act + (size_t)b * 384 + u0 + 4 * lg;
+  const LstmBpttScene S{{act_b, nullptr, dgbuf[0], dgates + (size_t)s0 * 256, nullptr, s0, B}, s0 + n};
+  lstm_bptt_rows<false>(W, S, To, dh, dc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1609,6 +1699,67 @@ extern "C" int sw_social_pool_fwd(const float* obsv, int To, const float* h, con
                                 nullptr, nullptr, 0, stream);
 }
 
+// The deferred weight-gradient problems of the per-pair-rows backward (social_pool_bwd_rows_kernel, social_enc_bwd_kernel):
+// into the caller's pending batch, or launched here
+static int soc_rows_problems(float* pair_ws, const PairRows& pr, const float* h, int B, long long P, float* d_emb_w,
+                             float* d_att_w, float* wgrad_ws, sw_wgrad_batch* defer, hipStream_t st) {
+  float* dwh_rows = pair_ws;
+  float* wh_rows = pair_ws + (size_t)B * 64;
+  float* q_rows = pair_ws + (size_t)B * 128;
+  float* sd_rows = pair_ws + (size_t)B * 192;
+  WgBatch wr_local;
+  WgBatch& wr = defer ? *wg_pending(defer) : wr_local;
+  wr = WgBatch();
+  int rc_r = 0;
+  rc_r |= wg_add(wr, dwh_rows, 64, h, 64, B, 64, 64, d_att_w + swp::ATT_W, 64, d_att_w + swp::ATT_B, nullptr, 0);
+  if (P > 0) {
+    // dW3 = sum_j Wh_j Q_j^T, db3 = sum_j Wh_j sd_j: B rows (the bias as a one-column problem: its "act" is sd)
+    rc_r |= wg_add(wr, wh_rows, 64, q_rows, 64, B, 64, 64, d_emb_w + swp::EMB_W2, 64, nullptr, nullptr, 0);
+    rc_r |= wg_add(wr, wh_rows, 64, sd_rows, 4, B, 64, 1, d_emb_w + swp::EMB_B2, 1, nullptr, nullptr, 0);
+    rc_r |= wg_add(wr, pr.dh2, 64, pr.h1, 32, (int)P, 64, 32, d_emb_w + swp::EMB_W1, 32, d_emb_w + swp::EMB_B1, nullptr, 0);
+    rc_r |= wg_add(wr, pr.dh1, 32, pr.feat, 4, (int)P, 32, 3, d_emb_w + swp::EMB_W0, 3, d_emb_w + swp::EMB_B0, nullptr, 0);
+  }
+  if (rc_r) return SW_ESHAPE;
+  if (defer) return SW_OK;   // launched together with the caller's later problems (sw_gen_wgrad)
+  return wg_launch(wr, wgrad_ws, st);
+}
+
+/* sw_social_pool_bwd's per-pair-rows form followed by sw_enc_lstm_bwd_aux (dy, c0, dh0, dc0 NULL, t0 = 0) in ONE launch of a
+ * workgroup per scene: every scene at most 16 agents, S <= sw_scene_wg_max_scenes(), and a layout the two launches run the
+ * rows form on (0 < P < sw_social_rows_max_pairs() S); SW_ESHAPE otherwise.  dhT is read, not updated.               */
+extern "C" int sw_scene_wg_max_scenes(void) { return SW_SCENE_WG_MAX_SCENES; }
+extern "C" int sw_social_rows_max_pairs(void) { return SW_SOC_FUSE_MIN_PAIRS; }
+extern "C" int sw_social_enc_bwd(const float* obsv, int To, const float* h, const int* scene_off, const long long* pair_off,
+                                 int S, int B, int Amax, long long P, const float* emb_w, const float* att_w, const float* attn,
+                                 const float* dS, const float* dhT, const float* dcT, float* d_emb_w, float* d_att_w,
+                                 float* pair_ws, float* wgrad_ws, const float* enc_w, const float* act, float* dgates,
+                                 const float* aux_src, float* aux_dst, const float* aux_mask, long long aux_n,
+                                 sw_wgrad_batch* defer, void* stream) {
+  if (!obsv || !h || !scene_off || !pair_off || !emb_w || !att_w || !attn || !dS || !dhT || !dcT || !d_emb_w || !d_att_w ||
+      !pair_ws || !wgrad_ws || !enc_w || !act || !dgates || S < 0 || B < 0 || P < 0 || To < 2)
+    return SW_EARG;
+  if (aux_n < 0 || (aux_n > 0 && (!aux_src || !aux_dst || !aux_mask))) return SW_EARG;
+  if (Amax > SW_SCENE_WG_MAX_AGENTS || S > SW_SCENE_WG_MAX_SCENES || P == 0 || P >= (long long)S * SW_SOC_FUSE_MIN_PAIRS)
+    return SW_ESHAPE;
+  if (S == 0 || B == 0) return SW_OK;
+  if (soc_lds(SW_SCENE_WG_MAX_AGENTS).bwd_total > SW_SCENE_BWD_LDS) {   // the carve outgrew the kernel's static array
+    sw_set_error("social_enc_bwd_kernel: SW_SCENE_BWD_LDS is smaller than soc_lds(16).bwd_total", hipErrorInvalidValue);
+    return SW_EHIP;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PairRows pr = pair_rows(pair_ws + (size_t)B * SW_AGENT_ROW_FLOATS, P);
+  int copiers = aux_n > 0 ? (int)((aux_n + SW_THREADS - 1) / SW_THREADS) : 0;
+  if (copiers > 64) copiers = 64;
+  if (S + copiers > SW_SCENE_WG_CUS) copiers = 0;   // no CU left for them: the scene workgroups copy
+  // timed under the BPTT launch's name: it is that launch, carrying the social backward
+  SW_LAUNCH_AS("enc_lstm_bwd_kernel", social_enc_bwd_kernel, dim3(S + copiers), dim3(SW_THREADS), 0, st, obsv, To, h, scene_off,
+               pair_off, S, emb_w, att_w, attn, dS, dhT, dcT, pair_ws, pair_ws + (size_t)B * 64, pair_ws + (size_t)B * 128,
+               pair_ws + (size_t)B * 192, pr, sw_soc_images_for(emb_w, att_w), enc_w + swp::ENC_WHH,
+               sw_gen_images_for(enc_w, nullptr), act, B, dgates, aux_src, aux_dst, aux_mask, aux_n);
+  SW_CHECK_LAUNCH("social_enc_bwd_kernel");
+  return soc_rows_problems(pair_ws, pr, h, B, P, d_emb_w, d_att_w, wgrad_ws, defer, st);
+}
+
 extern "C" int sw_social_pool_bwd(const float* obsv, int To, const float* h, const int* scene_off,
                                   const long long* pair_off, int S, int B, int Amax, long long P,
                                   const float* emb_w, const float* att_w, const float* attn, const float* dS,
@@ -1645,21 +1796,7 @@ extern "C" int sw_social_pool_bwd(const float* obsv, int To, const float* h, con
                        scene_off, pair_off, emb_w, att_w, attn, dS, dh, dwh_rows, wh_rows, q_rows, sd_rows, pr, a16,
                        sw_soc_images_for(emb_w, att_w));
     SW_CHECK_LAUNCH("social_pool_bwd_rows_kernel");
-    WgBatch wr_local;
-    WgBatch& wr = defer ? *wg_pending(defer) : wr_local;
-    wr = WgBatch();
-    int rc_r = 0;
-    rc_r |= wg_add(wr, dwh_rows, 64, h, 64, B, 64, 64, d_att_w + swp::ATT_W, 64, d_att_w + swp::ATT_B, nullptr, 0);
-    if (P > 0) {
-      // dW3 = sum_j Wh_j Q_j^T, db3 = sum_j Wh_j sd_j: B rows (the bias as a one-column problem: its "act" is sd)
-      rc_r |= wg_add(wr, wh_rows, 64, q_rows, 64, B, 64, 64, d_emb_w + swp::EMB_W2, 64, nullptr, nullptr, 0);
-      rc_r |= wg_add(wr, wh_rows, 64, sd_rows, 4, B, 64, 1, d_emb_w + swp::EMB_B2, 1, nullptr, nullptr, 0);
-      rc_r |= wg_add(wr, pr.dh2, 64, pr.h1, 32, (int)P, 64, 32, d_emb_w + swp::EMB_W1, 32, d_emb_w + swp::EMB_B1, nullptr, 0);
-      rc_r |= wg_add(wr, pr.dh1, 32, pr.feat, 4, (int)P, 32, 3, d_emb_w + swp::EMB_W0, 3, d_emb_w + swp::EMB_B0, nullptr, 0);
-    }
-    if (rc_r) return SW_ESHAPE;
-    if (defer) return SW_OK;   // launched together with the caller's later problems (sw_gen_wgrad)
-    return wg_launch(wr, wgrad_ws, st);
+    return soc_rows_problems(pair_ws, pr, h, B, P, d_emb_w, d_att_w, wgrad_ws, defer, st);
   }
   // in-register weight gradients: one partial slice per workgroup of the scene kernel (G) and of the row-block
   // kernel (NB), reduced together

@@ -119,7 +119,7 @@ def default_ws(device):
 
 
 class GenCtx:
-    __slots__ = ("obsv", "noise", "scenes", "hT", "cT", "S", "attn", "gsave", "B", "To", "Tp", "use_social", "wh", "ml")
+    __slots__ = ("obsv", "noise", "scenes", "hT", "cT", "S", "attn", "gsave", "B", "To", "Tp", "use_social", "wh", "ml", "ragged")
 
 
 def _ragged_arg(obs_len, B, device, noise_src=None, d_obs=None):
@@ -132,6 +132,22 @@ def _ragged_arg(obs_len, B, device, noise_src=None, d_obs=None):
     if d_obs is not None:
         raise ValueError("obs_len: there is no precomputed observation pass for ragged rows - d_obs must be None")
     return _check_obs_len_tensor(obs_len, B, device)
+
+
+SCENE_WG = True                # few small scenes: social backward + observation BPTT as one launch of a workgroup per scene (off: A/B)
+SCENE_WG_MAX_AGENTS = 16       # a scene is the columns of ONE 16-agent tile
+SCENE_WG_MAX_SCENES = 256      # one CU per scene workgroup (sw_scene_wg_max_scenes)
+SOCIAL_ROWS_MAX_PAIRS = 256    # mean pairs per scene below which the social backward leaves per-pair rows (sw_social_rows_max_pairs)
+
+
+def scene_wg(scenes, use_social, ragged=False):
+    """Does the backward pass of a training step on this batch layout run sw_social_enc_bwd in place of the social-backward
+    and observation-BPTT launches?  Decided once per layout: the switch and the social block are on, the histories are dense
+    (ragged rows keep their launches), every scene has at most SCENE_WG_MAX_AGENTS agents, there are at most
+    SCENE_WG_MAX_SCENES scenes, and the social backward is the per-pair-rows one, whose results the launch reproduces bit for
+    bit (0 < P < SOCIAL_ROWS_MAX_PAIRS * S).  Part of the captured step's key."""
+    return bool(SCENE_WG and use_social and not ragged and scenes.NB == 0 and 0 < scenes.amax <= SCENE_WG_MAX_AGENTS
+                and scenes.S <= SCENE_WG_MAX_SCENES and 0 < scenes.P < SOCIAL_ROWS_MAX_PAIRS * scenes.S)
 
 
 def _enc_save(obsv, enc_w, B, To, hT, cT, gsave, x4s_ptr, obs_len, aux, st):
@@ -207,7 +223,7 @@ def gen_forward(enc_w, emb_w, att_w, dec_w, obsv, noise, scenes, n_next, use_soc
     ctx = GenCtx()
     ctx.obsv, ctx.noise, ctx.scenes, ctx.hT, ctx.cT, ctx.S, ctx.attn = obsv, noise, scenes, hT, cT, S, attn
     ctx.gsave, ctx.B, ctx.To, ctx.Tp, ctx.use_social = gsave, B, To, n_next, use_social
-    ctx.wh, ctx.ml = wh, ml
+    ctx.wh, ctx.ml, ctx.ragged = wh, ml, obs_len is not None
     return pred4, ctx
 
 
@@ -249,7 +265,18 @@ def gen_backward(enc_w, emb_w, att_w, dec_w, ctx, dpred4, d_enc, d_emb, d_att, d
                L.ptr(gdelta), L.ptr(dhT), L.ptr(dcT), L.ptr(dS), L.ptr(aux[0]) if aux else None, L.ptr(aux[1]) if aux else None,
                L.ptr(aux[2]) if aux else None, aux[1].numel() if aux else 0, L.stream())
     pending = None
-    if ctx.use_social and (ctx.scenes.P > 0 or ctx.scenes.NB > 0):
+    fused = scene_wg(ctx.scenes, ctx.use_social, ctx.ragged)
+    if fused:
+        # few small scenes: one launch, a workgroup per scene keeps dh_T + its social gradient on chip and runs the BPTT on it
+        sc = ctx.scenes
+        pending = ws.wgrad_batch
+        pws = ws.get("pairs", L.workspace_floats(L.WS_PAIRS, B, To, Tp, 1, sc.P))
+        L.call("sw_social_enc_bwd", L.ptr(ctx.obsv), To, L.ptr(ctx.hT), L.ptr(sc.scene_off), L.ptr(sc.pair_off), sc.S, B, sc.amax,
+               sc.P, L.ptr(emb_w), L.ptr(att_w), L.ptr(ctx.attn), L.ptr(dS), L.ptr(dhT), L.ptr(dcT), L.ptr(d_emb), L.ptr(d_att),
+               L.ptr(pws), L.ptr(wgrad), L.ptr(enc_w), L.ptr(ctx.gsave), L.ptr(gdelta),
+               L.ptr(aux_late[0]) if aux_late else None, L.ptr(aux_late[1]) if aux_late else None,
+               L.ptr(aux_late[2]) if aux_late else None, aux_late[1].numel() if aux_late else 0, pending, L.stream())
+    elif ctx.use_social and (ctx.scenes.P > 0 or ctx.scenes.NB > 0):
         sc = ctx.scenes
         pending = ws.wgrad_batch
         pws = ws.get("pairs", L.workspace_floats(L.WS_PAIRS, B, To, Tp, 1, sc.P))
@@ -261,9 +288,10 @@ def gen_backward(enc_w, emb_w, att_w, dec_w, ctx, dpred4, d_enc, d_emb, d_att, d
     else:
         d_emb.zero_()
         d_att.zero_()
-    L.call("sw_enc_lstm_bwd_aux", L.ptr(enc_w), L.ptr(ctx.gsave), None, L.ptr(dhT), L.ptr(dcT), None, B, To, 0,
-           L.ptr(gdelta), None, None, L.ptr(aux_late[0]) if aux_late else None, L.ptr(aux_late[1]) if aux_late else None,
-           L.ptr(aux_late[2]) if aux_late else None, aux_late[1].numel() if aux_late else 0, L.stream())
+    if not fused:
+        L.call("sw_enc_lstm_bwd_aux", L.ptr(enc_w), L.ptr(ctx.gsave), None, L.ptr(dhT), L.ptr(dcT), None, B, To, 0,
+               L.ptr(gdelta), None, None, L.ptr(aux_late[0]) if aux_late else None, L.ptr(aux_late[1]) if aux_late else None,
+               L.ptr(aux_late[2]) if aux_late else None, aux_late[1].numel() if aux_late else 0, L.stream())
     if adam is not None:
         w_all, g_all, m, v, step, lr, b1, b2, eps = adam
         L.call("sw_gen_wgrad_adam", L.ptr(enc_w), L.ptr(dec_w), L.ptr(ctx.gsave), L.ptr(gdelta), L.ptr(ctx.noise), L.ptr(ctx.S),
@@ -322,6 +350,7 @@ def gen_forward_k(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use
     one = GenCtx()
     one.obsv, one.noise, one.scenes, one.hT, one.cT, one.S, one.attn = obsv, noise_k[:B], scenes, hT, cT, S, attn
     one.gsave, one.B, one.To, one.Tp, one.use_social, one.wh, one.ml = gsave_1, B, To, n_next, use_social, wh, ml
+    one.ragged = obs_len is not None
     ctx = GenCtxK()
     ctx.one, ctx.K, ctx.obsv_k, ctx.noise_k, ctx.S_k, ctx.gsave_k = one, K, obsv_k, noise_k, S_k, gsave_k
     return pred4, ctx

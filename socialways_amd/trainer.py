@@ -491,7 +491,7 @@ class SocialWaysTrainer:
         return (scenes.key, To, float(ss), float(Bg), self._row0, K, self.n_unrolling_steps, self.use_info_loss,
                 self.loss_info_w, self.use_l2_loss, self.use_variety_loss, self.loss_l2_w, self.variety_k,
                 og["lr"], tuple(og["betas"]), og["eps"], og.get("weight_decay", 0), od["lr"], tuple(od["betas"]), od["eps"],
-                od.get("weight_decay", 0), bool(ragged), bool(zdev))
+                od.get("weight_decay", 0), ops.scene_wg(scenes, self.use_social, ragged), bool(ragged), bool(zdev))
 
     def _graphs_current(self):
         """A workspace outgrown since the last capture means captured graphs hold retired addresses: they stay valid
