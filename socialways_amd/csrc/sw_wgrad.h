@@ -10,30 +10,66 @@
 #define SW_WG_WS_FLOATS ((size_t)SW_WG_MAXSPLIT * 65536)
 
 struct WgProblem {      // one column block (<= 64 act columns, optional trailing ones column) of a problem
+  // -- what a GEMM job reads comes first, in one piece: a job fetches it with a few wide scalar loads in ONE round trip
   const float* delta;   // [R][ldd], N columns used
   const float* act;     // [R][lda], K columns used (already offset to the block's first column)
-  float* dW;            // [N][ldw], already offset to the block's first column
-  float* db;            // [N] or null: receives the ones column
-  float* db2;           // second copy of the bias gradient (LSTM b_ih / b_hh) or null
-  size_t ws_off;
-  int ldd, lda, ldw, R, N, K, ones, accumulate;
-  int nbn, nbk, nsplit, job0, out0;
-  int pre;              // > 0: the `pre` slice partials are produced elsewhere (fused kernels); only reduced here
   // optional TAIL segment: K2 (< 16) more act columns from a second array, placed in the k tile after the K
   // (multiple of 16) columns of `act`, in front of the ones column - the LSTM's x_t next to h_{t-1}, so that the
   // dgates rows are fetched once for W_hh, W_ih and the biases.  Rows r < row0 have no `act` operand (t = 0).
   const float* act2;
+  size_t ws_off;
+  int ldd, lda, lda2, row0, R, N, K, job0;
+  // derived once on the host (wg_finalize) so that no job and no reduction wave divides or loops for them:
+  //   cases    = wg_run instance of a full 64-column output block | that of the last block << 8 | output blocks NB << 16
+  //   rows_per = rows of one wave's slice; nbmul = ceil(2^16 / NB): j / NB == (j * nbmul) >> 16 for j < 2^15 (a launch
+  //              has at most SW_WG_MAXP * SW_WG_MAXSPLIT * 4 = 24 576 jobs)
+  //   ldp      = row stride of the problem's partials in the workspace (Kc rounded up to 4 floats; a precomputed-partial
+  //              problem keeps its producer's Kc); kcmul = ceil(2^31 / Kc): e / Kc == umulhi(2 e, kcmul) for e < 2^31 / Kc
+  //   out0     = first element of the problem in the reduction's index space, a multiple of 16 (one wave = one problem)
+  int cases, rows_per, nbmul, ldp;
+  // -- the reduction's part
+  int K2, ones, nsplit, out0;
+  unsigned kcmul;
+  int ldw, ldw2, accumulate;
+  float* dW;            // [N][ldw], already offset to the block's first column
   float* dW2;
-  int lda2, ldw2, K2, row0;
+  float* db;            // [N] or null: receives the ones column
+  float* db2;           // second copy of the bias gradient (LSTM b_ih / b_hh) or null
+  int nbk;              // host only: k tiles (wg_cost)
+  int pre;              // > 0: the `pre` slice partials are produced elsewhere (fused kernels); only reduced here
 };
 struct WgBatch {
-  // compact search keys first: a workgroup finds its problem by scanning these (kernel-argument memory is
-  // fetched by dependent scalar loads: one or two cache lines here instead of one per problem descriptor)
+  // compact search keys first: a workgroup fetches ALL of them at once (wide scalar loads, one round trip) and finds its
+  // problem by comparing in registers (wg_find); entries from np on hold INT_MAX (wg_finalize)
+  int total_jobs = 0, total_out = 0;           // total_out: end of the reduction's (per problem padded) index space
   int job0s[SW_WG_MAXP], out0s[SW_WG_MAXP];
   WgProblem p[SW_WG_MAXP];
-  int np = 0, total_jobs = 0, total_out = 0;
+  int np = 0;
   size_t top_reserved = 0;   // floats handed out from the TOP of the workspace to precomputed-partial problems
 };
+
+// The search keys and the count that bounds them, fetched together: the empty asm statements make the compiler hold every
+// value in a scalar register HERE, so the loads go out as one clause of wide scalar loads with a single wait, instead of
+// one dword load and one wait at each use.
+#define WG_PIN(x) asm volatile("" ::"s"(x))   // (an input only: the value keeps what the compiler knows about it)
+__device__ __forceinline__ void wg_keys(const int (&keys)[SW_WG_MAXP], const int& total, int (&k)[SW_WG_MAXP], int& t) {
+  t = total;
+#pragma unroll
+  for (int i = 1; i < SW_WG_MAXP; ++i) k[i] = keys[i];
+  WG_PIN(t);
+#pragma unroll
+  for (int i = 1; i < SW_WG_MAXP; ++i) WG_PIN(k[i]);
+  k[0] = 0;
+}
+// problem of job / element `x` (wave-uniform, 0 <= x): the number of keys k[1 ..] at or below it, counted on the scalar
+// unit from registers - no load inside the search (keys ascend from 0; unused entries are INT_MAX).  The sign bit of
+// k - 1 - x is set exactly where k <= x.
+__device__ __forceinline__ int wg_find(const int (&k)[SW_WG_MAXP], int x) {
+  unsigned p = 0;
+#pragma unroll
+  for (int i = 1; i < SW_WG_MAXP; ++i) p += (unsigned)(k[i] - 1 - x) >> 31;
+  return (int)p;
+}
 
 // ---- Adam fused into the reduction: the thread that produces the final value of a gradient element also applies the
 // update to its weight (torch's fused Adam, aten/src/ATen/native/cuda/fused_adam_utils.cuh, restated operation by

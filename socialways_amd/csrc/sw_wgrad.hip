@@ -17,6 +17,7 @@
 #include "sw_common.h"
 #include "sw_wgrad.h"
 #include "sw_wgrad_dev.h"
+#include <stdint.h>
 #include <stdlib.h>
 
 // One wave = one job: a 64 x 64 output block (4 x 4 MFMA tiles, 16 accumulators) of one column block
@@ -31,8 +32,12 @@
 // MFMAs - no clamps, no masks, no exec-mask branches, no accumulator shuffling through control flow.
 // workgroups that carry jobs: the job count padded to whole rounds of 8 XCDs x chunks of 4 (see the kernel)
 __host__ __device__ inline int wg_grid_jobs(int total_jobs) { return (total_jobs + 31) & ~31; }
-#ifdef SW_WG_STAMP      // timing experiment (tools/build_variant.sh): start / end of every workgroup of the last launch
-__device__ unsigned long long g_wg_stamps[4 * 4096];
+#ifdef SW_WG_STAMP      // timing experiment (tools/build_variant.sh, tools/dbg/wgrad_stamps.py): wall-clock marks of the last launches
+// GEMM: 10 values per workgroup - start, end, problem, total_jobs, the six marks inside the job (sw_wgrad_dev.h) -, the last
+// launch of more than 12 problems (the generator's) in the first half, of fewer (a discriminator pass) in the second.
+// Reduction, behind them: 6 values per workgroup - start, problem found, state requested, sums done, end, problem.
+#define SW_WG_STAMP_GEMM (2 * 2048 * 10)
+__device__ unsigned long long g_wg_stamps[SW_WG_STAMP_GEMM + 2 * 2048 * 6];
 extern "C" int sw_debug_wg_stamps(unsigned long long* host, int n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_stamps), sizeof(unsigned long long) * (size_t)n) == hipSuccess ? 0 : -1;
 }
@@ -42,7 +47,9 @@ __global__ __launch_bounds__(SW_THREADS, 2) void wgrad_partial_kernel(WgBatch ba
                                                                       double beta2, float* __restrict__ bc_out) {
   __shared__ __attribute__((aligned(16))) float red[SW_WG_RED_FLOATS];   // per-wave 64 x <=69 blocks, summed before the store
   // Adam's bias corrections for the reduction that follows (it applies the update): one extra workgroup, no job delayed
-  if ((int)blockIdx.x >= wg_grid_jobs(batch.total_jobs)) {
+  int keys[SW_WG_MAXP], total_jobs;
+  wg_keys(batch.job0s, batch.total_jobs, keys, total_jobs);
+  if ((int)blockIdx.x >= wg_grid_jobs(total_jobs)) {
     if (threadIdx.x == 0) {
       float bc1, bc2s;
       wg_adam_bc_compute(adam_step, beta1, beta2, bc1, bc2s);
@@ -57,21 +64,23 @@ __global__ __launch_bounds__(SW_THREADS, 2) void wgrad_partial_kernel(WgBatch ba
   // one L2 instead of four, and every XCD gets the same mix of problems.
   const int v = blockIdx.x, l = v >> 3;
   const int job = ((((l >> 2) << 3) + (v & 7)) << 2) + (l & 3);
-  if (job >= batch.total_jobs) return;
+  if (job >= total_jobs) return;
 #ifdef SW_WG_STAMP
   const unsigned long long t0 = wall_clock64();
 #endif
-  wg_job(batch, ws, job, red);
 #ifdef SW_WG_STAMP
-  if (threadIdx.x == 0 && blockIdx.x < 2048) {      // launches below 400 jobs (discriminator passes at m1): second half
-    int p = 0;
-    while (p + 1 < batch.np && job >= batch.job0s[p + 1]) ++p;
-    unsigned long long* o = g_wg_stamps + (batch.total_jobs < 400 ? 4 * 2048 : 0) + 4 * blockIdx.x;
+  unsigned long long mk[6] = {t0, t0, t0, t0, t0, t0};
+  wg_job(batch, keys, ws, job, red, mk);
+  if (threadIdx.x == 0 && blockIdx.x < 2048) {
+    unsigned long long* o = g_wg_stamps + (batch.np <= 12 ? 10 * 2048 : 0) + 10 * blockIdx.x;
     o[0] = t0;
     o[1] = wall_clock64();
-    o[2] = p;
-    o[3] = batch.total_jobs;
+    o[2] = wg_find(keys, job);
+    o[3] = total_jobs;
+    for (int i = 0; i < 6; ++i) o[4 + i] = mk[i];
   }
+#else
+  wg_job(batch, keys, ws, job, red);
 #endif
 }
 // scratch for those two floats: a ring of slots per device (launches of one stream are ordered; 64 slots cover
@@ -101,21 +110,45 @@ static float* wg_bc_slot() {
 #endif
 #define SW_WG_REL (64 / SW_WG_RSUB)
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgBatch batch, const float* __restrict__ ws, WgAdam ad) {
+#ifdef SW_WG_STAMP
+  const unsigned long long rt0 = wall_clock64();
+  unsigned long long rt1 = rt0, rt2 = rt0, rt3 = rt0;
+#endif
   const int gid = blockIdx.x * 256 + threadIdx.x;
-  const int lane = gid & 63, el = lane % SW_WG_REL, sub = lane / SW_WG_REL;
-  const int i = (gid >> 6) * SW_WG_REL + el;
-  bool live = i < batch.total_out;
-  int ii = live ? i : batch.total_out - 1;
-  int p = 0;
-#pragma unroll 1
-  while (p + 1 < batch.np && ii >= batch.out0s[p + 1]) ++p;
-  const WgProblem& P = batch.p[p];
-  const int e = ii - P.out0;
-  const int Kc = P.K + P.K2 + P.ones;
-  const size_t stride = (size_t)P.N * Kc;
-  const float* src = ws + P.ws_off + e;
-  // destination(s) of this element; with the fused Adam update their optimizer state is fetched now, under the sums
-  const int n = e / Kc, k = e - n * Kc;
+  const int lane = threadIdx.x & 63, el = lane % SW_WG_REL, sub = lane / SW_WG_REL;
+  // The host pads every problem's elements to whole waves (out0 is a multiple of SW_WG_REL): the wave's first element
+  // picks the problem, the key is wave-uniform - all keys in one fetch, compared in scalar registers, and the problem's
+  // record comes by scalar loads.  Lanes past the problem's last element work on that element and store nothing.
+  const int i0 = __builtin_amdgcn_readfirstlane((gid >> 6) * SW_WG_REL);
+  int keys[SW_WG_MAXP], total_out;
+  wg_keys(batch.out0s, batch.total_out, keys, total_out);
+  if (i0 >= total_out) return;
+  const int p = wg_find(keys, i0);
+  // second (and last) scalar round trip: the reduction's part of the record and the optimizer's pointers, one clause
+  const WgProblem& Q = batch.p[p];
+  struct {
+    size_t ws_off;
+    int N, K, ldp, K2, ones, nsplit, out0;
+    unsigned kcmul;
+    int ldw, ldw2, accumulate;
+    float *dW, *dW2, *db, *db2;
+  } P = {Q.ws_off, Q.N, Q.K, Q.ldp, Q.K2, Q.ones, Q.nsplit, Q.out0, Q.kcmul, Q.ldw, Q.ldw2, Q.accumulate, Q.dW, Q.dW2, Q.db, Q.db2};
+  WG_PIN(P.ws_off); WG_PIN(P.N); WG_PIN(P.K); WG_PIN(P.ldp); WG_PIN(P.K2); WG_PIN(P.ones); WG_PIN(P.nsplit); WG_PIN(P.out0);
+  WG_PIN(P.kcmul); WG_PIN(P.ldw); WG_PIN(P.ldw2); WG_PIN(P.accumulate); WG_PIN(P.dW); WG_PIN(P.dW2); WG_PIN(P.db); WG_PIN(P.db2);
+  WG_PIN(ws); WG_PIN(ad.w); WG_PIN(ad.m); WG_PIN(ad.v); WG_PIN(ad.g0); WG_PIN(ad.n); WG_PIN(ad.img); WG_PIN(ad.tab);
+#ifdef SW_WG_STAMP
+  rt1 = wall_clock64();
+#endif
+  const int Kc = P.K + P.K2 + P.ones, nout = P.N * Kc;
+  const int ei = i0 - P.out0 + el;
+  const bool live = ei < nout;
+  const int e = live ? ei : nout - 1;
+  // (n, k) of the element without a division: e < 2^31 / Kc (WgProblem::kcmul)
+  const int n = (int)__umulhi((unsigned)e << 1, P.kcmul), k = e - n * Kc;
+  const size_t stride = (size_t)P.N * P.ldp;
+  const float* src = ws + P.ws_off + (size_t)n * P.ldp + k;
+  // destination(s) of this element; with the fused Adam update their optimizer state is requested now, together with the
+  // first partials: none of these loads waits for another
   float* dst = k < P.K ? P.dW + (size_t)n * P.ldw + k : k < P.K + P.K2 ? P.dW2 + (size_t)n * P.ldw2 + (k - P.K) : P.db + n;
   float* dst2 = (k >= P.K + P.K2 && P.db2) ? P.db2 + n : nullptr;   // LSTM b_ih / b_hh share their gradient
   WgAdamPre a1 = {}, a2 = {};
@@ -128,6 +161,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgBatch batch, const 
     old1 = *dst;
     if (dst2) old2 = *dst2;
   }
+#ifdef SW_WG_STAMP
+  rt2 = wall_clock64();
+#endif
   float s = 0.f;
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
   int q = sub;
@@ -141,8 +177,18 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgBatch batch, const 
   s = (s + s1) + (s2 + s3);
 #pragma unroll
   for (int o = SW_WG_REL; o < 64; o <<= 1) s += __shfl_xor(s, o);
+#ifdef SW_WG_STAMP
+  asm volatile("" : "+v"(s));
+  rt3 = wall_clock64();
+#endif
   float bc1 = 1.f, bc2s = 1.f;
   if (ad.w) wg_adam_bc(ad, bc1, bc2s);   // wave-uniform; computed here so that graph and eager steps share the code
+#ifdef SW_WG_STAMP
+  if (threadIdx.x == 0 && blockIdx.x < 2048) {      // (the element's own stores follow: `end` is the time they are issued)
+    unsigned long long* o = g_wg_stamps + SW_WG_STAMP_GEMM + (batch.np <= 12 ? 6 * 2048 : 0) + 6 * blockIdx.x;
+    o[0] = rt0; o[1] = rt1; o[2] = rt2; o[3] = rt3; o[4] = wall_clock64(); o[5] = p;
+  }
+#endif
   if (!live || sub != 0) return;
   const float g = P.accumulate ? old1 + s : s;
   *dst = g;
@@ -197,7 +243,6 @@ int wg_add(WgBatch& b, const float* delta, int ldd, const float* act, int lda, i
       P.pre = 0;
       P.act2 = nullptr; P.dW2 = nullptr; P.lda2 = P.ldw2 = P.K2 = P.row0 = 0;
       if (!wg_shape_ok(Nseg, P.K)) return SW_ESHAPE;
-      P.nbn = (Nseg + 15) / 16;
       P.nbk = P.K > 0 ? wg_tiles(P.K, true) : 1;     // the ones column costs no matrix tile (VALU)
     }
   }
@@ -215,7 +260,6 @@ int wg_add_tail(WgBatch& b, const float* delta, int ldd, const float* act, int l
   P.dW = dW; P.ldw = ldw; P.db = db; P.db2 = db ? db2 : nullptr; P.accumulate = accumulate; P.pre = 0;
   P.act2 = act2; P.lda2 = lda2; P.K2 = K2; P.dW2 = dW2; P.ldw2 = ldw2; P.row0 = row0;
   if (!wg_shape_ok(N, K)) return SW_ESHAPE;
-  P.nbn = (N + 15) / 16;
   P.nbk = 4;
   return SW_OK;
 }
@@ -225,7 +269,7 @@ int wg_add_pre(WgBatch& b, int N, int K, float* dW, int ldw, float* db, int nsli
   WgProblem& P = b.p[b.np++];
   P.delta = nullptr; P.act = nullptr; P.ldd = P.lda = 0; P.R = 0;
   P.N = N; P.K = K; P.ones = 1; P.dW = dW; P.ldw = ldw; P.db = db; P.db2 = nullptr; P.accumulate = 0;
-  P.nbn = (N + 15) / 16; P.nbk = (K + 1 + 15) / 16;
+  P.nbk = (K + 1 + 15) / 16;
   P.act2 = nullptr; P.dW2 = nullptr; P.lda2 = P.ldw2 = P.K2 = P.row0 = 0;
   P.pre = nslices;
   b.top_reserved += (size_t)nslices * N * (K + 1);
@@ -243,6 +287,12 @@ int wg_add_pre(WgBatch& b, int N, int K, float* dW, int ldw, float* db, int nsli
 // loads.  With the bounded buffer loads of sw_wgrad_dev.h the LSTM problem's jobs - 45 groups per wave - went from 33.1 to
 // 30.7 us, the longest job of the launch from 36.5 to 33.1 us (profiles/wgrad_bounded_ab.txt); the constants are kept as they
 // are: a refit moves the split, and with it which rows meet in which partial - the last bits of every gradient.)
+// The part of a job that is NOT the row stream, from the marks inside a job (-DSW_WG_STAMP, tools/dbg/wgrad_stamps.py,
+// profiles/wgrad_fixed_ab.txt; LSTM problem of a discriminator pass at the metric shape, 8 groups per wave, median job 9.6 us):
+// record fetched 0.2 us after the workgroup's start, first group arrived at 0.9 - 1.0 us, loop left at 7.4 us, first LDS sum
+// done at 9.1 us (block to LDS, barrier = the slowest of the four waves), stores issued at 9.6 us.  Before the keys came
+// in one fetch, the record in one clause, the epilogue in 16-byte pieces and a slice's last trip without its zero groups, the
+// same job took 12.0 us (generator's LSTM problem, 45 groups: 30.5 -> 26.8 us).
 #ifndef SW_WG_GROUP_C0
 #define SW_WG_GROUP_C0 256.0
 #endif
@@ -325,12 +375,23 @@ size_t wg_finalize(WgBatch& b) {
       if (!P.pre) job += ns * NB;
       P.out0 = out;
       const int Kc = P.K + P.K2 + P.ones;
-      out += P.N * Kc;
+      // every wave of the reduction (SW_WG_REL = 16 elements) belongs to ONE problem: its lookup key is wave-uniform
+      out += (P.N * Kc + 15) & ~15;
+      // what the kernels would otherwise derive per job / per element (WgProblem)
+      const int nsub = ns * 4;
+      P.rows_per = (((P.R + nsub - 1) / nsub) + 3) & ~3;
+      P.nbmul = (65536 + NB - 1) / NB;
+      P.kcmul = (unsigned)(((1ULL << 31) + Kc - 1) / Kc);
+      P.ldp = P.pre ? Kc : (Kc + 3) & ~3;      // a precomputed partial keeps the layout its producer writes
+      const int Nl = P.N - 64 * (NB - 1);
+      const int kr = wg_tiles(P.K, true), tl = (P.K2 ? 2 : 0) + (P.ones ? 1 : 0);
+      P.cases = ((wg_tiles(64, false) * 8 + kr) * 4 + tl) | ((wg_tiles(Nl, false) * 8 + kr) * 4 + tl) << 8 | NB << 16;
       if (!P.pre) {
         P.ws_off = ws;
-        ws += (size_t)ns * P.N * Kc;
+        ws += (size_t)ns * P.N * P.ldp;
       }
     }
+    for (int i = b.np; i < SW_WG_MAXP; ++i) b.job0s[i] = b.out0s[i] = 0x7fffffff;   // wg_find counts the keys <= x
     b.total_jobs = job;
     b.total_out = out;
     return ws;
@@ -370,6 +431,7 @@ int wg_launch_adam(WgBatch& b, float* ws, WgAdam& ad, hipStream_t stream) {
   size_t need = wg_finalize(b);
   if (need > SW_WG_WS_FLOATS) return SW_ESHAPE;
   if (b.total_out == 0) return SW_OK;
+  if ((uintptr_t)ws & 15) return SW_EARG;    // the partials go out in 16-byte stores
   ad.bc = nullptr;
   if (b.total_jobs > 0) {
     float* bc = ad.w ? wg_bc_slot() : nullptr;
@@ -383,6 +445,7 @@ int wg_launch_adam(WgBatch& b, float* ws, WgAdam& ad, hipStream_t stream) {
 
 int wg_launch_finalized(WgBatch& b, float* ws, hipStream_t stream) {
   if (b.total_out == 0) return SW_OK;
+  if ((uintptr_t)ws & 15) return SW_EARG;    // the partials go out in 16-byte stores
   if (b.total_jobs > 0) {
     SW_LAUNCH(wgrad_partial_kernel, dim3(wg_grid_jobs(b.total_jobs)), dim3(SW_THREADS), 0, stream, b, ws, (const float*)nullptr,
                        0.0, 0.0, (float*)nullptr);

@@ -13,8 +13,27 @@
 #ifndef SW_WG_DEPTH_TAIL
 #define SW_WG_DEPTH_TAIL SW_WG_DEPTH
 #endif
+#ifndef SW_WG_PEEL      // 1: a slice's last partial trip runs only its live groups (wg_run); 0: whole trips, the rest zeros
+#define SW_WG_PEEL 1
+#endif
 
-#define SW_WG_RLD 69   // LDS row stride of a wave's 64 x (<= 69) block: 64 act columns + tail segment + ones
+// Timing experiment (-DSW_WG_STAMP, tools/build_variant.sh): wall-clock marks inside a job, kept in registers by the first
+// lane of the workgroup and written out by wgrad_partial_kernel.  mk[0] job found (record fetched), [1] descriptors built,
+// [2] first group arrived, [3] loop left, [4] LDS sum done, [5] stores issued.  Nothing of it exists in a default build.
+#ifdef SW_WG_STAMP
+#define WG_MARKS_ARG , unsigned long long (&mk)[6]
+#define WG_MARKS_PASS , mk
+#define WG_MARK(i) mk[i] = wall_clock64()
+#else
+#define WG_MARKS_ARG
+#define WG_MARKS_PASS
+#define WG_MARK(i) ((void)0)
+#endif
+
+#define SW_WG_RLD 72   // LDS row stride of a wave's 64 x (<= 69) block: 64 act columns + tail segment + ones, rounded up
+                       // to 16 bytes (a lane's consecutive columns go out, and the four slices come back, as b128 / b64)
+static_assert(SW_WG_RLD % 4 == 0 && SW_WG_RLD >= 69, "16-byte LDS rows that hold 64 + 4 + 1 columns");
+static_assert(2 * 4 * 64 * SW_WG_RLD * 4 <= 160 * 1024, "two workgroups per CU must fit the 160 KB of LDS");
 
 // Bounded operand loads: a wave reads its row slice through one buffer descriptor per operand.  The descriptor's range
 // ends on the slice's last row boundary, so a row beyond it - prefetch overrun, the padding of the last 4-row group - comes
@@ -78,24 +97,8 @@ template <int NA, int KR, int K2, int ONES, int DSCALE = 1>
 __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const float* __restrict__ abase, int ldd, int lda,
                                        int rbeg, int rend, int acol, int bcol, int lg, int ln,
                                        float* __restrict__ mine,
-                                       const float* __restrict__ abase2, int lda2, int row0, int xoff) {
+                                       const float* __restrict__ abase2, int lda2, int row0, int xoff WG_MARKS_ARG) {
   constexpr int KT = KR, XC = K2 + ONES;
-  f32x4 acc[NA][KT];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) acc[i][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  // The tail segment (K2 = 4 columns of act2: the LSTM's x_t) and the ones column (bias gradient) do NOT get an MFMA
-  // tile of their own - it would carry 5 (or 1) useful columns of 16, a fifth of the LSTM problem's matrix work -:
-  // the lane that holds delta[row][n] multiplies it with the row's 4 x values / adds it up on the VALU, which runs
-  // beside the matrix pipe; the per-row-group partial sums meet in two lane shuffles at the end of the slice.
-  float xacc[NA][XC > 0 ? XC : 1];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-#pragma unroll
-    for (int c = 0; c < (XC > 0 ? XC : 1); ++c) xacc[i][c] = 0.f;
-  }
   // 4-row groups in flight (swept on the GPU at 8 waves per CU)
   constexpr int DEPTH = (K2 > 0 ? SW_WG_DEPTH_TAIL : SW_WG_DEPTH) * DSCALE;
   float a[DEPTH][NA], b[DEPTH][KT];
@@ -111,6 +114,7 @@ __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const fl
   unsigned doff = (unsigned)(lg * ldd + acol) * 4u, aoff = (unsigned)((rbeg - abeg + lg) * lda + bcol) * 4u;
   unsigned xoff2 = (unsigned)(lg * lda2) * 4u;
   const unsigned dstep = 16u * (unsigned)ldd, astep = 16u * (unsigned)lda, xstep = 16u * (unsigned)lda2;
+  WG_MARK(1);
   auto load = [&](float (&av)[NA], float (&bv)[KT], f32x4& xv) {     // the next 4-row group of the slice
     wg_ldv<NA>(av, drs, doff);
     doff += dstep;
@@ -125,47 +129,99 @@ __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const fl
   };
 #pragma unroll
   for (int q = 0; q < DEPTH - 1; ++q) load(a[q], b[q], xq[q]);
+  asm volatile("" ::: "memory");   // the first DEPTH - 1 groups are on their way before anything that does not feed an address
+  // The tail segment (K2 = 4 columns of act2: the LSTM's x_t) and the ones column (bias gradient) do NOT get an MFMA
+  // tile of their own - it would carry 5 (or 1) useful columns of 16, a fifth of the LSTM problem's matrix work -:
+  // the lane that holds delta[row][n] multiplies it with the row's 4 x values / adds it up on the VALU, which runs
+  // beside the matrix pipe; the per-row-group partial sums meet in two lane shuffles at the end of the slice.
+  f32x4 acc[NA][KT];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) acc[i][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float xacc[NA][XC > 0 ? XC : 1];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+#pragma unroll
+    for (int c = 0; c < (XC > 0 ? XC : 1); ++c) xacc[i][c] = 0.f;
+  }
   // No masks at all.  Rows outside [rbeg, rend) load zeros (a zero delta row kills its products, its tail columns and its
   // ones column), rows below row0 a zero act row.  There are no COLUMN masks either: a lane beyond the block's live delta /
   // act columns (clamped to the last live ones) only feeds output rows / columns that are never written out - an MFMA
   // output element mixes nothing but its own row and column.  (Peeling the interior into a branch of its own was
-  // measured 1.8 x slower: memory operations under a branch cost the exact vmcnt bookkeeping, see DESIGN.md.)
+  // measured 1.8 x slower: memory operations under a branch cost the exact vmcnt bookkeeping, see DESIGN.md.  The peeled
+  // END of a slice below holds no memory operation: the generator's LSTM jobs at the metric shape - 45 groups, 3 of 48
+  // were zeros - 28.1 -> 26.8 us, profiles/wgrad_fixed_ab.txt.)
+  auto consume = [&](int q) {           // q is a constant after unrolling
+#pragma unroll
+    for (int i = 0; i < NA; ++i) asm volatile("" : "+v"(a[q][i]));   // group q is first touched here
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) asm volatile("" : "+v"(b[q][kt]));
+    if constexpr (K2 > 0) asm volatile("" : "+v"(xq[q]));
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt) {
+        acc[i][kt] = SW_MFMA(a[q][i], b[q][kt], acc[i][kt]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      if constexpr (K2 > 0) {
+#pragma unroll
+        for (int c = 0; c < K2; ++c) xacc[i][c] = fmaf(a[q][i], xq[q][c], xacc[i][c]);
+      }
+      if constexpr (ONES) xacc[i][K2] += a[q][i];
+    }
+  };
+#if SW_WG_PEEL
+  // Whole trips of DEPTH groups, then the slice's last 1 .. DEPTH - 1 groups WITHOUT loads: they are already in flight, and
+  // what the full trip would fetch and multiply beyond them is zeros.  The group count is wave-uniform; the branches hold
+  // no memory operation, so every path sees the same loads in the same order (the vector-memory counter rule).
+  const int groups = (rend - rbeg + 3) >> 2, whole = groups / DEPTH, rest = groups - whole * DEPTH;
+  for (int t = 0; t < whole; ++t) {
+#else
   for (int r = rbeg; r < rend; r += 4 * DEPTH) {
+#endif
 #pragma unroll
     for (int q = 0; q < DEPTH; ++q) {
       load(a[(q + DEPTH - 1) % DEPTH], b[(q + DEPTH - 1) % DEPTH], xq[(q + DEPTH - 1) % DEPTH]);
       asm volatile("" ::: "memory");   // the loads are issued HERE (DEPTH - 1 groups ahead), not sunk to their uses
-#pragma unroll
-      for (int i = 0; i < NA; ++i) asm volatile("" : "+v"(a[q][i]));   // ... and group q is first touched here
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) asm volatile("" : "+v"(b[q][kt]));
-      if constexpr (K2 > 0) asm volatile("" : "+v"(xq[q]));
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          acc[i][kt] = SW_MFMA(a[q][i], b[q][kt], acc[i][kt]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        if constexpr (K2 > 0) {
-#pragma unroll
-          for (int c = 0; c < K2; ++c) xacc[i][c] = fmaf(a[q][i], xq[q][c], xacc[i][c]);
-        }
-        if constexpr (ONES) xacc[i][K2] += a[q][i];
-      }
+      consume(q);
+#ifdef SW_WG_STAMP
+#if SW_WG_PEEL
+      if (q == 0 && t == 0) WG_MARK(2);
+#else
+      if (q == 0 && r == rbeg) WG_MARK(2);
+#endif
+#endif
     }
   }
+#if SW_WG_PEEL
+#pragma unroll
+  for (int q = 0; q < DEPTH - 1; ++q) {
+    if (q < rest) consume(q);
+  }
+#endif
+  WG_MARK(3);
   // tile (i, kt) element (m = 4 lg + r, n = ln)  =  output row NA m + i, act column KR n + kt
+  // A lane's KR columns are consecutive and wholly live or wholly dead (K % KR == 0): one b128 / b64 write per output row
+  // where KR is 4 / 2 (the row stride and KR ln keep it aligned)
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
+    for (int r = 0; r < 4; ++r) {
+      float* o = mine + (NA * (4 * lg + r) + i) * SW_WG_RLD + KR * ln;
+      if (KR * ln < xoff) {                                                                  // xoff = K: live columns only
+        if constexpr (KR == 4) {
+          *reinterpret_cast<float4*>(o) = float4{acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]};
+        } else if constexpr (KR == 2) {
+          *reinterpret_cast<float2*>(o) = float2{acc[i][0][r], acc[i][1][r]};
+        } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int orow = NA * (4 * lg + r) + i;
-        if (KR * ln + kt < xoff) mine[orow * SW_WG_RLD + KR * ln + kt] = acc[i][kt][r];      // xoff = K: live columns only
+          for (int kt = 0; kt < KT; ++kt) o[kt] = acc[i][kt][r];
+        }
       }
     }
   }
@@ -173,12 +229,23 @@ __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const fl
   if constexpr (XC > 0) {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
+      float xv[XC];
 #pragma unroll
       for (int c = 0; c < XC; ++c) {
         float v = xacc[i][c];
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
-        if (lg == 0) mine[(NA * ln + i) * SW_WG_RLD + xoff + c] = v;
+        xv[c] = v;
+      }
+      float* o = mine + (NA * ln + i) * SW_WG_RLD + xoff;
+      if (lg == 0) {
+        if constexpr (K2 == 4) {                        // the tail sits behind K = 64 columns: aligned
+          *reinterpret_cast<float4*>(o) = float4{xv[0], xv[1], xv[2], xv[3]};
+          if constexpr (ONES) o[4] = xv[4];
+        } else {
+#pragma unroll
+          for (int c = 0; c < XC; ++c) o[c] = xv[c];
+        }
       }
     }
   }
@@ -188,23 +255,35 @@ __device__ __forceinline__ void wg_run(const float* __restrict__ dbase, const fl
 // wave streams independently (no LDS, no barriers in the loop).  `red` = 4 x 64 x SW_WG_RLD floats of LDS.
 #define SW_WG_RED_FLOATS (4 * 64 * SW_WG_RLD)
 template <int DSCALE = 1>
-__device__ __forceinline__ void wg_job(const WgBatch& batch, float* __restrict__ ws, int job, float* red) {
+__device__ __forceinline__ void wg_job(const WgBatch& batch, const int (&keys)[SW_WG_MAXP], float* __restrict__ ws, int job,
+                                       float* red WG_MARKS_ARG) {
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  int p = 0;
-#pragma unroll 1
-  while (p + 1 < batch.np && job >= batch.job0s[p + 1]) ++p;
-  const WgProblem& P = batch.p[p];
+  // Job start = two dependent scalar round trips: the search keys (fetched by the caller, wg_keys), then the GEMM part of
+  // the problem's record in one clause - it carries everything a job used to derive with divisions and loops
+  // (WgProblem: cases, rows_per, nbmul).
+  const int p = wg_find(keys, job);
+  const WgProblem& Q = batch.p[p];
+  struct {
+    const float *delta, *act, *act2;
+    size_t ws_off;
+    int ldd, lda, lda2, row0, R, N, K, job0, cases, rows_per, nbmul, ldp;
+  } P = {Q.delta, Q.act,  Q.act2, Q.ws_off, Q.ldd, Q.lda,   Q.lda2,     Q.row0,
+         Q.R,     Q.N,    Q.K,    Q.job0,   Q.cases, Q.rows_per, Q.nbmul, Q.ldp};
+  WG_PIN(P.delta); WG_PIN(P.act); WG_PIN(P.act2); WG_PIN(P.ws_off);
+  WG_PIN(P.ldd); WG_PIN(P.lda); WG_PIN(P.lda2); WG_PIN(P.row0); WG_PIN(P.R); WG_PIN(P.N); WG_PIN(P.K); WG_PIN(P.job0);
+  WG_PIN(P.cases); WG_PIN(P.rows_per); WG_PIN(P.nbmul); WG_PIN(P.ldp);
+  WG_MARK(0);
   const int j = job - P.job0;
-  const int NB = (P.N + 63) >> 6;       // 64-row output blocks
-  const int sg = j / NB, nb = j - sg * NB;
+  const int NB = P.cases >> 16;         // 64-row output blocks
+  const int sg = (int)(((unsigned)j * (unsigned)P.nbmul) >> 16), nb = j - sg * NB;
   const int s = sg * 4 + wave;          // this wave's row slice (may be empty)
-  const int N = P.N, K = P.K, Kc = P.K + P.K2 + P.ones;
+  const int N = P.N, K = P.K;
   const int n0 = nb * 64;
   const int Nb = min(64, N - n0);                       // live delta columns of this block
-  const int NA = wg_tiles(Nb, false);                   // delta tiles
-  const int KR = K > 0 ? wg_tiles(K, true) : 1;         // real act tiles (a block with only the ones column: one masked tile)
-  const int nsub = P.nsplit * 4;
-  const int rows_per = (((P.R + nsub - 1) / nsub) + 3) & ~3;
+  const int cs = (nb == NB - 1 ? P.cases >> 8 : P.cases) & 255;   // ((NA * 8 + KR) * 2 + tail) * 2 + ones
+  const int NA = cs >> 5;                               // delta tiles
+  const int KR = (cs >> 2) & 7;                         // real act tiles
+  const int rows_per = P.rows_per;
   // the slice bounds feed the buffer descriptors: wave-uniform, and through readfirstlane the compiler knows it
   const int rbeg = __builtin_amdgcn_readfirstlane(min(P.R, s * rows_per));
   const int rend = __builtin_amdgcn_readfirstlane(min(P.R, rbeg + rows_per));
@@ -217,34 +296,41 @@ __device__ __forceinline__ void wg_job(const WgBatch& batch, float* __restrict__
 #define WG_CASE(na, kr, k2, on)                                                                                     \
   case ((na * 8 + kr) * 2 + (k2 ? 1 : 0)) * 2 + on:                                                                 \
     wg_run<na, kr, k2, on, DSCALE>(P.delta, P.act, P.ldd, P.lda, rbeg, rend, acol, bcol, lg, ln,                      \
-                                   mine, P.act2 ? P.act2 : P.delta, P.act2 ? P.lda2 : P.ldd, P.row0, K);            \
+                                   mine, P.act2 ? P.act2 : P.delta, P.act2 ? P.lda2 : P.ldd, P.row0, K WG_MARKS_PASS); \
     break;
 #define WG_CASES(na)                                                                                                \
   WG_CASE(na, 1, 0, 0) WG_CASE(na, 2, 0, 0) WG_CASE(na, 3, 0, 0) WG_CASE(na, 4, 0, 0)                               \
   WG_CASE(na, 1, 0, 1) WG_CASE(na, 2, 0, 1) WG_CASE(na, 3, 0, 1) WG_CASE(na, 4, 0, 1)                               \
   WG_CASE(na, 4, 4, 0) WG_CASE(na, 4, 4, 1)
-  switch (((NA * 8 + KR) * 2 + (P.K2 ? 1 : 0)) * 2 + (P.ones ? 1 : 0)) {
+  switch (cs) {
     WG_CASES(1) WG_CASES(2) WG_CASES(4)
   }
 #undef WG_CASES
 #undef WG_CASE
   sw_barrier();
-  // one partial per workgroup (4 row slices summed): ws[ws_off + (sg*N + n)*Kc + k]
-  float* out = ws + P.ws_off + (size_t)sg * N * Kc;
-  const int rows = min(64, N - n0), cols = min(SW_WG_RLD, Kc);
-  // element e = rr * cols + cc walks the block row-major; (rr, cc) advance incrementally (one division per thread)
-  const int dq = SW_THREADS / cols, dr = SW_THREADS - dq * cols;
-  int rr = threadIdx.x / cols, cc = threadIdx.x - rr * cols;
-  const float* r0 = red, *r1 = red + 64 * SW_WG_RLD, *r2 = red + 2 * 64 * SW_WG_RLD, *r3 = red + 3 * 64 * SW_WG_RLD;
-  for (int e = threadIdx.x; e < rows * cols; e += SW_THREADS) {
-    const int o = rr * SW_WG_RLD + cc;
-    const float v = (r0[o] + r1[o]) + (r2[o] + r3[o]);
-    out[(size_t)(n0 + rr) * Kc + cc] = v;
-    cc += dr;
-    rr += dq;
-    if (cc >= cols) {
-      cc -= cols;
-      ++rr;
-    }
+  // one partial per workgroup (4 row slices summed): ws[ws_off + (sg*N + n)*ldp + k], ldp = Kc rounded up to 4 floats.
+  // A thread sums one 16-byte chunk of a row at a time: 4 b128 LDS reads, one 16-byte store.  (The <= 3 columns between
+  // Kc and ldp carry whatever the LDS held: the reduction never reads them.)
+  const int ldp = P.ldp, c4 = ldp >> 2;
+  float* out = ws + P.ws_off + ((size_t)sg * N + n0) * ldp;
+  // chunk c = rr * c4 + cq: rr = c / c4 through a float reciprocal, exact here: c < 64 * 18 + 256, c4 <= 18, so
+  // (c + 0.5) / c4 stays >= 1 / 36 away from an integer, far beyond the 2^-22 relative error of rcp and the product
+  const float rc4 = __builtin_amdgcn_rcpf((float)c4);
+  const float4* r0 = reinterpret_cast<const float4*>(red);
+  constexpr int S4 = 64 * SW_WG_RLD / 4;
+  for (int c = threadIdx.x; c < Nb * c4; c += SW_THREADS) {
+    const int rr = (int)(((float)c + 0.5f) * rc4), cq = c - rr * c4;
+    const int o = rr * (SW_WG_RLD / 4) + cq;
+    const float4 v0 = r0[o], v1 = r0[o + S4], v2 = r0[o + 2 * S4], v3 = r0[o + 3 * S4];
+    float4 v;
+    v.x = (v0.x + v1.x) + (v2.x + v3.x);
+    v.y = (v0.y + v1.y) + (v2.y + v3.y);
+    v.z = (v0.z + v1.z) + (v2.z + v3.z);
+    v.w = (v0.w + v1.w) + (v2.w + v3.w);
+    reinterpret_cast<float4*>(out)[rr * c4 + cq] = v;
+#ifdef SW_WG_STAMP
+    if (c == (int)threadIdx.x) WG_MARK(4);      // the first chunk's sum: its four LDS reads have come back
+#endif
   }
+  WG_MARK(5);
 }
