@@ -13,6 +13,9 @@
   (one rank per GPU over RCCL; every packed batch is sharded scene-aligned, rank 0 evaluates and saves)
   `SW_ALLREDUCE=direct` exchanges the gradients through the library's own two-hop kernel over hipIpc-mapped peer buffers
   (one launch per optimizer step: exchange + Adam, inside the step's hipGraph) instead of RCCL's ring
+* `--compose DIST`: the composed scene futures (evaluate_composed): one draw per agent - given the observations the agents'
+  draws are independent, so any tuple of them is a joint sample -, the top-scored ones moved to other draws until no two chosen
+  paths come closer than DIST; errors, scores and collision rates before and after.
 * `--min-past M`: the held-out windows also keep the pedestrians seen for only M .. 7 frames (create_dataset_ragged:
   right-aligned observations + obs_len), so they are predicted and their neighbours see them; the errors are reported per
   history length (evaluate_history).  Training stays on full windows unless
@@ -72,6 +75,9 @@ def main(argv=None):
     ap.add_argument("--diverse", type=float, default=None, metavar="RADIUS",
                     help="also report the diverse top-5 of the K draws: modes kept by suppressing, in the discriminator's score "
                          "order, every draw whose end point lies within RADIUS (world units) of a kept one")
+    ap.add_argument("--compose", type=float, default=None, metavar="DIST",
+                    help="also report the composed scene futures: one draw per agent, the discriminator's top-scored ones moved to "
+                         "other draws until no two chosen paths come closer than DIST (world units)")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -172,6 +178,14 @@ def main(argv=None):
                       "first mode holds %.0f %% of the draws, the min-ADE mode %.0f %%"
                       % (dv["top_m"], args.diverse, dv["ade_div1"], dv["fde_div1"], dv["ade_divm"], dv["fde_divm"], dv["n_modes"],
                          100 * dv["w_first"], 100 * dv["w_hit"]))
+            if args.compose is not None:
+                cp = tr.evaluate_composed(data, n_gen_samples=args.k, coll_dist=args.compose)
+                print("Composed futures (one of %d draws per agent, no two paths within %.2f): ADE,FDE top-scored = (%.3f, %.3f), "
+                      "composed = (%.3f, %.3f) | scenes with a collision %.1f %% -> %.1f %%, pairs per scene %.2f -> %.2f, %.1f %% of "
+                      "agents moved, mean score %.3f -> %.3f | %d scenes, %d with company"
+                      % (args.k, args.compose, cp["ade_top1"], cp["fde_top1"], cp["ade_comp"], cp["fde_comp"], 100 * cp["col_top1"],
+                         100 * cp["col_comp"], cp["pairs_top1"], cp["pairs_comp"], 100 * cp["moved"], cp["score_top1"],
+                         cp["score_comp"], cp["n_scenes"], cp["n_multi"]))
             if ragged is not None:
                 hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
                 print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"

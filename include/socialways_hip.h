@@ -350,6 +350,49 @@ int sw_sample_nms(const float* pos, int pstride, const float* score /*[K,B]*/, c
                   int B, int K, int Tp, int M, int metric, float inv_ss, float radius, const float* err /*[K,B,2] or NULL*/,
                   const int* best /*[B] or NULL*/, int* order /*[G,M]*/, int* count /*[G]*/, float* weight /*[G,M]*/,
                   int* assign /*[G,K]*/, float* per_row /*[B,6] or NULL*/, void* stream);
+/* COMPOSED joint future of a scene: one draw PER AGENT.  Given the observations the K draws of different agents are
+ * independent (the social block runs once, on the observations; row (k, a) of the rollout reads z[k][a] and the encoding of
+ * agent a alone), so every tuple (k_a) of per-agent draws is as much a joint sample as the diagonal (k, .., k) that
+ * sw_scene_clearance / sw_scene_reduce look at.  Per scene this picks the tuple the score prefers, moved away from it only
+ * where two chosen paths would come closer than coll_dist.  All fp32; agents a, b are rows of one scene (scene_off as above).
+ *   path of (k, a)   as in sw_scene_clearance: start[a] first when start != NULL, then pos[k][a][0 .. Tp-1];
+ *   c(a,j; b,k)      = sqrtf(m) * inv_ss, m = the minimum over the countable segments of the squared closest approach of
+ *                    path (j, a) to path (k, b), each segment with the arithmetic of sw_scene_clearance operation for
+ *                    operation (r0, dv, tau = clamp(-(r0.dv) / (dv.dv), 0, 1), 0 when dv.dv = 0, |r0 + tau dv|^2).  With len
+ *                    [B] int32 (clamped into 1 .. Tp) the segment that ends at future frame t counts only while
+ *                    t < min(len[a], len[b]) - the rule of sw_scene_clearance_len; what lies behind a length, NaN included,
+ *                    reaches nothing.  +inf when no segment counts.  Exactly symmetric: c(a,j; b,k) = c(b,k; a,j);
+ *   conflict         c < coll_dist, the comparison sw_scene_reduce applies to clear.
+ * The selection, per scene, its agents a = 0 .. n-1 in ascending row order:
+ *   sel0[a] = the draw with the highest score[k][a], the lowest k of equal ones (order[a][0] of sw_sample_rank); sel = sel0;
+ *   conf_a(j) = the number of agents b != a of the scene with c(a,j; b,sel[b]) in conflict;
+ *   up to `sweeps` sweeps; in a sweep, for a = 0 .. n-1 in order: if conf_a(sel[a]) == 0 nothing happens; else with j* = the
+ *   draw that minimises (conf_a(j), -score[j][a], j) lexicographically, sel[a] = j* if conf_a(j*) < conf_a(sel[a]) - seen by
+ *   the agents after a in the same sweep - and sel[a] stays otherwise.  Every change lowers the number of conflicting pairs
+ *   of the scene by at least one, so the loop ends; it stops after the first sweep in which nothing changed.
+ * Outputs:  sel [B] int32, sel0 [B] int32 (or NULL);
+ *   clear [B]        clear[a] = the minimum over b != a of c(a,sel[a]; b,sel[b]), +inf in a single-agent scene: the bits of
+ *                    sw_scene_clearance(_len) with K = 1 on the selected paths;
+ *   per_scene [S,4]  int32 { conflicting pairs under sel0, conflicting pairs under sel, agents with sel != sel0, sweeps in
+ *                    which some agent changed };
+ *   per_row [B,4]    or NULL, needs err [K,B,2] (the row errors of sw_dec_sample_fwd, 8-byte aligned):
+ *                    { ADE, FDE of draw sel0[a], ADE, FDE of draw sel[a] }.
+ * Rows outside every scene are not written; a scene whose offsets leave 0 .. B reads nothing and has per_scene 0.  Scores are
+ * expected to be ordered (no NaN).  coll_dist == 0 admits no conflict: sel == sel0.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, score, scene_off, sel, clear, per_scene; S < 0;
+ * B < 0; K < 1; Tp < 1; sweeps < 1; pstride not 2 or 4; pos or err off their 8-byte alignment; start with sstride < 2;
+ * inv_ss <= 0 or NaN; coll_dist < 0 or NaN; per_row without err.  SW_ESHAPE: K > 4096.  B == 0 or S == 0: SW_OK without a
+ * launch.  One 256-thread workgroup per scene, any scene size and any Tp; one writer per output element, integer conflict
+ * counts, no atomics: two calls give the same bits.  The n^2 K^2 table of clearances is never formed.
+ * LDS per workgroup: min(8 256 + roundup(4 B, 16) + 8 B ((Tp + [start != NULL]) | 1), 65 536) bytes - 8 192 for a batch of one
+ * agent's candidate paths, the rest for the selection and the selected paths of a scene (at most B agents); a scene whose
+ * paths do not fit reads them from global memory instead.                                                            */
+int sw_scene_compose(const float* pos, int pstride, const float* start /*or NULL*/, int sstride,
+                     const float* score /*[K,B]*/, const int* scene_off /*[S+1]*/, const int* len /*[B] or NULL*/,
+                     int S, int B, int K, int Tp, float inv_ss, float coll_dist, int sweeps,
+                     const float* err /*[K,B,2] or NULL*/,
+                     int* sel /*[B]*/, int* sel0 /*[B] or NULL*/, float* clear /*[B]*/,
+                     int* per_scene /*[S,4]*/, float* per_row /*[B,4] or NULL*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

@@ -757,6 +757,67 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
     return order, count, weight, assign, per_row
 
 
+def scene_compose(pos, start, score, scenes, K, coll_dist, inv_ss=1.0, sweeps=8, lens=None, err=None):
+    """A joint future per scene put together from the per-agent draws (sw_scene_compose): every agent starts on its
+    highest-scored draw (sel0), and in up to `sweeps` sweeps over a scene's agents one that comes closer than coll_dist to
+    another's selected path - inv_ss * the closest approach along the paths, both moving linearly between frames - moves to
+    the draw with the fewest such conflicts, the highest score among equals, if that is fewer than it has.  Given the
+    observations the draws of different agents are independent, so any such tuple is a joint sample of the generator.
+    pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or None: the point in front of the Tp positions
+    (any row stride, as scene_clearance); score (K, B), higher = better; scenes: a SceneIndex; lens (B,) int32 on the device:
+    ragged futures, as scene_clearance(lens=...); err (K, B, 2): the row errors of gen_sample.
+    Returns (sel (B,) int32, sel0 (B,) int32, clear (B,): the closest approach of every agent's selected path to the other
+    selected paths of its scene, +inf in single-agent scenes; per_scene (S, 4) int32: conflicting pairs under sel0 | under sel |
+    agents that moved | sweeps that changed something; per_row (B, 4) or None without err: ADE | FDE of draw sel0, ADE | FDE
+    of draw sel)."""
+    if score.dim() != 2 or score.shape[0] != K or K < 1:
+        raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
+    B = score.shape[1]
+    if K > RANK_MAX_K:
+        raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
+    if not float(coll_dist) >= 0.0:
+        raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+    if not float(inv_ss) > 0.0:
+        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    if int(sweeps) < 1:
+        raise ValueError("sweeps must be at least 1, got %r" % (sweeps,))
+    if pos.dim() not in (3, 4) or pos.shape[-1] not in (2, 4) or pos.shape[-2] < 1 \
+            or pos.numel() != K * B * pos.shape[-2] * pos.shape[-1] or (pos.dim() == 4 and tuple(pos.shape[:2]) != (K, B)):
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
+    if pos.device != score.device:
+        raise ValueError("pos must be on the device of score")
+    if scenes.B != B:
+        raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
+    if start is not None and (start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != score.device):
+        raise ValueError("start must be (B, >= 2) = (%d, >= 2) on the device of score, got %s" % (B, tuple(start.shape)))
+    if err is not None and (tuple(err.shape) != (K, B, 2) or err.device != score.device):
+        raise ValueError("err must be (K, B, 2) = (%d, %d, 2) on the device of score, got %s" % (K, B, tuple(err.shape)))
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, score.device, "lens")
+    L.require_gpu(score)
+    score, pos = score.float().contiguous(), pos.float().contiguous()
+    dev = score.device
+    sstride = 0
+    if start is not None:
+        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
+            start = start[:, :2].float().contiguous()
+        sstride = start.stride(0)
+    sel = torch.empty(B, dtype=torch.int32, device=dev)
+    sel0 = torch.empty(B, dtype=torch.int32, device=dev)
+    clear = torch.empty(B, device=dev)
+    per_scene = torch.empty(scenes.S, 4, dtype=torch.int32, device=dev)
+    per_row = None
+    if err is not None:
+        err = err.float().contiguous()
+        per_row = torch.empty(B, 4, device=dev)
+    if B == 0:
+        return sel, sel0, clear, per_scene, per_row
+    L.call("sw_scene_compose", L.ptr(pos), pos.shape[-1], L.ptr_strided(start), sstride, L.ptr(score), L.ptr(scenes.scene_off),
+           L.ptr(lens), scenes.S, B, K, pos.shape[-2], float(inv_ss), float(coll_dist), int(sweeps), L.ptr(err), L.ptr(sel),
+           L.ptr(sel0), L.ptr(clear), L.ptr(per_scene), L.ptr(per_row), L.stream())
+    return sel, sel0, clear, per_scene, per_row
+
+
 def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None, tag="d"):
     """Backward of Discriminator.forward.  d_d_w (packed, overwritten) None = no weight gradients;
     want_dpred[k] True = return d loss / d pred4 of branch k."""

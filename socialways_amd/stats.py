@@ -6,7 +6,8 @@ the reference (calc_statistics.py:62).
 
 Beyond the reference: `scene_clearance`, the closest approach between the agents of a scene along K joint futures - the
 quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere - and
-`sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise."""
+`sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise, and
+`compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`."""
 import os
 
 import numpy as np
@@ -172,3 +173,32 @@ def sample_modes(trajs, score, radius, top_m, metric="fde", sub_batches=None, sc
     if sub_batches is not None:
         scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
     return ops.sample_nms(t, s, K, int(top_m), radius, metric, scenes, inv_ss=float(scale))[:4]
+
+
+def compose_scenes(trajs, score, sub_batches, coll_dist, start=None, scale=1.0, sweeps=8, lens=None, device="cuda"):
+    """One draw per agent, per scene, so that no two chosen paths come closer than coll_dist (`sw_scene_compose`), for
+    trajectories and scores from anywhere.  trajs (K, B, T, 2 | 4), x and y first: K futures per agent, drawn independently
+    per agent given what was observed - then every tuple of per-agent draws is a joint future; score (K, B), higher = better;
+    sub_batches (S, 2) [start, end) rows tiling [0, B), [] = one scene; start (B, 2) or None: a point in front of every path, as
+    scene_clearance(); distances are multiplied by `scale`; lens (B,) or None: the frames every agent is present for, as
+    scene_clearance_len().  Every agent starts on its highest-scored draw; in up to `sweeps` sweeps over a scene's agents one
+    that conflicts with another's chosen path moves to the draw with the fewest conflicts (the highest score among equals) if
+    that is fewer than it has.  Returns device tensors: sel (B,) int32 the chosen draws, sel0 (B,) int32 the highest-scored
+    ones, clear (B,) the closest approach of each chosen path to the others of its scene (+inf alone), per_scene (S, 4) int32 =
+    conflicting pairs before | after | agents moved | sweeps that changed something."""
+    t, s = _dev(trajs, device), _dev(score, device)
+    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    if tuple(s.shape) != (K, B):
+        raise ValueError("score must be (K, B) = (%d, %d), got %s" % (K, B, tuple(s.shape)))
+    if start is not None:
+        start = _dev(start, device)
+        if tuple(start.shape) != (B, 2):
+            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    if lens is not None:
+        host = lens.cpu().numpy() if isinstance(lens, torch.Tensor) else lens
+        lens = torch.from_numpy(check_pred_len(host, B, T)).to(t.device)
+    L.require_gpu(t)
+    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    return ops.scene_compose(t, start, s, scenes, K, coll_dist, float(scale), int(sweeps), lens=lens)[:4]

@@ -1534,6 +1534,89 @@ class SocialWaysTrainer:
         out.update(n_agents=n_agents, n_groups=n_groups, K=K, top_m=M, radius=float(radius), metric=metric)
         return out
 
+    @staticmethod
+    def _check_compose(coll_dist, sweeps):
+        """The arguments sample_composed() and evaluate_composed() share, checked before anything is sampled."""
+        if not float(coll_dist) >= 0.0:
+            raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+        if int(sweeps) < 1:
+            raise ValueError("sweeps must be at least 1, got %r" % (sweeps,))
+
+    def sample_composed(self, obsv_p, n_samples, coll_dist, sub_batches=[], noise=None, row0=0, scale=1.0, sweeps=8,
+                        obs_len=None):
+        """sample_ranked(top_m=1) with the picks checked against each other: ONE future per agent, chosen per scene of
+        sub_batches so that no two chosen paths come closer than coll_dist (times `scale`, the `scale` of
+        stats.scene_clearance) at any moment - agents moving linearly between frames, every path starting at the last observed
+        position.  Given the observations the generator's K draws of different agents are independent: the social block
+        sees the observed steps only and a draw's rollout reads its own noise and its own agent's encoding.  So a tuple
+        with a different draw per agent is as much a sample of the scene's joint future as "draw k of everybody" - this
+        call chooses among the K^n tuples that one sampling launch has paid for, it does not patch a joint draw.  Every
+        agent starts on the draw D scores highest; in up to `sweeps` sweeps over the scene's agents one in conflict moves to
+        the draw with the fewest conflicts against the others' current picks, the highest score among equals, if that is
+        fewer than it has (ops.scene_compose).  obsv_p, noise, row0, obs_len as sample_ranked().
+        Returns (trajs (B, n_next, 4), score (B,) the chosen draws' own scores, sel (B,) int32: trajs[a] is draw sel[a],
+        clear (B,): the closest approach of every chosen path to the others of its scene, +inf alone - an agent with
+        clear < coll_dist could not be freed -, per_scene (S, 4) int32: conflicting pairs among the top-scored picks | among
+        the chosen | agents that left their top-scored draw | sweeps that changed something).  Sampling, scoring, one
+        composing launch and a gather."""
+        self._check_compose(coll_dist, sweeps)
+        K, _, ph, score = _scored_draws(self, obsv_p, n_samples, 1, sub_batches, noise, row0, obs_len)
+        with torch.no_grad():
+            B = ph.shape[1]
+            scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device)
+            sel, _, clear, per_scene, _ = ops.scene_compose(ph, obsv_p[:, -1], score, scenes, K, coll_dist, inv_ss=scale,
+                                                            sweeps=sweeps)
+            idx = sel.long()[None]
+            trajs = ph.gather(0, idx[:, :, None, None].expand(1, B, self.n_next, 4))[0]
+            return trajs, score.gather(0, idx)[0], sel, clear, per_scene
+
+    COMPOSED_KEYS = ("ade_top1", "fde_top1", "ade_comp", "fde_comp", "score_top1", "score_comp", "moved", "col_top1", "col_comp",
+                     "pairs_top1", "pairs_comp")
+
+    def evaluate_composed(self, data, n_gen_samples=20, coll_dist=0.1, sweeps=8, just_one=False, collect=None, noise=None):
+        """evaluate() plus what composing a scene's future from the per-agent draws buys (sample_composed(): given the
+        observations the agents' draws are independent, so one draw per agent, whichever, is a joint sample).  The draws are
+        scored as in evaluate_ranked(); per held-out scene every agent starts on its top-scored draw and agents in conflict -
+        closer than coll_dist to another's pick, in world units through data.ss like evaluate_scenes() - move to other draws
+        (ops.scene_compose, `sweeps` sweeps at most).  Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          ade_top1, fde_top1     the error of each agent's top-scored draw (evaluate_ranked()'s);
+          ade_comp, fde_comp     the error of each agent's composed draw: what avoiding the collisions costs;
+          score_top1, score_comp the mean raw LSGAN score of the two picks (score_comp <= score_top1);
+          moved                  share of agents whose draw changed;
+          col_top1, col_comp     share of the scenes of two or more agents with at least one conflicting pair, before and after;
+          pairs_top1, pairs_comp mean conflicting pairs per such scene, before and after (pairs_comp <= pairs_top1);
+          n_scenes, n_multi, K, coll_dist, sweeps.
+        Per-agent sums are divided by data.n_test_samples like evaluate_ranked()'s, per-scene sums by n_multi (0: they are
+        0); float64 sums on the device, one host sync at the end.  Chunking, noise streams and sampling launches are
+        evaluate_ranked()'s.  With `collect` every record of evaluate() also has `sel`, `sel0`, `clear` (n,) and `per_scene`
+        (4,) (columns: ops.scene_compose).  A dataset with pred_len (ragged futures): the errors are over each agent's valid
+        frames and a pair's segment counts only while both agents are present, as in evaluate_scenes()."""
+        self._check_compose(coll_dist, sweeps)
+        dn = self._device_noise(noise)
+        dev, K = self.device, int(n_gen_samples)
+        inv_ss = 1.0 / float(data.ss)
+        base = _EvalSums(dev)
+        acc = torch.zeros(len(self.COMPOSED_KEYS), dtype=torch.float64, device=dev)
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            score, _ = self.D.score_samples(c.obsv, c.ph, obs_len=c.obs_len)
+            sel, sel0, clear, per_scene, per_row = ops.scene_compose(c.ph, c.obsv[:, -1], score, c.scenes, K, coll_dist, inv_ss,
+                                                                     sweeps, lens=c.pred_len, err=c.err)
+            picks = score.gather(0, torch.stack([sel0, sel]).long()).double().sum(1)      # single-agent scenes: no pairs
+            ps = per_scene.double()
+            acc += torch.cat([per_row.double().sum(0), picks, ps[:, 2].sum()[None], (ps[:, :2] > 0).double().sum(0),
+                              ps[:, :2].sum(0)])
+            if collect is not None:
+                collect.extend(self._eval_records(data, c, c.ph, dict(sel=(sel, 0), sel0=(sel0, 0), clear=(clear, 0),
+                                                                      per_scene=(per_scene, None))))
+        nt = data.n_test_samples
+        n_multi = sum(1 for a, b in base.scenes if b - a > 1)
+        out = base.result(data)
+        div = torch.tensor([nt] * 7 + [max(n_multi, 1)] * 4, dtype=torch.float64, device=dev)
+        out.update(zip(self.COMPOSED_KEYS, (acc / div).tolist()))
+        out.update(n_scenes=len(base.scenes), n_multi=n_multi, K=K, coll_dist=float(coll_dist), sweeps=int(sweeps))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
         """The reference's checkpoint dict (train.py:653-663), plus a 'noise' entry ({seed, step}) when self.noise is set."""
