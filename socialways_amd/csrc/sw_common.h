@@ -163,6 +163,23 @@ __device__ __forceinline__ bool sw_aux_masked_copy(int B, const float* src, floa
   return true;
 }
 
+// The first `extra` workgroups of an encoder / social-pool launch copy src -> dst instead (n floats, a multiple of 4: the
+// training step's z out of its pinned host slot): THREADS per workgroup, DEPTH float4 reads per thread in flight (PCIe
+// round trips), the tail one at a time.
+template <int THREADS, int DEPTH>
+__device__ __forceinline__ void sw_z_pull(const float* __restrict__ src, float* __restrict__ dst, long long n, int extra) {
+  const long long n4 = n >> 2, stride = (long long)extra * THREADS;
+  long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+  for (; i + (DEPTH - 1) * stride < n4; i += DEPTH * stride) {
+    f32x4 v[DEPTH];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) v[u] = ld4(src + 4 * (i + u * stride));
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) st4(dst + 4 * (i + u * stride), v[u]);
+  }
+  for (; i < n4; i += stride) st4(dst + 4 * i, ld4(src + 4 * i));
+}
+
 // Split forms of stage_w / stage_wT: a prologue issues the loads of ALL its matrices first (NV float4 registers
 // per matrix and thread, NV = ceil(#float4 / 256)) and stores them afterwards - one L2 round trip for the whole
 // prologue instead of one per matrix (each staging call used to wait for its own loads before its LDS stores).
@@ -326,29 +343,81 @@ constexpr int RAW_W3 = RAW_BE + 64;      // [40][80]   fc3 weight
 constexpr int RAW_B3 = RAW_W3 + 3200;    // [40]       fc3 bias
 constexpr int RAW_W4 = RAW_B3 + 40;      // [2][40]    fc4 weight
 constexpr int RAW_END = RAW_W4 + 80;
-// MFMA A-OPERAND images of a matrix M [rows][K]: float4 q of lane l of k-step j of 16-row tile t =
-// M[16 t + (l & 15)][16 j + 4 (l >> 4) .. + 3] at OP_x + ((t KJ + j) 64 + l) 4 - a wave's operand load is 1 KB of
-// consecutive memory instead of 16 rows x 4 pieces (64 cache-line accesses per instruction).  The backward kernels
-// use the TRANSPOSED matrices (M = W^T).
-constexpr int OP_WHH = RAW_END;          // encoder LSTM weight_hh [256][64]: 16 tiles, KJ 4 (tile = 4 gate + wave)
-constexpr int OP_W1H = OP_WHH + 16384;   // fc1.0.weight[:, 0:64]:   10 tiles, KJ 4
-constexpr int OP_W1SZ = OP_W1H + 10240;  // fc1.0.weight[:, 64:160]: 10 tiles, KJ 6
-constexpr int OP_W2 = OP_W1SZ + 15360;   // fc1.2.weight [80][160]:   5 tiles, KJ 10
-constexpr int OP_WHHT = OP_W2 + 12800;   // weight_hh^T [64][256]:    4 tiles, KJ 16
-constexpr int OP_W2T = OP_WHHT + 16384;  // fc1.2.weight^T [160][80]: 10 tiles, KJ 5
-constexpr int OP_W1HT = OP_W2T + 12800;  // fc1.0.weight[:, 0:64]^T [64][160]: 4 tiles, KJ 10
-// the social block's weights (feature embedder fc.2 / fc.4, attention W), when registered with the images
-constexpr int OP_E1 = OP_W1HT + 10240;   // embedder fc.2.weight [64][32]:   4 tiles, KJ 2
-constexpr int OP_E2 = OP_E1 + 2048;      // embedder fc.4.weight [64][64]:   4 tiles, KJ 4
-constexpr int OP_E1T = OP_E2 + 4096;     // fc.2.weight^T [32][64]:          2 tiles, KJ 4
-constexpr int OP_E2T = OP_E1T + 2048;    // fc.4.weight^T [64][64]:          4 tiles, KJ 4
-constexpr int OP_ATT_T = OP_E2T + 4096;  // attention weight^T [64][64]:     4 tiles, KJ 4
-// W_hh once more for the 8-WAVE encoder pilot (enc_lstm_fwd8_kernel, round 5): wave w owns units 8w .. 8w+7 of all four
-// gates as TWO row tiles whose row m = 4 g + r is gate 2 tile + (r >> 1) of unit 8 w + 2 g + (r & 1), so that a lane's result
-// registers hold i, f (tile 0) and g, o (tile 1) of the same two units: [wave 8][tile 2][j 4][lane 64] float4
-constexpr int OP_WHH8 = OP_ATT_T + 4096;
-constexpr int N = OP_WHH8 + 16384;
 }  // namespace swimg
+// MFMA A-OPERAND image of a matrix M [16 tiles][16 kj] (rows x columns): float4 q of lane l of k-step j of 16-row tile t =
+// M[16 t + (l & 15)][16 j + 4 (l >> 4) .. + 3] at base + ((t kj + j) 64 + l) 4 - a wave's operand load is 1 KB of
+// consecutive memory instead of 16 rows x 4 pieces (64 cache-line accesses per instruction).  The descriptor IS the
+// format: the writer (gen_images_block, sw_misc.hip) walks it, every reader goes through SW_OP_LD.
+struct OpImage {
+  int base, tiles, kj;   // first float, 16-row tiles, k-steps of 16 columns
+  constexpr int size() const { return tiles * kj * 256; }
+  constexpr int end() const { return base + size(); }
+  constexpr OpImage then(int tiles_, int kj_) const { return OpImage{end(), tiles_, kj_}; }   // the image behind this one
+};
+// The float4 of (tile, k-step j, lane) of image d of the buffer img: the one place that spells the address out.  A macro,
+// not a function, and the arithmetic runs in the type of `tile` (size_t or int, as each prologue had it): behind a function
+// boundary, or in another width, the compiler derives other no-wrap facts for the address chain and the prologues - which
+// issue all their global loads before the first wait - come out with their loads in another order (compared kernel by
+// kernel against the hand-written sites: profiles/image_layout_resource_usage.txt).
+#define SW_OP_LD(img, d, tile, j, lane) ld4((img) + (d).base + (((tile) * (d).kj + (j)) * 64 + (lane)) * 4)
+// ... and the other way round: the place of M[row][col] (the discriminator's scatter table, sw_disc.hip)
+__host__ __device__ constexpr int sw_op_at(const OpImage d, int row, int col) {
+  return d.base + (((row >> 4) * d.kj + (col >> 4)) * 64 + ((col & 15) >> 2) * 16 + (row & 15)) * 4 + (col & 3);
+}
+namespace swimg {
+// The backward kernels use the TRANSPOSED matrices (M = W^T).
+constexpr OpImage OP_WHH{RAW_END, 16, 4};         // encoder LSTM weight_hh [256][64] (tile = 4 gate + wave)
+constexpr OpImage OP_W1H = OP_WHH.then(10, 4);    // fc1.0.weight[:, 0:64]
+constexpr OpImage OP_W1SZ = OP_W1H.then(10, 6);   // fc1.0.weight[:, 64:160]
+constexpr OpImage OP_W2 = OP_W1SZ.then(5, 10);    // fc1.2.weight [80][160]
+constexpr OpImage OP_WHHT = OP_W2.then(4, 16);    // weight_hh^T [64][256]
+constexpr OpImage OP_W2T = OP_WHHT.then(10, 5);   // fc1.2.weight^T [160][80]
+constexpr OpImage OP_W1HT = OP_W2T.then(4, 10);   // fc1.0.weight[:, 0:64]^T [64][160]
+// the social block's weights (feature embedder fc.2 / fc.4, attention W), when registered with the images
+constexpr OpImage OP_E1 = OP_W1HT.then(4, 2);     // embedder fc.2.weight [64][32]
+constexpr OpImage OP_E2 = OP_E1.then(4, 4);       // embedder fc.4.weight [64][64]
+constexpr OpImage OP_E1T = OP_E2.then(2, 4);      // fc.2.weight^T [32][64]
+constexpr OpImage OP_E2T = OP_E1T.then(4, 4);     // fc.4.weight^T [64][64]
+constexpr OpImage OP_ATT_T = OP_E2T.then(4, 4);   // attention weight^T [64][64]
+// W_hh once more for the 8-WAVE encoder pilot (enc_lstm_fwd8_kernel, round 5): wave w owns units 8w .. 8w+7 of all four
+// gates as TWO row tiles (tile = 2 wave + tl) whose row m = 4 g + r is gate 2 tl + (r >> 1) of unit 8 w + 2 g + (r & 1), so
+// that a lane's result registers hold i, f (tile 0) and g, o (tile 1) of the same two units
+constexpr OpImage OP_WHH8 = OP_ATT_T.then(16, 4);
+constexpr int N = OP_WHH8.end();
+static_assert(N == 148456, "the image buffer's layout is part of what callers allocate (sw_gen_image_floats)");
+static_assert(N < (1 << 28), "SW_OP_LD sites that pass an int tile index the buffer in 32-bit arithmetic");
+}  // namespace swimg
+// fc4 . fc3 (swimg::W43): thread t < 160 forms W43[t / 80][t % 80] = sum_m W4[c][m] W3[m][k] as four chains over m mod 4,
+// thread 160 + c (B43) the bias b43[c] = W4[c] . b3 + b4[c], into out[t].  The ONE copy of this arithmetic: the image
+// (gen_images_block) and the decode prologues that run without one call it, so both hold the same bits
+// (tests/test_gpu_gen_images.py).
+template <bool B43>
+__device__ __forceinline__ void fc43_compose(const float* dec_w, float* out) {
+  using namespace swp;
+  const int t = threadIdx.x;
+  if (t < 160) {
+    const int c = t / 80, k = t - c * 80;
+    const float* w4 = dec_w + DEC_W4 + c * 40;
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+#pragma unroll
+    for (int m = 0; m < 40; m += 4) {
+      v0 = fmaf(w4[m], dec_w[DEC_W3 + m * 80 + k], v0);
+      v1 = fmaf(w4[m + 1], dec_w[DEC_W3 + (m + 1) * 80 + k], v1);
+      v2 = fmaf(w4[m + 2], dec_w[DEC_W3 + (m + 2) * 80 + k], v2);
+      v3 = fmaf(w4[m + 3], dec_w[DEC_W3 + (m + 3) * 80 + k], v3);
+    }
+    out[t] = (v0 + v1) + (v2 + v3);
+  } else if (B43 && t < 162) {
+    const int c = t - 160;
+    float v = dec_w[DEC_B4 + c];
+#pragma unroll
+    for (int m = 0; m < 40; m += 4) {
+      const f32x4 w = ld4(dec_w + DEC_W4 + c * 40 + m), bb = ld4(dec_w + DEC_B3 + m);
+      v = fmaf(w[0], bb[0], fmaf(w[1], bb[1], fmaf(w[2], bb[2], fmaf(w[3], bb[3], v))));
+    }
+    out[t] = v;
+  }
+}
 // the images registered for (enc_w, dec_w) by the current step, or null (sw_gen_images)
 const float* sw_gen_images_for(const float* enc_w, const float* dec_w);
 // ... whose social part (swimg::OP_E*, OP_ATT_T) was derived from these embedder / attention weights, or null
@@ -368,9 +437,9 @@ const float* sw_soc_images_for(const float* emb_w, const float* att_w);
 //            bank conflicts.  Padding floats are zero from the allocation on and never written.
 // ---------------------------------------------------------------------------------------------
 namespace swdimg {
-constexpr int OP_WHH = 0;
-constexpr int OP_WHHT = 16384;
-constexpr int HEADT = 32768;
+constexpr OpImage OP_WHH{0, 16, 4};
+constexpr OpImage OP_WHHT = OP_WHH.then(4, 16);
+constexpr int HEADT = OP_WHHT.end();
 }  // namespace swdimg
 struct DiscImages {
   const float* img = nullptr;   // null: not registered (row-per-lane / gather prologues)

@@ -178,25 +178,25 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
     // 16-byte piece, so a wave's load instruction reads 1 KB of consecutive memory.  The row-per-lane loads of the
     // fallback below touch 64 cache lines per instruction - 95 of them kept the four waves' address units busy for
     // ~6.5 us (cycle stamps)
-    auto op = [&](int base, int KJ, int tile, int j) { return ld4(gimg + base + (((size_t)tile * KJ + j) * 64 + lane) * 4); };
+    auto op = [&](const OpImage d, int tile, int j) { return SW_OP_LD(gimg, d, (size_t)tile, j, lane); };
     lstm_load_img(W, gimg, wave, lane);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      w1a[j] = op(swimg::OP_W1H, 4, 2 * wave, j);
-      w1b[j] = op(swimg::OP_W1H, 4, 2 * wave + 1, j);
+      w1a[j] = op(swimg::OP_W1H, 2 * wave, j);
+      w1b[j] = op(swimg::OP_W1H, 2 * wave + 1, j);
     }
-    w1p[0] = op(swimg::OP_W1H, 4, 8 + t1p, 2 * hf);
-    w1p[1] = op(swimg::OP_W1H, 4, 8 + t1p, 2 * hf + 1);
+    w1p[0] = op(swimg::OP_W1H, 8 + t1p, 2 * hf);
+    w1p[1] = op(swimg::OP_W1H, 8 + t1p, 2 * hf + 1);
 #pragma unroll
-    for (int j = 0; j < 10; ++j) w2f[j] = op(swimg::OP_W2, 10, wave, j);
-    w2p[0] = op(swimg::OP_W2, 10, 4, J0);
-    w2p[1] = op(swimg::OP_W2, 10, 4, J0 + 1);
-    w2p[2] = op(swimg::OP_W2, 10, 4, J0 + (wave < 2 ? 2 : 1));   // waves 2, 3 have two k-steps: the third set is unused
+    for (int j = 0; j < 10; ++j) w2f[j] = op(swimg::OP_W2, wave, j);
+    w2p[0] = op(swimg::OP_W2, 4, J0);
+    w2p[1] = op(swimg::OP_W2, 4, J0 + 1);
+    w2p[2] = op(swimg::OP_W2, 4, J0 + (wave < 2 ? 2 : 1));   // waves 2, 3 have two k-steps: the third set is unused
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-      wu[0][j] = op(swimg::OP_W1SZ, 6, 2 * wave, j);
-      wu[1][j] = op(swimg::OP_W1SZ, 6, 2 * wave + 1, j);
-      wu[2][j] = op(swimg::OP_W1SZ, 6, 8 + t1p, j);
+      wu[0][j] = op(swimg::OP_W1SZ, 2 * wave, j);
+      wu[1][j] = op(swimg::OP_W1SZ, 2 * wave + 1, j);
+      wu[2][j] = op(swimg::OP_W1SZ, 8 + t1p, j);
     }
   } else if constexpr (NB == 1) {
     lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
@@ -273,29 +273,7 @@ __device__ __forceinline__ void dec_rollout_fwd_tiles(
   } else if constexpr (NB == 1) {
     lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
                    enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
-    const int t = threadIdx.x;
-    if (t < 160) {
-      const int cc = t / 80, k = t - cc * 80;
-      const float* w4 = dec_w + swp::DEC_W4 + cc * 40;
-      float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-#pragma unroll
-      for (int m = 0; m < 40; m += 4) {
-        v0 = fmaf(w4[m], dec_w[swp::DEC_W3 + m * 80 + k], v0);
-        v1 = fmaf(w4[m + 1], dec_w[swp::DEC_W3 + (m + 1) * 80 + k], v1);
-        v2 = fmaf(w4[m + 2], dec_w[swp::DEC_W3 + (m + 2) * 80 + k], v2);
-        v3 = fmaf(w4[m + 3], dec_w[swp::DEC_W3 + (m + 3) * 80 + k], v3);
-      }
-      w43_lds[t] = (v0 + v1) + (v2 + v3);
-    } else if (t < 162) {
-      const int cc = t - 160;
-      float v = dec_w[swp::DEC_B4 + cc];
-#pragma unroll
-      for (int m = 0; m < 40; m += 4) {
-        const f32x4 w = ld4(dec_w + swp::DEC_W4 + cc * 40 + m), bb = ld4(dec_w + swp::DEC_B3 + m);
-        v = fmaf(w[0], bb[0], fmaf(w[1], bb[1], fmaf(w[2], bb[2], fmaf(w[3], bb[3], v))));
-      }
-      w43_lds[t] = v;
-    }
+    fc43_compose<true>(dec_w, w43_lds);
   }
   SW_STAMP(13);
 #pragma unroll
@@ -719,18 +697,18 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_bwd_kernel(
   f32x4 wxT[4], w2t[2][5], w2p[3], w1t[10];
   f32x4 w43c[2][2];     // (fc4 . fc3) columns of this wave's two dz2 tiles in C layout: [tile][c][r] = W43[c][m0 + 4 lg + r]
   if (gimg) {
-    auto op = [&](int base, int KJ, int tile, int j) { return ld4(gimg + base + (((size_t)tile * KJ + j) * 64 + lane) * 4); };
+    auto op = [&](const OpImage d, int tile, int j) { return SW_OP_LD(gimg, d, (size_t)tile, j, lane); };
 #pragma unroll
-    for (int j = 0; j < 16; ++j) WT.whhT[j] = op(swimg::OP_WHHT, 16, wave, j);
+    for (int j = 0; j < 16; ++j) WT.whhT[j] = op(swimg::OP_WHHT, wave, j);
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-      w2t[0][j] = op(swimg::OP_W2T, 5, 2 * wave, j);
-      w2t[1][j] = op(swimg::OP_W2T, 5, 2 * wave + 1, j);
+      w2t[0][j] = op(swimg::OP_W2T, 2 * wave, j);
+      w2t[1][j] = op(swimg::OP_W2T, 2 * wave + 1, j);
     }
 #pragma unroll
-    for (int jj = 0; jj < 3; ++jj) w2p[jj] = op(swimg::OP_W2T, 5, 8 + t1p, hf ? 3 + min(jj, 1) : jj);
+    for (int jj = 0; jj < 3; ++jj) w2p[jj] = op(swimg::OP_W2T, 8 + t1p, hf ? 3 + min(jj, 1) : jj);
 #pragma unroll
-    for (int j = 0; j < 10; ++j) w1t[j] = op(swimg::OP_W1HT, 10, wave, j);
+    for (int j = 0; j < 10; ++j) w1t[j] = op(swimg::OP_W1HT, wave, j);
     // Wx^T slice of this wave's K-quarter as A operands: row c = ln (< 4 live), k = 64 wave + 16 j + 4 lg + r
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -747,22 +725,7 @@ __global__ __launch_bounds__(SW_THREADS) void dec_rollout_bwd_kernel(
     lstm_load_wT(WT, enc_w + swp::ENC_WHH, u0, ln, lg);
     lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
                    enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
-    {
-      const int t = threadIdx.x;
-      if (t < 160) {
-        const int cc = t / 80, k = t - cc * 80;
-        const float* w4 = dec_w + swp::DEC_W4 + cc * 40;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-#pragma unroll
-        for (int m = 0; m < 40; m += 4) {
-          v0 = fmaf(w4[m], dec_w[swp::DEC_W3 + m * 80 + k], v0);
-          v1 = fmaf(w4[m + 1], dec_w[swp::DEC_W3 + (m + 1) * 80 + k], v1);
-          v2 = fmaf(w4[m + 2], dec_w[swp::DEC_W3 + (m + 2) * 80 + k], v2);
-          v3 = fmaf(w4[m + 3], dec_w[swp::DEC_W3 + (m + 3) * 80 + k], v3);
-        }
-        w43_lds[t] = (v0 + v1) + (v2 + v3);
-      }
-    }
+    fc43_compose<false>(dec_w, w43_lds);      // (no b43: the backward pass has no use for it)
 #pragma unroll
     for (int j = 0; j < 5; ++j)
 #pragma unroll

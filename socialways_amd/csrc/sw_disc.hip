@@ -1025,8 +1025,8 @@ extern "C" int sw_disc_image_table(int Tp, int* tab) {
   for (int R = 0; R < 256; ++R)
     for (int C = 0; C < 64; ++C) {
       const int i = O.whh + R * 64 + C;
-      tab[2 * i] = swdimg::OP_WHH + ((((R >> 4) * 4 + (C >> 4)) * 64 + ((C & 15) >> 2) * 16 + (R & 15)) * 4) + (C & 3);
-      tab[2 * i + 1] = swdimg::OP_WHHT + ((((C >> 4) * 16 + (R >> 4)) * 64 + ((R & 15) >> 2) * 16 + (C & 15)) * 4) + (R & 3);
+      tab[2 * i] = sw_op_at(swdimg::OP_WHH, R, C);
+      tab[2 * i + 1] = sw_op_at(swdimg::OP_WHHT, C, R);
     }
   auto head = [&](int w_off, int M, int K, int img_off, int ld) {   // XT[c][r] = X[r][c]
     for (int r = 0; r < M; ++r)

@@ -203,7 +203,7 @@ __device__ __forceinline__ void disc_obs_operands(LstmW& W, const float* d_w, co
   for (int g = 0; g < 4; ++g) {
     if (dimg) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) W.whh[g][j] = ld4(dimg + swdimg::OP_WHH + ((((size_t)4 * g + wave) * 4 + j) * 64 + lane) * 4);
+      for (int j = 0; j < 4; ++j) W.whh[g][j] = SW_OP_LD(dimg, swdimg::OP_WHH, (size_t)4 * g + wave, j, lane);
     }
     W.wx[g] = d_w[O.wih + (g * 64 + u0 + ln) * 4 + lg];
     W.bias[g] = ld4(d_w + O.bih + g * 64 + u0 + 4 * lg) + ld4(d_w + O.bhh + g * 64 + u0 + 4 * lg);

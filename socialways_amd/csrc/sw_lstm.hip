@@ -25,17 +25,7 @@ __global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_kernel(
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   const int extra = (int)gridDim.x - tiles;
   if ((int)blockIdx.x < extra) {
-    const long long n4 = aux_n >> 2, stride = (long long)extra * SW_THREADS;
-    long long i = (long long)blockIdx.x * SW_THREADS + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-      const f32x4 v0 = ld4(aux_src + 4 * i), v1 = ld4(aux_src + 4 * (i + stride));
-      const f32x4 v2 = ld4(aux_src + 4 * (i + 2 * stride)), v3 = ld4(aux_src + 4 * (i + 3 * stride));
-      st4(aux_dst + 4 * i, v0);
-      st4(aux_dst + 4 * (i + stride), v1);
-      st4(aux_dst + 4 * (i + 2 * stride), v2);
-      st4(aux_dst + 4 * (i + 3 * stride), v3);
-    }
-    for (; i < n4; i += stride) st4(aux_dst + 4 * i, ld4(aux_src + 4 * i));
+    sw_z_pull<SW_THREADS, 4>(aux_src, aux_dst, aux_n, extra);
     return;
   }
   // h exchange between the waves: with ACT the whole saved row of a step is assembled in LDS (lstm_put_act_tile) and its
@@ -117,14 +107,7 @@ __global__ __launch_bounds__(512) void enc_lstm_fwd8_kernel(
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
   const int extra = (int)gridDim.x - tiles;
   if ((int)blockIdx.x < extra) {      // z's pull out of the pinned slot, as in enc_lstm_fwd_kernel
-    const long long n4 = aux_n >> 2, stride = (long long)extra * 512;
-    long long i = (long long)blockIdx.x * 512 + threadIdx.x;
-    for (; i + stride < n4; i += 2 * stride) {
-      const f32x4 v0 = ld4(aux_src + 4 * i), v1 = ld4(aux_src + 4 * (i + stride));
-      st4(aux_dst + 4 * i, v0);
-      st4(aux_dst + 4 * (i + stride), v1);
-    }
-    for (; i < n4; i += stride) st4(aux_dst + 4 * i, ld4(aux_src + 4 * i));
+    sw_z_pull<512, 2>(aux_src, aux_dst, aux_n, extra);
     return;
   }
   __shared__ __attribute__((aligned(16))) float hbuf[2][SW_TILE * SW_ALD];
@@ -137,7 +120,7 @@ __global__ __launch_bounds__(512) void enc_lstm_fwd8_kernel(
 #pragma unroll
   for (int tl = 0; tl < 2; ++tl) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) whh[tl][j] = ld4(gimg + swimg::OP_WHH8 + ((((size_t)wave * 2 + tl) * 4 + j) * 64 + lane) * 4);
+    for (int j = 0; j < 4; ++j) whh[tl][j] = SW_OP_LD(gimg, swimg::OP_WHH8, (size_t)wave * 2 + tl, j, lane);
     const int rowA = (2 * tl + ((ln & 3) >> 1)) * 64 + 8 * wave + 2 * (ln >> 2) + (ln & 1);   // A row of lane ln
     wx[tl] = gimg[swimg::WX + rowA * 4 + lg];
 #pragma unroll

@@ -90,7 +90,7 @@ __device__ __forceinline__ void lstm_load_img(LstmW& W, const float* __restrict_
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) W.whh[g][j] = ld4(gimg + swimg::OP_WHH + ((((size_t)4 * g + wave) * 4 + j) * 64 + lane) * 4);
+    for (int j = 0; j < 4; ++j) W.whh[g][j] = SW_OP_LD(gimg, swimg::OP_WHH, (size_t)4 * g + wave, j, lane);
     W.wx[g] = gimg[swimg::WX + (g * 64 + u0 + ln) * 4 + lg];
     W.bias[g] = ld4(gimg + swimg::BX + g * 64 + u0 + 4 * lg);
   }
@@ -255,12 +255,12 @@ __device__ __forceinline__ f32x4 lstm_dh_prev(const LstmWT& W, const float* dgro
   }
   return a0 + a1;
 }
-// W_hh^T from the operand-layout image at img + off (16 contiguous 1 KB loads per wave) or, without an image, from the
+// W_hh^T from its operand-layout image d of img (16 contiguous 1 KB loads per wave) or, without an image, from the
 // weights Whh (Whh == nullptr: the image is always there)
-__device__ __forceinline__ void lstm_load_whhT(LstmWT& W, const float* img, int off, const float* Whh, int wave, int lane) {
+__device__ __forceinline__ void lstm_load_whhT(LstmWT& W, const float* img, const OpImage d, const float* Whh, int wave, int lane) {
   if (img || !Whh) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) W.whhT[j] = ld4(img + off + (((size_t)wave * 16 + j) * 64 + lane) * 4);
+    for (int j = 0; j < 16; ++j) W.whhT[j] = SW_OP_LD(img, d, (size_t)wave, j, lane);
   } else {
     lstm_load_wT(W, Whh, wave * 16, lane & 15, lane >> 4);
   }

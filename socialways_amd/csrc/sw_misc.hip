@@ -823,30 +823,8 @@ __device__ __forceinline__ void gen_images_block(const float* __restrict__ enc_w
                    img + swimg::WX, img + swimg::BX);
     return;
   }
-  if (blk == 1) {          // fc4 . fc3: same partial-sum order as the kernels' own fallback code
-    const int t = threadIdx.x;
-    if (t < 160) {
-      const int c = t / 80, k = t - c * 80;
-      const float* w4 = dec_w + DEC_W4 + c * 40;
-      float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-#pragma unroll
-      for (int m = 0; m < 40; m += 4) {
-        v0 = fmaf(w4[m], dec_w[DEC_W3 + m * 80 + k], v0);
-        v1 = fmaf(w4[m + 1], dec_w[DEC_W3 + (m + 1) * 80 + k], v1);
-        v2 = fmaf(w4[m + 2], dec_w[DEC_W3 + (m + 2) * 80 + k], v2);
-        v3 = fmaf(w4[m + 3], dec_w[DEC_W3 + (m + 3) * 80 + k], v3);
-      }
-      img[swimg::W43 + c * 80 + k] = (v0 + v1) + (v2 + v3);
-    } else if (t < 162) {
-      const int c = t - 160;
-      float v = dec_w[DEC_B4 + c];
-#pragma unroll
-      for (int m = 0; m < 40; m += 4) {   // the order dec_rollout_fwd uses (bit-identical b43)
-        const f32x4 w = ld4(dec_w + DEC_W4 + c * 40 + m), bb = ld4(dec_w + DEC_B3 + m);
-        v = fmaf(w[0], bb[0], fmaf(w[1], bb[1], fmaf(w[2], bb[2], fmaf(w[3], bb[3], v))));
-      }
-      img[swimg::W43 + 160 + c] = v;
-    }
+  if (blk == 1) {          // fc4 . fc3 and its bias: the function the decode kernels call when they run without images
+    fc43_compose<true>(dec_w, img + swimg::W43);
     return;
   }
   const int nth = (SW_IMG_BLOCKS - 2) * 256, tid = (blk - 2) * 256 + threadIdx.x;
@@ -861,38 +839,44 @@ __device__ __forceinline__ void gen_images_block(const float* __restrict__ enc_w
                                            : dec_w + DEC_W4 + (o - swimg::RAW_W4);
     st4(img + o, ld4(src));
   }
-  // MFMA A-operand images (swimg::OP_*) of W[rows][c0 + K] and of transposes M = W^T (M[m][k] = W[k][m])
-  auto op_image = [&](int dst0, const float* W, int ldw, int c0, int KJ, int ntile) {
-    for (int f = tid; f < ntile * KJ * 64; f += nth) {
+  // MFMA A-operand images: the descriptors of swimg (sw_common.h) with their sources - columns c0 .. of the matrix W at
+  // `off` of a packed buffer (row stride ldw), or of its transpose M = W^T (M[m][k] = W[k][m])
+  enum { ENC, DEC, EMB, ATT };
+  struct OpSource { OpImage img; int buf, off, ldw, c0; bool transposed; };
+  constexpr OpSource SOURCES[] = {
+      {swimg::OP_WHH, ENC, ENC_WHH, 64, 0, false},  {swimg::OP_W1H, DEC, DEC_W1, 160, 0, false},
+      {swimg::OP_W1SZ, DEC, DEC_W1, 160, 64, false}, {swimg::OP_W2, DEC, DEC_W2, 160, 0, false},
+      {swimg::OP_WHHT, ENC, ENC_WHH, 64, 0, true},  {swimg::OP_W2T, DEC, DEC_W2, 160, 0, true},
+      {swimg::OP_W1HT, DEC, DEC_W1, 160, 0, true},
+      // the social block's, when its weights are given
+      {swimg::OP_E1, EMB, EMB_W1, 32, 0, false},    {swimg::OP_E2, EMB, EMB_W2, 64, 0, false},
+      {swimg::OP_E1T, EMB, EMB_W1, 32, 0, true},    {swimg::OP_E2T, EMB, EMB_W2, 64, 0, true},
+      {swimg::OP_ATT_T, ATT, ATT_W, 64, 0, true}};
+  auto fill = [&](const OpSource s) {
+    const float* W = (s.buf == ENC ? enc_w : s.buf == DEC ? dec_w : s.buf == EMB ? emb_w : att_w) + s.off;
+    const int KJ = s.img.kj, ldw = s.ldw;
+    for (int f = tid; f < s.img.size() / 4; f += nth) {
       const int t = f / (KJ * 64), rem = f - t * (KJ * 64), j = rem >> 6, l = rem & 63;
-      st4(img + dst0 + 4 * (size_t)f, ld4(W + (size_t)(16 * t + (l & 15)) * ldw + c0 + 16 * j + 4 * (l >> 4)));
+      if (!s.transposed) {
+        st4(img + s.img.base + 4 * (size_t)f, ld4(W + (size_t)(16 * t + (l & 15)) * ldw + s.c0 + 16 * j + 4 * (l >> 4)));
+      } else {
+        const float* col = W + (size_t)(16 * j + 4 * (l >> 4)) * ldw + 16 * t + (l & 15);
+        st4(img + s.img.base + 4 * (size_t)f, f32x4{col[0], col[ldw], col[2 * ldw], col[3 * ldw]});
+      }
     }
   };
-  auto op_image_T = [&](int dst0, const float* W, int ldw, int KJ, int ntile) {
-    for (int f = tid; f < ntile * KJ * 64; f += nth) {
-      const int t = f / (KJ * 64), rem = f - t * (KJ * 64), j = rem >> 6, l = rem & 63;
-      const float* col = W + (size_t)(16 * j + 4 * (l >> 4)) * ldw + 16 * t + (l & 15);
-      st4(img + dst0 + 4 * (size_t)f, f32x4{col[0], col[ldw], col[2 * ldw], col[3 * ldw]});
-    }
-  };
-  op_image(swimg::OP_WHH, enc_w + ENC_WHH, 64, 0, 4, 16);
-  op_image(swimg::OP_W1H, dec_w + DEC_W1, 160, 0, 4, 10);
-  op_image(swimg::OP_W1SZ, dec_w + DEC_W1, 160, 64, 6, 10);
-  op_image(swimg::OP_W2, dec_w + DEC_W2, 160, 0, 10, 5);
-  op_image_T(swimg::OP_WHHT, enc_w + ENC_WHH, 64, 16, 4);
-  op_image_T(swimg::OP_W2T, dec_w + DEC_W2, 160, 5, 10);
-  op_image_T(swimg::OP_W1HT, dec_w + DEC_W1, 160, 10, 4);
-  for (int f = tid; f < 8 * 2 * 4 * 64; f += nth) {      // OP_WHH8 (sw_common.h): the 8-wave row assignment of W_hh
+#pragma unroll
+  for (const OpSource s : SOURCES)
+    if (s.buf < EMB) fill(s);
+  for (int f = tid; f < swimg::OP_WHH8.size() / 4; f += nth) {      // OP_WHH8 (sw_common.h): the 8-wave row assignment of W_hh
     const int l = f & 63, j = (f >> 6) & 3, tile = (f >> 8) & 1, w = f >> 9, m = l & 15;
     const int row = (2 * tile + ((m & 3) >> 1)) * 64 + 8 * w + 2 * (m >> 2) + (m & 1);
-    st4(img + swimg::OP_WHH8 + 4 * (size_t)f, ld4(enc_w + ENC_WHH + (size_t)row * 64 + 16 * j + 4 * (l >> 4)));
+    st4(img + swimg::OP_WHH8.base + 4 * (size_t)f, ld4(enc_w + ENC_WHH + (size_t)row * 64 + 16 * j + 4 * (l >> 4)));
   }
   if (emb_w) {
-    op_image(swimg::OP_E1, emb_w + EMB_W1, 32, 0, 2, 4);
-    op_image(swimg::OP_E2, emb_w + EMB_W2, 64, 0, 4, 4);
-    op_image_T(swimg::OP_E1T, emb_w + EMB_W1, 32, 4, 2);
-    op_image_T(swimg::OP_E2T, emb_w + EMB_W2, 64, 4, 4);
-    op_image_T(swimg::OP_ATT_T, att_w + ATT_W, 64, 4, 4);
+#pragma unroll
+    for (const OpSource s : SOURCES)
+      if (s.buf >= EMB) fill(s);
   }
 }
 __global__ __launch_bounds__(256) void gen_images_kernel(const float* __restrict__ enc_w, const float* __restrict__ dec_w,
@@ -936,37 +920,61 @@ extern "C" int sw_gen_images(const float* enc_w, const float* dec_w, const float
 // The kernel is a node of the captured graph with FIXED arguments; what changes per step travels through
 // the slot.  It copies the tracks into the graph's static buffers, forms the real future as (p, v) rows
 // (get_traj_4d, train.py:135-137) and pulls the scalars + z over PCIe.
-__global__ __launch_bounds__(256) void stage_step_kernel(const float* __restrict__ slot, int B, int To, int Tp,
-                                                          float* __restrict__ obsv_dst, float* __restrict__ pred_dst,
-                                                          float* __restrict__ pred4_dst, float* __restrict__ targets_dst,
-                                                          float* __restrict__ z_dst, float* __restrict__ steps_dst,
-                                                          int n_d_updates, const float* __restrict__ enc_w,
-                                                          const float* __restrict__ dec_w, const float* __restrict__ emb_w,
-                                                          const float* __restrict__ att_w, float* __restrict__ img,
-                                                          int img_blocks, const float* __restrict__ d_w,
-                                                          float* __restrict__ d_img, const int* __restrict__ d_tab, int d_n,
-                                                          int dimg_blocks, int z_device) {
+struct StageArgs {
+  const float* slot;
+  int B, To, Tp;
+  float *obsv_dst, *pred_dst, *pred4_dst, *targets_dst, *z_dst, *steps_dst;
+  int n_d_updates;
+  const float *enc_w, *dec_w, *emb_w, *att_w;   // the generator's weights; its image buffer (sw_gen_images) and workgroups
+  float* img;
+  int img_blocks;
+  const float* d_w;                             // the discriminator's d_n packed weights; image buffer, table (sw_disc_images)
+  float* d_img;                                 // and workgroups
+  const int* d_tab;
+  int d_n, dimg_blocks, z_device;
+  int* obs_len_dst;                             // RAGGED only
+};
+// RAGGED: the step over ragged observation histories (sw_stage_step_ragged), with a slot layout of its own
+// (SW_STAGE_HEADER_RAGGED = 12 words in front of z):
+//   [0..7] as above   [8,9] device pointer of z when z_device = 1   [10,11] device pointer of this step's obs_len (B int32)
+//   [12 ..] z (B*32) when z_device = 0 - 48 bytes in: the 16-byte alignment of the ld4 reads holds
+// It writes what the dense form writes with z_dst given (the ragged encoder launch pulls no z: this launch fills z in
+// both z modes) and obs_len_dst[i] = clamp(obs_len[i], 2, To), the static int32 buffer the graph's ragged kernels read.
+template <bool RAGGED>
+__device__ __forceinline__ void stage_step_body(const StageArgs& a) {
   // the last img_blocks workgroups derive the generator's weight images of this step (sw_gen_images), the dimg_blocks
   // in front of them scatter the discriminator's weights into theirs (sw_disc_images)
-  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks) {
-    gen_images_block(enc_w, dec_w, emb_w, att_w, img, (int)blockIdx.x - ((int)gridDim.x - img_blocks));
+  const int copiers = (int)gridDim.x - a.img_blocks - a.dimg_blocks;
+  if ((int)blockIdx.x >= copiers + a.dimg_blocks) {
+    gen_images_block(a.enc_w, a.dec_w, a.emb_w, a.att_w, a.img, (int)blockIdx.x - copiers - a.dimg_blocks);
     return;
   }
-  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks - dimg_blocks) {
-    disc_images_scatter(d_w, d_img, d_tab, d_n, (int)blockIdx.x - ((int)gridDim.x - img_blocks - dimg_blocks), dimg_blocks);
+  if ((int)blockIdx.x >= copiers) {
+    disc_images_scatter(a.d_w, a.d_img, a.d_tab, a.d_n, (int)blockIdx.x - copiers, a.dimg_blocks);
     return;
   }
+  const int B = a.B, To = a.To, Tp = a.Tp;
+  const float* __restrict__ slot = a.slot;
+  float* __restrict__ z_dst = a.z_dst;
+  float* __restrict__ obsv_dst = a.obsv_dst;
+  float* __restrict__ pred_dst = a.pred_dst;
+  float* __restrict__ pred4_dst = a.pred4_dst;
   const unsigned long long* ptrs = reinterpret_cast<const unsigned long long*>(slot);
-  const float* obsv = reinterpret_cast<const float*>(ptrs[0]);
-  const float* pred = reinterpret_cast<const float*>(ptrs[1]);
-  const int gid = blockIdx.x * 256 + threadIdx.x, gsz = ((int)gridDim.x - img_blocks - dimg_blocks) * 256;
+  const float* __restrict__ obsv = reinterpret_cast<const float*>(ptrs[0]);
+  const float* __restrict__ pred = reinterpret_cast<const float*>(ptrs[1]);
+  const int gid = blockIdx.x * 256 + threadIdx.x, gsz = copiers * 256;
   if (z_dst) {
-    const float* zs = z_device ? reinterpret_cast<const float*>(ptrs[4]) : slot + 8;
+    const float* __restrict__ zs = a.z_device ? reinterpret_cast<const float*>(ptrs[4]) : slot + (RAGGED ? SW_STAGE_HEADER_RAGGED : 8);
     for (int i = gid; i < B * SW_Z / 4; i += gsz) st4(z_dst + 4 * (size_t)i, ld4(zs + 4 * (size_t)i));
   }
-  if (gid < 2) targets_dst[gid] = slot[4 + gid];
+  if constexpr (RAGGED) {
+    const int* obs_len = reinterpret_cast<const int*>(ptrs[5]);
+    for (int i = gid; i < B; i += gsz) a.obs_len_dst[i] = min(max(obs_len[i], 2), To);
+  }
+  if (gid < 2) a.targets_dst[gid] = slot[4 + gid];
   // 1-based Adam step indices of this training step's updates: D update u -> [u], the G update -> [n_d_updates]
-  if (steps_dst && gid <= n_d_updates) steps_dst[gid] = gid < n_d_updates ? slot[6] + 1.0f + (float)gid : slot[7] + 1.0f;
+  if (a.steps_dst && gid <= a.n_d_updates)
+    a.steps_dst[gid] = gid < a.n_d_updates ? slot[6] + 1.0f + (float)gid : slot[7] + 1.0f;
   for (int i = gid; i < B * To; i += gsz)
     *reinterpret_cast<float2*>(obsv_dst + 2 * (size_t)i) = *reinterpret_cast<const float2*>(obsv + 2 * (size_t)i);
   for (int k = gid; k < B * Tp; k += gsz) {
@@ -977,94 +985,46 @@ __global__ __launch_bounds__(256) void stage_step_kernel(const float* __restrict
     st4(pred4_dst + 4 * (size_t)k, f32x4{p.x, p.y, p.x - q.x, p.y - q.y});
   }
 }
+// (two kernels: profiles and bench.py's per-kernel table key on the names)
+__global__ __launch_bounds__(256) void stage_step_kernel(StageArgs a) { stage_step_body<false>(a); }
+__global__ __launch_bounds__(256) void stage_step_ragged_kernel(StageArgs a) { stage_step_body<true>(a); }
 #define SW_DIMG_BLOCKS 16
+static int stage_step_launch(bool ragged, StageArgs a, void* stream) {
+  if (ragged ? (!a.obs_len_dst || !a.z_dst) : (a.z_device && !a.z_dst)) return SW_EARG;
+  if (!a.slot || !a.obsv_dst || !a.pred_dst || !a.pred4_dst || !a.targets_dst || a.B < 1 || a.To < 2 || a.Tp < 1 ||
+      a.n_d_updates < 0 || a.n_d_updates > 254)
+    return SW_EARG;
+  if (a.img && (!a.enc_w || !a.dec_w || ((a.emb_w != nullptr) != (a.att_w != nullptr)))) return SW_EARG;
+  if (a.d_img && (!a.d_w || !a.d_tab || a.Tp > 64)) return SW_EARG;
+  int n = a.z_dst ? a.B * SW_Z / 4 : a.B * (a.To > a.Tp ? a.To : a.Tp);
+  int blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  a.img_blocks = a.img ? SW_IMG_BLOCKS : 0;
+  a.dimg_blocks = a.d_img ? SW_DIMG_BLOCKS : 0;
+  a.d_n = a.d_img ? swp::disc(a.Tp).n : 0;
+  a.z_device = a.z_device ? 1 : 0;
+  const dim3 grid(blocks + a.img_blocks + a.dimg_blocks);
+  if (ragged) SW_LAUNCH(stage_step_ragged_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else SW_LAUNCH(stage_step_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  SW_CHECK_LAUNCH(ragged ? "stage_step_ragged_kernel" : "stage_step_kernel");
+  if (a.img) gen_images_register(a.enc_w, a.dec_w, a.emb_w, a.att_w, a.img);
+  if (a.d_img) sw_disc_images_register(a.d_w, a.d_img, a.d_tab, a.Tp);
+  return SW_OK;
+}
 extern "C" int sw_stage_step_zdev(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst,
                                   float* pred4_dst, float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates,
                                   const float* enc_w, const float* dec_w, const float* emb_w, const float* att_w, float* img,
                                   const float* d_w, float* d_img, const int* d_tab, int z_device, void* stream) {
-  if (z_device && !z_dst) return SW_EARG;
-  if (!slot || !obsv_dst || !pred_dst || !pred4_dst || !targets_dst || B < 1 || To < 2 || Tp < 1 ||
-      n_d_updates < 0 || n_d_updates > 254)
-    return SW_EARG;
-  if (img && (!enc_w || !dec_w || ((emb_w != nullptr) != (att_w != nullptr)))) return SW_EARG;
-  if (d_img && (!d_w || !d_tab || Tp > 64)) return SW_EARG;
-  int n = z_dst ? B * SW_Z / 4 : B * (To > Tp ? To : Tp);
-  int blocks = (n + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  const int ib = img ? SW_IMG_BLOCKS : 0, db = d_img ? SW_DIMG_BLOCKS : 0;
-  SW_LAUNCH(stage_step_kernel, dim3(blocks + ib + db), dim3(256), 0, (hipStream_t)stream, slot, B, To, Tp, obsv_dst,
-                     pred_dst, pred4_dst, targets_dst, z_dst, steps_dst, n_d_updates, enc_w, dec_w, emb_w, att_w, img, ib,
-                     d_w, d_img, d_tab, d_img ? swp::disc(Tp).n : 0, db, z_device ? 1 : 0);
-  SW_CHECK_LAUNCH("stage_step_kernel");
-  if (img) gen_images_register(enc_w, dec_w, emb_w, att_w, img);
-  if (d_img) sw_disc_images_register(d_w, d_img, d_tab, Tp);
-  return SW_OK;
-}
-// ---- ... of a captured step over RAGGED observation histories (sw_stage_step_ragged) -----------------
-// A sibling of stage_step_kernel with a slot layout of its own (SW_STAGE_HEADER_RAGGED = 12 words in front of z):
-//   [0..7] as above   [8,9] device pointer of z when z_device = 1   [10,11] device pointer of this step's obs_len (B int32)
-//   [12 ..] z (B*32) when z_device = 0 - 48 bytes in: the 16-byte alignment of the ld4 reads holds
-// It writes what stage_step_kernel writes with z_dst given (the ragged encoder launch pulls no z: this launch fills z in
-// both z modes) and obs_len_dst[i] = clamp(obs_len[i], 2, To), the static int32 buffer the graph's ragged kernels read.
-__global__ __launch_bounds__(256) void stage_step_ragged_kernel(const float* __restrict__ slot, int B, int To, int Tp,
-                                                                 float* __restrict__ obsv_dst, float* __restrict__ pred_dst,
-                                                                 float* __restrict__ pred4_dst, float* __restrict__ targets_dst,
-                                                                 float* __restrict__ z_dst, float* __restrict__ steps_dst,
-                                                                 int n_d_updates, const float* __restrict__ enc_w,
-                                                                 const float* __restrict__ dec_w, const float* __restrict__ emb_w,
-                                                                 const float* __restrict__ att_w, float* __restrict__ img,
-                                                                 int img_blocks, const float* __restrict__ d_w,
-                                                                 float* __restrict__ d_img, const int* __restrict__ d_tab, int d_n,
-                                                                 int dimg_blocks, int z_device, int* __restrict__ obs_len_dst) {
-  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks) {
-    gen_images_block(enc_w, dec_w, emb_w, att_w, img, (int)blockIdx.x - ((int)gridDim.x - img_blocks));
-    return;
-  }
-  if ((int)blockIdx.x >= (int)gridDim.x - img_blocks - dimg_blocks) {
-    disc_images_scatter(d_w, d_img, d_tab, d_n, (int)blockIdx.x - ((int)gridDim.x - img_blocks - dimg_blocks), dimg_blocks);
-    return;
-  }
-  const unsigned long long* ptrs = reinterpret_cast<const unsigned long long*>(slot);
-  const float* obsv = reinterpret_cast<const float*>(ptrs[0]);
-  const float* pred = reinterpret_cast<const float*>(ptrs[1]);
-  const int* obs_len = reinterpret_cast<const int*>(ptrs[5]);
-  const int gid = blockIdx.x * 256 + threadIdx.x, gsz = ((int)gridDim.x - img_blocks - dimg_blocks) * 256;
-  const float* zs = z_device ? reinterpret_cast<const float*>(ptrs[4]) : slot + SW_STAGE_HEADER_RAGGED;
-  for (int i = gid; i < B * SW_Z / 4; i += gsz) st4(z_dst + 4 * (size_t)i, ld4(zs + 4 * (size_t)i));
-  for (int i = gid; i < B; i += gsz) obs_len_dst[i] = min(max(obs_len[i], 2), To);
-  if (gid < 2) targets_dst[gid] = slot[4 + gid];
-  if (steps_dst && gid <= n_d_updates) steps_dst[gid] = gid < n_d_updates ? slot[6] + 1.0f + (float)gid : slot[7] + 1.0f;
-  for (int i = gid; i < B * To; i += gsz)
-    *reinterpret_cast<float2*>(obsv_dst + 2 * (size_t)i) = *reinterpret_cast<const float2*>(obsv + 2 * (size_t)i);
-  for (int k = gid; k < B * Tp; k += gsz) {
-    const int b = k / Tp, t = k - b * Tp;
-    const float2 p = *reinterpret_cast<const float2*>(pred + 2 * (size_t)k);
-    const float2 q = *reinterpret_cast<const float2*>(t == 0 ? obsv + ((size_t)b * To + To - 1) * 2 : pred + 2 * (size_t)k - 2);
-    *reinterpret_cast<float2*>(pred_dst + 2 * (size_t)k) = p;
-    st4(pred4_dst + 4 * (size_t)k, f32x4{p.x, p.y, p.x - q.x, p.y - q.y});
-  }
+  return stage_step_launch(false, StageArgs{slot, B, To, Tp, obsv_dst, pred_dst, pred4_dst, targets_dst, z_dst, steps_dst, n_d_updates,
+                                            enc_w, dec_w, emb_w, att_w, img, 0, d_w, d_img, d_tab, 0, 0, z_device, nullptr}, stream);
 }
 extern "C" int sw_stage_step_ragged(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst,
                                     float* pred4_dst, float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates,
                                     const float* enc_w, const float* dec_w, const float* emb_w, const float* att_w, float* img,
                                     const float* d_w, float* d_img, const int* d_tab, int z_device, int* obs_len_dst,
                                     void* stream) {
-  if (!obs_len_dst || !z_dst) return SW_EARG;
-  if (!slot || !obsv_dst || !pred_dst || !pred4_dst || !targets_dst || B < 1 || To < 2 || Tp < 1 ||
-      n_d_updates < 0 || n_d_updates > 254)
-    return SW_EARG;
-  if (img && (!enc_w || !dec_w || ((emb_w != nullptr) != (att_w != nullptr)))) return SW_EARG;
-  if (d_img && (!d_w || !d_tab || Tp > 64)) return SW_EARG;
-  int blocks = (B * SW_Z / 4 + 255) / 256;      // the grid rule of sw_stage_step_zdev with z_dst
-  if (blocks > 1024) blocks = 1024;
-  const int ib = img ? SW_IMG_BLOCKS : 0, db = d_img ? SW_DIMG_BLOCKS : 0;
-  SW_LAUNCH(stage_step_ragged_kernel, dim3(blocks + ib + db), dim3(256), 0, (hipStream_t)stream, slot, B, To, Tp, obsv_dst,
-            pred_dst, pred4_dst, targets_dst, z_dst, steps_dst, n_d_updates, enc_w, dec_w, emb_w, att_w, img, ib,
-            d_w, d_img, d_tab, d_img ? swp::disc(Tp).n : 0, db, z_device ? 1 : 0, obs_len_dst);
-  SW_CHECK_LAUNCH("stage_step_ragged_kernel");
-  if (img) gen_images_register(enc_w, dec_w, emb_w, att_w, img);
-  if (d_img) sw_disc_images_register(d_w, d_img, d_tab, Tp);
-  return SW_OK;
+  return stage_step_launch(true, StageArgs{slot, B, To, Tp, obsv_dst, pred_dst, pred4_dst, targets_dst, z_dst, steps_dst, n_d_updates,
+                                           enc_w, dec_w, emb_w, att_w, img, 0, d_w, d_img, d_tab, 0, 0, z_device, obs_len_dst}, stream);
 }
 extern "C" int sw_stage_step_img(const float* slot, int B, int To, int Tp, float* obsv_dst, float* pred_dst,
                                  float* pred4_dst, float* targets_dst, float* z_dst, float* steps_dst, int n_d_updates,

@@ -66,7 +66,7 @@ __device__ __forceinline__ void load_pair_w1_img(PairW1& W, const float* __restr
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) W.w1[mt][j] = ld4(img + swimg::OP_E1 + ((mt * 2 + j) * 64 + lane) * 4);
+    for (int j = 0; j < 2; ++j) W.w1[mt][j] = SW_OP_LD(img, swimg::OP_E1, mt, j, lane);
   }
 }
 
@@ -468,17 +468,7 @@ __global__ __launch_bounds__(SW_THREADS) void social_pool_fwd_kernel(
   // out of its pinned host slot here - the decode launch behind is the first consumer; see enc_lstm_fwd_kernel)
   const int extra = (int)gridDim.x - S;
   if ((int)blockIdx.x < extra) {
-    const long long n4 = aux_n >> 2, stride = (long long)extra * SW_THREADS;
-    long long i = (long long)blockIdx.x * SW_THREADS + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-      const f32x4 v0 = ld4(aux_src + 4 * i), v1 = ld4(aux_src + 4 * (i + stride));
-      const f32x4 v2 = ld4(aux_src + 4 * (i + 2 * stride)), v3 = ld4(aux_src + 4 * (i + 3 * stride));
-      st4(aux_dst + 4 * i, v0);
-      st4(aux_dst + 4 * (i + stride), v1);
-      st4(aux_dst + 4 * (i + 2 * stride), v2);
-      st4(aux_dst + 4 * (i + 3 * stride), v3);
-    }
-    for (; i < n4; i += stride) st4(aux_dst + 4 * i, ld4(aux_src + 4 * i));
+    sw_z_pull<SW_THREADS, 4>(aux_src, aux_dst, aux_n, extra);
     return;
   }
   const int scene = (int)blockIdx.x - extra;
@@ -999,13 +989,13 @@ __device__ __forceinline__ f32x4 social_bwd_rows_scene(
     load_pair_w1_img(W, simg, lane);
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo) {
-      w1T[0][mo] = ld4(simg + swimg::OP_E1T + ((0 * 4 + mo) * 64 + lane) * 4);
-      w1T[1][mo] = ld4(simg + swimg::OP_E1T + ((1 * 4 + mo) * 64 + lane) * 4);
-      w3t[mo] = ld4(simg + swimg::OP_E2T + ((wave * 4 + mo) * 64 + lane) * 4);
-      w2own[mo] = ld4(simg + swimg::OP_E2 + ((wave * 4 + mo) * 64 + lane) * 4);
+      w1T[0][mo] = SW_OP_LD(simg, swimg::OP_E1T, 0, mo, lane);
+      w1T[1][mo] = SW_OP_LD(simg, swimg::OP_E1T, 1, mo, lane);
+      w3t[mo] = SW_OP_LD(simg, swimg::OP_E2T, wave, mo, lane);
+      w2own[mo] = SW_OP_LD(simg, swimg::OP_E2, wave, mo, lane);
     }
 #pragma unroll
-    for (int kt = 0; kt < 4; ++kt) wT[kt] = ld4(simg + swimg::OP_ATT_T + ((wave * 4 + kt) * 64 + lane) * 4);
+    for (int kt = 0; kt < 4; ++kt) wT[kt] = SW_OP_LD(simg, swimg::OP_ATT_T, wave, kt, lane);
   } else {
     load_pair_w1(W, emb_w, ln, lg);
     load_w1T(w1T, emb_w, ln, lg);
