@@ -87,8 +87,8 @@ int sw_enc_lstm_fwd_aux(const float* x, int x_mode, const float* enc_w, const fl
  * with and without registered generator images (sw_gen_images).  The padding is never read: no output bit depends on
  * it, NaN / Inf included.  An obs_len outside its range is clamped into it on the device (no out-of-bounds read, no
  * host sync).  The step loop keeps the shape of the dense kernel - every lane computes every step and selects the zero
- * state in front of its start, no conditional memory operation, one uniform barrier per step - in a kernel of its own:
- * the kernels sw_enc_lstm_fwd* launch are unchanged.
+ * state in front of its start, no conditional memory operation, one uniform barrier per step: it is the RAGGED instance
+ * of the kernel sw_enc_lstm_fwd launches (one loop, csrc/sw_lstm_dev.h lstm_obs_loop), on a grid of tiles only.
  * SW_EARG before any device call: x, enc_w, hT or cT NULL, B < 0, T < 1, x_mode not 0 / 1, T < 2 with x_mode 0.
  * B == 0: SW_OK without a launch.                                                                                       */
 int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const int* obs_len /*[B] int32 or NULL = all T*/,
@@ -104,7 +104,7 @@ int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const
  * front of s_a (i = g = o = 0, c_t = c_{t-1} = 0) and takes c_{s-1} = h_{s-1} = 0 as the initial state at s_a, and the
  * weight-gradient sums (sw_gen_wgrad*) get zero dgates against zero inputs there.  The step loop keeps the shape of the
  * dense kernel (every lane computes every step, unconditional stores of selected values, one barrier per step, the saved
- * row assembled in the LDS row tile) in a kernel of its own: the kernels sw_enc_lstm_fwd* launch are unchanged.  No
+ * row assembled in the LDS row tile): the RAGGED instance of the kernel sw_enc_lstm_fwd(..., act, x4s) launches.  No
  * auxiliary copy: the caller moves z itself.
  * SW_EARG before any device call: x, enc_w, hT, cT, act or x4s NULL, B < 0, T < 1, x_mode not 0 / 1, T < 2 with x_mode 0.
  * B == 0: SW_OK without a launch.                                                                                       */

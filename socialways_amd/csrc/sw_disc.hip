@@ -284,11 +284,11 @@ __host__ __device__ inline UpdLds upd_lds(int Tp) {
 }  // namespace
 
 // RAGGED (sw_disc_update_ragged): the observation pass starts row b at step s = To - obs_len[b] (clamped, obs_start) and
-// keeps the zero state in front of it by a SELECT on the cell's result - the values lstm_obs_loop_ragged<0, SAVE_ROWS> leaves
+// keeps the zero state in front of it by a SELECT on the cell's result - the values lstm_obs_loop<0, SAVE_ROWS, true> leaves
 // (sw_lstm_dev.h), its products per step included: the recurrent product stays on step 0.  Zero gates with zero c_t, c_{t-1}
 // give zero gate gradients and dc_{t-1} = 0, so everything behind the observation pass - heads, loss gradients, BPTT - is
-// the dense code.  A template parameter with obs_len as the LAST argument, as disc_score_kernel: the dense instance keeps
-// the dense loop and its code.  There is no precomputed observation pass for ragged rows (obs_pre = 0).
+// the dense code.  A template parameter with obs_len as the LAST argument, as disc_score_kernel.  There is no precomputed
+// observation pass for ragged rows (obs_pre = 0).
 template <bool RAGGED>
 __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     const float* __restrict__ obsv, int To, const float* __restrict__ pred_a, const float* __restrict__ pred_b,
@@ -340,51 +340,36 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
     __builtin_assume(obs_len != nullptr);
     s0 = obs_start(obs_len, b, To, 0);
   }
-  if (RAGGED && reg8) {
-    // the unrolled loop below for a start step per lane: every lane computes every step (W_hh h on step 0 too: exact
-    // zeros, the products of lstm_obs_loop_ragged) and selects the zero state in front of its start, so sg[t] / sc[t] and
-    // the h row / input that go to dsave hold SELECTED zeros there.  The stores stay unconditional.
+  if (reg8) {
+    // lstm_obs_loop (sw_lstm_dev.h, with what it keeps) unrolled, the steps' gates and cell states left in sg / sc; only the
+    // h row and the input go to dsave.  Dense: step 0 from h = 0 without recurrent products.  RAGGED: every lane computes
+    // every step (W_hh h on step 0 too: exact zeros) and selects the zero state in front of its start, so sg[t] / sc[t] and
+    // what goes to dsave hold SELECTED zeros there.  The stores stay unconditional.
     float xa, xq;
-    obs_x4_load_from(obsv, b, 0, s0, 8, lg, xa, xq);
+    if constexpr (RAGGED) obs_x4_load_from(obsv, b, 0, s0, 8, lg, xa, xq);
+    else obs_x4_load(obsv, b, 0, 8, lg, xa, xq);
     asm volatile("" : "+v"(xa), "+v"(xq));
     float* hrow_g = dsave + ds.act + (size_t)b * 384 + 320 + u0 + 4 * lg;
     float* xrow = dsave + ds.x4s + (size_t)b * 4 + lg;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      const float xb = xa - (lg >= 2 ? xq : 0.f);
-      obs_x4_load_from(obsv, b, t + 1 < 8 ? t + 1 : 7, s0, 8, lg, xa, xq);
+      float xb = xa - (lg >= 2 ? xq : 0.f);
+      if constexpr (RAGGED) obs_x4_load_from(obsv, b, t + 1 < 8 ? t + 1 : 7, s0, 8, lg, xa, xq);
+      else obs_x4_load(obsv, b, t + 1 < 8 ? t + 1 : 7, 8, lg, xa, xq);
       const float* hrow = &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg];
-      lstm_cell(W, xb, hrow, sg[t], c, h);
-      const bool on = t >= s0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        c[r] = on ? c[r] : 0.f;
-        h[r] = on ? h[r] : 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) sg[t][g][r] = on ? sg[t][g][r] : 0.f;
-      }
-      sc[t] = c;
-      st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
-      st4g(hrow_g, h);
-      *xrow = on ? xb : 0.f;
-      hrow_g += (size_t)B * 384;
-      xrow += (size_t)B * 4;
-      sw_barrier();
-      asm volatile("" : "+v"(xa), "+v"(xq));
-    }
-  } else if (reg8) {
-    float xa, xq;
-    obs_x4_load(obsv, b, 0, 8, lg, xa, xq);
-    asm volatile("" : "+v"(xa), "+v"(xq));
-    float* hrow_g = dsave + ds.act + (size_t)b * 384 + 320 + u0 + 4 * lg;
-    float* xrow = dsave + ds.x4s + (size_t)b * 4 + lg;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float xb = xa - (lg >= 2 ? xq : 0.f);
-      obs_x4_load(obsv, b, t + 1 < 8 ? t + 1 : 7, 8, lg, xa, xq);
-      const float* hrow = &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg];
-      if (t == 0) lstm_cell<false>(W, xb, hrow, sg[t], c, h);     // from h = 0: no recurrent products (unrolled: no branch)
+      if (!RAGGED && t == 0) lstm_cell<false>(W, xb, hrow, sg[t], c, h);   // (unrolled: no branch)
       else lstm_cell(W, xb, hrow, sg[t], c, h);
+      if constexpr (RAGGED) {
+        const bool on = t >= s0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          c[r] = on ? c[r] : 0.f;
+          h[r] = on ? h[r] : 0.f;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) sg[t][g][r] = on ? sg[t][g][r] : 0.f;
+        }
+        xb = on ? xb : 0.f;
+      }
       sc[t] = c;
       st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
       st4g(hrow_g, h);
@@ -395,8 +380,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_update_kernel(
       asm volatile("" : "+v"(xa), "+v"(xq));
     }
   } else if (!obs_pre) {
-    if constexpr (RAGGED) lstm_obs_loop_ragged<0, SAVE_ROWS, 1>(W, hbuf, obsv, To, b, s0, c, h, dsave + ds.act, dsave + ds.x4s, B);
-    else lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, dsave + ds.act, dsave + ds.x4s);
+    lstm_obs_loop<0, SAVE_ROWS, RAGGED>(W, hbuf, obsv, To, B, b, s0, false, c, h, dsave + ds.act, dsave + ds.x4s);
   }
   const float* hlast = &hbuf[(To & 1) * 16 * SW_HLD];
 
@@ -690,9 +674,8 @@ __host__ __device__ inline ScoreLds score_lds(int Tp) {
 }
 }  // namespace
 
-// RAGGED: the observation pass starts row b at step To - obs_len[b] (lstm_obs_loop_ragged); everything behind it is the same
-// code.  A template parameter with obs_len as the LAST argument: the dense instance keeps the dense loop, its argument
-// layout and its code.
+// RAGGED: the observation pass starts row b at step To - obs_len[b] (lstm_obs_loop<., ., true>); everything behind it is the
+// same code.  A template parameter with obs_len as the LAST argument: the dense instance keeps its argument layout.
 template <bool RAGGED>
 __global__ __launch_bounds__(SW_THREADS) void disc_score_kernel(
     const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred4, const float* __restrict__ d_w, int B, int K,
@@ -723,13 +706,7 @@ __global__ __launch_bounds__(SW_THREADS) void disc_score_kernel(
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};   // h0 = c0 = 0 (train.py:296-297)
   disc_seed_h(hbuf, false, nullptr, To, B, b);
   sw_barrier();
-  if constexpr (RAGGED) {
-    if (x_mode == 0) lstm_obs_loop_ragged<0>(W, hbuf, obsv, To, b, obs_start(obs_len, b, To, 0), c, h);
-    else lstm_obs_loop_ragged<1>(W, hbuf, obsv, To, b, obs_start(obs_len, b, To, 1), c, h);
-  } else {
-    if (x_mode == 0) lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
-    else lstm_obs_loop<1, false>(W, hbuf, obsv, To, B, b, c, h, nullptr, nullptr);
-  }
+  lstm_obs_pass<RAGGED>(x_mode, false, W, hbuf, obsv, To, B, b, RAGGED ? obs_start(obs_len, b, To, x_mode) : 0, c, h, nullptr, nullptr);
   // observation fc (waves 0, 1) -> both[0 | 1][:, 0:32]
   disc_obs_fc(smem, F, &hbuf[(To & 1) * 16 * SW_HLD], smem + F.o1, nullptr, live, smem + S.both, 2);
 

@@ -352,8 +352,8 @@ __device__ __forceinline__ f32x4 disc_obs_bwd_tail(const float* of1T, const floa
 // so that another launch can run the generator-phase pass of a tile in front of its own work (dec_rollout_bwd_kernel<true>,
 // sw_decoder.hip: the pass is tile-local and its only consumer is that tile's decode BPTT).
 // RAGGED (sw_disc_fwd_ragged, sw_disc_dpred_ragged): the observation pass starts row b at step To - obs_len[b] and saves
-// the selected rows (lstm_obs_loop_ragged, sw_lstm_dev.h); everything behind it is the same code.  A template parameter with
-// obs_len as the LAST argument, as disc_score_kernel: the dense instances keep the dense loop and their code.
+// the selected rows (lstm_obs_loop<., ., true>, sw_lstm_dev.h); everything behind it is the same code.  A template parameter
+// with obs_len as the LAST argument, as disc_score_kernel.
 template <bool RAGGED = false>
 __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, const unsigned nbx,
     const float* __restrict__ obsv, int To, int x_mode, const float* __restrict__ pred_a,
@@ -413,25 +413,10 @@ __device__ __forceinline__ void disc_fwd_tile(float* smem, const unsigned bx, co
   SW_DSTAMP(0);
   if (!obs_pre) {
     const bool sv = dsave && save_lstm && save_obs;
+    const int s = RAGGED ? obs_start(obs_len, b, To, x_mode) : 0;
     float* act = sv ? dsave + ds.act : nullptr;
     float* x4s = sv ? dsave + ds.x4s : nullptr;
-    if constexpr (RAGGED) {
-      if (x_mode == 0) {
-        const int s = obs_start(obs_len, b, To, 0);
-        if (sv) lstm_obs_loop_ragged<0, SAVE_ROWS>(W, hbuf, obsv, To, b, s, c, h, act, x4s, B);
-        else lstm_obs_loop_ragged<0>(W, hbuf, obsv, To, b, s, c, h);
-      } else {
-        const int s = obs_start(obs_len, b, To, 1);
-        if (sv) lstm_obs_loop_ragged<1, SAVE_ROWS>(W, hbuf, obsv, To, b, s, c, h, act, x4s, B);
-        else lstm_obs_loop_ragged<1>(W, hbuf, obsv, To, b, s, c, h);
-      }
-    } else if (x_mode == 0) {
-      if (sv) lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
-      else lstm_obs_loop<0, false>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
-    } else {
-      if (sv) lstm_obs_loop<1, true>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
-      else lstm_obs_loop<1, false>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
-    }
+    lstm_obs_pass<RAGGED>(x_mode, sv, W, hbuf, obsv, To, B, b, s, c, h, act, x4s);
   }
   const float* hlast = &hbuf[(To & 1) * 16 * SW_HLD];
   SW_DSTAMP(1);

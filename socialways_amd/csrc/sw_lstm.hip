@@ -6,24 +6,22 @@
 #include <cstdlib>
 
 // XMODE 0: x = positions [B][T][2] (4-d state formed on the fly); 1: x = [B][T][4].  ACT / Y / X4S: which per-step
-// rows are stored.  All of them are template parameters so that the step loop has NO conditional memory operation:
-// the compiler then knows how many loads / stores are in flight and never waits for the stores of a step (with
-// run-time conditions it put s_waitcnt vmcnt(0) in front of every step's barrier: one store round trip per step).
-// Padding lanes of the last tile are exact replicas of agent B-1 (every load is clamped to it) and store the same
-// values to the same rows.
-template <int XMODE, bool ACT, bool Y, bool X4S>
+// rows are stored.  RAGGED (sw_enc_lstm_fwd_ragged*): row b runs its last obs_len[b] steps from the zero state (obs_len
+// the LAST argument, as in disc_score_kernel; those launches pass no h0 / c0 / y and add no z-pull workgroups).  All of
+// them are template parameters so that the step loop (lstm_obs_loop, sw_lstm_dev.h) has NO conditional memory operation.
+template <int XMODE, bool ACT, bool Y, bool X4S, bool RAGGED>
 __global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ enc_w, const float* __restrict__ h0,
     const float* __restrict__ c0, int B, int T, float* __restrict__ hT, float* __restrict__ cT,
     float* __restrict__ y, float* __restrict__ act, float* __restrict__ x4s, int t0, const float* __restrict__ aux_src,
-    float* __restrict__ aux_dst, long long aux_n, const float* __restrict__ gimg) {
+    float* __restrict__ aux_dst, long long aux_n, const float* __restrict__ gimg, const int* __restrict__ obs_len) {
   // The FIRST workgroups of the grid only copy aux_src -> aux_dst (the training step pulls z out of its pinned host slot
   // here).  128 tiles leave half of the CUs idle for the whole latency-bound kernel: the PCIe read is free.  With more
   // tiles than CUs (dense crowds: 4 MB of z) the copy must START with the kernel - workgroups are dispatched in index
   // order; appended behind the tiles (round 3) they began when the last round of tiles did and the 4 MB then took
   // longer than that round: 113 -> 173 us - and keep several reads per thread in flight (PCIe round trips).
   const int tiles = (B + SW_TILE - 1) / SW_TILE;
-  const int extra = (int)gridDim.x - tiles;
+  const int extra = RAGGED ? 0 : (int)gridDim.x - tiles;   // (the ragged launches: tiles only, zero initial state)
   if ((int)blockIdx.x < extra) {
     sw_z_pull<SW_THREADS, 4>(aux_src, aux_dst, aux_n, extra);
     return;
@@ -39,57 +37,24 @@ __global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_kernel(
   const int a0 = ((int)blockIdx.x - extra) * SW_TILE;
   const int b = min(a0 + ln, B - 1);
   LstmW W;
-  if (gimg) {   // weight images of this step, derived once by the staging launch (swimg, sw_common.h)
-    lstm_load_img(W, gimg, wave, lane);
-  } else {
-    lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
-    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
-                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
-  }
+  lstm_load_enc(W, gimg, enc_w, wx_lds, bx_lds, wave, lane);
+  const int s = RAGGED ? obs_start(obs_len, b, T, XMODE) : 0;
   // initial state
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
-  if (h0) h = ld4(h0 + (size_t)b * 64 + u0 + 4 * lg);
-  if (c0) c = ld4(c0 + (size_t)b * 64 + u0 + 4 * lg);
+  if (!RAGGED && h0) h = ld4(h0 + (size_t)b * 64 + u0 + 4 * lg);
+  if (!RAGGED && c0) c = ld4(c0 + (size_t)b * 64 + u0 + 4 * lg);
   st4(&hbuf[0][ln * HS + HO + u0 + 4 * lg], h);
   sw_barrier();
   if (!gimg) lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
 
-  // the input of step t+1 is fetched while step t computes: its L2/HBM latency would otherwise sit in front of
-  // the first MFMA of every step (the last step re-fetches its own input: no conditional load)
-  float xa, xq = 0.f;
-  auto load_x = [&](int t) {
-    if constexpr (XMODE == 0) obs_x4_load(x, b, t, T, lg, xa, xq);
-    else xa = x[((size_t)b * T + t) * 4 + lg];
-  };
-  load_x(0);
-  asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE: the loop header must see no pending load on any path in
   float* yrow = Y ? y + (size_t)b * T * 64 + u0 + 4 * lg : nullptr;
-  float* xrow = X4S ? x4s + ((size_t)t0 * B + b) * 4 + lg : nullptr;
-  auto step = [&](int t, auto hp) {
-    const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
-    load_x(min(t + 1, T - 1));
-    f32x4 gate[4];
-    lstm_cell<decltype(hp)::value>(W, xb, &hbuf[t & 1][ln * HS + HO + 4 * lg], gate, c, h);
-    if constexpr (ACT) lstm_put_act_tile(hbuf[(t + 1) & 1], gate, c, h, ln, lg, u0);
-    else st4(&hbuf[(t + 1) & 1][ln * HS + u0 + 4 * lg], h);
-    if constexpr (Y) {
-      st4(yrow, h);
-      yrow += 64;
-    }
-    if constexpr (X4S) {   // all four waves hold the same x_t: they all store it (no per-wave branch)
-      *xrow = xb;
-      xrow += (size_t)B * 4;
-    }
-    sw_barrier();
-    if constexpr (ACT) lstm_store_act_tile(hbuf[(t + 1) & 1], act + (size_t)(t0 + t) * B * 384, a0, B, wave, lane);
-    asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
-  };
-  // Step 0 is peeled.  Without h0 it starts from h = 0 and issues only Wx x + b: no recurrent products, no read of the
-  // zeroed h tile.  h0 is a kernel argument (a uniform branch), and both sides issue the same global loads and stores in
-  // the same order, so the loop header sees one count of operations in flight whichever way it was reached.
-  if (h0) step(0, std::true_type{});
-  else step(0, std::false_type{});
-  for (int t = 1; t < T; ++t) step(t, std::true_type{});
+  lstm_obs_loop<XMODE, ACT ? SAVE_TILE : SAVE_NONE, RAGGED, X4S>(
+      W, hbuf[0], x, T, B, b, s, h0 != nullptr, c, h, act, x4s, a0, t0, [&](const f32x4& hn) {
+        if constexpr (Y) {
+          st4(yrow, hn);
+          yrow += 64;
+        }
+      });
   st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
   st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
 }
@@ -261,6 +226,44 @@ extern "C" int sw_traj_4d(const float* obsv, const float* pred, int B, int To, i
   return SW_OK;
 }
 
+// The instance of enc_lstm_fwd_kernel for what is asked for, launched on tiles + extra workgroups under the name it is
+// timed as (SW_LAUNCH_AS).  The ragged entry points reach four instances: x_mode x (nothing saved | act + x4s).
+static int enc_fwd_launch(const char* name, const float* x, int x_mode, const float* enc_w, const float* h0, const float* c0, int B,
+                          int T, float* hT, float* cT, float* y, float* act, float* x4s, int t0, const float* aux_src,
+                          float* aux_dst, long long aux_n, int extra, const float* gimg, bool ragged, const int* obs_len,
+                          void* stream) {
+  const int tiles = (B + SW_TILE - 1) / SW_TILE;
+#define SW_ENC_FWD(XM, A, Y_, X4, RG)                                                                                    \
+  SW_LAUNCH_AS(name, (enc_lstm_fwd_kernel<XM, A, Y_, X4, RG>), dim3(tiles + extra), dim3(SW_THREADS), 0, (hipStream_t)stream, \
+               x, enc_w, h0, c0, B, T, hT, cT, y, act, x4s, t0, aux_src, aux_dst, aux_n, gimg, obs_len)
+  switch ((ragged ? 16 : 0) | (x_mode ? 8 : 0) | (act ? 4 : 0) | (y ? 2 : 0) | (x4s ? 1 : 0)) {
+    case 0: SW_ENC_FWD(0, false, false, false, false); break;
+    case 1: SW_ENC_FWD(0, false, false, true, false); break;
+    case 2: SW_ENC_FWD(0, false, true, false, false); break;
+    case 3: SW_ENC_FWD(0, false, true, true, false); break;
+    case 4: SW_ENC_FWD(0, true, false, false, false); break;
+    case 5: SW_ENC_FWD(0, true, false, true, false); break;
+    case 6: SW_ENC_FWD(0, true, true, false, false); break;
+    case 7: SW_ENC_FWD(0, true, true, true, false); break;
+    case 8: SW_ENC_FWD(1, false, false, false, false); break;
+    case 9: SW_ENC_FWD(1, false, false, true, false); break;
+    case 10: SW_ENC_FWD(1, false, true, false, false); break;
+    case 11: SW_ENC_FWD(1, false, true, true, false); break;
+    case 12: SW_ENC_FWD(1, true, false, false, false); break;
+    case 13: SW_ENC_FWD(1, true, false, true, false); break;
+    case 14: SW_ENC_FWD(1, true, true, false, false); break;
+    case 15: SW_ENC_FWD(1, true, true, true, false); break;
+    case 16: SW_ENC_FWD(0, false, false, false, true); break;
+    case 16 + 5: SW_ENC_FWD(0, true, false, true, true); break;
+    case 16 + 8: SW_ENC_FWD(1, false, false, false, true); break;
+    case 16 + 13: SW_ENC_FWD(1, true, false, true, true); break;
+    default: return SW_EARG;   // (not reached: the ragged entry points check their outputs)
+  }
+#undef SW_ENC_FWD
+  SW_CHECK_LAUNCH(name);
+  return SW_OK;
+}
+
 extern "C" int sw_enc_lstm_fwd_aux(const float* x, int x_mode, const float* enc_w, const float* h0,
                                    const float* c0, int B, int T, float* hT, float* cT, float* y, float* act,
                                    float* x4s, int t0, const float* aux_src, float* aux_dst, long long aux_n,
@@ -283,30 +286,8 @@ extern "C" int sw_enc_lstm_fwd_aux(const float* x, int x_mode, const float* enc_
     SW_CHECK_LAUNCH("enc_lstm_fwd8_kernel");
     return SW_OK;
   }
-#define SW_ENC_FWD(XM, A, Y_, X4)                                                                                   \
-  SW_LAUNCH((enc_lstm_fwd_kernel<XM, A, Y_, X4>), dim3(tiles + extra), dim3(SW_THREADS), 0, (hipStream_t)stream,    \
-            x, enc_w, h0, c0, B, T, hT, cT, y, act, x4s, t0, aux_src, aux_dst, aux_n, gimg)
-  switch ((x_mode ? 8 : 0) | (act ? 4 : 0) | (y ? 2 : 0) | (x4s ? 1 : 0)) {
-    case 0: SW_ENC_FWD(0, false, false, false); break;
-    case 1: SW_ENC_FWD(0, false, false, true); break;
-    case 2: SW_ENC_FWD(0, false, true, false); break;
-    case 3: SW_ENC_FWD(0, false, true, true); break;
-    case 4: SW_ENC_FWD(0, true, false, false); break;
-    case 5: SW_ENC_FWD(0, true, false, true); break;
-    case 6: SW_ENC_FWD(0, true, true, false); break;
-    case 7: SW_ENC_FWD(0, true, true, true); break;
-    case 8: SW_ENC_FWD(1, false, false, false); break;
-    case 9: SW_ENC_FWD(1, false, false, true); break;
-    case 10: SW_ENC_FWD(1, false, true, false); break;
-    case 11: SW_ENC_FWD(1, false, true, true); break;
-    case 12: SW_ENC_FWD(1, true, false, false); break;
-    case 13: SW_ENC_FWD(1, true, false, true); break;
-    case 14: SW_ENC_FWD(1, true, true, false); break;
-    default: SW_ENC_FWD(1, true, true, true); break;
-  }
-#undef SW_ENC_FWD
-  SW_CHECK_LAUNCH("enc_lstm_fwd_kernel");
-  return SW_OK;
+  return enc_fwd_launch("enc_lstm_fwd_kernel", x, x_mode, enc_w, h0, c0, B, T, hT, cT, y, act, x4s, t0, aux_src, aux_dst, aux_n,
+                        extra, gimg, false, nullptr, stream);
 }
 extern "C" int sw_enc_lstm_fwd(const float* x, int x_mode, const float* enc_w, const float* h0,
                                const float* c0, int B, int T, float* hT, float* cT, float* y, float* act,
@@ -314,102 +295,25 @@ extern "C" int sw_enc_lstm_fwd(const float* x, int x_mode, const float* enc_w, c
   return sw_enc_lstm_fwd_aux(x, x_mode, enc_w, h0, c0, B, T, hT, cT, y, act, x4s, t0, nullptr, nullptr, 0, stream);
 }
 
-// The inference form of enc_lstm_fwd_kernel (zero initial state, nothing saved) for ragged observation histories: row b
-// runs its last obs_len[b] steps (lstm_obs_loop_ragged, sw_lstm_dev.h).  A kernel of its own, so that the instantiations
-// above - the training step's among them - keep their code.
-template <int XMODE>
-__global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_ragged_kernel(
-    const float* __restrict__ x, const float* __restrict__ enc_w, const int* __restrict__ obs_len, int B, int T,
-    float* __restrict__ hT, float* __restrict__ cT, const float* __restrict__ gimg) {
-  __shared__ __attribute__((aligned(16))) float hbuf[2 * SW_TILE * SW_HLD];
-  __shared__ __attribute__((aligned(16))) float wx_lds[256 * 4];
-  __shared__ __attribute__((aligned(16))) float bx_lds[256];
-  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  const int u0 = wave * 16;
-  const int b = min((int)blockIdx.x * SW_TILE + ln, B - 1);   // padding lanes of the last tile: replicas of agent B-1
-  LstmW W;
-  if (gimg) {
-    lstm_load_img(W, gimg, wave, lane);
-  } else {
-    lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
-    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
-                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
-  }
-  const int s = obs_start(obs_len, b, T, XMODE);
-  f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
-  st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], h);
-  sw_barrier();
-  if (!gimg) lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
-  lstm_obs_loop_ragged<XMODE>(W, hbuf, x, T, b, s, c, h);
-  st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
-  st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
-}
-
+// Ragged observation histories: row b runs its last obs_len[b] steps (lstm_obs_loop<., ., true>, sw_lstm_dev.h) - the RAGGED
+// instances of enc_lstm_fwd_kernel from the zero state, on a grid of tiles only (no z pull: the ragged step copies z itself).
+// The inference form saves nothing ...
 extern "C" int sw_enc_lstm_fwd_ragged(const float* x, int x_mode, const float* enc_w, const int* obs_len, int B, int T,
                                       float* hT, float* cT, void* stream) {
   if (!x || !enc_w || !hT || !cT || B < 0 || T < 1 || (x_mode != 0 && x_mode != 1) || (x_mode == 0 && T < 2)) return SW_EARG;
   if (B == 0) return SW_OK;
-  const float* gimg = sw_gen_images_for(enc_w, nullptr);
-  const int tiles = (B + SW_TILE - 1) / SW_TILE;
-  if (x_mode == 0)
-    SW_LAUNCH(enc_lstm_fwd_ragged_kernel<0>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T, hT, cT,
-              gimg);
-  else
-    SW_LAUNCH(enc_lstm_fwd_ragged_kernel<1>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T, hT, cT,
-              gimg);
-  SW_CHECK_LAUNCH("enc_lstm_fwd_ragged_kernel");
-  return SW_OK;
+  return enc_fwd_launch("enc_lstm_fwd_ragged_kernel", x, x_mode, enc_w, nullptr, nullptr, B, T, hT, cT, nullptr, nullptr, nullptr,
+                        0, nullptr, nullptr, 0, 0, sw_gen_images_for(enc_w, nullptr), true, obs_len, stream);
 }
-
-// The training form of the ragged encoder (zero initial state, saved rows + inputs out): enc_lstm_fwd_kernel<., true, false,
-// true> at t0 = 0 with the ragged loop's SAVE_TILE form (sw_lstm_dev.h) - the saved row of a step is assembled in the LDS
-// row tile and leaves behind the step's barrier, zeros in front of a row's start.  A kernel of its own: the dense kernels
-// above keep their code.  No z pull by spare workgroups: the ragged step copies z itself.
-template <int XMODE>
-__global__ __launch_bounds__(SW_THREADS) void enc_lstm_fwd_ragged_save_kernel(
-    const float* __restrict__ x, const float* __restrict__ enc_w, const int* __restrict__ obs_len, int B, int T,
-    float* __restrict__ hT, float* __restrict__ cT, float* __restrict__ act, float* __restrict__ x4s,
-    const float* __restrict__ gimg) {
-  __shared__ __attribute__((aligned(16))) float hbuf[2 * SW_TILE * SW_ALD];
-  __shared__ __attribute__((aligned(16))) float wx_lds[256 * 4];
-  __shared__ __attribute__((aligned(16))) float bx_lds[256];
-  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  const int u0 = wave * 16;
-  const int a0 = (int)blockIdx.x * SW_TILE;
-  const int b = min(a0 + ln, B - 1);   // padding lanes of the last tile: replicas of agent B-1
-  LstmW W;
-  if (gimg) {
-    lstm_load_img(W, gimg, wave, lane);
-  } else {
-    lstm_load_whh(W, enc_w + swp::ENC_WHH, u0, ln, lg);
-    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
-                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
-  }
-  const int s = obs_start(obs_len, b, T, XMODE);
-  f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = {0.f, 0.f, 0.f, 0.f};
-  st4(&hbuf[ln * SW_ALD + 320 + u0 + 4 * lg], h);
-  sw_barrier();
-  if (!gimg) lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
-  lstm_obs_loop_ragged<XMODE, SAVE_TILE>(W, hbuf, x, T, b, s, c, h, act, x4s, B, a0);
-  st4(hT + (size_t)b * 64 + u0 + 4 * lg, h);
-  st4(cT + (size_t)b * 64 + u0 + 4 * lg, c);
-}
-
+// ... the training form the saved rows + inputs of enc_lstm_fwd_kernel<., true, false, true> at t0 = 0, zeros in front of a
+// row's start.
 extern "C" int sw_enc_lstm_fwd_ragged_save(const float* x, int x_mode, const float* enc_w, const int* obs_len, int B, int T,
                                            float* hT, float* cT, float* act, float* x4s, void* stream) {
   if (!x || !enc_w || !hT || !cT || !act || !x4s || B < 0 || T < 1 || (x_mode != 0 && x_mode != 1) || (x_mode == 0 && T < 2))
     return SW_EARG;
   if (B == 0) return SW_OK;
-  const float* gimg = sw_gen_images_for(enc_w, nullptr);
-  const int tiles = (B + SW_TILE - 1) / SW_TILE;
-  if (x_mode == 0)
-    SW_LAUNCH(enc_lstm_fwd_ragged_save_kernel<0>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T,
-              hT, cT, act, x4s, gimg);
-  else
-    SW_LAUNCH(enc_lstm_fwd_ragged_save_kernel<1>, dim3(tiles), dim3(SW_THREADS), 0, (hipStream_t)stream, x, enc_w, obs_len, B, T,
-              hT, cT, act, x4s, gimg);
-  SW_CHECK_LAUNCH("enc_lstm_fwd_ragged_save_kernel");
-  return SW_OK;
+  return enc_fwd_launch("enc_lstm_fwd_ragged_save_kernel", x, x_mode, enc_w, nullptr, nullptr, B, T, hT, cT, nullptr, act, x4s,
+                        0, nullptr, nullptr, 0, 0, sw_gen_images_for(enc_w, nullptr), true, obs_len, stream);
 }
 
 extern "C" int sw_enc_lstm_bwd_aux(const float* enc_w, const float* act, const float* c0, const float* dhT,

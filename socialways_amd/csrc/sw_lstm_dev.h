@@ -95,6 +95,18 @@ __device__ __forceinline__ void lstm_load_img(LstmW& W, const float* __restrict_
     W.bias[g] = ld4(gimg + swimg::BX + g * 64 + u0 + 4 * lg);
   }
 }
+// The encoder's operands: from the images of the step (gimg), or from the weights - W_hh straight into its registers, the
+// composed Wx | bx through LDS (then the caller: sw_barrier(), if (!gimg) lstm_load_wx).
+__device__ __forceinline__ void lstm_load_enc(LstmW& W, const float* gimg, const float* enc_w,
+                                              float* wx_lds, float* bx_lds, int wave, int lane) {
+  if (gimg) {   // weight images of this step, derived once by the staging launch (swimg, sw_common.h)
+    lstm_load_img(W, gimg, wave, lane);
+  } else {
+    lstm_load_whh(W, enc_w + swp::ENC_WHH, wave * 16, lane & 15, lane >> 4);
+    lstm_prep_rows(enc_w + swp::ENC_EMB_W, enc_w + swp::ENC_EMB_B, enc_w + swp::ENC_WIH, enc_w + swp::ENC_BIH,
+                   enc_w + swp::ENC_BHH, true, wx_lds, bx_lds);
+  }
+}
 
 // The products of one cell step for NB 16-agent tiles: acc[k][g] = Wx x_k + b + W_hh h_k (pre-activation rows of gate g),
 // every W_hh operand issued against the NB h tiles in turn.  xb[k] = x4[agent ln][component lg] of tile k;
@@ -377,49 +389,7 @@ __device__ __forceinline__ float obs_x4(const float* pos, int b, int t, int T, i
   return a - (comp >= 2 ? q : 0.f);
 }
 
-// The time loop of an LSTM over a 4-d input sequence FROM THE ZERO STATE (c = h = 0 on entry; every caller is the
-// discriminator's observation pass, train.py:296-297) for the 16-agent tile of agent row b (clamped), W loaded.  XMODE 0:
-// x = positions [B][T][2]; 1: x = [B][T][4].  SAVE: per step t and agent b, act + (t B + b) 384 = gates i|f|g|o [256],
-// c [64], h [64] and the step's input at x4s + (t B + b) 4.  Step 0 is peeled and issues only Wx x + b (lstm_products
-// with HP = false): hbuf[0] is not read.  No conditional memory operation inside (see enc_lstm_fwd_kernel); padding
-// lanes of the last tile are replicas of agent B-1.  On return h_T sits in hbuf[T & 1].
-template <int XMODE, bool SAVE>
-__device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int B, int b,
-                                              f32x4& c, f32x4& h, float* __restrict__ act, float* __restrict__ x4s) {
-  const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
-  const int u0 = wave * 16;
-  float xa, xq = 0.f;
-  auto load_x = [&](int t) {
-    if constexpr (XMODE == 0) obs_x4_load(x, b, t, T, lg, xa, xq);
-    else xa = x[((size_t)b * T + t) * 4 + lg];
-  };
-  load_x(0);
-  asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE: the loop header must see no pending load on any path in
-  float* arow = SAVE ? act + (size_t)b * 384 + u0 + 4 * lg : nullptr;
-  float* xrow = SAVE ? x4s + (size_t)b * 4 + lg : nullptr;
-  auto step = [&](int t, auto hp) {
-    const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
-    load_x(min(t + 1, T - 1));   // the input of step t+1 is fetched while step t computes
-    f32x4 gate[4];
-    lstm_cell<decltype(hp)::value>(W, xb, &hbuf[(t & 1) * 16 * SW_HLD + ln * SW_HLD + 4 * lg], gate, c, h);
-    st4(&hbuf[((t + 1) & 1) * 16 * SW_HLD + ln * SW_HLD + u0 + 4 * lg], h);
-    if constexpr (SAVE) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) st4g(arow + g * 64, gate[g]);
-      st4g(arow + 256, c);
-      st4g(arow + 320, h);
-      *xrow = xb;   // all four waves hold the same x_t and all store it
-      arow += (size_t)B * 384;
-      xrow += (size_t)B * 4;
-    }
-    sw_barrier();
-    asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
-  };
-  step(0, std::false_type{});
-  for (int t = 1; t < T; ++t) step(t, std::true_type{});
-}
-
-// ---- ragged observation histories (sw_enc_lstm_fwd_ragged, sw_disc_score_ragged) ---------------------------------------
+// ---- ragged observation histories (sw_enc_lstm_fwd_ragged*, sw_disc_*_ragged) -----------------------------------------
 // Row b of x holds n = obs_len[b] valid frames RIGHT-ALIGNED in its T columns: its LSTM starts from the zero state at step
 // s = T - n, the columns in front of s are padding that is never read.  n is clamped on the device into 2 .. T for positions
 // (the velocity rule needs two points), 1 .. T for 4-d input; obs_len == nullptr: every row starts at 0.
@@ -436,64 +406,89 @@ __device__ __forceinline__ void obs_x4_load_from(const float* pos, int b, int t,
   a = p[(vel ? tt : te) * 2 + c];
   q = p[(vel ? tt - 1 : te) * 2 + c];
 }
-// lstm_obs_loop<XMODE, false> from the ZERO state (hbuf[0] zeroed, c = h = 0) with a start step s per lane.  The loop keeps
-// its shape - every lane computes the cell on every step, no conditional memory operation, one uniform barrier per step -
-// and a lane in front of its start SELECTS the zero state instead of the cell's result (the input index is clamped to
-// >= s, so that cell ran on finite values and nothing of the padding was loaded).  From step s on the lane's agent sees
-// exactly the operands of the T - s step run on its valid frames: an agent is one column of the products, so h_T / c
-// carry the bits of lstm_obs_loop on the truncated buffer.  A separate function: the dense loop above keeps its code.
-//
-// SAVE (the training forms: sw_enc_lstm_fwd_ragged_save, sw_disc_fwd_ragged) stores per step the SELECTED row in the layout
-// of the dense kernels - the cell's gates | c | h and the step's 4-d input from the lane's start on, ZEROS in front of it -
-// so that the dense BPTT and weight-gradient kernels give the ragged gradients as they are: with i = g = o = 0 and
-// c_t = c_{t-1} = 0 lstm_cell_bwd yields zero dgates and dc_{t-1} = 0 whatever arrives from step s, and the weight
-// gradients sum zero dgates against zero inputs.  Selected, never computed from the padding: 0 * NaN would poison the GEMM.
-// The stores stay unconditional (the value is selected, not the store).
-//   SAVE_ROWS: straight from the registers, as lstm_obs_loop<., true> (act / x4s = row 0 of step 0, B = rows per step)
-//   SAVE_TILE: through the LDS row tile, as enc_lstm_fwd_kernel<., true, ., true>: hbuf is then [2][16][SW_ALD], whose h
-//              columns (320 ..) are the next step's operand, and the rows leave behind the step's barrier (a0 = the tile's
-//              first agent)
-//   USER: no meaning inside.  A second kernel that inlines ONE instantiation moves instructions in the first (seen on
-//         disc_fwd_ragged_kernel's address arithmetic when disc_update_kernel<true> took <0, SAVE_ROWS> as well); a later
-//         user names an instantiation of its own and the earlier kernels keep their code.
+
+// ---- THE forward time loop of the 64-unit LSTM over an observed track -------------------------------------------------
+// (enc_lstm_fwd_kernel and, through lstm_obs_pass below, every observation pass of the discriminator) for the 16-agent tile
+// of agent row b (clamped), W loaded, c / h the initial state with h already in hbuf[0].  One step: fetch the next input,
+// cell, [select the zero state], h into the LDS tile, [save the row], barrier.
+//   XMODE   0: x = positions [B][T][2], the 4-d state formed on the fly; 1: x = [B][T][4]
+//   SAVE    what step t leaves at act + ((t0 + t) B + b) 384 = gates i|f|g|o [256], c [64], h [64] (t0: the encoder's first
+//           row; the index itself is an argument, not an offset of act: the tile stores keep their 32-bit row arithmetic):
+//           SAVE_NONE  nothing; hbuf is [2][16][SW_HLD]
+//           SAVE_ROWS  the row straight from the registers (act = row 0 of step 0)
+//           SAVE_TILE  through the LDS row tile: hbuf is [2][16][SW_ALD], its h columns (320 ..) are the next step's
+//                      operand, and the rows leave behind the step's barrier as 1 KB stores (a0 = the tile's first agent)
+//   X4S     the step's 4-d input goes to x4s + ((t0 + t) B + b) 4 (with every saving form; the encoder also asks for it alone)
+//   RAGGED  false: step 0 is peeled and, unless hp0 (the caller passed an initial h: a UNIFORM run-time branch whose two
+//           sides issue the same global loads and stores in the same order), issues only Wx x + b - from h = 0 neither the
+//           recurrent products nor the read of hbuf[0] (lstm_products with HP = false).
+//           true: a start step s per lane (obs_start) FROM THE ZERO STATE.  Every lane computes the cell on every step -
+//           step 0 keeps its full products: a lane may start anywhere - with the input index clamped to >= s, so that the
+//           cell runs on finite values and nothing of the padding is loaded, and a lane in front of its start SELECTS the
+//           zero state instead of the cell's result.  From s on the lane's agent sees exactly the operands of the T - s
+//           step run on its valid frames (an agent is one column of the products): h_T / c carry the bits of the dense
+//           loop on the truncated buffer.  A saving form stores the SELECTED row and input - zeros in front of s - so that
+//           the dense BPTT and weight-gradient kernels give the ragged gradients as they are (zero gates with zero c_t,
+//           c_{t-1}: zero dgates, dc_{t-1} = 0).  Selected, never computed from the padding: 0 * NaN would poison the GEMM.
+//   post(h) runs per step behind the LDS store of h (the encoder's y rows).
+// What every form keeps:
+//   - the loop body has NO memory operation under a lane- or wave-dependent branch: everything that differs between the
+//     forms is `if constexpr`.  With run-time conditions the compiler loses count of what is in flight and waits for
+//     everything (s_waitcnt vmcnt(0)) in front of every step's barrier: one store round trip per step;
+//   - the first input is waited for in front of the loop header (the asm anchor), which must see no pending load on any
+//     path in;
+//   - the input of step t+1 is fetched while step t computes (the last step re-fetches its own: no conditional load) and
+//     is not touched before the step's barrier (the second anchor);
+//   - stores are unconditional, their VALUES are selected; all four waves hold the same x_t and all store it;
+//   - padding lanes of the last tile are exact replicas of agent B-1 (every load is clamped to it) and store the same
+//     values to the same rows;
+//   - on return h_T sits in hbuf[T & 1].
 enum { SAVE_NONE = 0, SAVE_ROWS = 1, SAVE_TILE = 2 };
-template <int XMODE, int SAVE = SAVE_NONE, int USER = 0>
-__device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int b, int s,
-                                                     f32x4& c, f32x4& h, float* __restrict__ act = nullptr,
-                                                     float* __restrict__ x4s = nullptr, int B = 0, int a0 = 0) {
+template <int XMODE, int SAVE, bool RAGGED, bool X4S = SAVE != SAVE_NONE, class Post = SwNop>
+__device__ __forceinline__ void lstm_obs_loop(const LstmW& W, float* hbuf, const float* __restrict__ x, int T, int B, int b, int s,
+                                              bool hp0, f32x4& c, f32x4& h, float* __restrict__ act, float* __restrict__ x4s,
+                                              int a0 = 0, int t0 = 0, Post post = {}) {
   const int lane = sw_lane(), wave = sw_wave(), ln = lane & 15, lg = lane >> 4;
   const int u0 = wave * 16;
   constexpr int HS = SAVE == SAVE_TILE ? SW_ALD : SW_HLD, HO = SAVE == SAVE_TILE ? 320 : 0;
   float xa, xq = 0.f;
   auto load_x = [&](int t) {
-    if constexpr (XMODE == 0) obs_x4_load_from(x, b, t, s, T, lg, xa, xq);
-    else xa = x[((size_t)b * T + max(t, s)) * 4 + lg];
+    if constexpr (RAGGED) {
+      if constexpr (XMODE == 0) obs_x4_load_from(x, b, t, s, T, lg, xa, xq);
+      else xa = x[((size_t)b * T + max(t, s)) * 4 + lg];
+    } else {
+      if constexpr (XMODE == 0) obs_x4_load(x, b, t, T, lg, xa, xq);
+      else xa = x[((size_t)b * T + t) * 4 + lg];
+    }
   };
   load_x(0);
-  asm volatile("" : "+v"(xa), "+v"(xq));   // waited for HERE, as in lstm_obs_loop
-  float* arow = SAVE == SAVE_ROWS ? act + (size_t)b * 384 + u0 + 4 * lg : nullptr;
-  float* xrow = SAVE != SAVE_NONE ? x4s + (size_t)b * 4 + lg : nullptr;
-  for (int t = 0; t < T; ++t) {
-    const float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
+  asm volatile("" : "+v"(xa), "+v"(xq));
+  float* arow = SAVE == SAVE_ROWS ? act + ((size_t)t0 * B + b) * 384 + u0 + 4 * lg : nullptr;
+  float* xrow = X4S ? x4s + ((size_t)t0 * B + b) * 4 + lg : nullptr;
+  auto step = [&](int t, auto hp) {
+    float xb = XMODE == 0 ? xa - (lg >= 2 ? xq : 0.f) : xa;
     load_x(min(t + 1, T - 1));
     f32x4 gate[4];
-    lstm_cell(W, xb, &hbuf[(t & 1) * 16 * HS + ln * HS + HO + 4 * lg], gate, c, h);
-    const bool on = t >= s;
+    lstm_cell<decltype(hp)::value>(W, xb, &hbuf[(t & 1) * 16 * HS + ln * HS + HO + 4 * lg], gate, c, h);
+    if constexpr (RAGGED) {
+      const bool on = t >= s;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      c[r] = on ? c[r] : 0.f;
-      h[r] = on ? h[r] : 0.f;
+      for (int r = 0; r < 4; ++r) {
+        c[r] = on ? c[r] : 0.f;
+        h[r] = on ? h[r] : 0.f;
+      }
+      if constexpr (SAVE != SAVE_NONE) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gate[g][r] = on ? gate[g][r] : 0.f;
+      }
+      if constexpr (X4S) xb = on ? xb : 0.f;
     }
-    if constexpr (SAVE != SAVE_NONE) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gate[g][r] = on ? gate[g][r] : 0.f;
-      *xrow = on ? xb : 0.f;   // all four waves hold the same x_t and all store it
-      xrow += (size_t)B * 4;
-    }
-    if constexpr (SAVE == SAVE_TILE) lstm_put_act_tile(hbuf + ((t + 1) & 1) * 16 * HS, gate, c, h, ln, lg, u0);
+    float* hnext = hbuf + ((t + 1) & 1) * 16 * HS;
+    if constexpr (SAVE == SAVE_TILE) lstm_put_act_tile(hnext, gate, c, h, ln, lg, u0);
     else st4(&hbuf[((t + 1) & 1) * 16 * HS + ln * HS + u0 + 4 * lg], h);
+    post(h);
     if constexpr (SAVE == SAVE_ROWS) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) st4g(arow + g * 64, gate[g]);
@@ -501,9 +496,35 @@ __device__ __forceinline__ void lstm_obs_loop_ragged(const LstmW& W, float* hbuf
       st4g(arow + 320, h);
       arow += (size_t)B * 384;
     }
+    if constexpr (X4S) {
+      *xrow = xb;
+      xrow += (size_t)B * 4;
+    }
     sw_barrier();
-    if constexpr (SAVE == SAVE_TILE) lstm_store_act_tile(hbuf + ((t + 1) & 1) * 16 * HS, act + (size_t)t * B * 384, a0, B, wave, lane);
-    asm volatile("" : "+v"(xa), "+v"(xq));   // the prefetched input is not touched before this point
+    if constexpr (SAVE == SAVE_TILE) lstm_store_act_tile(hnext, act + (size_t)(t0 + t) * B * 384, a0, B, wave, lane);
+    asm volatile("" : "+v"(xa), "+v"(xq));
+  };
+  if constexpr (RAGGED) {
+    for (int t = 0; t < T; ++t) step(t, std::true_type{});
+  } else {
+    if (hp0) step(0, std::true_type{});
+    else step(0, std::false_type{});
+    for (int t = 1; t < T; ++t) step(t, std::true_type{});
+  }
+}
+// The observation pass of the discriminator (FROM THE ZERO STATE: c = h = 0, hbuf[0] zeroed; train.py:296-297): the run-time
+// x_mode and `save` (rows straight from the registers, or nothing) to the instantiation, chosen once in front of the loop.
+// s: the lane's start step (obs_start; RAGGED only).
+template <bool RAGGED>
+__device__ __forceinline__ void lstm_obs_pass(int x_mode, bool save, const LstmW& W, float* hbuf, const float* __restrict__ x,
+                                              int T, int B, int b, int s, f32x4& c, f32x4& h, float* __restrict__ act,
+                                              float* __restrict__ x4s) {
+  if (x_mode == 0) {
+    if (save) lstm_obs_loop<0, SAVE_ROWS, RAGGED>(W, hbuf, x, T, B, b, s, false, c, h, act, x4s);
+    else lstm_obs_loop<0, SAVE_NONE, RAGGED>(W, hbuf, x, T, B, b, s, false, c, h, act, x4s);
+  } else {
+    if (save) lstm_obs_loop<1, SAVE_ROWS, RAGGED>(W, hbuf, x, T, B, b, s, false, c, h, act, x4s);
+    else lstm_obs_loop<1, SAVE_NONE, RAGGED>(W, hbuf, x, T, B, b, s, false, c, h, act, x4s);
   }
 }
 
@@ -527,6 +548,5 @@ __device__ __forceinline__ void disc_obs_lstm_tile(float* smem, const float* __r
   st4(&hbuf[ln * SW_HLD + u0 + 4 * lg], h);
   sw_barrier();
   lstm_load_wx(W, wx_lds, bx_lds, u0, ln, lg);
-  if (x_mode == 0) lstm_obs_loop<0, true>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
-  else lstm_obs_loop<1, true>(W, hbuf, obsv, To, B, b, c, h, act, x4s);
+  lstm_obs_pass<false>(x_mode, true, W, hbuf, obsv, To, B, b, 0, c, h, act, x4s);
 }

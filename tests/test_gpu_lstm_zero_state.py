@@ -64,6 +64,49 @@ def test_encoder_from_no_state_equals_encoder_from_explicit_zeros(T, x_mode, ima
                 assert torch.equal(a, b), (name, B, float((a - b).abs().max()))
 
 
+@pytest.mark.parametrize("images", (False, True), ids=("weights", "images"))
+@pytest.mark.parametrize("x_mode,T", ((0, 2), (0, 3), (1, 1), (1, 2), (1, 3)))
+def test_encoder_output_combinations_equal_the_all_outputs_call(x_mode, T, images):
+    """sw_enc_lstm_fwd picks one of 16 instances of enc_lstm_fwd_kernel by x_mode and by which of y / act / x4s are asked
+    for.  The other tests reach six of them: nothing saved and act + x4s for both x_modes, and through the module API
+    x_mode 1 with y alone and with all three.  Here every combination of outputs runs for both x_modes (with images and
+    positions, act + x4s without y is the eight-wave kernel); every requested output, pre-filled with NaN, must be finite and
+    equal to the same output of the call that asks for all three.  T = 1 (x_mode 1): only the peeled step runs and the
+    prefetch index is clamped to 0.  B = 1, 16, 17, 40: one live lane, a full tile, a tile of replicas, three tiles."""
+    import itertools
+    import socialways_amd as sw
+    from socialways_amd import _lib as L
+    dev = torch.device("cuda:0")
+    torch.manual_seed(11)
+    G = sw.Generator(use_social=True, device=dev)
+    G.unify()
+    enc = G.encoder._flat
+    shapes = {"hT": lambda B: (B, 64), "cT": lambda B: (B, 64), "y": lambda B: (B, T, 64), "act": lambda B: (T, B, 384),
+              "x4s": lambda B: (T, B, 4)}
+
+    def run(B, x, want):
+        out = {k: torch.full(shapes[k](B), float("nan"), device=dev) for k in ("hT", "cT") + want}
+        p = lambda k: L.ptr(out[k]) if k in out else None
+        L.call("sw_enc_lstm_fwd", L.ptr(x), x_mode, L.ptr(enc), None, None, B, T, p("hT"), p("cT"), p("y"), p("act"), p("x4s"), 0,
+               L.stream())
+        torch.cuda.synchronize()
+        return out
+
+    with _gen_images(G, images):
+        for B in (1, 16, 17, 40):
+            g = torch.Generator().manual_seed(1000 * T + B)
+            x = (torch.rand(B, T, 2 if x_mode == 0 else 4, generator=g).cumsum(1) * 0.1).to(dev).contiguous()
+            ref = run(B, x, ("y", "act", "x4s"))
+            for k, v in ref.items():
+                assert torch.isfinite(v).all(), (k, B)
+            for n in range(3):
+                for want in itertools.combinations(("y", "act", "x4s"), n):
+                    got = run(B, x, want)
+                    for k, v in got.items():
+                        assert torch.isfinite(v).all(), (want, k, B)
+                        assert torch.equal(v, ref[k]), (want, k, B, float((v - ref[k]).abs().max()))
+
+
 def _disc_setup(B, To, x_cols=2):
     import socialways_amd as sw
     dev = torch.device("cuda:0")
