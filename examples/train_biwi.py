@@ -28,6 +28,9 @@
   create_dataset_ragged(min_next=M), left-aligned futures + pred_len), so they are predicted, scored against the frames
   they were seen for and stay in their neighbours' scenes; the errors are reported per future length (evaluate_horizon).
   Combines with `--min-past`.  Training windows are always built without it: a truncated future is no discriminator input.
+* `--clearance-loss DIST[:W]`: train against collisions - the generator loss gains the scene-clearance term
+  (set_clearance_loss(DIST, W), W default 1: pairs of predicted futures that come closer than DIST world units within a
+  segment are pushed apart), and every test prints col_joint and col_agent of evaluate_scenes(coll_dist=DIST) beside ADE/FDE.
 """
 import argparse
 import os
@@ -91,7 +94,19 @@ def main(argv=None):
                          "eager steps on the unfused route) instead of the full windows only")
     ap.add_argument("--ragged-fused", action="store_true",
                     help="with --train-ragged: the fused ragged step (ragged_fused=True: one-launch D updates, graph-captured steps)")
+    ap.add_argument("--clearance-loss", default=None, metavar="DIST[:W]",
+                    help="add the scene-clearance term to the generator loss: futures of one scene closer than DIST (world "
+                         "units) are penalised with weight W (default 1); reports the collision rates at DIST")
     args = ap.parse_args(argv)
+    clearance = None
+    if args.clearance_loss is not None:
+        try:
+            dist, _, w = args.clearance_loss.partition(":")
+            clearance = (float(dist), float(w) if w else 1.0)
+        except ValueError:
+            ap.error("--clearance-loss takes DIST or DIST:W, got %r" % args.clearance_loss)
+        if args.hidden_size != 64:
+            ap.error("--clearance-loss: the clearance term is implemented for the fused 64-unit path (--hidden-size 64)")
     if args.ragged_fused and not args.train_ragged:
         ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
@@ -153,6 +168,8 @@ def main(argv=None):
                               process_group=pg, **(dict(ragged_fused=True) if args.ragged_fused else {}))
     if args.device_noise is not None:     # the same seed on every rank: the union of the shards is the single-process z
         tr.noise = sw.DeviceNoise(args.device_noise)
+    if clearance is not None:
+        tr.set_clearance_loss(*clearance)
     for epoch in range(1, args.epochs + 1):
         t0 = time.perf_counter()
         if train_set is not None:
@@ -172,6 +189,12 @@ def main(argv=None):
                   "%.1f %% of agents (ground truth %.1f %%) | %d scenes, %d with company"
                   % (args.k, sm["jade_min"], sm["jfde_min"], 100 * sm["col_joint"], 100 * sm["col_best"], 100 * sm["col_agent"],
                      100 * sm["col_gt"], sm["n_scenes"], sm["n_multi"]))
+            if clearance is not None:
+                sc = tr.evaluate_scenes(data, n_gen_samples=args.k, coll_dist=clearance[0])
+                print("Clearance loss (dist %.2f, weight %.2f): Min(%d) ADE,FDE = (%.3f, %.3f) | collisions < %.2f: col_joint %.1f %%, "
+                      "col_agent %.1f %% (ground truth %.1f %%)"
+                      % (clearance[0], clearance[1], args.k, sc["ade_min"], sc["fde_min"], clearance[0], 100 * sc["col_joint"],
+                         100 * sc["col_agent"], 100 * sc["col_gt"]))
             if args.diverse is not None:
                 dv = tr.evaluate_diverse(data, n_gen_samples=args.k, top_m=min(5, args.k), radius=args.diverse)
                 print("Diverse top-%d (radius %.2f): ADE,FDE first = (%.3f, %.3f), best mode = (%.3f, %.3f) | %.2f modes per agent, "

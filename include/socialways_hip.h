@@ -311,6 +311,38 @@ int sw_scene_clearance(const float* pos, int pstride, const float* start /*or NU
 int sw_scene_clearance_len(const float* pos, int pstride, const float* start /*or NULL*/, int sstride, const int* scene_off,
                            const int* len /*[B] int32 or NULL*/, int S, int B, int K, int Tp, float inv_ss,
                            float* clear /*[K,B]*/, void* stream);
+/* SCENE-CLEARANCE PENALTY of the generator loss and its gradient with respect to the positions: the training-side
+ * counterpart of sw_scene_clearance - the same closest approach, squashed and differentiated.  B agents in S scenes
+ * (scene_off as above), all fp32.  The path of agent a is P_a[0] = start[a] (when start != NULL), then pos[a][0 .. Tp-1]:
+ * Tp segments with start, Tp - 1 without.  For two agents a != b of one scene and segment s (from point s-1 to point s):
+ *   r0 = P_a[s-1] - P_b[s-1],  r1 = P_a[s] - P_b[s],  dv = r1 - r0,
+ *   tau = clamp(-(r0.dv) / (dv.dv), 0, 1), tau = 0 when dv.dv = 0      (the arithmetic of sw_scene_clearance),
+ *   c = r0 + tau dv,  u = max(0, 1 - |c|^2 / d0^2),  phi = u^2.
+ * The penalty of the batch is the sum over scenes, pairs a < b and segments of phi.  tau minimises |r0 + tau dv|^2 over
+ * [0, 1], so d|c|^2 / dP_a[s] = 2 tau c and d|c|^2 / dP_a[s-1] = 2 (1 - tau) c, and with d phi / d|c|^2 = -2 u / d0^2
+ *   g_a[s] = sum over b != a of [ -(4 u_s / d0^2) tau_s c_s - (4 u_{s+1} / d0^2) (1 - tau_{s+1}) c_{s+1} ]
+ * (the second term absent at the last point).  phi is C1 at the threshold |c| = d0 (u reaches 0 there, and g with it); g
+ * is continuous across both clamps of tau (inside, c is orthogonal to dv; at a clamp the formula holds with the clamped tau),
+ * finite everywhere, and exactly 0 where c = 0 - coincident agents are not pushed apart: a saddle of measure zero.  Its only
+ * discontinuity is at dv.dv = 0, where tau = 0 is the definition.
+ *   pos    [B,Tp,pstride], pstride 2 or 4 floats (x, y first), 8-byte aligned;  start [B,sstride] or NULL, sstride >= 2;
+ *   d0 > 0 and finite, in the units of pos;  scale finite;
+ *   dpos   [B,Tp,dstride], dstride 2 or 4, 8-byte aligned: dpos[a][t][0:2] += scale * g of the point pos[a][t]; components
+ *          2 and 3 of a 4-float row are neither read nor written.  With start, P[0] is data and takes no gradient; without,
+ *          pos[a][0] takes its share as the r0 end of segment 1;
+ *   loss   [B] or NULL: loss[a] = 1/2 * the sum over b != a and s of phi - unscaled, the agent's share: the sum over a of
+ *          loss[a] is the penalty;   count [B] int32 or NULL: the number of (b, s) with |c|^2 < d0^2.
+ * STORES ARE SKIPPED, not +0: per agent and chunk of 16 segments, the dpos rows of the chunk are read and written only if
+ * one of its (b, s) has |c|^2 < d0^2.  An agent whose every |c|^2 >= d0^2, and any agent of a single-agent scene, leaves
+ * its dpos rows bit for bit as they were (loss 0, count 0).  Rows outside every scene are not written.
+ * One wave per (scene, tile of 64 agents), one owner per dpos row, loss[a] and count[a], partners then segments in ascending
+ * order, no atomics: two calls give the same bits, and a scene's outputs do not depend on the other scenes of the batch.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, dpos, scene_off; S < 0; B < 0; Tp < 1; d0 <= 0
+ * or not finite (or d0^2 or 1 / d0^2 outside fp32's range); scale not finite; pstride or dstride not 2 or 4; pos or dpos off their
+ * 8-byte alignment; start with sstride < 2.  B == 0 or S == 0: SW_OK without a launch.                                 */
+int sw_clearance_grad(const float* pos, int pstride, const float* start /*or NULL*/, int sstride, const int* scene_off,
+                      int S, int B, int Tp, float d0, float scale, float* dpos /*[B,Tp,dstride], += */, int dstride,
+                      float* loss /*[B] or NULL*/, int* count /*[B] or NULL*/, void* stream);
 /* sw_scene_reduce: with sade[k][s] / sfde[k][s] = the mean over the scene's agents of err[k][a][0] / [1] and
  * sclear[k][s] = the minimum over them of clear[k][a],
  *   per_scene [S,6] = { min_k sade, min_k sfde, share of k with sclear < coll_dist, 1 if draw kbest collides else 0,

@@ -51,6 +51,7 @@ PROTOTYPES = {
     "sw_sample_rank": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sw_scene_clearance": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "sw_scene_clearance_len": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "sw_clearance_grad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp, _vp]),
     "sw_scene_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sw_sample_nms": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sw_scene_compose": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -42,6 +42,22 @@ __device__ __forceinline__ void sc_segment(float2 pa, float2 pb, float& rx, floa
   ry = ey;
 }
 
+// sc_segment that hands back where the closest approach lies instead of folding a minimum: tau and c = r0 + tau dv, by
+// sc_segment's arithmetic (the same reciprocal, the same clamp, tau = 0 at dd = 0), so |c|^2 carries the bits sc_segment
+// would have folded.  tau minimises |r0 + tau dv|^2 over [0, 1]: d|c|^2 / d(r1) = 2 tau c and d|c|^2 / d(r0) = 2 (1 - tau) c
+// (sw_clearance_grad.hip).  (rx, ry) = r0 on entry, the next segment's r0 on exit.
+__device__ __forceinline__ void sc_segment_at(float2 pa, float2 pb, float& rx, float& ry, float& tau, float& cx, float& cy) {
+  const float ex = pa.x - pb.x, ey = pa.y - pb.y;
+  const float dx = ex - rx, dy = ey - ry;
+  const float dd = dx * dx + dy * dy, rd = rx * dx + ry * dy;
+  tau = -rd * __builtin_amdgcn_rcpf(dd);
+  tau = dd > 0.f ? fminf(fmaxf(tau, 0.f), 1.f) : 0.f;
+  cx = rx + tau * dx;
+  cy = ry + tau * dy;
+  rx = ex;
+  ry = ey;
+}
+
 // sc_segment whose minimum is gated by a select: r0 advances, m moves only when `on` - whatever the segment holds, NaN
 // included, reaches nothing when it does not count
 __device__ __forceinline__ void sc_segment_if(bool on, float2 pa, float2 pb, float& rx, float& ry, float& m) {

@@ -535,6 +535,18 @@ class GenericTrainer(SocialWaysTrainer):
                                        "for the reference's host stream" % type(self).__name__)
         return None
 
+    # ... and so is the scene-clearance term of the generator loss (set_clearance_loss()): refused, not ignored
+    @property
+    def clearance_loss(self):
+        return None
+
+    @clearance_loss.setter
+    def clearance_loss(self, value):
+        if value is not None:
+            raise L.SocialWaysHipError("%s does not take a clearance loss: the scene-clearance term is implemented for the "
+                                       "fused 64-unit SocialWaysTrainer only (hidden_size <= 64, n_latent_codes = 2); leave "
+                                       "clearance_loss = None" % type(self).__name__)
+
     def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None, noise=None):
         """The contract of SocialWaysTrainer.evaluate(); at these widths it is test() (no sampling kernels)."""
         self._device_noise(noise)

@@ -542,6 +542,45 @@ def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     return clear
 
 
+def clearance_grad(pos, start, scenes, d0, scale, dpos, loss=None, count=None):
+    """The scene-clearance penalty and its gradient (sw_clearance_grad): dpos[a, t, 0:2] += scale * d/d(pos[a, t]) of the sum
+    over the pairs a < b of every scene and the segments of max(0, 1 - |c|^2 / d0^2)^2, c the closest approach of the pair
+    within the segment (the quantity scene_clearance measures).  pos (B, Tp, 2 | 4) and dpos (B, Tp, 2 | 4), x and y
+    first, contiguous; dpos is accumulated into in place and returned; columns 2 and 3 of a 4-wide dpos are not touched.
+    start (B, >= 2) or None: the point in front of the Tp positions (any row stride: a view such as obsv[:, -1] is read in
+    place); it is data and takes no gradient.  d0 > 0 in the units of pos.  loss (B,) float32 / count (B,) int32 or None:
+    written with the agent's share of the unscaled penalty (loss.sum() = the penalty) and its number of (partner, segment)s
+    closer than d0.  Rows of agents with nothing closer than d0 are not written."""
+    for name, t in (("pos", pos), ("dpos", dpos)):
+        if t.dim() != 3 or t.shape[0] != scenes.B or t.shape[1] < 1 or t.shape[2] not in (2, 4) or t.dtype != torch.float32:
+            raise ValueError("%s must be float32 (B, Tp, 2 or 4) with B = %d, got %s" % (name, scenes.B, tuple(t.shape)))
+    B, Tp, pstride, dstride = pos.shape[0], pos.shape[1], pos.shape[2], dpos.shape[2]
+    if dpos.shape[1] != Tp:
+        raise ValueError("dpos must hold the Tp = %d steps of pos, got %s" % (Tp, tuple(dpos.shape)))
+    if not dpos.is_contiguous():
+        raise ValueError("dpos is accumulated into in place: it must be contiguous")
+    d0, scale = float(d0), float(scale)
+    if not (d0 > 0.0 and np.isfinite(d0)) or not np.isfinite(scale):
+        raise ValueError("d0 must be finite and > 0 and scale finite, got d0 = %r, scale = %r" % (d0, scale))
+    if start is not None and (start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != pos.device):
+        raise ValueError("start must be (B, >= 2) on the device of pos, got %s" % (tuple(start.shape),))
+    for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
+        if t is not None and (tuple(t.shape) != (B,) or t.dtype != dt or not t.is_contiguous() or t.device != pos.device):
+            raise ValueError("%s must be a contiguous %s tensor (B,) on the device of pos" % (name, dt))
+    if dpos.device != pos.device:
+        raise ValueError("dpos must be on the device of pos")
+    L.require_gpu(pos)
+    pos = pos.contiguous()
+    sstride = 0
+    if start is not None:
+        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
+            start = start[:, :2].float().contiguous()
+        sstride = start.stride(0)
+    L.call("sw_clearance_grad", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, Tp,
+           d0, scale, L.ptr(dpos), dstride, L.ptr(loss), L.ptr(count), L.stream())
+    return dpos
+
+
 def scene_reduce(err, clear, scenes, K, coll_dist):
     """per_scene (S, 6) = joint min ADE | joint min FDE | share of colliding draws | does draw kbest collide | min_k of the
     scene's clearance | share of colliding (draw, agent), and kbest (S,) int32 (sw_scene_reduce); clear may be None."""

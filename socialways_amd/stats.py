@@ -7,7 +7,8 @@ the reference (calc_statistics.py:62).
 Beyond the reference: `scene_clearance`, the closest approach between the agents of a scene along K joint futures - the
 quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere - and
 `sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise, and
-`compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`."""
+`compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`, and
+`clearance_penalty`, the pairwise clearance penalty and its gradient behind `SocialWaysTrainer.set_clearance_loss()`."""
 import os
 
 import numpy as np
@@ -150,6 +151,35 @@ def scene_clearance_len(trajs, sub_batches, lens, start=None, scale=1.0, device=
     scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
     clear = ops.scene_clearance(t4, start, scenes, K, float(scale), lens=lens)
     return clear if t.dim() == 4 else clear[0]
+
+
+def clearance_penalty(trajs, sub_batches, dist, start=None, scale=1.0, device="cuda"):
+    """The scene-clearance penalty SocialWaysTrainer.set_clearance_loss() trains against, for trajectories from anywhere
+    (`sw_clearance_grad`): per pair of agents of a scene and per segment, max(0, 1 - (scale |c|)^2 / dist^2)^2 with c the
+    closest approach of scene_clearance() - both agents moving linearly within the segment.  trajs (B, T, 2 | 4), x and y
+    first; sub_batches (S, 2) [start, end) rows tiling [0, B), [] = one scene; start (B, 2) or None: a point in front of
+    every path (the last observed position; it takes no gradient), giving T segments instead of T - 1.  `scale` converts
+    trajs to the units of `dist`, as in scene_clearance().  Returns device tensors (loss (B,), grad (B, T, 2), count (B,)
+    int32): the agent's share of the penalty (loss.sum() = the sum over pairs and segments), its gradient with respect to
+    trajs[..., :2] in the units of trajs, and the agent's number of (partner, segment)s closer than dist."""
+    t = _dev(trajs, device)
+    if t.dim() != 3 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
+        raise ValueError("trajs must be (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    B, T = t.shape[0], t.shape[1]
+    dist, scale = float(dist), float(scale)
+    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
+    if start is not None:
+        start = _dev(start, device)
+        if tuple(start.shape) != (B, 2):
+            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    L.require_gpu(t)
+    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    grad = torch.zeros(B, T, 2, device=t.device)
+    loss = torch.zeros(B, device=t.device)
+    count = torch.zeros(B, dtype=torch.int32, device=t.device)
+    ops.clearance_grad(t, start, scenes, dist / scale, 1.0, grad, loss, count)        # |scale c| < dist  <=>  |c| < dist / scale
+    return loss, grad, count
 
 
 def sample_modes(trajs, score, radius, top_m, metric="fde", sub_batches=None, scale=1.0, device="cuda"):

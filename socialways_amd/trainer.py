@@ -215,6 +215,8 @@ class SocialWaysTrainer:
     exchange_probe = None   # auto mode's probe measured - class-level defaults: the wider trainers have their own __init__
     noise = None            # a DeviceNoise: z of train_epoch() / evaluate*() from the device stream; None = the reference's host streams
     ragged_fused = False    # step(obs_len=...): D updates in one launch (sw_disc_update_ragged) and, with use_graph, captured steps
+    clearance_loss = None   # (dist, weight): the scene-clearance term of the generator loss (set_clearance_loss()); None = off
+    last_clearance = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_clearance_grad's outputs)
 
     def __new__(cls, n_next=None, hidden_size=64, *args, **kw):
         """Widths above the fused kernels' 64 units and latent-code counts other than 2 (train.py:42-44, 65) train on
@@ -236,6 +238,32 @@ class SocialWaysTrainer:
         if dn is not None and not isinstance(dn, DeviceNoise):
             raise TypeError("noise must be a DeviceNoise or None, got %s" % type(dn).__name__)
         return dn
+
+    def set_clearance_loss(self, dist, weight=1.0):
+        """Train against collisions: the generator loss gains L_col = weight / (Bg * Tp) * the sum over the scenes of the
+        packed batch, the pairs a < b of a scene and the Tp segments of max(0, 1 - |c|^2 / d0^2)^2 - c the closest approach of
+        the two predicted futures within the segment, each path starting at the agent's last observed position, both agents
+        moving linearly (the quantity behind col_* of evaluate_scenes(), sw_clearance_grad) - with d0 = dist * ss: `dist` is
+        in world units like evaluate_scenes()'s coll_dist, Bg the agents of the global packed batch (the L2 term's
+        normalisation).  The penalty is C1 where a pair reaches d0, its gradient continuous across the ends of a segment,
+        finite everywhere and exactly 0 for coincident agents.  One extra launch per step between the other terms on
+        d/d(pred_hat) and the generator's backward pass (which then runs un-fused from the D pass, as with use_l2_loss); dense
+        and ragged steps, eager and captured, single process and data parallel (scenes are sharded whole: every pair is
+        rank-local).  `last_clearance` = (loss (B,), count (B,) int32) then holds the last step's per-agent shares of the
+        unscaled sum and numbers of (partner, segment)s closer than d0 - views of buffers the next step overwrites;
+        L_col = weight / (Bg * Tp) * loss.sum().  weight 0 measures without training on it.  set_clearance_loss(None)
+        switches the term off: the step then makes exactly the launches it made before.  Assigning the tuple
+        (dist, weight) or None to `clearance_loss` does the same without the checks."""
+        if dist is None:
+            self.clearance_loss = None
+            self.last_clearance = None
+            return
+        dist, weight = float(dist), float(weight)
+        if not (np.isfinite(dist) and dist > 0.0):
+            raise ValueError("set_clearance_loss: dist must be finite and > 0, got %r" % dist)
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("set_clearance_loss: weight must be finite and >= 0, got %r" % weight)
+        self.clearance_loss = (dist, weight)
 
     def _pad_z(self, z):
         return z if z.shape[-1] == self.Z_COLS else torch.nn.functional.pad(z, (0, self.Z_COLS - z.shape[-1]))
@@ -491,7 +519,8 @@ class SocialWaysTrainer:
         return (scenes.key, To, float(ss), float(Bg), self._row0, K, self.n_unrolling_steps, self.use_info_loss,
                 self.loss_info_w, self.use_l2_loss, self.use_variety_loss, self.loss_l2_w, self.variety_k,
                 og["lr"], tuple(og["betas"]), og["eps"], og.get("weight_decay", 0), od["lr"], tuple(od["betas"]), od["eps"],
-                od.get("weight_decay", 0), ops.scene_wg(scenes, self.use_social, ragged), bool(ragged), bool(zdev))
+                od.get("weight_decay", 0), getattr(self, "clearance_loss", None),
+                ops.scene_wg(scenes, self.use_social, ragged), bool(ragged), bool(zdev))
 
     def _graphs_current(self):
         """A workspace outgrown since the last capture means captured graphs hold retired addresses: they stay valid
@@ -702,12 +731,14 @@ class SocialWaysTrainer:
         def body(kk):          # the K steps of one executable, back to back
             for j in range(K):
                 yield from one_step(j, pre=lambda j=j: stage(kk, j))
-        if st["graph"] is not None:
+        replayed = st["graph"] is not None
+        if replayed:
             st["flip"] = k
             for g, buf in st["graph"][k]:
                 g.replay()
                 if buf is not None:
                     self._allreduce(buf)
+            self.last_clearance = st["clearance"]              # the replayed launches wrote the buffers the capture saw
         elif st["n"] < 2:          # first steps of a layout run eagerly (lazy inits, workspace growth)
             st["n"] += 1
             for j in range(K):
@@ -750,6 +781,8 @@ class SocialWaysTrainer:
                 g.replay()
                 if buf is not None:
                     self._allreduce(buf)
+        if not replayed:
+            st["clearance"] = self.last_clearance              # set by _step_body (eager warm-up steps and the capture)
         st["done"][k].record()
         return st["outs"]
 
@@ -872,8 +905,9 @@ class SocialWaysTrainer:
         # the heads as two launches (same d/d(pred_hat), same loss sums)
         dfuse = None
         one_pass = ops.disc_dpred_supported(Tp)
+        clr = self.clearance_loss                               # an extra term on d/d(pred_hat), like use_l2_loss
         if (ops.DFUSE and one_pass and KV == 1 and not self.use_l2_loss and self.use_variety_loss is False
-                and obsv.shape[2] == 2 and ol is None):
+                and obsv.shape[2] == 2 and ol is None and clr is None):
             dfuse = (D._flat, pred_hat, targets, 1, noise, g_label, g_code, out[U + 1])
         dpred = None
         if dfuse is None and one_pass:
@@ -896,6 +930,13 @@ class SocialWaysTrainer:
                    L.ptr(kmin), L.ptr(l2min), L.stream())
             self.last_variety = (l2min, kmin)
             dpred = dk
+        self.last_clearance = None
+        if clr is not None:
+            # the scene-clearance term (set_clearance_loss()) on the prediction every other term sees (copy 0 of the K-sample
+            # step): rows [0, B).  Its outputs live in the workspace so that a replayed graph finds them where it was captured.
+            closs, ccount = ws.get("clr_loss", B)[:B], ws.get("clr_count", B)[:B].view(torch.int32)
+            ops.clearance_grad(pred_hat, obsv[:, -1], scenes, clr[0] * float(ss), clr[1] / (Bg * Tp), dpred[:B], closs, ccount)
+            self.last_clearance = (closs, ccount)
         restore = None
         if self.n_unrolling_steps > 0:     # D.load(backup) restores the Linear layers only (train.py:311-316, 541-542); D is
             if self._lin_maskf is None:    # not read again in this step: done by idle workgroups of the decode BPTT launch
