@@ -42,24 +42,15 @@ __global__ __launch_bounds__(64) void clearance_grad_kernel(const float* __restr
     for (int t0 = 0; t0 < NS; t0 += SC_TC) {
       const int nseg = NS - t0 < SC_TC ? NS - t0 : SC_TC;
       float2 own[SC_NP], g[SC_NP];
+      sc_load_own(own, pos, pstride, start, sstride, row, s0 + ac, Tp, t0, nseg);
 #pragma unroll
-      for (int p = 0; p < SC_NP; ++p) {
-        own[p] = p <= nseg ? sc_point(pos, pstride, start, sstride, row, s0 + ac, Tp, t0 + p) : float2{0.f, 0.f};
-        g[p] = float2{0.f, 0.f};
-      }
+      for (int p = 0; p < SC_NP; ++p) g[p] = float2{0.f, 0.f};
       int hit = 0;                                         // active (partner, segment)s of this chunk
       for (int b0 = 0; b0 < n; b0 += 64) {
         const int nb = n - b0 < 64 ? n - b0 : 64;
+        const int bc = b0 + lane < n ? b0 + lane : n - 1;
         __syncthreads();                                   // the previous tile has been read
-        if (b0 == a0) {
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p) tile[lane * SC_NP + p] = own[p];
-        } else {
-          const int bc = b0 + lane < n ? b0 + lane : n - 1;
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p)
-            if (p <= nseg) tile[lane * SC_NP + p] = sc_point(pos, pstride, start, sstride, (size_t)s0 + bc, s0 + bc, Tp, t0 + p);
-        }
+        sc_stage_row(tile + lane * SC_NP, own, b0 == a0, pos, pstride, start, sstride, (size_t)s0 + bc, s0 + bc, Tp, t0, nseg);
         __syncthreads();
         for (int b = 0; b < nb; ++b) {
           const float2* q = tile + b * SC_NP;              // one address for the wave: a broadcast read

@@ -35,6 +35,39 @@ __device__ __forceinline__ void sw_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 __device__ __forceinline__ int sw_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ int sw_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
+// What the one-workgroup-per-agent attention kernels (sw_modules.hip, sw_generic.hip) share.  The scene of row i among S
+// scenes, scene_off[s] <= i < scene_off[s + 1] -> s; [s0, s1) = its rows.
+__device__ __forceinline__ int sw_scene_of(const int* __restrict__ scene_off, int S, int i, int& s0, int& s1) {
+  int lo = 0, hi = S - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (scene_off[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  s0 = scene_off[lo];
+  s1 = scene_off[lo + 1];
+  return lo;
+}
+// Sum / maximum of v over a workgroup of 256 threads, in every thread (red: 4 floats of LDS, free again on return)
+__device__ __forceinline__ float sw_block_sum(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return v;
+}
+__device__ __forceinline__ float sw_block_max(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return v;
+}
+
 // Gate non-linearities.  SW_FAST_ACT=1 (default): v_exp_f32 / v_rcp_f32 forms (each ~1 ulp of its own
 // result; |abs err| of sigmoid/tanh <= ~2e-7), 5-7 VALU ops instead of the ~40-op ocml expf/tanhf -
 // the LSTM cell is latency-bound on exactly this chain.  SW_FAST_ACT=0 builds the ocml versions.

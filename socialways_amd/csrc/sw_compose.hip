@@ -23,7 +23,7 @@ struct CmpArgs {
 };
 
 __device__ __forceinline__ int cmp_len(const CmpArgs& A, int row) {           // countable segments of an agent
-  return A.len ? min(max(A.len[row], 1), A.Tp) - A.first : A.NS;
+  return A.len ? sc_len(A.len, row, A.Tp, A.first) : A.NS;
 }
 
 // sel0: the draw with the highest score, the lowest k of equal ones (ascending k, strict >)
@@ -92,21 +92,8 @@ struct CmpScene {
                    : (ST && CUR) ? sp[a * NPs + t0 + p]
                    : (!CUR && slot >= 0) ? cand[slot * NPs + t0 + p]
                                          : sc_point(A.pos, A.pstride, A.start, A.sstride, row, s0 + a, A.Tp, t0 + p);
-        const float2 q0 = partner(bc, brow, t0);
-        const int limc = lim - t0;                           // countable segments of the pair in this chunk (<= 0: none)
-        float rx = own[0].x - q0.x, ry = own[0].y - q0.y;    // r0 of the first segment
-#pragma unroll
-        for (int t4 = 0; t4 < SC_TC; t4 += 4) {
-          if (t4 + 4 <= nseg) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-              sc_segment_if(t4 + u < limc, own[t4 + u + 1], partner(bc, brow, t0 + t4 + u + 1), rx, ry, m);
-          } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-              if (t4 + u < nseg) sc_segment_if(t4 + u < limc, own[t4 + u + 1], partner(bc, brow, t0 + t4 + u + 1), rx, ry, m);
-          }
-        }
+        const auto q = [&](int p) { return partner(bc, brow, t0 + p); };
+        SC_CHUNK(true, own, q, nseg, lim - t0, m);          // lim - t0: the pair's countable segments in this chunk (<= 0: none)
       }
       count += __popcll(__ballot(other && sqrtf(m) * A.inv_ss < A.coll) & gmask);
       best = other ? fminf(best, m) : best;

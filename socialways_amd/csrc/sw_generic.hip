@@ -10,38 +10,6 @@
 #include "../../include/socialways_hip.h"
 #include "sw_common.h"
 
-namespace {
-__device__ __forceinline__ void scene_of(const int* __restrict__ scene_off, int S, int i, int& s, int& s0, int& s1) {
-  int lo = 0, hi = S - 1;
-  while (lo < hi) {       // the scene with scene_off[s] <= i < scene_off[s+1]
-    const int mid = (lo + hi + 1) >> 1;
-    if (scene_off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  s = lo;
-  s0 = scene_off[lo];
-  s1 = scene_off[lo + 1];
-}
-__device__ __forceinline__ float gblock_sum(float v, float* red) {   // 256 threads
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
-__device__ __forceinline__ float gblock_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
-}
-}  // namespace
-
 // ---- LSTM cell, element-wise part: pre [B][4H] = W_ih x + b_ih + W_hh h + b_hh (gate blocks i | f | g | o) ------------
 __global__ __launch_bounds__(256) void lstm_point_fwd_kernel(const float* __restrict__ pre, const float* __restrict__ c_prev,
                                                              int B, int H, float* __restrict__ gates, float* __restrict__ c,
@@ -167,8 +135,8 @@ __global__ __launch_bounds__(256) void attn_pairs_fwd_kernel(const float* __rest
                                                              float* __restrict__ attn, float* __restrict__ S_out) {
   __shared__ float red[4];
   const int i = blockIdx.x, t = threadIdx.x;
-  int s, s0, s1;
-  scene_of(scene_off, S, i, s, s0, s1);
+  int s0, s1;
+  const int s = sw_scene_of(scene_off, S, i, s0, s1);
   const int n = s1 - s0;
   if (n == 1) {
     for (int u = t; u < H; u += 256) S_out[(size_t)i * H + u] = 0.f;
@@ -194,14 +162,14 @@ __global__ __launch_bounds__(256) void attn_pairs_fwd_kernel(const float* __rest
     arow[j] = sc;
     m = fmaxf(m, sc);
   }
-  m = gblock_max(m, red);
+  m = sw_block_max(m, red);
   float sum = 0.f;
   for (int j = t; j < n; j += 256) {
     const float e = expf(arow[j] - m);
     arow[j] = e;
     sum += e;
   }
-  sum = gblock_sum(sum, red);
+  sum = sw_block_sum(sum, red);
   for (int j = t; j < n; j += 256) arow[j] = arow[j] / sum;
   __syncthreads();
   for (int u = t; u < H; u += 256) {
@@ -219,8 +187,8 @@ __global__ __launch_bounds__(256) void attn_pairs_bwd_row_kernel(const float* __
                                                                  float* __restrict__ dsig, float* __restrict__ df) {
   __shared__ float red[4];
   const int i = blockIdx.x, t = threadIdx.x;
-  int s, s0, s1;
-  scene_of(scene_off, S, i, s, s0, s1);
+  int s0, s1;
+  const int s = sw_scene_of(scene_off, S, i, s0, s1);
   const int n = s1 - s0;
   if (n == 1) return;
   const long long p0 = pair_off[s] + (long long)(i - s0) * n;
@@ -235,7 +203,7 @@ __global__ __launch_bounds__(256) void attn_pairs_bwd_row_kernel(const float* __
     drow[j] = da;
     tsum = fmaf(arow[j], da, tsum);
   }
-  tsum = gblock_sum(tsum, red);
+  tsum = sw_block_sum(tsum, red);
   for (int j = t; j < n; j += 256) drow[j] = (s0 + j == i) ? 0.f : arow[j] * (drow[j] - tsum);
   __syncthreads();
   if (df) {
@@ -252,8 +220,8 @@ __global__ __launch_bounds__(256) void attn_pairs_bwd_col_kernel(const float* __
                                                                  const long long* __restrict__ pair_off, int S, int F, int H,
                                                                  float* __restrict__ dwh, float* __restrict__ dh) {
   const int j = blockIdx.x, t = threadIdx.x;
-  int s, s0, s1;
-  scene_of(scene_off, S, j, s, s0, s1);
+  int s0, s1;
+  const int s = sw_scene_of(scene_off, S, j, s0, s1);
   const int n = s1 - s0;
   if (n == 1) {
     for (int k = t; k < F; k += 256) dwh[(size_t)j * F + k] = 0.f;

@@ -94,34 +94,6 @@ extern "C" int sw_linear_wgrad(const float* delta, int ldd, const float* act, in
 // ---- AttentionPooling on a dense embedding tensor, one workgroup per agent, any scene size -------------------------
 // f [B][B][64] (only in-scene blocks are read), h [B][64], wh = W h + b [B][64] (sw_rows_gemm), scene_off [S+1].
 namespace {
-__device__ __forceinline__ void find_scene(const int* __restrict__ scene_off, int S, int i, int& s0, int& s1) {
-  int lo = 0, hi = S - 1;
-  while (lo < hi) {       // the scene with scene_off[s] <= i < scene_off[s+1]
-    const int mid = (lo + hi + 1) >> 1;
-    if (scene_off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  s0 = scene_off[lo];
-  s1 = scene_off[lo + 1];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
 __device__ __forceinline__ float dot64(const float* __restrict__ a, const float* __restrict__ b) {
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -144,7 +116,7 @@ __global__ __launch_bounds__(256) void attention_dense_row_fwd_kernel(const floa
   __shared__ float part[4][64];
   const int i = blockIdx.x;
   int s0, s1;
-  find_scene(scene_off, S, i, s0, s1);
+  sw_scene_of(scene_off, S, i, s0, s1);
   const int n = s1 - s0, t = threadIdx.x;
   float* arow = attn + (size_t)i * B + s0;
   if (n == 1) {
@@ -158,14 +130,14 @@ __global__ __launch_bounds__(256) void attention_dense_row_fwd_kernel(const floa
     arow[j] = sc;
     m = fmaxf(m, sc);
   }
-  m = block_max(m, red);
+  m = sw_block_max(m, red);
   float sum = 0.f;
   for (int j = t; j < n; j += 256) {
     const float e = expf(arow[j] - m);
     arow[j] = e;
     sum += e;
   }
-  sum = block_sum(sum, red);
+  sum = sw_block_sum(sum, red);
   for (int j = t; j < n; j += 256) arow[j] = arow[j] / sum;
   __syncthreads();
   const int u = t & 63, g = t >> 6;
@@ -186,7 +158,7 @@ __global__ __launch_bounds__(256) void attention_dense_row_bwd_kernel(const floa
   __shared__ float red[4];
   const int i = blockIdx.x;
   int s0, s1;
-  find_scene(scene_off, S, i, s0, s1);
+  sw_scene_of(scene_off, S, i, s0, s1);
   const int n = s1 - s0, t = threadIdx.x;
   const float* arow = attn + (size_t)i * B + s0;
   float* drow = dsig + (size_t)i * B + s0;
@@ -201,7 +173,7 @@ __global__ __launch_bounds__(256) void attention_dense_row_bwd_kernel(const floa
     drow[j] = da;
     tsum = fmaf(arow[j], da, tsum);
   }
-  tsum = block_sum(tsum, red);
+  tsum = sw_block_sum(tsum, red);
   for (int j = t; j < n; j += 256) drow[j] = (s0 + j == i) ? 0.f : arow[j] * (drow[j] - tsum);
   __syncthreads();
   if (df) {
@@ -223,7 +195,7 @@ __global__ __launch_bounds__(256) void attention_dense_col_bwd_kernel(const floa
   __shared__ float p1[4][64], p2[4][64];
   const int j = blockIdx.x;
   int s0, s1;
-  find_scene(scene_off, S, j, s0, s1);
+  sw_scene_of(scene_off, S, j, s0, s1);
   const int n = s1 - s0, t = threadIdx.x, u = t & 63, g = t >> 6;
   float a1 = 0.f, a2 = 0.f;
   if (n > 1) {

@@ -7,104 +7,27 @@
 #include "sw_scene_dev.h"
 #include <stdint.h>
 
-// ---- clearance (definition in include/socialways_hip.h) -----------------------------------------------------------------
+// ---- clearance, dense and with ragged futures (definitions in include/socialways_hip.h) ----------------------------------
 //   One wave per (scene, group of 64 / n_pad draws); blockIdx.x = scene * K + group, groups past the scene's last one
 //   leave at once (the host does not know the scene sizes).  Lane (kk, al) owns clear[k0 + kk][agent a0 + al]: its own
 //   SC_TC + 1 points sit in registers, the paths of a tile of up to 64 partner agents sit in LDS (one row per lane, the
 //   lane's own points when the partner tile is its tile), and the lane walks partners x segments taking the minimum of
 //   the squared distance - one owner per output, no atomics.  Scenes above 64 agents loop over agent tiles on both sides,
 //   longer futures over time chunks.  Lanes past n or K compute on clamped indices and do not store.
+//   LEN: a length per agent.  Agent a has va = len[a] - (start ? 0 : 1) countable segments (len clamped into 1 .. Tp); the
+//   segment of pair (a, b) with global index j counts if j < min(va, vb).  The partner's count travels with its tile (tlen,
+//   written between the tile's two barriers).  r0 advances through every segment and only the minimum is gated, by a
+//   select: the countable segments are a prefix, so whatever the padding holds - NaN included - never reaches one.  All
+//   lengths n: the bits of the dense kernel on the paths cut to n frames (same chunk boundaries, same segment arithmetic;
+//   min is exact).  Without LEN there is no tlen, len is not read and the minimum is not gated.
+template <bool LEN>
 __global__ __launch_bounds__(64) void scene_clearance_kernel(const float* __restrict__ pos, int pstride,
                                                              const float* __restrict__ start, int sstride,
-                                                             const int* __restrict__ scene_off, int B, int K, int Tp,
+                                                             const int* __restrict__ scene_off,
+                                                             const int* __restrict__ len, int B, int K, int Tp,
                                                              float inv_ss, float* __restrict__ clear) {
-  __shared__ float2 tile[64 * SC_NP];
-  const int s = blockIdx.x / K, g = blockIdx.x - s * K;
-  const int s0 = scene_off[s], n = scene_off[s + 1] - s0;
-  const int lg = sc_log2_pad(n), n_pad = 1 << lg;
-  const int k0 = g * (64 >> lg);
-  if (k0 >= K || n <= 0) return;                           // uniform: in front of every barrier
-  const int lane = threadIdx.x, al = lane & (n_pad - 1), kk = lane >> lg;
-  const int k = k0 + kk, kc = k < K ? k : K - 1;
-  const int NS = Tp - (start ? 0 : 1);                     // segments of a path
-  const float INF = __builtin_inff();
-  const float2* mine = tile + (size_t)(kk << lg) * SC_NP;  // the partner rows of this lane's draw
-
-  for (int a0 = 0; a0 < n; a0 += n_pad) {
-    const int a = a0 + al, ac = a < n ? a : n - 1;
-    const size_t row = (size_t)kc * B + s0 + ac;
-    float best = INF;
-    for (int t0 = 0; t0 < NS; t0 += SC_TC) {
-      const int nseg = NS - t0 < SC_TC ? NS - t0 : SC_TC;
-      float2 own[SC_NP];
-#pragma unroll
-      for (int p = 0; p < SC_NP; ++p)
-        own[p] = p <= nseg ? sc_point(pos, pstride, start, sstride, row, s0 + ac, Tp, t0 + p) : float2{0.f, 0.f};
-      for (int b0 = 0; b0 < n; b0 += n_pad) {
-        const int nb = n - b0 < n_pad ? n - b0 : n_pad;
-        __syncthreads();                                   // the previous tile has been read
-        if (b0 == a0) {
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p) tile[lane * SC_NP + p] = own[p];
-        } else {
-          const int bc = b0 + al < n ? b0 + al : n - 1;
-          const size_t brow = (size_t)kc * B + s0 + bc;
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p)
-            if (p <= nseg) tile[lane * SC_NP + p] = sc_point(pos, pstride, start, sstride, brow, s0 + bc, Tp, t0 + p);
-        }
-        __syncthreads();
-        for (int b = 0; b < nb; ++b) {
-          const float2* q = mine + b * SC_NP;
-          const float2 q0 = q[0];
-          float rx = own[0].x - q0.x, ry = own[0].y - q0.y;      // r0 of the first segment
-          float m = INF;
-#pragma unroll
-          for (int t4 = 0; t4 < SC_TC; t4 += 4) {              // whole groups of four segments without a branch between them
-            if (t4 + 4 <= nseg) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) sc_segment(own[t4 + u + 1], q[t4 + u + 1], rx, ry, m);
-            } else {
-#pragma unroll
-              for (int u = 0; u < 4; ++u)
-                if (t4 + u < nseg) sc_segment(own[t4 + u + 1], q[t4 + u + 1], rx, ry, m);
-            }
-          }
-          best = (b0 + b == a) ? best : fminf(best, m);
-        }
-      }
-    }
-    if (a < n && k < K) clear[(size_t)k * B + s0 + a] = sqrtf(best) * inv_ss;
-  }
-}
-
-extern "C" int sw_scene_clearance(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
-                                  int S, int B, int K, int Tp, float inv_ss, float* clear, void* stream) {
-  if (!pos || !scene_off || !clear || S < 0 || B < 0 || K < 1 || Tp < 1 || !(inv_ss > 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || ((uintptr_t)pos & 7)) return SW_EARG;       // positions are read as float2
-  if (start && sstride < 2) return SW_EARG;
-  if ((long long)S * K > 0x7fffffffLL) return SW_EARG;
-  if (B == 0 || S == 0) return SW_OK;
-  SW_LAUNCH(scene_clearance_kernel, dim3((unsigned)(S * K)), dim3(64), 0, (hipStream_t)stream, pos, pstride, start, sstride,
-            scene_off, B, K, Tp, inv_ss, clear);
-  SW_CHECK_LAUNCH("scene_clearance_kernel");
-  return SW_OK;
-}
-
-// ---- clearance with ragged futures (definition in include/socialways_hip.h) ----------------------------------------------
-//   scene_clearance_kernel with a length per agent: the same lanes, time chunks and agent tiles, one owner per output.
-//   Agent a has va = len[a] - (start ? 0 : 1) countable segments (len clamped into 1 .. Tp); the segment of pair (a, b)
-//   with global index j counts if j < min(va, vb).  The partner's count travels with its tile (tlen, written between the
-//   tile's two barriers).  r0 advances through every segment and only the minimum is gated, by a select: the countable
-//   segments are a prefix, so whatever the padding holds - NaN included - never reaches one.  All lengths n: the bits of
-//   the dense kernel on the paths cut to n frames (same chunk boundaries, same segment arithmetic; min is exact).
-__global__ __launch_bounds__(64) void scene_clearance_len_kernel(const float* __restrict__ pos, int pstride,
-                                                                 const float* __restrict__ start, int sstride,
-                                                                 const int* __restrict__ scene_off,
-                                                                 const int* __restrict__ len, int B, int K, int Tp,
-                                                                 float inv_ss, float* __restrict__ clear) {
-  __shared__ float2 tile[64 * SC_NP];
-  __shared__ int tlen[64];
+  __shared__ float2 tile[64 * SC_NP + (LEN ? 32 : 0)];    // LEN: the 64 counts of the tile's agents behind its points
+  int* tlen = reinterpret_cast<int*>(tile + 64 * SC_NP);
   const int s = blockIdx.x / K, g = blockIdx.x - s * K;
   const int s0 = scene_off[s], n = scene_off[s + 1] - s0;
   const int lg = sc_log2_pad(n), n_pad = 1 << lg;
@@ -121,47 +44,27 @@ __global__ __launch_bounds__(64) void scene_clearance_len_kernel(const float* __
   for (int a0 = 0; a0 < n; a0 += n_pad) {
     const int a = a0 + al, ac = a < n ? a : n - 1;
     const size_t row = (size_t)kc * B + s0 + ac;
-    const int va = min(max(len[s0 + ac], 1), Tp) - first;
+    int va = 0;
+    if constexpr (LEN) va = sc_len(len, s0 + ac, Tp, first);
     float best = INF;
     for (int t0 = 0; t0 < NS; t0 += SC_TC) {
       const int nseg = NS - t0 < SC_TC ? NS - t0 : SC_TC;
       float2 own[SC_NP];
-#pragma unroll
-      for (int p = 0; p < SC_NP; ++p)
-        own[p] = p <= nseg ? sc_point(pos, pstride, start, sstride, row, s0 + ac, Tp, t0 + p) : float2{0.f, 0.f};
+      sc_load_own(own, pos, pstride, start, sstride, row, s0 + ac, Tp, t0, nseg);
       for (int b0 = 0; b0 < n; b0 += n_pad) {
         const int nb = n - b0 < n_pad ? n - b0 : n_pad;
+        const int bc = b0 + al < n ? b0 + al : n - 1;
         __syncthreads();                                   // the previous tile has been read
-        if (b0 == a0) {
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p) tile[lane * SC_NP + p] = own[p];
-          tlen[lane] = va;
-        } else {
-          const int bc = b0 + al < n ? b0 + al : n - 1;
-          const size_t brow = (size_t)kc * B + s0 + bc;
-#pragma unroll
-          for (int p = 0; p < SC_NP; ++p)
-            if (p <= nseg) tile[lane * SC_NP + p] = sc_point(pos, pstride, start, sstride, brow, s0 + bc, Tp, t0 + p);
-          tlen[lane] = min(max(len[s0 + bc], 1), Tp) - first;
-        }
+        sc_stage_row(tile + lane * SC_NP, own, b0 == a0, pos, pstride, start, sstride, (size_t)kc * B + s0 + bc, s0 + bc, Tp,
+                     t0, nseg);
+        if constexpr (LEN) tlen[lane] = b0 == a0 ? va : sc_len(len, s0 + bc, Tp, first);
         __syncthreads();
         for (int b = 0; b < nb; ++b) {
-          const float2* q = mine + b * SC_NP;
-          const float2 q0 = q[0];
-          const int lim = min(va, mlen[b]) - t0;               // countable segments of the pair in this chunk (<= 0: none)
-          float rx = own[0].x - q0.x, ry = own[0].y - q0.y;      // r0 of the first segment
+          const auto q = [row = mine + b * SC_NP](int p) { return row[p]; };
+          int lim = 0;                                     // countable segments of the pair in this chunk (<= 0: none)
+          if constexpr (LEN) lim = min(va, mlen[b]) - t0;
           float m = INF;
-#pragma unroll
-          for (int t4 = 0; t4 < SC_TC; t4 += 4) {              // whole groups of four segments without a branch between them
-            if (t4 + 4 <= nseg) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) sc_segment_if(t4 + u < lim, own[t4 + u + 1], q[t4 + u + 1], rx, ry, m);
-            } else {
-#pragma unroll
-              for (int u = 0; u < 4; ++u)
-                if (t4 + u < nseg) sc_segment_if(t4 + u < lim, own[t4 + u + 1], q[t4 + u + 1], rx, ry, m);
-            }
-          }
+          SC_CHUNK(LEN, own, q, nseg, lim, m);
           best = (b0 + b == a) ? best : fminf(best, m);
         }
       }
@@ -170,18 +73,29 @@ __global__ __launch_bounds__(64) void scene_clearance_len_kernel(const float* __
   }
 }
 
+// both entries: the dense launch without lengths
 extern "C" int sw_scene_clearance_len(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
                                       const int* len, int S, int B, int K, int Tp, float inv_ss, float* clear, void* stream) {
-  if (!len) return sw_scene_clearance(pos, pstride, start, sstride, scene_off, S, B, K, Tp, inv_ss, clear, stream);
   if (!pos || !scene_off || !clear || S < 0 || B < 0 || K < 1 || Tp < 1 || !(inv_ss > 0.f)) return SW_EARG;
   if ((pstride != 2 && pstride != 4) || ((uintptr_t)pos & 7)) return SW_EARG;       // positions are read as float2
   if (start && sstride < 2) return SW_EARG;
   if ((long long)S * K > 0x7fffffffLL) return SW_EARG;
   if (B == 0 || S == 0) return SW_OK;
-  SW_LAUNCH(scene_clearance_len_kernel, dim3((unsigned)(S * K)), dim3(64), 0, (hipStream_t)stream, pos, pstride, start, sstride,
-            scene_off, len, B, K, Tp, inv_ss, clear);
-  SW_CHECK_LAUNCH("scene_clearance_len_kernel");
+  if (len) {
+    SW_LAUNCH_AS("scene_clearance_len_kernel", scene_clearance_kernel<true>, dim3((unsigned)(S * K)), dim3(64), 0,
+                 (hipStream_t)stream, pos, pstride, start, sstride, scene_off, len, B, K, Tp, inv_ss, clear);
+    SW_CHECK_LAUNCH("scene_clearance_len_kernel");
+  } else {
+    SW_LAUNCH_AS("scene_clearance_kernel", scene_clearance_kernel<false>, dim3((unsigned)(S * K)), dim3(64), 0,
+                 (hipStream_t)stream, pos, pstride, start, sstride, scene_off, len, B, K, Tp, inv_ss, clear);
+    SW_CHECK_LAUNCH("scene_clearance_kernel");
+  }
   return SW_OK;
+}
+
+extern "C" int sw_scene_clearance(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
+                                  int S, int B, int K, int Tp, float inv_ss, float* clear, void* stream) {
+  return sw_scene_clearance_len(pos, pstride, start, sstride, scene_off, nullptr, S, B, K, Tp, inv_ss, clear, stream);
 }
 
 // ---- per-scene reduction -------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
-// sw_scene_dev.h - the device pieces sw_scene.hip and sw_compose.hip share: the points of a path, the closest approach
-// of two linearly moving points within one segment, and the lane layout of a scene.  Both files form a clearance from
-// these and nothing else, so a clearance of sw_scene_compose carries the bits sw_scene_clearance gives the same two paths.
+// sw_scene_dev.h - the device pieces sw_scene.hip, sw_compose.hip and sw_clearance_grad.hip share: the points of a path,
+// the closest approach of two linearly moving points within one segment, the lane layout of a scene, and the walk over the
+// pairs of a scene (the chunk of a pair, a lane's own points, the partner tile).  sw_scene.hip and sw_compose.hip form a
+// clearance from these and nothing else, so a clearance of sw_scene_compose carries the bits sw_scene_clearance gives the
+// same two paths.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -64,4 +66,61 @@ __device__ __forceinline__ void sc_segment_if(bool on, float2 pa, float2 pb, flo
   float mm = m;
   sc_segment(pa, pb, rx, ry, mm);
   m = on ? mm : m;
+}
+
+// countable segments of an agent with ragged futures: len clamped into 1 .. Tp, first = the frame at which segment 0 ends
+__device__ __forceinline__ int sc_len(const int* __restrict__ len, int agent, int Tp, int first) {
+  return min(max(len[agent], 1), Tp) - first;
+}
+
+// ---- the pair walk: agent tiles x time chunks of SC_TC segments x partner tiles x partners x segments -------------------
+// The chunk of one pair: m = min(m, squared closest approach) over its nseg segments, in ascending order.  own = the lane's
+// points t0 .. t0 + nseg of the chunk, q(p) = the partner's point t0 + p (an LDS row, or wherever it lies).  GATED: r0
+// advances through every segment and only segment j < lim folds (sc_segment_if); else all of them do (sc_segment; lim is
+// not evaluated).  Whole groups of four segments without a branch between them, the tail guarded.
+// A macro, not a function: behind a function boundary - partner by functor or by pointer, own by reference or by pointer,
+// r0 and m in the caller or in the callee - the dense clearance kernel's groups come out of the scheduler one s_nop longer
+// (62 instructions for 61), 1.5 - 1.9 % of the launch on 64-agent scenes (profiles/scene_walk_resource_usage.txt).
+#define SC_CHUNK_SEG_(GATED, j, own, q, lim, rx, ry, m)                                  \
+  do {                                                                                   \
+    if constexpr (GATED) sc_segment_if((j) < (lim), (own)[(j) + 1], q((j) + 1), rx, ry, m); \
+    else sc_segment((own)[(j) + 1], q((j) + 1), rx, ry, m);                              \
+  } while (0)
+#define SC_CHUNK(GATED, own, q, nseg, lim, m)                                            \
+  do {                                                                                   \
+    const float2 q0_ = q(0);                                                             \
+    float rx_ = (own)[0].x - q0_.x, ry_ = (own)[0].y - q0_.y; /* r0 of the first segment */ \
+    _Pragma("unroll") for (int t4_ = 0; t4_ < SC_TC; t4_ += 4) {                         \
+      if (t4_ + 4 <= (nseg)) {                                                           \
+        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_) SC_CHUNK_SEG_(GATED, t4_ + u_, own, q, lim, rx_, ry_, m); \
+      } else {                                                                           \
+        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_)                                 \
+          if (t4_ + u_ < (nseg)) SC_CHUNK_SEG_(GATED, t4_ + u_, own, q, lim, rx_, ry_, m); \
+      }                                                                                  \
+    }                                                                                    \
+  } while (0)
+
+// the lane's own points of the chunk at t0 into registers (zeros behind the chunk's last point)
+__device__ __forceinline__ void sc_load_own(float2 (&own)[SC_NP], const float* __restrict__ pos, int pstride,
+                                            const float* __restrict__ start, int sstride, size_t row, int agent, int Tp,
+                                            int t0, int nseg) {
+#pragma unroll
+  for (int p = 0; p < SC_NP; ++p)
+    own[p] = p <= nseg ? sc_point(pos, pstride, start, sstride, row, agent, Tp, t0 + p) : float2{0.f, 0.f};
+}
+
+// One lane's row of the partner tile: its own points when the partner tile is its tile (same), else the chunk's points of
+// (brow, bagent), which the caller has clamped into the scene.  The caller puts a barrier in front (the previous tile has
+// been read) and one behind, both outside every lane-dependent condition; `same` is the same in every lane.
+__device__ __forceinline__ void sc_stage_row(float2* trow, const float2 (&own)[SC_NP], bool same,
+                                             const float* __restrict__ pos, int pstride, const float* __restrict__ start,
+                                             int sstride, size_t brow, int bagent, int Tp, int t0, int nseg) {
+  if (same) {
+#pragma unroll
+    for (int p = 0; p < SC_NP; ++p) trow[p] = own[p];
+  } else {
+#pragma unroll
+    for (int p = 0; p < SC_NP; ++p)
+      if (p <= nseg) trow[p] = sc_point(pos, pstride, start, sstride, brow, bagent, Tp, t0 + p);
+  }
 }

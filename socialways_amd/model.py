@@ -21,7 +21,6 @@ Differentiable entry points: the two functions train() differentiates - `predict
 composed differently from predict() still trains.  `SocialFeatures` / `get_traj_4d` act on track data and carry no
 gradient.
 """
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -175,8 +174,7 @@ class _Packed(nn.Module):
         return [gflat[off:off + k].view(p.shape) for (off, k), p in zip(self._slices, self.parameters())]
 
 
-def _scene_index(sub_batches, B, device):
-    return ops.SceneIndex.get(sub_batches if len(sub_batches) else np.zeros((0, 2), np.int64), B, device)
+_scene_index = ops.SceneIndex.get
 
 
 # ------------------------------------------------------------------------------------------------

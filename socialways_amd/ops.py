@@ -53,7 +53,8 @@ class SceneIndex:
 
     @classmethod
     def get(cls, sub_batches, B, device):
-        sb = np.ascontiguousarray(np.asarray(sub_batches, dtype=np.int64))
+        """The cached index of `sub_batches`, given as anything numpy reads as (S, 2) integer rows; [] = one scene of all B rows."""
+        sb = np.ascontiguousarray(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2))
         key = (sb.tobytes(), int(B), str(device))
         hit = cls._cache.get(key)
         if hit is None:
@@ -512,6 +513,30 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
     return pred4, (per_agent, best, err)
 
 
+def _check_pos(pos, K, B, score=None):
+    """The K draws' positions as the scene-level wrappers take them, checked without touching the device: pos (K * B, Tp, 2 | 4)
+    or (K, B, Tp, 2 | 4), x and y first, on the device of `score` when one is given -> (Tp, pstride)."""
+    sh = tuple(pos.shape)
+    if len(sh) not in (3, 4) or sh[-1] not in (2, 4) or sh[-2] < 1 or (sh[:2] != (K, B) if len(sh) == 4 else sh[0] != K * B):
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, sh))
+    if score is not None and pos.device != score.device:
+        raise ValueError("pos must be on the device of score")
+    return sh[-2], sh[-1]
+
+
+def _start_arg(start, B, device, of="pos"):
+    """start (B, >= 2) or None - the point in front of the Tp positions, on `device` (that of the argument `of`) - checked without
+    touching the device -> (start, sstride) as the kernels read it: float32 rows of any stride >= 2 in place (a view such as
+    obsv[:, -1]), anything else as a packed copy of its first two columns; (None, 0) without one."""
+    if start is None:
+        return None, 0
+    if start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != device:
+        raise ValueError("start must be (B, >= 2) = (%d, >= 2) on the device of %s, got %s" % (B, of, tuple(start.shape)))
+    if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
+        start = start[:, :2].float().contiguous()
+    return start, start.stride(0)
+
+
 def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     """clear (K, B): per draw and agent the closest approach to another agent of its scene, times inv_ss; +inf in
     single-agent scenes (sw_scene_clearance).  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or
@@ -519,26 +544,16 @@ def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     lens (B,) int32 on the device: ragged futures - agent a is present for its first lens[a] frames (in every draw), and the
     segment of a pair that ends at frame t counts only if both are present at t; +inf where nothing counts
     (sw_scene_clearance_len).  None: the dense launch."""
+    B = scenes.B
+    Tp, pstride = _check_pos(pos, K, B)
+    start, sstride = _start_arg(start, B, pos.device)
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
     L.require_gpu(pos)
     pos = pos.contiguous()
-    Tp, pstride, B = pos.shape[-2], pos.shape[-1], scenes.B
-    if pstride not in (2, 4) or pos.numel() != K * B * Tp * pstride:
-        raise ValueError("pos must be (K * B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
-    sstride = 0
-    if start is not None:
-        if start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != pos.device:
-            raise ValueError("start must be (B, >= 2) on the device of pos, got %s" % (tuple(start.shape),))
-        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
-            start = start[:, :2].float().contiguous()
-        sstride = start.stride(0)
     clear = torch.empty(K, B, device=pos.device)
-    if lens is None:
-        L.call("sw_scene_clearance", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, K,
-               Tp, float(inv_ss), L.ptr(clear), L.stream())
-    else:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
-        L.call("sw_scene_clearance_len", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off),
-               L.ptr(lens), scenes.S, B, K, Tp, float(inv_ss), L.ptr(clear), L.stream())
+    L.call("sw_scene_clearance_len", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), L.ptr(lens),
+           scenes.S, B, K, Tp, float(inv_ss), L.ptr(clear), L.stream())                  # lens NULL: forwards to sw_scene_clearance
     return clear
 
 
@@ -562,8 +577,7 @@ def clearance_grad(pos, start, scenes, d0, scale, dpos, loss=None, count=None):
     d0, scale = float(d0), float(scale)
     if not (d0 > 0.0 and np.isfinite(d0)) or not np.isfinite(scale):
         raise ValueError("d0 must be finite and > 0 and scale finite, got d0 = %r, scale = %r" % (d0, scale))
-    if start is not None and (start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != pos.device):
-        raise ValueError("start must be (B, >= 2) on the device of pos, got %s" % (tuple(start.shape),))
+    start, sstride = _start_arg(start, B, pos.device)
     for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
         if t is not None and (tuple(t.shape) != (B,) or t.dtype != dt or not t.is_contiguous() or t.device != pos.device):
             raise ValueError("%s must be a contiguous %s tensor (B,) on the device of pos" % (name, dt))
@@ -571,11 +585,6 @@ def clearance_grad(pos, start, scenes, d0, scale, dpos, loss=None, count=None):
         raise ValueError("dpos must be on the device of pos")
     L.require_gpu(pos)
     pos = pos.contiguous()
-    sstride = 0
-    if start is not None:
-        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
-            start = start[:, :2].float().contiguous()
-        sstride = start.stride(0)
     L.call("sw_clearance_grad", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, Tp,
            d0, scale, L.ptr(dpos), dstride, L.ptr(loss), L.ptr(count), L.stream())
     return dpos
@@ -709,12 +718,13 @@ def disc_score(d_w, obsv, pred4, K, want_code=True, obs_len=None):
 RANK_MAX_K = 4096      # sw_sample_rank holds an agent's K scores in LDS
 
 
-def _check_picks(score, K, M, err, best):
-    """The arguments sample_rank and sample_nms share, checked without touching the device -> (B, best made contiguous)."""
+def _check_picks(score, K, M, err, best=None):
+    """The arguments sample_rank, sample_nms and scene_compose (M None: it picks one draw per agent) share, checked without
+    touching the device -> (B, best made contiguous)."""
     if score.dim() != 2 or score.shape[0] != K or K < 1:
         raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
     B = score.shape[1]
-    if not 1 <= M <= K:
+    if M is not None and not 1 <= M <= K:
         raise ValueError("M must lie in 1 .. K = %d, got %d" % (K, M))
     if K > RANK_MAX_K:
         raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
@@ -769,11 +779,7 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
         raise ValueError("radius must be >= 0, got %r" % (radius,))
     if not float(inv_ss) > 0.0:
         raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
-    if pos.dim() not in (3, 4) or pos.shape[-1] not in (2, 4) or pos.shape[-2] < 1 \
-            or pos.numel() != K * B * pos.shape[-2] * pos.shape[-1] or (pos.dim() == 4 and tuple(pos.shape[:2]) != (K, B)):
-        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
-    if pos.device != score.device:
-        raise ValueError("pos must be on the device of score")
+    Tp, pstride = _check_pos(pos, K, B, score)
     if scenes is not None and scenes.B != B:
         raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
     L.require_gpu(score)
@@ -790,8 +796,8 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
         per_row = torch.empty(B, 6, device=dev)
     if B == 0:
         return order, count, weight, assign, per_row
-    L.call("sw_sample_nms", L.ptr(pos), pos.shape[-1], L.ptr(score), L.ptr(scenes.scene_off) if scenes is not None else None,
-           G if scenes is not None else 0, B, K, pos.shape[-2], M, NMS_METRICS[metric], float(inv_ss), float(radius), L.ptr(err),
+    L.call("sw_sample_nms", L.ptr(pos), pstride, L.ptr(score), L.ptr(scenes.scene_off) if scenes is not None else None,
+           G if scenes is not None else 0, B, K, Tp, M, NMS_METRICS[metric], float(inv_ss), float(radius), L.ptr(err),
            L.ptr(best), L.ptr(order), L.ptr(count), L.ptr(weight), L.ptr(assign), L.ptr(per_row), L.stream())
     return order, count, weight, assign, per_row
 
@@ -809,38 +815,22 @@ def scene_compose(pos, start, score, scenes, K, coll_dist, inv_ss=1.0, sweeps=8,
     selected paths of its scene, +inf in single-agent scenes; per_scene (S, 4) int32: conflicting pairs under sel0 | under sel |
     agents that moved | sweeps that changed something; per_row (B, 4) or None without err: ADE | FDE of draw sel0, ADE | FDE
     of draw sel)."""
-    if score.dim() != 2 or score.shape[0] != K or K < 1:
-        raise ValueError("score must be (K, B) with K = %d >= 1, got %s" % (K, tuple(score.shape)))
-    B = score.shape[1]
-    if K > RANK_MAX_K:
-        raise ValueError("K must be at most %d, got %d" % (RANK_MAX_K, K))
+    B, _ = _check_picks(score, K, None, err)
     if not float(coll_dist) >= 0.0:
         raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
     if not float(inv_ss) > 0.0:
         raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
     if int(sweeps) < 1:
         raise ValueError("sweeps must be at least 1, got %r" % (sweeps,))
-    if pos.dim() not in (3, 4) or pos.shape[-1] not in (2, 4) or pos.shape[-2] < 1 \
-            or pos.numel() != K * B * pos.shape[-2] * pos.shape[-1] or (pos.dim() == 4 and tuple(pos.shape[:2]) != (K, B)):
-        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, tuple(pos.shape)))
-    if pos.device != score.device:
-        raise ValueError("pos must be on the device of score")
+    Tp, pstride = _check_pos(pos, K, B, score)
     if scenes.B != B:
         raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
-    if start is not None and (start.dim() != 2 or start.shape[0] != B or start.shape[1] < 2 or start.device != score.device):
-        raise ValueError("start must be (B, >= 2) = (%d, >= 2) on the device of score, got %s" % (B, tuple(start.shape)))
-    if err is not None and (tuple(err.shape) != (K, B, 2) or err.device != score.device):
-        raise ValueError("err must be (K, B, 2) = (%d, %d, 2) on the device of score, got %s" % (K, B, tuple(err.shape)))
+    start, sstride = _start_arg(start, B, score.device, "score")
     if lens is not None:
         lens = _check_pred_len_tensor(lens, B, score.device, "lens")
     L.require_gpu(score)
     score, pos = score.float().contiguous(), pos.float().contiguous()
     dev = score.device
-    sstride = 0
-    if start is not None:
-        if start.dtype != torch.float32 or start.stride(1) != 1 or start.stride(0) < 2:
-            start = start[:, :2].float().contiguous()
-        sstride = start.stride(0)
     sel = torch.empty(B, dtype=torch.int32, device=dev)
     sel0 = torch.empty(B, dtype=torch.int32, device=dev)
     clear = torch.empty(B, device=dev)
@@ -851,8 +841,8 @@ def scene_compose(pos, start, score, scenes, K, coll_dist, inv_ss=1.0, sweeps=8,
         per_row = torch.empty(B, 4, device=dev)
     if B == 0:
         return sel, sel0, clear, per_scene, per_row
-    L.call("sw_scene_compose", L.ptr(pos), pos.shape[-1], L.ptr_strided(start), sstride, L.ptr(score), L.ptr(scenes.scene_off),
-           L.ptr(lens), scenes.S, B, K, pos.shape[-2], float(inv_ss), float(coll_dist), int(sweeps), L.ptr(err), L.ptr(sel),
+    L.call("sw_scene_compose", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(score), L.ptr(scenes.scene_off),
+           L.ptr(lens), scenes.S, B, K, Tp, float(inv_ss), float(coll_dist), int(sweeps), L.ptr(err), L.ptr(sel),
            L.ptr(sel0), L.ptr(clear), L.ptr(per_scene), L.ptr(per_row), L.stream())
     return sel, sel0, clear, per_scene, per_row
 

@@ -104,6 +104,35 @@ def calc_and_store_stats(main_dir, real_samples, n_past=2, n_next=2, stats_file=
     return stats_1nn, stats_wst
 
 
+# ---- the argument front of the public forms below: host data or tensors from anywhere -> checked device tensors ------------
+def _start_arg(start, B, device):
+    """start (B, 2) or None: a point in front of every path."""
+    if start is None:
+        return None
+    start = _dev(start, device)
+    if tuple(start.shape) != (B, 2):
+        raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    return start
+
+
+def _lens_arg(lens, B, T, device):
+    """lens (B,) or None - list, numpy array or tensor of integers 1 .. T - checked on the host -> int32 on the device."""
+    if lens is None:
+        return None
+    host = lens.cpu().numpy() if isinstance(lens, torch.Tensor) else lens
+    return torch.from_numpy(check_pred_len(host, B, T)).to(device)
+
+
+def _scored_arg(trajs, score, device):
+    """trajs (K >= 1, B, T, 2 | 4) and score (K, B) -> both on the device."""
+    t, s = _dev(trajs, device), _dev(score, device)
+    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    if tuple(s.shape) != tuple(t.shape[:2]):
+        raise ValueError("score must be (K, B) = (%d, %d), got %s" % (t.shape[0], t.shape[1], tuple(s.shape)))
+    return t, s
+
+
 def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
     """Closest approach of every agent to the other agents of its scene, per joint draw (`sw_scene_clearance`).
     trajs (K, B, T, 2 | 4) or (B, T, 2 | 4): K joint futures of B agents, x and y first (prediction files, `collect`
@@ -111,21 +140,7 @@ def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
     point in front of every path (the last observed position), giving T segments instead of T - 1.  Within a segment
     both agents move linearly, so two agents that swap places between two frames have clearance 0.  The distance is
     multiplied by `scale`.  Returns a device tensor (K, B), or (B,) for a 3-d input; +inf in single-agent scenes."""
-    t = _dev(trajs, device)
-    L.require_gpu(t)
-    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
-        raise ValueError("trajs must be (K, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    t4 = t if t.dim() == 4 else t.unsqueeze(0)
-    K, B = t4.shape[0], t4.shape[1]
-    if K < 1:
-        raise ValueError("no draws")
-    if start is not None:
-        start = _dev(start, device)
-        if tuple(start.shape) != (B, 2):
-            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
-    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
-    clear = ops.scene_clearance(t4, start, scenes, K, float(scale))
-    return clear if t.dim() == 4 else clear[0]
+    return scene_clearance_len(trajs, sub_batches, None, start, scale, device)
 
 
 def scene_clearance_len(trajs, sub_batches, lens, start=None, scale=1.0, device="cuda"):
@@ -133,23 +148,18 @@ def scene_clearance_len(trajs, sub_batches, lens, start=None, scale=1.0, device=
     tensor of integers 1 .. T - gives the frames agent a is present for, left-aligned in trajs (what lies behind them is
     padding and reaches no output).  A collision needs both agents present: the segment of a pair that ends at frame t counts
     only if t < min(lens[a], lens[b]).  An agent for which no segment counts has clearance +inf.  Everything else as
-    scene_clearance()."""
+    scene_clearance(), which is this call with lens None."""
     t = _dev(trajs, device)
-    L.require_gpu(t)
     if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
         raise ValueError("trajs must be (K, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
     t4 = t if t.dim() == 4 else t.unsqueeze(0)
     K, B, T = t4.shape[0], t4.shape[1], t4.shape[2]
     if K < 1:
         raise ValueError("no draws")
-    host = lens.cpu().numpy() if isinstance(lens, torch.Tensor) else lens
-    lens = torch.from_numpy(check_pred_len(host, B, T)).to(t.device)
-    if start is not None:
-        start = _dev(start, device)
-        if tuple(start.shape) != (B, 2):
-            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
-    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
-    clear = ops.scene_clearance(t4, start, scenes, K, float(scale), lens=lens)
+    lens = _lens_arg(lens, B, T, t.device)
+    start = _start_arg(start, B, device)
+    L.require_gpu(t)
+    clear = ops.scene_clearance(t4, start, ops.SceneIndex.get(sub_batches, B, t.device), K, float(scale), lens=lens)
     return clear if t.dim() == 4 else clear[0]
 
 
@@ -169,15 +179,12 @@ def clearance_penalty(trajs, sub_batches, dist, start=None, scale=1.0, device="c
     dist, scale = float(dist), float(scale)
     if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
         raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
-    if start is not None:
-        start = _dev(start, device)
-        if tuple(start.shape) != (B, 2):
-            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
+    start = _start_arg(start, B, device)
     L.require_gpu(t)
-    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
     grad = torch.zeros(B, T, 2, device=t.device)
     loss = torch.zeros(B, device=t.device)
     count = torch.zeros(B, dtype=torch.int32, device=t.device)
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
     ops.clearance_grad(t, start, scenes, dist / scale, 1.0, grad, loss, count)        # |scale c| < dist  <=>  |c| < dist / scale
     return loss, grad, count
 
@@ -192,16 +199,10 @@ def sample_modes(trajs, score, radius, top_m, metric="fde", sub_batches=None, sc
     Returns device tensors over the G = B or S groups: order (G, top_m) int32 (the kept draws, best first, -1 past count),
     count (G,) int32, weight (G, top_m) (the share of the K draws in each mode, rows sum to 1), assign (G, K) int32 (the
     mode of every draw)."""
-    t, s = _dev(trajs, device), _dev(score, device)
-    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    K, B = t.shape[0], t.shape[1]
-    if tuple(s.shape) != (K, B):
-        raise ValueError("score must be (K, B) = (%d, %d), got %s" % (K, B, tuple(s.shape)))
+    t, s = _scored_arg(trajs, score, device)
+    K, B = s.shape
     L.require_gpu(t)
-    scenes = None
-    if sub_batches is not None:
-        scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device) if sub_batches is not None else None
     return ops.sample_nms(t, s, K, int(top_m), radius, metric, scenes, inv_ss=float(scale))[:4]
 
 
@@ -216,19 +217,10 @@ def compose_scenes(trajs, score, sub_batches, coll_dist, start=None, scale=1.0, 
     that is fewer than it has.  Returns device tensors: sel (B,) int32 the chosen draws, sel0 (B,) int32 the highest-scored
     ones, clear (B,) the closest approach of each chosen path to the others of its scene (+inf alone), per_scene (S, 4) int32 =
     conflicting pairs before | after | agents moved | sweeps that changed something."""
-    t, s = _dev(trajs, device), _dev(score, device)
-    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    K, B, T = t.shape[0], t.shape[1], t.shape[2]
-    if tuple(s.shape) != (K, B):
-        raise ValueError("score must be (K, B) = (%d, %d), got %s" % (K, B, tuple(s.shape)))
-    if start is not None:
-        start = _dev(start, device)
-        if tuple(start.shape) != (B, 2):
-            raise ValueError("start must be (B, 2) = (%d, 2), got %s" % (B, tuple(start.shape)))
-    if lens is not None:
-        host = lens.cpu().numpy() if isinstance(lens, torch.Tensor) else lens
-        lens = torch.from_numpy(check_pred_len(host, B, T)).to(t.device)
+    t, s = _scored_arg(trajs, score, device)
+    K, B = s.shape
+    start = _start_arg(start, B, device)
+    lens = _lens_arg(lens, B, t.shape[2], t.device)
     L.require_gpu(t)
-    scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, t.device)
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
     return ops.scene_compose(t, start, s, scenes, K, coll_dist, float(scale), int(sweeps), lens=lens)[:4]

@@ -1296,6 +1296,33 @@ class SocialWaysTrainer:
                     self._eval_emit(rec, collect, write_to_file)
         return tuple(base.result(data).values())
 
+    def _evaluate_by_length(self, data, K, just_one, noise, attr, top, key):
+        """evaluate() split by a per-agent length: chunk attribute `attr` (obs_len / pred_len; None: every agent in bucket
+        `top`), buckets 0 .. top, the buckets that hold agents under result key `key`.  The sums are float64 on the device,
+        one host sync at the end.  A select per bucket, not a product with a 0 / 1 mask: a row whose error is not finite
+        stays in its own bucket."""
+        dn = self._device_noise(noise)
+        dev = self.device
+        base = _EvalSums(dev)
+        acc = torch.zeros(top + 1, 5, dtype=torch.float64, device=dev)      # per length: count | the four sums
+        lens = torch.arange(top + 1, device=dev)[:, None]
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        for c in self._eval_draws(data, K, just_one, dn, base, want_pred=False):
+            n = getattr(c, attr)
+            if n is None:
+                n = torch.full((c.n,), top, dtype=torch.int32, device=dev)
+            rows = torch.cat([torch.ones(c.n, 1, dtype=torch.float64, device=dev), c.per_agent.double()], dim=1)
+            acc += torch.where((n[None, :] == lens)[:, :, None], rows[None], zero).sum(1)      # (top + 1, n, 5) -> (top + 1, 5)
+        vals = torch.cat([base.sums / data.n_test_samples, acc.flatten()]).tolist()
+        out = dict(zip(_EvalSums.KEYS, vals[:4]))
+        by = {}
+        for n in range(top + 1):
+            cnt, *sums = vals[4 + 5 * n:9 + 5 * n]
+            if cnt > 0:
+                by[n] = dict(count=int(cnt), **{k: v / cnt for k, v in zip(_EvalSums.KEYS, sums)})
+        out.update({key: by}, n_agents=sum(b - a for a, b in base.scenes))
+        return out
+
     def evaluate_history(self, data, n_gen_samples=20, just_one=False, noise=None):
         """evaluate() split by history length: what an agent seen for n frames is predicted with.  Returns a dict:
           ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
@@ -1303,25 +1330,9 @@ class SocialWaysTrainer:
                    evaluated (data.obs_len; a dataset without it: the single bucket n_past), the means over that length's
                    agents: sum_n count_n * by_len[n][key] / data.n_test_samples is the overall key;
           n_agents.
-        Chunking, noise and sampling launches are evaluate()'s; the sums are float64 on the device, one host sync at the end."""
-        dn = self._device_noise(noise)
-        dev, To = self.device, data.n_past
-        base = _EvalSums(dev)
-        acc = torch.zeros(To + 1, 5, dtype=torch.float64, device=dev)      # per length: count | the four sums
-        lens = torch.arange(To + 1, device=dev)[:, None]
-        for c in self._eval_draws(data, n_gen_samples, just_one, dn, base, want_pred=False):
-            n = c.obs_len if c.obs_len is not None else torch.full((c.n,), To, dtype=torch.int32, device=dev)
-            rows = torch.cat([torch.ones(c.n, 1, dtype=torch.float64, device=dev), c.per_agent.double()], dim=1)
-            acc += ((n[None, :] == lens).double()[:, :, None] * rows[None]).sum(1)      # (To + 1, n, 5) -> (To + 1, 5)
-        vals = torch.cat([base.sums / data.n_test_samples, acc.flatten()]).tolist()
-        out = dict(zip(_EvalSums.KEYS, vals[:4]))
-        by_len = {}
-        for n in range(To + 1):
-            cnt, *sums = vals[4 + 5 * n:9 + 5 * n]
-            if cnt > 0:
-                by_len[n] = dict(count=int(cnt), **{k: v / cnt for k, v in zip(_EvalSums.KEYS, sums)})
-        out.update(by_len=by_len, n_agents=sum(b - a for a, b in base.scenes))
-        return out
+        Chunking, noise and sampling launches are evaluate()'s; the sums are float64 on the device, one host sync at the end.
+        A row whose error is not finite stays in its own bucket (a select per bucket, as in evaluate_horizon())."""
+        return self._evaluate_by_length(data, n_gen_samples, just_one, noise, "obs_len", data.n_past, "by_len")
 
     def evaluate_horizon(self, data, n_gen_samples=20, just_one=False, noise=None):
         """evaluate() split by FUTURE length, the twin of evaluate_history(): what an agent that stays for m more frames is
@@ -1332,25 +1343,7 @@ class SocialWaysTrainer:
                    agents: sum_m count_m * by_next[m][key] / data.n_test_samples is the overall key;
           n_agents.
         Chunking, noise and sampling launches are evaluate()'s; the sums are float64 on the device, one host sync at the end."""
-        dn = self._device_noise(noise)
-        dev, Tp = self.device, data.n_next
-        base = _EvalSums(dev)
-        acc = torch.zeros(Tp + 1, 5, dtype=torch.float64, device=dev)      # per length: count | the four sums
-        lens = torch.arange(Tp + 1, device=dev)[:, None]
-        for c in self._eval_draws(data, n_gen_samples, just_one, dn, base, want_pred=False):
-            m = c.pred_len if c.pred_len is not None else torch.full((c.n,), Tp, dtype=torch.int32, device=dev)
-            rows = torch.cat([torch.ones(c.n, 1, dtype=torch.float64, device=dev), c.per_agent.double()], dim=1)
-            # a select per bucket, not a product with a 0 / 1 mask: a row whose error is not finite stays in its own bucket
-            acc += torch.where((m[None, :] == lens)[:, :, None], rows[None], torch.zeros((), dtype=torch.float64, device=dev)).sum(1)
-        vals = torch.cat([base.sums / data.n_test_samples, acc.flatten()]).tolist()
-        out = dict(zip(_EvalSums.KEYS, vals[:4]))
-        by_next = {}
-        for m in range(Tp + 1):
-            cnt, *sums = vals[4 + 5 * m:9 + 5 * m]
-            if cnt > 0:
-                by_next[m] = dict(count=int(cnt), **{k: v / cnt for k, v in zip(_EvalSums.KEYS, sums)})
-        out.update(by_next=by_next, n_agents=sum(b - a for a, b in base.scenes))
-        return out
+        return self._evaluate_by_length(data, n_gen_samples, just_one, noise, "pred_len", data.n_next, "by_next")
 
     def evaluate_scenes(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None):
         """evaluate() plus what its K joint draws say about the scene as a whole.  Draw k of a scene is draw k of each of
@@ -1500,7 +1493,7 @@ class SocialWaysTrainer:
         K, M, ph, score = _scored_draws(self, obsv_p, n_samples, top_m, sub_batches, noise, row0, obs_len)
         with torch.no_grad():
             B = ph.shape[1]
-            scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device) if joint else None
+            scenes = ops.SceneIndex.get(sub_batches, B, ph.device) if joint else None
             order, count, weight, _, _ = ops.sample_nms(ph, score, K, M, radius, metric, scenes, inv_ss=scale)
             rows = order
             if joint:      # the scene of every row: the number of scene ends at or below it
@@ -1604,7 +1597,7 @@ class SocialWaysTrainer:
         K, _, ph, score = _scored_draws(self, obsv_p, n_samples, 1, sub_batches, noise, row0, obs_len)
         with torch.no_grad():
             B = ph.shape[1]
-            scenes = ops.SceneIndex.get(np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2), B, ph.device)
+            scenes = ops.SceneIndex.get(sub_batches, B, ph.device)
             sel, _, clear, per_scene, _ = ops.scene_compose(ph, obsv_p[:, -1], score, scenes, K, coll_dist, inv_ss=scale,
                                                             sweeps=sweeps)
             idx = sel.long()[None]

@@ -168,6 +168,23 @@ def test_hand_built_cases(name):
         assert out[0].tolist() == [0, 1] and out[2].tolist() == [3.0, 3.0] and out[3].tolist() == [[1, 0, 1, 1]]
 
 
+def test_ragged_clear_is_the_length_clearance_of_the_selected_paths():
+    """Mixed lengths over two time chunks and two agent tiles (18 segments with the start point, a scene of 70): compose's
+    clear equals sw_scene_clearance_len on the selected paths as raw bits, +inf where nothing counts (the scene of one)
+    included.  Both walk a pair's chunk with the one SC_CHUNK of sw_scene_dev.h."""
+    from socialways_amd import ops
+    case = R.lane_case(sizes=[1, 2, 5, 70], K=3, Tp=18, seed=23, stride=1, with_start=True, ragged=True)
+    lens = case["lens"]
+    assert lens.min() >= 1 and lens.max() <= 18 and len(set(lens.tolist())) > 8 and (lens <= 16).any() and (lens > 16).any()
+    sel, _, clear, _, _ = run(case, with_err=False)
+    pos, B = dev(case["pos"]), len(lens)
+    scenes = ops.SceneIndex.get(scene_list(case["sizes"]), B, pos.device)
+    picked = pos.gather(0, sel.long()[None, :, None, None].expand(1, B, pos.shape[2], pos.shape[3]))
+    again = ops.scene_clearance(picked, dev(case["start"]), scenes, 1, case["inv_ss"], lens=dev(lens))[0]
+    assert torch.equal(again.view(torch.int32), clear.view(torch.int32))
+    assert float(clear[0]) == float("inf") and bool(torch.isfinite(clear[1:]).all())
+
+
 def test_stats_compose_scenes_is_the_public_form():
     from socialways_amd import stats
     case, sweeps, want = constructed("k65_tp17_start_ragged")
