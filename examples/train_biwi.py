@@ -16,6 +16,9 @@
 * `--compose DIST`: the composed scene futures (evaluate_composed): one draw per agent - given the observations the agents'
   draws are independent, so any tuple of them is a joint sample -, the top-scored ones moved to other draws until no two chosen
   paths come closer than DIST; errors, scores and collision rates before and after.
+* `--risk DIST`: the generator as a collision predictor (evaluate_risk): every held-out agent with company is the ego once, its
+  true future the plan, the others' K draws the crowd; the predicted chance of coming within DIST of somebody against what
+  happened (Brier score, against the index-paired estimate and the constant base rate).
 * `--min-past M`: the held-out windows also keep the pedestrians seen for only M .. 7 frames (create_dataset_ragged:
   right-aligned observations + obs_len), so they are predicted and their neighbours see them; the errors are reported per
   history length (evaluate_history).  Training stays on full windows unless
@@ -81,6 +84,9 @@ def main(argv=None):
     ap.add_argument("--compose", type=float, default=None, metavar="DIST",
                     help="also report the composed scene futures: one draw per agent, the discriminator's top-scored ones moved to "
                          "other draws until no two chosen paths come closer than DIST (world units)")
+    ap.add_argument("--risk", type=float, default=None, metavar="DIST",
+                    help="also report the collision risk of every held-out agent's true future against the K draws of the others "
+                         "(closer than DIST, world units) and how well it is calibrated")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -209,6 +215,13 @@ def main(argv=None):
                       % (args.k, args.compose, cp["ade_top1"], cp["fde_top1"], cp["ade_comp"], cp["fde_comp"], 100 * cp["col_top1"],
                          100 * cp["col_comp"], cp["pairs_top1"], cp["pairs_comp"], 100 * cp["moved"], cp["score_top1"],
                          cp["score_comp"], cp["n_scenes"], cp["n_multi"]))
+            if args.risk is not None:
+                rk = tr.evaluate_risk(data, n_gen_samples=args.k, coll_dist=args.risk)
+                print("Plan risk (leave-one-out, %d draws, within %.2f): mean risk %.3f, %.1f %% of the agents do collide | Brier %.4f "
+                      "(index-paired %.4f, base rate %.4f) | mean risk of those who collide %.3f, of the others %.3f | first conflict "
+                      "off by %.2f frames | %d agents with company"
+                      % (args.k, args.risk, rk["risk_mean"], 100 * rk["col_gt_agent"], rk["brier"], rk["brier_diag"], rk["brier_base"],
+                         rk["risk_hit"], rk["risk_miss"], rk["t_first_err"], rk["n_ego"]))
             if ragged is not None:
                 hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
                 print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"

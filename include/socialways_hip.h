@@ -425,6 +425,57 @@ int sw_scene_compose(const float* pos, int pstride, const float* start /*or NULL
                      const float* err /*[K,B,2] or NULL*/,
                      int* sel /*[B]*/, int* sel0 /*[B] or NULL*/, float* clear /*[B]*/,
                      int* per_scene /*[S,4]*/, float* per_row /*[B,4] or NULL*/, void* stream);
+/* PLAN RISK: candidate ego paths - paths that are NOT rows of pos - scored against the K sampled futures of a scene: how
+ * likely is a plan to come closer than coll_dist to somebody?  pos, start, scene_off, len, inv_ss and the path of (k, a) are
+ * exactly as in sw_scene_clearance_len.  The draws are open-loop: the pedestrians do not react to the plan.  A QUERY q names
+ * a scene q_scene[q] (int32), an ego row q_ego[q] to leave out - an ABSOLUTE row of the batch; q_ego == NULL, -1 or a row
+ * outside the scene leaves nobody out - and P candidate plans: plan (q, p) is plan_start[q] first when there is a start point
+ * (plan_start != NULL iff start != NULL), then plans[q][p][0 .. Tp-1] (x, y; 8-byte aligned).  Several queries may name one
+ * scene; leave-one-out is Q = B.  All fp32; "agent a" below is a row of the scene other than the ego row.
+ *   d(q,p; k,a; t)   = sqrtf(m) * inv_ss, m = the squared closest approach of plan (q, p) and path (k, a) within the segment
+ *                    that ENDS at future frame t, with the arithmetic of sw_scene_clearance operation for operation: r0 = the
+ *                    agent's point minus the plan's point at the segment's first end, r1 the same at its second end,
+ *                    dv = r1 - r0, tau = clamp(-(r0.dv) / (dv.dv), 0, 1), 0 when dv.dv = 0, m = |r0 + tau dv|^2; r0 advances
+ *                    through every segment.  Segments run from t = 0 with a start point, else from t = 1.  The segment counts
+ *                    only while t < min(len[a], plan_len[q]), both clamped into 1 .. Tp, NULL meaning Tp; what lies behind a
+ *                    length, NaN included, reaches nothing (the minimum is gated by a select).
+ *   c(q,p; k,a)      = the minimum over the counted segments of d, +inf when none counts.  A conflict is c < coll_dist, the
+ *                    fp32 comparison sw_scene_reduce makes; sqrtf and the multiplication are monotone, so a path conflicts
+ *                    iff one of its counted segments has d < coll_dist.
+ *   h_a(q,p)         = the number of draws k in which path (k, a) conflicts with plan (q, p), 0 .. K.
+ * Outputs, per (q, p):
+ *   clear_min        = the minimum over the agents a and the draws k of c; +inf with no other agent or no counted segment;
+ *   counts[0]        = the number of draws k in which SOME agent's draw k conflicts: the index-paired estimate of the risk is
+ *                    counts[0] / K;
+ *   counts[1]        = the frame t at which the earliest conflicting counted segment over all (a, k) ends, -1 if none;
+ *   counts[2]        = the absolute row a with the largest h_a, the lowest row of equal ones, -1 if every h_a is 0;
+ *   counts[3]        = that row's h_a (0 if none);
+ *   risk             = 1 - prod over the agents a of f_a, f_a = (float)(K - h_a) / (float)K: one fp32 IEEE division per agent,
+ *                    fp32 products taken over the agents in ascending row order starting from 1.0f (a factor f_a = 1 leaves the
+ *                    bits as they are), one fp32 subtraction.  Given the observations the draws of different agents are
+ *                    independent (see sw_scene_compose), so the product is the share of ALL K^n tuples of per-agent draws in
+ *                    which the plan hits somebody; the index-paired counts[0] / K looks
+ *                    at K of them.  risk is exactly 0 when every h_a is 0, exactly 1 when some h_a = K, and within
+ *                    2 (n + 1) 2^-24 of the exact product otherwise (n divisions, n - 1 products and one subtraction on
+ *                    values in [0, 1]: a rounding bound).
+ * A query whose scene index lies outside 0 .. S-1 or whose offsets leave 0 .. B reads nothing and writes risk 0, clear_min
+ * +inf, counts {0, -1, -1, 0}; so does a scene without rows.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, scene_off, plans, q_scene, risk, clear_min,
+ * counts; plan_start NULL with start non-NULL or the other way round; S, B or Q < 0; K, Tp or P < 1; pstride not 2 or 4; pos
+ * or plans off their 8-byte alignment; start with sstride < 2; inv_ss <= 0 or NaN; coll_dist < 0 or NaN.  SW_ESHAPE: K > 4096.
+ * Q == 0: SW_OK without a launch.
+ * One 256-thread workgroup per (query, tile of up to 64 plans - fewer with few queries, so that the launch fills the device);
+ * a lane owns an (agent, draw) pair and walks the tile's plans.
+ * One writer per output element; what is accumulated across lanes is an integer (counts, bit masks, the first frame) or a
+ * minimum, through LDS integer atomics whose result does not depend on the order: two calls give the same bits.  LDS per
+ * workgroup: at most 65 536 bytes - per plan of the tile 8 (Tp + [start != NULL]) for its points, 8, 4 ceil(K / 32) and
+ * 4 ((256 / min(K, 256)) | 1); the tile shrinks until it fits, and a plan that does not fit alone is read where it lies.   */
+int sw_plan_risk(const float* pos, int pstride, const float* start /*or NULL*/, int sstride,
+                 const int* scene_off /*[S+1]*/, const int* len /*[B] or NULL*/, int S, int B, int K, int Tp,
+                 const float* plans /*[Q,P,Tp,2]*/, const float* plan_start /*[Q,2]; NULL iff start == NULL*/,
+                 const int* plan_len /*[Q] or NULL*/, const int* q_scene /*[Q]*/, const int* q_ego /*[Q] or NULL*/,
+                 int Q, int P, float inv_ss, float coll_dist,
+                 float* risk /*[Q,P]*/, float* clear_min /*[Q,P]*/, int* counts /*[Q,P,4]*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

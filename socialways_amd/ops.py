@@ -49,6 +49,14 @@ class SceneIndex:
         self.pair_off = torch.from_numpy(poff).to(device)
         self.sizes = n
 
+    def row_scene(self):
+        """(scene of every row (B,) int32, is that scene one of two or more agents (B,) bool) on the device, made once."""
+        if getattr(self, "_rows", None) is None:
+            sc = np.repeat(np.arange(self.S, dtype=np.int32), self.sizes)
+            dev = self.scene_off.device
+            self._rows = (torch.from_numpy(sc).to(dev), torch.from_numpy(np.repeat(self.sizes > 1, self.sizes)).to(dev))
+        return self._rows
+
     _cache = {}
 
     @classmethod
@@ -845,6 +853,70 @@ def scene_compose(pos, start, score, scenes, K, coll_dist, inv_ss=1.0, sweeps=8,
            L.ptr(lens), scenes.S, B, K, Tp, float(inv_ss), float(coll_dist), int(sweeps), L.ptr(err), L.ptr(sel),
            L.ptr(sel0), L.ptr(clear), L.ptr(per_scene), L.ptr(per_row), L.stream())
     return sel, sel0, clear, per_scene, per_row
+
+
+def _check_query_tensor(t, Q, device, name):
+    """What plan_risk takes per query: an int32 tensor (Q,) on `device`."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (Q,) or t.device != device:
+        raise ValueError("%s must be an int32 tensor (Q,) = (%d,) on %s" % (name, Q, device))
+    return t.contiguous()
+
+
+def plan_risk(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, coll_dist, inv_ss=1.0, lens=None, plan_lens=None):
+    """The risk of candidate ego paths against the K sampled futures of a scene (sw_plan_risk): how likely is a plan - a path
+    that is NOT one of the draws - to come closer than coll_dist to somebody, inv_ss * the closest approach along the paths,
+    both moving linearly between frames.  The draws are open-loop: the pedestrians do not react to the plan.
+    pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or None: the point in front of the Tp positions
+    (any row stride, as scene_clearance); scenes: a SceneIndex; lens (B,) int32 on the device: ragged futures, as
+    scene_clearance(lens=...).  Query q names scene q_scene[q] (int32 (Q,) on the device), an ego row q_ego[q] to leave out
+    (int32 (Q,) or None; an absolute row of the batch; -1 or a row outside the scene: nobody) and P plans: plans (Q, P, Tp, 2),
+    or (P, Tp, 2) for Q = 1, float32; plan_start (Q, 2), given exactly when start is: the point in front of the plans of
+    query q; plan_lens (Q,) int32 or None: a segment counts only while both the agent and the plan are present.
+    Returns (risk (Q, P): 1 - the product over the scene's other agents of the share of each agent's draws that stay clear of
+    the plan - given the observations the agents' draws are independent, so this is the share of all K^n tuples; exactly 0 / 1
+    when no draw / every draw of some agent conflicts;  clear_min (Q, P): the closest approach to any draw of any agent, +inf
+    without one;  counts (Q, P, 4) int32: draws k in which some agent's draw k conflicts (the index-paired estimate is
+    counts[..., 0] / K) | the frame at which the earliest conflicting segment ends, -1 without | the absolute row with the most
+    conflicting draws, the lowest of equal ones, -1 without | that row's number of conflicting draws)."""
+    B = scenes.B
+    Tp, pstride = _check_pos(pos, K, B)
+    if not float(coll_dist) >= 0.0:
+        raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+    if not float(inv_ss) > 0.0:
+        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.float32 or plans.dim() not in (3, 4) or plans.device != pos.device:
+        raise ValueError("plans must be a float32 tensor (Q, P, Tp, 2) or (P, Tp, 2) on the device of pos")
+    if plans.dim() == 3:
+        plans = plans.unsqueeze(0)
+    Q, P = plans.shape[0], plans.shape[1]
+    if P < 1 or tuple(plans.shape[2:]) != (Tp, 2):
+        raise ValueError("plans must be (Q, P >= 1, Tp, 2) with Tp = %d, got %s" % (Tp, tuple(plans.shape)))
+    if (start is None) != (plan_start is None):
+        raise ValueError("start and plan_start go together: a point in front of the paths and of the plans, or of neither")
+    start, sstride = _start_arg(start, B, pos.device)
+    if plan_start is not None:
+        if not isinstance(plan_start, torch.Tensor) or tuple(plan_start.shape) != (Q, 2) or plan_start.device != pos.device:
+            raise ValueError("plan_start must be (Q, 2) = (%d, 2) on the device of pos" % Q)
+        plan_start = plan_start.float().contiguous()
+    q_scene = _check_query_tensor(q_scene, Q, pos.device, "q_scene")
+    if q_ego is not None:
+        q_ego = _check_query_tensor(q_ego, Q, pos.device, "q_ego")
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    if plan_lens is not None:
+        plan_lens = _check_query_tensor(plan_lens, Q, pos.device, "plan_lens")
+    L.require_gpu(pos)
+    pos, plans = pos.float().contiguous(), plans.contiguous()
+    dev = pos.device
+    risk = torch.empty(Q, P, device=dev)
+    clear_min = torch.empty(Q, P, device=dev)
+    counts = torch.empty(Q, P, 4, dtype=torch.int32, device=dev)
+    if Q == 0:
+        return risk, clear_min, counts
+    L.call("sw_plan_risk", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), L.ptr(lens), scenes.S, B,
+           K, Tp, L.ptr(plans), L.ptr(plan_start), L.ptr(plan_lens), L.ptr(q_scene), L.ptr(q_ego), Q, P, float(inv_ss),
+           float(coll_dist), L.ptr(risk), L.ptr(clear_min), L.ptr(counts), L.stream())
+    return risk, clear_min, counts
 
 
 def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None, tag="d"):

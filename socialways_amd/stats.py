@@ -8,7 +8,8 @@ Beyond the reference: `scene_clearance`, the closest approach between the agents
 quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, for trajectories from anywhere - and
 `sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise, and
 `compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`, and
-`clearance_penalty`, the pairwise clearance penalty and its gradient behind `SocialWaysTrainer.set_clearance_loss()`."""
+`clearance_penalty`, the pairwise clearance penalty and its gradient behind `SocialWaysTrainer.set_clearance_loss()`, and
+`plan_risk`, the collision risk of candidate ego paths against the K draws behind `SocialWaysTrainer.plan_risk()`."""
 import os
 
 import numpy as np
@@ -224,3 +225,58 @@ def compose_scenes(trajs, score, sub_batches, coll_dist, start=None, scale=1.0, 
     L.require_gpu(t)
     scenes = ops.SceneIndex.get(sub_batches, B, t.device)
     return ops.scene_compose(t, start, s, scenes, K, coll_dist, float(scale), int(sweeps), lens=lens)[:4]
+
+
+def _query_arg(x, Q, name, device):
+    """A per-query integer argument (Q,) - list, numpy array or tensor - checked on the host -> int32 on the device."""
+    host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
+    if host.shape != (Q,) or host.dtype.kind not in "iu":
+        raise ValueError("%s must hold Q = %d integers, got shape %s dtype %s" % (name, Q, host.shape, host.dtype))
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None, scene=None, ego=None, scale=1.0, lens=None,
+              plan_lens=None, device="cuda"):
+    """How likely is a candidate ego path to run into somebody (`sw_plan_risk`), for trajectories from anywhere.  trajs
+    (K, B, T, 2 | 4), x and y first: K futures per agent, drawn independently per agent given what was observed; sub_batches
+    (S, 2) [start, end) rows tiling [0, B), [] = one scene.  plans (Q, P, T, 2), or (P, T, 2) for one query: P candidate paths
+    per query - paths that are not among the draws.  Query q looks at scene scene[q] (None: query q belongs to scene q, Q = S)
+    and leaves out row ego[q] (None or -1: nobody; an absolute row of trajs - the ego's own draws, when the ego is an agent of
+    the scene so that the social block saw its observed track).  start (B, 2) and plan_start (Q, 2), both or neither: a point
+    in front of every path and every plan (the last observed positions), giving T segments instead of T - 1.  Distances are
+    multiplied by `scale`; a conflict is a closest approach below coll_dist, both moving linearly within a segment.  lens (B,)
+    / plan_lens (Q,) or None: the frames an agent / the plans of a query are present for, as scene_clearance_len().
+    The draws are OPEN-LOOP: the pedestrians do not react to the plan.
+    Returns device tensors (risk (Q, P): 1 - the product over the other agents of the share of their draws that stay clear;
+    clear_min (Q, P): the closest approach to any draw; counts (Q, P, 4) int32: draws k with a conflict of some agent's draw k |
+    frame of the earliest conflict, -1 | the row with the most conflicting draws, -1 | its number of them)."""
+    if not float(coll_dist) >= 0.0 or not float(scale) > 0.0:
+        raise ValueError("coll_dist must be >= 0 and scale > 0, got %r and %r" % (coll_dist, scale))
+    t = _dev(trajs, device)
+    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    p = _dev(plans, device)
+    if p.dim() == 3:
+        p = p.unsqueeze(0)
+    if p.dim() != 4 or p.shape[1] < 1 or tuple(p.shape[2:]) != (T, 2):
+        raise ValueError("plans must be (Q, P >= 1, T, 2) or (P, T, 2) with T = %d, got %s" % (T, tuple(p.shape)))
+    Q = p.shape[0]
+    if (start is None) != (plan_start is None):
+        raise ValueError("start and plan_start go together: a point in front of the paths and of the plans, or of neither")
+    start = _start_arg(start, B, device)
+    if plan_start is not None:
+        plan_start = _dev(plan_start, device)
+        if tuple(plan_start.shape) != (Q, 2):
+            raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
+    if scene is None:
+        if Q != scenes.S:
+            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, scenes.S))
+        scene = np.arange(Q)
+    scene = _query_arg(scene, Q, "scene", t.device)
+    ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
+    lens = _lens_arg(lens, B, T, t.device)
+    plan_lens = _lens_arg(plan_lens, Q, T, t.device)
+    L.require_gpu(t)
+    return ops.plan_risk(t, start, scenes, K, p, plan_start, scene, ego, coll_dist, float(scale), lens=lens, plan_lens=plan_lens)

@@ -1651,6 +1651,142 @@ class SocialWaysTrainer:
         out.update(n_scenes=len(base.scenes), n_multi=n_multi, K=K, coll_dist=float(coll_dist), sweeps=int(sweeps))
         return out
 
+    def plan_risk(self, obsv_p, plans, n_samples, coll_dist, sub_batches=[], scene=None, ego=None, plan_start=None, noise=None,
+                  row0=0, scale=1.0, obs_len=None):
+        """"If the ego takes this path, how likely is it to run into somebody?" - candidate paths that are NOT among the draws,
+        scored against the K sampled futures of the scene's pedestrians.  obsv_p (B, To, 2), sub_batches, noise (K, B,
+        noise_len), None or a DeviceNoise (rows from `row0`) and obs_len as sample_ranked(): ONE sampling launch, the draws
+        Generator.sample() returns, then ONE risk launch (ops.plan_risk).  plans (Q, P, n_next, 2), or (P, n_next, 2) for one
+        query: P candidate futures per query, in the coordinates of obsv_p.  Query q looks at scene scene[q] of sub_batches
+        (None: query q belongs to scene q, Q = the number of scenes).  ego (Q,) rows of obsv_p or None: the ego's OBSERVED track is
+        an agent of the scene, so the social block sees it; its own draws are left out of the risk and its plans start at
+        obsv_p[ego[q], -1].  Without ego the plans start at plan_start[q] (Q, 2), which is then required.  Every pedestrian
+        path starts at its last observed position; all move linearly between frames; a conflict is a closest approach times
+        `scale` below coll_dist.  The draws are OPEN-LOOP: the pedestrians do not react to the plan.
+        Given the observations the generator's draws of different agents are independent (sample_composed()), so the chance
+        that a plan stays clear of everybody is the product over the agents of each agent's share of clear draws - all K^n
+        tuples that one sampling launch has paid for, where the index-paired draws give a multiple of 1 / K.
+        Returns (risk (Q, P), clear_min (Q, P), counts (Q, P, 4) int32 - the columns of ops.plan_risk -, trajs (K, B, n_next, 4)).
+        Works at any hidden size: it needs only Generator.sample()."""
+        K = int(n_samples)
+        if K < 1:
+            raise ValueError("n_samples must be at least 1, got %r" % (n_samples,))
+        if not float(coll_dist) >= 0.0:
+            raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+        if not float(scale) > 0.0:
+            raise ValueError("scale must be > 0, got %r" % (scale,))
+        if obsv_p.dim() != 3 or obsv_p.shape[1] < 1 or obsv_p.shape[2] < 2:
+            raise ValueError("obsv_p must be (B, To, >= 2), got %s" % (tuple(obsv_p.shape),))
+        B, dev = obsv_p.shape[0], obsv_p.device
+        plans = torch.as_tensor(plans, dtype=torch.float32)
+        if plans.dim() == 3:
+            plans = plans.unsqueeze(0)
+        if plans.dim() != 4 or plans.shape[1] < 1 or tuple(plans.shape[2:]) != (self.n_next, 2):
+            raise ValueError("plans must be (Q, P >= 1, n_next, 2) or (P, n_next, 2) with n_next = %d, got %s"
+                             % (self.n_next, tuple(plans.shape)))
+        Q = plans.shape[0]
+        sb = np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2)
+        S = max(len(sb), 1)
+
+        def rows(x, name, hi):
+            host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
+            if host.shape != (Q,) or host.dtype.kind not in "iu" or (host < 0).any() or (host >= hi).any():
+                raise ValueError("%s must hold Q = %d integers in 0 .. %d, got %r" % (name, Q, hi - 1, x))
+            return host.astype(np.int32)
+
+        if scene is None:
+            if Q != S:
+                raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, S))
+            scene = np.arange(Q)
+        scene = rows(scene, "scene", S)
+        if ego is not None:
+            if plan_start is not None:
+                raise ValueError("plan_start and ego exclude each other: with ego the plans start at obsv_p[ego[q], -1]")
+            ego = rows(ego, "ego", B)
+        elif plan_start is None:
+            raise ValueError("without ego the plans need plan_start (Q, 2)")
+        else:
+            plan_start = torch.as_tensor(plan_start, dtype=torch.float32)
+            if tuple(plan_start.shape) != (Q, 2):
+                raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+        L.require_gpu(obsv_p)
+        if obs_len is not None:
+            if not isinstance(self.G, Generator):      # the generic-width and wide paths: no ragged kernels
+                refuse_obs_len(obs_len, type(self).__name__)
+            obs_len = ops.obs_len_arg(obs_len, B, obsv_p.shape[1], 2, dev)
+        with torch.no_grad():
+            scenes = ops.SceneIndex.get(sb, B, dev)
+            q_scene = torch.from_numpy(scene).to(dev)
+            q_ego = None
+            if ego is not None:
+                q_ego = torch.from_numpy(ego).to(dev)
+                plan_start = obsv_p[q_ego.long(), -1, :2]
+            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
+            risk, clear_min, counts = ops.plan_risk(ph, obsv_p[:, -1], scenes, K, plans.to(dev), plan_start.to(dev), q_scene, q_ego,
+                                                    coll_dist, inv_ss=float(scale))
+            return risk, clear_min, counts, ph
+
+    RISK_KEYS = ("risk_mean", "col_gt_agent", "brier", "brier_diag", "risk_hit", "risk_miss", "t_first_err")
+
+    def evaluate_risk(self, data, n_gen_samples=20, coll_dist=0.1, just_one=False, collect=None, noise=None):
+        """evaluate() plus a score of the generator as a COLLISION PREDICTOR, leave-one-out: every held-out agent of a scene of
+        two or more agents is the ego once.  Its plan is its ground-truth future (its pred_len frames when the dataset carries
+        one), the others are the K draws of the scene's other agents (plan_risk(): open-loop, the draws do not react to the
+        plan), and coll_dist is in world units through data.ss like evaluate_scenes().  With r_a the product risk, d_a =
+        counts[.., 0] / K the index-paired estimate and y_a = [the clearance of agent a among the ground-truth futures <
+        coll_dist] (the K = 1 launch behind col_gt), over those agents - returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          risk_mean              the mean of r;      col_gt_agent   the mean of y;
+          brier, brier_diag      the mean of (r - y)^2 and of (d - y)^2: does a predicted 0.3 come true 30 % of the time;
+          brier_base             the Brier score of the constant col_gt_agent, which a useful predictor beats;
+          risk_hit, risk_miss    the mean of r over the agents with y = 1 / y = 0 (0 without such agents);
+          t_first_err            over the agents with y = 1 and r > 0, the mean |frame of the predicted first conflict - frame of
+                                 the true one| (0 without such agents);
+          n_ego, K, coll_dist.
+        Chunking, noise streams and sampling launches are evaluate()'s; per chunk one risk launch on the draws where they are, the
+        ground-truth clearance launch and one K = 1 risk launch on the ground truth for the true first frame.  Sums are float64
+        on the device, one host sync at the end.  With `collect` every record of evaluate() also has `risk`, `risk_diag`, `hit_gt`
+        (n,) and `risk_counts` (n, 4) (columns: ops.plan_risk; agents alone in their scene: risk 0, no hit)."""
+        if not float(coll_dist) >= 0.0:
+            raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+        dn = self._device_noise(noise)
+        dev, K = self.device, int(n_gen_samples)
+        inv_ss = 1.0 / float(data.ss)
+        base = _EvalSums(dev)
+        # over the egos: sum r | sum y | sum (r - y)^2 | sum (d - y)^2 | sum r y | sum r (1 - y) | sum |dt| | agents in that sum
+        acc = torch.zeros(8, dtype=torch.float64, device=dev)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            q_scene, multi = c.scenes.row_scene()
+            q_ego = torch.arange(c.n, dtype=torch.int32, device=dev)
+            start = c.obsv[:, -1]
+            plans, pstart = c.pred[:, None, :, :2].contiguous(), start[:, :2].contiguous()
+            risk, _, counts = ops.plan_risk(c.ph, start, c.scenes, K, plans, pstart, q_scene, q_ego, coll_dist, inv_ss,
+                                            lens=c.pred_len, plan_lens=c.pred_len)
+            gt_clear = ops.scene_clearance(c.pred, start, c.scenes, 1, inv_ss, lens=c.pred_len)[0]
+            _, _, gt_counts = ops.plan_risk(c.pred, start, c.scenes, 1, plans, pstart, q_scene, q_ego, coll_dist, inv_ss,
+                                            lens=c.pred_len, plan_lens=c.pred_len)
+            hit = (gt_clear < coll_dist) & multi
+            r, y = risk[:, 0].double(), hit.double()
+            d = counts[:, 0, 0].double() / K
+            timed = hit & (risk[:, 0] > 0)
+            dt = (counts[:, 0, 1] - gt_counts[:, 0, 1]).abs().double()
+            rows = torch.stack([r, y, (r - y) ** 2, (d - y) ** 2, r * y, r * (1 - y), torch.where(timed, dt, zero), timed.double()])
+            acc += torch.where(multi[None], rows, zero).sum(1)
+            if collect is not None:
+                collect.extend(self._eval_records(data, c, c.ph, dict(risk=(risk[:, 0], 0), risk_diag=(d.float(), 0), hit_gt=(hit, 0),
+                                                                      risk_counts=(counts[:, 0], 0))))
+        n_ego = sum(b - a for a, b in base.scenes if b - a > 1)
+        out = base.result(data)
+        sr, sy, sb2, sd2, shit, smiss, sdt, ndt = acc.tolist()
+        ne = max(n_ego, 1)
+        ybar = sy / ne
+        out.update(risk_mean=sr / ne, col_gt_agent=ybar, brier=sb2 / ne, brier_diag=sd2 / ne,
+                   brier_base=ybar * (1.0 - ybar) if n_ego else 0.0,
+                   risk_hit=shit / sy if sy else 0.0, risk_miss=smiss / (n_ego - sy) if n_ego - sy else 0.0,
+                   t_first_err=sdt / ndt if ndt else 0.0, n_ego=n_ego, K=K, coll_dist=float(coll_dist))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def checkpoint(self, epoch=None):
         """The reference's checkpoint dict (train.py:653-663), plus a 'noise' entry ({seed, step}) when self.noise is set."""
