@@ -19,6 +19,9 @@
 * `--risk DIST`: the generator as a collision predictor (evaluate_risk): every held-out agent with company is the ego once, its
   true future the plan, the others' K draws the crowd; the predicted chance of coming within DIST of somebody against what
   happened (Brier score, against the index-paired estimate and the constant base rate).
+* `--refine DIST`: plan refinement (evaluate_refine): every held-out agent with company is the ego once, its naive plan the
+  constant-velocity extrapolation of its track, moved away from the others' K draws by gradient descent on the expected
+  clearance penalty at DIST - does the refined plan collide less with what the others really did?
 * `--min-past M`: the held-out windows also keep the pedestrians seen for only M .. 7 frames (create_dataset_ragged:
   right-aligned observations + obs_len), so they are predicted and their neighbours see them; the errors are reported per
   history length (evaluate_history).  Training stays on full windows unless
@@ -87,6 +90,9 @@ def main(argv=None):
     ap.add_argument("--risk", type=float, default=None, metavar="DIST",
                     help="also report the collision risk of every held-out agent's true future against the K draws of the others "
                          "(closer than DIST, world units) and how well it is calibrated")
+    ap.add_argument("--refine", type=float, default=None, metavar="DIST",
+                    help="also refine every held-out agent's constant-velocity plan against the K draws of the others (clearance "
+                         "penalty at DIST, world units) and report predicted risk and true collisions before and after")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -222,6 +228,13 @@ def main(argv=None):
                       "off by %.2f frames | %d agents with company"
                       % (args.k, args.risk, rk["risk_mean"], 100 * rk["col_gt_agent"], rk["brier"], rk["brier_diag"], rk["brier_base"],
                          rk["risk_hit"], rk["risk_miss"], rk["t_first_err"], rk["n_ego"]))
+            if args.refine is not None:
+                rf = tr.evaluate_refine(data, n_gen_samples=args.k, dist=args.refine)
+                print("Plan refinement (leave-one-out, %d draws, penalty within %.2f, conflict within %.2f): predicted risk %.3f -> %.3f | "
+                      "collisions with the true futures %.1f %% -> %.1f %% | expected penalty %.3f -> %.3f | mean largest move %.3f | "
+                      "%d agents with company"
+                      % (args.k, args.refine, rf["coll_dist"], rf["risk_cv"], rf["risk_ref"], 100 * rf["col_cv"], 100 * rf["col_ref"],
+                         rf["pen_cv"], rf["pen_ref"], rf["moved"], rf["n_ego"]))
             if ragged is not None:
                 hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
                 print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"

@@ -476,6 +476,56 @@ int sw_plan_risk(const float* pos, int pstride, const float* start /*or NULL*/, 
                  const int* plan_len /*[Q] or NULL*/, const int* q_scene /*[Q]*/, const int* q_ego /*[Q] or NULL*/,
                  int Q, int P, float inv_ss, float coll_dist,
                  float* risk /*[Q,P]*/, float* clear_min /*[Q,P]*/, int* counts /*[Q,P,4]*/, void* stream);
+/* PLAN REFINEMENT: the question behind sw_plan_risk turned round - not "how likely is this plan to run into somebody" but
+ * "which plan near it is not": n_iter steps of gradient descent on the expected clearance penalty of a plan against the K
+ * sampled futures of a scene, all inside one launch.  pos, start, scene_off, len, inv_ss, the path of (k, a), the queries
+ * (q_scene, q_ego: which rows of which scene count as "agent a") and the layout of plans / plan_start are exactly as in
+ * sw_plan_risk, except that a start point is REQUIRED on both sides (start and plan_start non-NULL) and that there is no
+ * plan_len.  The draws are open-loop: the pedestrians do not react to the plan.  All fp32.
+ * For one (query q, plan p) the WAYPOINTS are X = (x_1 .. x_T), T = Tp, x_t = plans[q][p][t-1] on entry (X0, kept); x_0 =
+ * plan_start[q] is data and never moves.  The pedestrian path of (k, a) is A_0 = start[a], A_s = pos[k][a][s-1].  The objective:
+ *   J(X) = pen(X) + (w_track / d0^2) trk(X) + (w_smooth / d0^2) smo(X),
+ *   pen(X) = (1 / K) * sum over the agents a of the query, the draws k < K and the segments s = 1 .. min(T, len[a]) of phi,
+ *            (len clamped into 1 .. Tp, NULL meaning Tp) with, for segment s (from point s-1 to point s),
+ *              r0 = A_{s-1} - x_{s-1},  r1 = A_s - x_s  (pedestrian minus plan),  dv = r1 - r0,
+ *              tau = clamp(-(r0.dv) / (dv.dv), 0, 1), tau = 0 when dv.dv = 0     (the arithmetic of sw_scene_clearance),
+ *              c = r0 + tau dv,  u = max(0, 1 - |c|^2 / d0^2),  phi = u^2        (the penalty of sw_clearance_grad);
+ *   trk(X) = sum over t = 1 .. T of |x_t - x0_t|^2;
+ *   smo(X) = sum over t = 1 .. T-1 of |acc_t|^2,  acc_t = x_{t+1} - 2 x_t + x_{t-1}  (acc_1 reads x_0; none for T = 1).
+ * Given the observations the draws of different agents are independent (sw_scene_compose), so pen is the expectation of the
+ * penalty over all K^n joint futures.  Its gradient (tau minimises |r0 + tau dv|^2 over [0, 1], see sw_clearance_grad; the
+ * sign turns because r is pedestrian minus plan):
+ *   d phi / d x_s = (4 u / d0^2) tau c,   d phi / d x_{s-1} = (4 u / d0^2) (1 - tau) c   (nothing for x_0);
+ *   d trk / d x_t = 2 (x_t - x0_t);   d smo / d x_t = 2 (acc_{t-1} - 2 acc_t + acc_{t+1}),  acc_i = 0 outside 1 .. T-1.
+ * One ITERATION, all waypoints at once from the same X:
+ *   step_t = lr d0^2 dJ/dx_t = lr [ (1 / K) sum of 4 u {tau | 1 - tau} c  +  2 w_track (x_t - x0_t)  +  2 w_smooth (acc_{t-1} - 2 acc_t + acc_{t+1}) ];
+ *   if |step_t| > max_move d0:  step_t = step_t * (max_move d0 / |step_t|);      x_t = x_t - step_t.
+ * Descent moves the plan away from the pedestrians.  With this scaling lr, w_track, w_smooth and max_move are dimensionless;
+ * on the quadratic part alone the iteration is stable for lr (2 w_track + 32 w_smooth) < 2 (the acceleration operator's largest
+ * eigenvalue is 16) and free of overshoot below 1; not checked here: the Python layers refuse what is not stable.
+ * Outputs, per (q, p), after n_iter iterations:
+ *   out   [Q,P,Tp,2]  the refined waypoints;  n_iter = 0 copies plans bit for bit;
+ *   cost  [Q,P,2,3]   { pen, trk / d0^2, smo / d0^2 } of X0 (row 0; trk is exactly 0) and of the refined plan (row 1),
+ *                     unweighted; with n_iter = 0 the two rows carry the same bits;
+ *   moved [Q,P]       inv_ss * the largest |x_t - x0_t| over t.
+ * Gating is by select: the ego row, segments behind len[a] and whatever they hold - NaN included - reach no output.  A query
+ * whose scene index lies outside 0 .. S-1 or whose offsets leave 0 .. B, and a scene with nobody but the ego, take no penalty
+ * (pen = 0); the quadratic terms still act.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, start, scene_off, plans, plan_start, q_scene,
+ * out, cost, moved; S, B or Q < 0; K, Tp or P < 1; pstride not 2 or 4; pos or plans off their 8-byte alignment; sstride < 2;
+ * inv_ss <= 0 or NaN; n_iter outside 0 .. 1024; d0 <= 0 or not finite (or d0^2 or 1 / d0^2 outside fp32's range); lr,
+ * w_track, w_smooth or max_move negative or not finite.  SW_ESHAPE: K > 4096 or Tp > 1024.  Q == 0: SW_OK without a launch.
+ * One 256-thread workgroup per (query, plan); a lane owns an (agent, draw) pair as in sw_plan_risk and keeps its path in
+ * registers across the iterations when the scene is one lane batch and the path one time chunk; X, X0 and the per-wave
+ * partial gradients live in LDS (56 (Tp + 2) + 16 bytes).  Every sum across lanes is taken in a fixed order (a fixed tree inside
+ * the wave, then waves 0 .. 3) and there are no atomics: two calls give the same bits, and the result of a (query, plan)
+ * does not depend on the other queries, plans or scenes of the batch.                                                   */
+int sw_plan_refine(const float* pos, int pstride, const float* start /*[B,sstride]*/, int sstride,
+                   const int* scene_off /*[S+1]*/, const int* len /*[B] or NULL*/, int S, int B, int K, int Tp,
+                   const float* plans /*[Q,P,Tp,2]*/, const float* plan_start /*[Q,2]*/, const int* q_scene /*[Q]*/,
+                   const int* q_ego /*[Q] or NULL*/, int Q, int P, float inv_ss, float d0, int n_iter, float lr,
+                   float w_track, float w_smooth, float max_move,
+                   float* out /*[Q,P,Tp,2]*/, float* cost /*[Q,P,2,3]*/, float* moved /*[Q,P]*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

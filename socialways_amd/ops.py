@@ -919,6 +919,83 @@ def plan_risk(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, coll_dis
     return risk, clear_min, counts
 
 
+DESCENT_DEFAULTS = dict(n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5)
+
+
+def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5):
+    """The descent parameters of plan_refine, checked on the host before anything is sampled or launched -> (d0, n_iter, lr,
+    w_track, w_smooth, max_move).  Beyond what sw_plan_refine itself refuses: the quadratic part of the objective must be
+    stable: lr (2 w_track + 32 w_smooth) < 2 (the largest eigenvalue of the acceleration operator is 16; below 1 no mode of
+    the quadratic part overshoots, between 1 and 2 the stiffest ones alternate while they decay)."""
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 0 <= int(n_iter) <= 1024:
+        raise ValueError("n_iter must be an integer in 0 .. 1024, got %r" % (n_iter,))
+    d0 = float(d0)
+    d02 = np.float32(d0) * np.float32(d0)
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (d0 > 0.0 and np.isfinite(d0) and d02 > 0 and np.isfinite(d02) and np.isfinite(np.float32(1) / d02)):
+            raise ValueError("the distance must be finite and > 0 (its square and the inverse of it fp32 numbers), got %r" % (d0,))
+    vals = dict(lr=float(lr), w_track=float(w_track), w_smooth=float(w_smooth), max_move=float(max_move))
+    for name, v in vals.items():
+        if not (v >= 0.0 and np.isfinite(v)):
+            raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+    if not vals["lr"] * (2.0 * vals["w_track"] + 32.0 * vals["w_smooth"]) < 2.0:
+        raise ValueError("unstable descent: lr (2 w_track + 32 w_smooth) must be < 2, got %r"
+                         % (vals["lr"] * (2.0 * vals["w_track"] + 32.0 * vals["w_smooth"]),))
+    return d0, int(n_iter), vals["lr"], vals["w_track"], vals["w_smooth"], vals["max_move"]
+
+
+def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, inv_ss=1.0, lens=None, n_iter=32, lr=0.1,
+                w_track=0.05, w_smooth=0.5, max_move=0.5):
+    """Candidate ego paths moved away from the K sampled futures of a scene (sw_plan_refine): n_iter steps of gradient descent,
+    all in one launch, on  J(X) = the expected clearance penalty - per pedestrian draw and segment max(0, 1 - |c|^2 / d0^2)^2 of
+    the closest approach c, averaged over the K draws; given the observations the agents' draws are independent, so this is
+    the mean over all K^n joint futures -  + (w_track / d0^2) sum |x_t - x0_t|^2  + (w_smooth / d0^2) sum |x_{t+1} - 2 x_t +
+    x_{t-1}|^2.  Every iteration moves all waypoints by lr d0^2 dJ/dx_t, no waypoint further than max_move d0.  The draws are
+    open-loop: the pedestrians do not react to the plan.
+    pos, start, scenes, K, plans, plan_start, q_scene, q_ego, inv_ss, lens as ops.plan_risk, but start and plan_start are
+    REQUIRED (the start point is data and does not move) and there are no plan_lens.  d0 > 0 in the coordinates of pos; lr,
+    w_track, w_smooth, max_move are dimensionless, lr (2 w_track + 32 w_smooth) < 2.
+    Returns (refined (Q, P, Tp, 2); cost (Q, P, 2, 3): before | after x expected penalty | sum |x - x0|^2 / d0^2 | sum |acc|^2 /
+    d0^2, unweighted; moved (Q, P): inv_ss * the largest displacement of a waypoint).  n_iter = 0 returns the plans' bits."""
+    B = scenes.B
+    Tp, pstride = _check_pos(pos, K, B)
+    d0, n_iter, lr, w_track, w_smooth, max_move = check_descent(d0, n_iter, lr, w_track, w_smooth, max_move)
+    if not float(inv_ss) > 0.0:
+        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.float32 or plans.dim() not in (3, 4) or plans.device != pos.device:
+        raise ValueError("plans must be a float32 tensor (Q, P, Tp, 2) or (P, Tp, 2) on the device of pos")
+    if plans.dim() == 3:
+        plans = plans.unsqueeze(0)
+    Q, P = plans.shape[0], plans.shape[1]
+    if P < 1 or tuple(plans.shape[2:]) != (Tp, 2):
+        raise ValueError("plans must be (Q, P >= 1, Tp, 2) with Tp = %d, got %s" % (Tp, tuple(plans.shape)))
+    if K > 4096 or Tp > 1024:
+        raise ValueError("plan_refine takes K <= 4096 draws and Tp <= 1024 steps, got K = %d, Tp = %d" % (K, Tp))
+    if start is None or plan_start is None:
+        raise ValueError("plan_refine needs a start point in front of the paths (start) and of the plans (plan_start)")
+    start, sstride = _start_arg(start, B, pos.device)
+    if not isinstance(plan_start, torch.Tensor) or tuple(plan_start.shape) != (Q, 2) or plan_start.device != pos.device:
+        raise ValueError("plan_start must be (Q, 2) = (%d, 2) on the device of pos" % Q)
+    plan_start = plan_start.float().contiguous()
+    q_scene = _check_query_tensor(q_scene, Q, pos.device, "q_scene")
+    if q_ego is not None:
+        q_ego = _check_query_tensor(q_ego, Q, pos.device, "q_ego")
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    L.require_gpu(pos)
+    pos, plans = pos.float().contiguous(), plans.contiguous()
+    dev = pos.device
+    refined = torch.empty(Q, P, Tp, 2, device=dev)
+    cost = torch.empty(Q, P, 2, 3, device=dev)
+    moved = torch.empty(Q, P, device=dev)
+    if Q == 0:
+        return refined, cost, moved
+    L.call("sw_plan_refine", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), L.ptr(lens), scenes.S, B,
+           K, Tp, L.ptr(plans), L.ptr(plan_start), L.ptr(q_scene), L.ptr(q_ego), Q, P, float(inv_ss), d0, n_iter, lr, w_track,
+           w_smooth, max_move, L.ptr(refined), L.ptr(cost), L.ptr(moved), L.stream())
+    return refined, cost, moved
+
+
 def disc_backward(d_w, ctx, dlabels, dcodes, d_d_w=None, want_dpred=(), ws=None, tag="d"):
     """Backward of Discriminator.forward.  d_d_w (packed, overwritten) None = no weight gradients;
     want_dpred[k] True = return d loss / d pred4 of branch k."""

@@ -9,7 +9,8 @@ quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, fo
 `sample_modes`, the greedy score-ordered suppression behind `SocialWaysTrainer.sample_diverse()`, likewise, and
 `compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`, and
 `clearance_penalty`, the pairwise clearance penalty and its gradient behind `SocialWaysTrainer.set_clearance_loss()`, and
-`plan_risk`, the collision risk of candidate ego paths against the K draws behind `SocialWaysTrainer.plan_risk()`."""
+`plan_risk`, the collision risk of candidate ego paths against the K draws behind `SocialWaysTrainer.plan_risk()`, and
+`refine_plans`, the descent that moves such paths away from the draws behind `SocialWaysTrainer.refine_plans()`."""
 import os
 
 import numpy as np
@@ -280,3 +281,48 @@ def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None,
     plan_lens = _lens_arg(plan_lens, Q, T, t.device)
     L.require_gpu(t)
     return ops.plan_risk(t, start, scenes, K, p, plan_start, scene, ego, coll_dist, float(scale), lens=lens, plan_lens=plan_lens)
+
+
+def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None, ego=None, scale=1.0, lens=None, device="cuda",
+                 **descent):
+    """The nearest paths that stay clear of the sampled futures (`sw_plan_refine`), for trajectories from anywhere: every plan
+    is moved by n_iter steps of gradient descent, in one launch, on the expected clearance penalty against the K draws - the
+    penalty of clearance_penalty() at distance `dist`, averaged over each agent's draws - plus a term that keeps it near the
+    original and one that keeps it smooth.  trajs, sub_batches, plans, scene, ego, scale, lens as plan_risk(); start (B, 2)
+    and plan_start (Q, 2) are REQUIRED: the point in front of every path and of every plan, which does not move.  `dist` is in
+    the units of scale * trajs, like the coll_dist of plan_risk().  descent: n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5,
+    max_move=0.5 (dimensionless; no waypoint moves further than max_move * dist per iteration; lr (2 w_track + 32 w_smooth) < 2).
+    The draws are OPEN-LOOP: the pedestrians do not react to the plan.
+    Returns device tensors (refined (Q, P, T, 2) in the units of trajs; cost (Q, P, 2, 3): before | after x expected penalty |
+    sum |x - x0|^2 / dist^2 | sum |x_{t+1} - 2 x_t + x_{t-1}|^2 / dist^2, unweighted; moved (Q, P): the largest displacement of a
+    waypoint, times scale)."""
+    dist, scale = float(dist), float(scale)
+    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
+    ops.check_descent(dist / scale, **descent)
+    t = _dev(trajs, device)
+    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    p = _dev(plans, device)
+    if p.dim() == 3:
+        p = p.unsqueeze(0)
+    if p.dim() != 4 or p.shape[1] < 1 or tuple(p.shape[2:]) != (T, 2):
+        raise ValueError("plans must be (Q, P >= 1, T, 2) or (P, T, 2) with T = %d, got %s" % (T, tuple(p.shape)))
+    Q = p.shape[0]
+    if start is None or plan_start is None:
+        raise ValueError("refine_plans needs start (B, 2) and plan_start (Q, 2): the points in front of the paths and of the plans")
+    start = _start_arg(start, B, device)
+    plan_start = _dev(plan_start, device)
+    if tuple(plan_start.shape) != (Q, 2):
+        raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
+    if scene is None:
+        if Q != scenes.S:
+            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, scenes.S))
+        scene = np.arange(Q)
+    scene = _query_arg(scene, Q, "scene", t.device)
+    ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
+    lens = _lens_arg(lens, B, T, t.device)
+    L.require_gpu(t)
+    return ops.plan_refine(t, start, scenes, K, p, plan_start, scene, ego, dist / scale, scale, lens=lens, **descent)

@@ -190,6 +190,51 @@ def _scored_draws(tr, obsv_p, n_samples, top_m, sub_batches, noise, row0, obs_le
     return K, M, ph, tr.D.score_samples(obsv_p, ph, obs_len=obs_len)[0]
 
 
+def _plan_queries(n_next, obsv_p, plans, n_samples, sub_batches, scene, ego, plan_start, scale):
+    """The arguments plan_risk() and refine_plans() share, checked on the host before anything is sampled -> (K, B, plans
+    (Q, P, n_next, 2), sb, scene (Q,) int32, ego (Q,) int32 or None, plan_start (Q, 2) or None with ego)."""
+    K = int(n_samples)
+    if K < 1:
+        raise ValueError("n_samples must be at least 1, got %r" % (n_samples,))
+    if not float(scale) > 0.0:
+        raise ValueError("scale must be > 0, got %r" % (scale,))
+    if obsv_p.dim() != 3 or obsv_p.shape[1] < 1 or obsv_p.shape[2] < 2:
+        raise ValueError("obsv_p must be (B, To, >= 2), got %s" % (tuple(obsv_p.shape),))
+    B = obsv_p.shape[0]
+    plans = torch.as_tensor(plans, dtype=torch.float32)
+    if plans.dim() == 3:
+        plans = plans.unsqueeze(0)
+    if plans.dim() != 4 or plans.shape[1] < 1 or tuple(plans.shape[2:]) != (n_next, 2):
+        raise ValueError("plans must be (Q, P >= 1, n_next, 2) or (P, n_next, 2) with n_next = %d, got %s"
+                         % (n_next, tuple(plans.shape)))
+    Q = plans.shape[0]
+    sb = np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2)
+    S = max(len(sb), 1)
+
+    def rows(x, name, hi):
+        host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
+        if host.shape != (Q,) or host.dtype.kind not in "iu" or (host < 0).any() or (host >= hi).any():
+            raise ValueError("%s must hold Q = %d integers in 0 .. %d, got %r" % (name, Q, hi - 1, x))
+        return host.astype(np.int32)
+
+    if scene is None:
+        if Q != S:
+            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, S))
+        scene = np.arange(Q)
+    scene = rows(scene, "scene", S)
+    if ego is not None:
+        if plan_start is not None:
+            raise ValueError("plan_start and ego exclude each other: with ego the plans start at obsv_p[ego[q], -1]")
+        ego = rows(ego, "ego", B)
+    elif plan_start is None:
+        raise ValueError("without ego the plans need plan_start (Q, 2)")
+    else:
+        plan_start = torch.as_tensor(plan_start, dtype=torch.float32)
+        if tuple(plan_start.shape) != (Q, 2):
+            raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+    return K, B, plans, sb, scene, ego, plan_start
+
+
 def _refuse_ragged(data, what, why):
     """Calls without ragged kernels behind them refuse a dataset that carries obs_len, loudly, before any launch."""
     if getattr(data, "obs_len", None) is not None:
@@ -1668,47 +1713,11 @@ class SocialWaysTrainer:
         tuples that one sampling launch has paid for, where the index-paired draws give a multiple of 1 / K.
         Returns (risk (Q, P), clear_min (Q, P), counts (Q, P, 4) int32 - the columns of ops.plan_risk -, trajs (K, B, n_next, 4)).
         Works at any hidden size: it needs only Generator.sample()."""
-        K = int(n_samples)
-        if K < 1:
-            raise ValueError("n_samples must be at least 1, got %r" % (n_samples,))
         if not float(coll_dist) >= 0.0:
             raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
-        if not float(scale) > 0.0:
-            raise ValueError("scale must be > 0, got %r" % (scale,))
-        if obsv_p.dim() != 3 or obsv_p.shape[1] < 1 or obsv_p.shape[2] < 2:
-            raise ValueError("obsv_p must be (B, To, >= 2), got %s" % (tuple(obsv_p.shape),))
-        B, dev = obsv_p.shape[0], obsv_p.device
-        plans = torch.as_tensor(plans, dtype=torch.float32)
-        if plans.dim() == 3:
-            plans = plans.unsqueeze(0)
-        if plans.dim() != 4 or plans.shape[1] < 1 or tuple(plans.shape[2:]) != (self.n_next, 2):
-            raise ValueError("plans must be (Q, P >= 1, n_next, 2) or (P, n_next, 2) with n_next = %d, got %s"
-                             % (self.n_next, tuple(plans.shape)))
-        Q = plans.shape[0]
-        sb = np.asarray(sub_batches, dtype=np.int64).reshape(-1, 2)
-        S = max(len(sb), 1)
-
-        def rows(x, name, hi):
-            host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
-            if host.shape != (Q,) or host.dtype.kind not in "iu" or (host < 0).any() or (host >= hi).any():
-                raise ValueError("%s must hold Q = %d integers in 0 .. %d, got %r" % (name, Q, hi - 1, x))
-            return host.astype(np.int32)
-
-        if scene is None:
-            if Q != S:
-                raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, S))
-            scene = np.arange(Q)
-        scene = rows(scene, "scene", S)
-        if ego is not None:
-            if plan_start is not None:
-                raise ValueError("plan_start and ego exclude each other: with ego the plans start at obsv_p[ego[q], -1]")
-            ego = rows(ego, "ego", B)
-        elif plan_start is None:
-            raise ValueError("without ego the plans need plan_start (Q, 2)")
-        else:
-            plan_start = torch.as_tensor(plan_start, dtype=torch.float32)
-            if tuple(plan_start.shape) != (Q, 2):
-                raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+        K, B, plans, sb, scene, ego, plan_start = _plan_queries(self.n_next, obsv_p, plans, n_samples, sub_batches, scene, ego,
+                                                                plan_start, scale)
+        dev = obsv_p.device
         L.require_gpu(obsv_p)
         if obs_len is not None:
             if not isinstance(self.G, Generator):      # the generic-width and wide paths: no ragged kernels
@@ -1785,6 +1794,110 @@ class SocialWaysTrainer:
                    brier_base=ybar * (1.0 - ybar) if n_ego else 0.0,
                    risk_hit=shit / sy if sy else 0.0, risk_miss=smiss / (n_ego - sy) if n_ego - sy else 0.0,
                    t_first_err=sdt / ndt if ndt else 0.0, n_ego=n_ego, K=K, coll_dist=float(coll_dist))
+        return out
+
+    def refine_plans(self, obsv_p, plans, n_samples, dist, coll_dist=None, sub_batches=[], scene=None, ego=None, plan_start=None,
+                     noise=None, row0=0, scale=1.0, obs_len=None, **descent):
+        """"What is the nearest path that does NOT run into somebody?" - plan_risk() turned round: every candidate path is moved
+        away from the K sampled futures of the scene's pedestrians by gradient descent on the expected clearance penalty (the
+        penalty of set_clearance_loss() at distance `dist`, averaged over each agent's K draws - given the observations the
+        agents' draws are independent, so this is the mean over all K^n joint futures), held near the original by a tracking
+        and a smoothness term.  obsv_p, plans, n_samples, sub_batches, scene, ego, plan_start, noise, row0, scale, obs_len as
+        plan_risk(): `ego` xor `plan_start`; with ego the plans start at obsv_p[ego[q], -1], the ego's own draws are left out and
+        its observed track stays in the social block.  dist and coll_dist (default dist) are in the units of scale * obsv_p.
+        descent: n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5 (ops.plan_refine).  ONE sampling launch, the draws
+        Generator.sample() returns, ONE refine launch for all iterations (ops.plan_refine) and ONE risk launch on the original
+        and the refined plans side by side (ops.plan_risk at coll_dist).  The draws are OPEN-LOOP: the pedestrians do not
+        react to the plan, neither to the original nor to the refined one.
+        Returns (refined (Q, P, n_next, 2), risk (Q, P, 2) before | after, cost (Q, P, 2, 3) and moved (Q, P) - the columns of
+        ops.plan_refine -, trajs (K, B, n_next, 4)).  Works at any hidden size: it needs only Generator.sample()."""
+        dist = float(dist)
+        coll_dist = dist if coll_dist is None else coll_dist
+        if not float(coll_dist) >= 0.0:
+            raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+        K, B, plans, sb, scene, ego, plan_start = _plan_queries(self.n_next, obsv_p, plans, n_samples, sub_batches, scene, ego,
+                                                                plan_start, scale)
+        ops.check_descent(dist / float(scale), **descent)
+        dev = obsv_p.device
+        L.require_gpu(obsv_p)
+        if obs_len is not None:
+            if not isinstance(self.G, Generator):      # the generic-width and wide paths: no ragged kernels
+                refuse_obs_len(obs_len, type(self).__name__)
+            obs_len = ops.obs_len_arg(obs_len, B, obsv_p.shape[1], 2, dev)
+        with torch.no_grad():
+            scenes = ops.SceneIndex.get(sb, B, dev)
+            q_scene = torch.from_numpy(scene).to(dev)
+            q_ego = None
+            if ego is not None:
+                q_ego = torch.from_numpy(ego).to(dev)
+                plan_start = obsv_p[q_ego.long(), -1, :2]
+            plans, plan_start = plans.to(dev), plan_start.to(dev)
+            P = plans.shape[1]
+            ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
+            refined, cost, moved = ops.plan_refine(ph, obsv_p[:, -1], scenes, K, plans, plan_start, q_scene, q_ego,
+                                                   dist / float(scale), inv_ss=float(scale), **descent)
+            risk = ops.plan_risk(ph, obsv_p[:, -1], scenes, K, torch.cat([plans, refined], 1), plan_start, q_scene, q_ego,
+                                 coll_dist, inv_ss=float(scale))[0]
+            return refined, torch.stack([risk[:, :P], risk[:, P:]], dim=2), cost, moved, ph
+
+    REFINE_KEYS = ("risk_cv", "risk_ref", "col_cv", "col_ref", "pen_cv", "pen_ref", "moved")
+
+    def evaluate_refine(self, data, n_gen_samples=20, dist=0.5, coll_dist=0.1, just_one=False, collect=None, noise=None, **descent):
+        """evaluate() plus an answer to: does refining a naive plan against the PREDICTED futures make it collide less with the
+        TRUE ones?  Leave-one-out like evaluate_risk(): every held-out agent of a scene of two or more agents is the ego once.
+        Its naive plan is the constant-velocity extrapolation of its observations (predict_cv: the preds_lnr of the records; on
+        ragged histories of its valid frames); refine_plans() moves it away from the K draws of the scene's other agents (dist,
+        coll_dist in world units through data.ss like evaluate_scenes(); descent: ops.plan_refine).  Over the egos - returns a
+        dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          risk_cv, risk_ref    the mean predicted risk (plan_risk() at coll_dist) of the naive and of the refined plan;
+          col_cv, col_ref      the share of egos whose naive / refined plan comes closer than coll_dist to the TRUE future of
+                               another agent of its scene (the K = 1 risk launch on the ground truth);
+          pen_cv, pen_ref      the mean expected penalty of the two (pen_ref <= pen_cv is what the descent is for);
+          moved                the mean largest displacement of a waypoint, in world units;
+          n_ego, K, dist, coll_dist.
+        The draws are open-loop and so is the ground truth: nobody reacts to the refined plan.  Chunking, noise streams and
+        sampling launches are evaluate()'s; per chunk one refine launch and two risk launches.  A dataset with pred_len (ragged
+        futures): a pedestrian counts while it is present, in the refinement and in both risks, and both risks count the ego's
+        frames as evaluate_risk() does.  Sums are float64 on the device,
+        one host sync at the end.  With `collect` every record of evaluate() also has `plan_ref` (n, n_next, 2; denormalised),
+        `risk_plan`, `hit_plan` (n, 2: naive | refined) and `moved` (n,)."""
+        if not float(coll_dist) >= 0.0:
+            raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
+        ss = float(data.ss)
+        d0 = ops.check_descent(float(dist) * ss, **descent)[0]      # world units -> the coordinates of the dataset
+        dn = self._device_noise(noise)
+        dev, K = self.device, int(n_gen_samples)
+        inv_ss = 1.0 / ss
+        base = _EvalSums(dev)
+        acc = torch.zeros(len(self.REFINE_KEYS), dtype=torch.float64, device=dev)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            q_scene, multi = c.scenes.row_scene()
+            q_ego = torch.arange(c.n, dtype=torch.int32, device=dev)
+            start = c.obsv[:, -1]
+            naive = predict_cv(c.obsv, self.n_next)
+            if c.obs_len is not None and c.obsv.shape[1] > 2:      # the rule of the records' preds_lnr
+                naive = torch.where((c.obs_len <= 2)[:, None, None], predict_cv(c.obsv[:, -2:], self.n_next), naive)
+            naive, pstart = naive[:, None, :, :2].contiguous(), start[:, :2].contiguous()
+            refined, cost, moved = ops.plan_refine(c.ph, start, c.scenes, K, naive, pstart, q_scene, q_ego, d0, inv_ss,
+                                                   lens=c.pred_len, **descent)
+            both = torch.cat([naive, refined], 1)
+            risk = ops.plan_risk(c.ph, start, c.scenes, K, both, pstart, q_scene, q_ego, coll_dist, inv_ss, lens=c.pred_len,
+                                 plan_lens=c.pred_len)[0]
+            hit = ops.plan_risk(c.pred, start, c.scenes, 1, both, pstart, q_scene, q_ego, coll_dist, inv_ss, lens=c.pred_len,
+                                plan_lens=c.pred_len)[2][:, :, 0] > 0
+            rows = torch.cat([risk.double(), hit.double(), cost[:, 0, :, 0].double(), moved.double()], dim=1)      # (n, 7)
+            acc += torch.where(multi[:, None], rows, zero).sum(0)
+            if collect is not None:
+                for rec in self._eval_records(data, c, c.ph, dict(plan_ref=(refined[:, 0], 0), risk_plan=(risk, 0), hit_plan=(hit, 0),
+                                                                  moved=(moved[:, 0], 0))):
+                    rec["plan_ref"] = data.scale.denormalize(rec["plan_ref"])
+                    collect.append(rec)
+        n_ego = sum(b - a for a, b in base.scenes if b - a > 1)
+        out = base.result(data)
+        out.update(zip(self.REFINE_KEYS, (acc / max(n_ego, 1)).tolist()))
+        out.update(n_ego=n_ego, K=K, dist=float(dist), coll_dist=float(coll_dist))
         return out
 
     # ------------------------------------------------------------------------------------------
