@@ -1,5 +1,8 @@
 """The float64 training step: what SocialWaysTrainer.step() / step_many() / _train_epoch() are held to by
-test_step_ref_host.py (CPU), test_gpu_step_reference.py (one process) and test_gpu_step_dp_reference.py (process groups).
+test_step_ref_host.py (CPU), test_gpu_step_reference.py (one process) and test_gpu_step_dp_reference.py (process groups), and
+WideTrainer.step() / GenericTrainer.step() by test_gpu_wide_step_reference.py: the info term's mean runs over the latent-code
+count of the discriminator handed in (`n_codes`: 2 on the fused path), and `wide_grads` / `tap_updates` / `generic_grads` read
+those two engines' gradients in the reference's names and shapes.
 
 The reference is the oracle's modules (oracle/sw_oracle.py) cast to double and loaded from the trainer's state_dicts
 (`oracle_of`), run through the arithmetic of SocialWaysOracle.train_step() (oracle/sw_oracle.py:372-475) WITHOUT the optimizer
@@ -25,7 +28,7 @@ import _ragged_ref as RR
 from _ref64 import G_NAMES, RefRun, _f64, count_ambiguous, gen_mods, gen_params, pick_fewest, recording, run64
 
 W_INFO, W_L2 = 0.5, 0.5     # the constructor defaults of loss_info_w / loss_l2_w (train.py:65, 69)
-NL = 2                      # latent codes of the fused path
+NL = 2                      # latent codes of the fused path, and of any discriminator that does not say otherwise
 
 
 def flags(U=1, info=True, l2=False, variety=False, variety_k=20):
@@ -40,11 +43,21 @@ def trainer_kw(f):
     return dict(n_unrolling_steps=f.U, use_info_loss=f.info, use_l2_loss=f.l2, use_variety_loss=f.variety, variety_k=f.variety_k)
 
 
+def n_codes(D):
+    """The latent-code count of a discriminator: the width of its latent_decoder's last layer, as _ref64.wide_oracle64 reads
+    it; NL where D has no such layer."""
+    try:
+        return int(D.latent_decoder[2].out_features)
+    except (AttributeError, IndexError, TypeError):
+        return NL
+
+
 def oracle_of(G, D, Tp, hidden_size=64, use_social=True, dtype=torch.float64):
     """The oracle with the weights of G (anything that has the four generator modules: a trainer's G, an oracle) and of the
-    discriminator D, in `dtype` - float64: built under _f64() and cast, as _pair / wide_oracle64 do."""
+    discriminator D - whose latent-code count it takes -, in `dtype` - float64: built under _f64() and cast, as _pair /
+    wide_oracle64 do."""
     with (_f64() if dtype == torch.float64 else contextlib.nullcontext()):
-        orc = O.SocialWaysOracle(Tp, hidden_size=hidden_size, use_social=use_social)
+        orc = O.SocialWaysOracle(Tp, hidden_size=hidden_size, use_social=use_social, n_latent_codes=n_codes(D))
     for name, src in [(n, getattr(G, n)) for n in G_NAMES] + [("D", D)]:
         m = getattr(orc, name).to(dtype)
         m.load_state_dict({k: v.detach().cpu().to(dtype) for k, v in src.state_dict().items()})
@@ -146,6 +159,7 @@ def step64(orc, D64, obsv, pred, sb, zv, ov, z, *, ss, obs_len=None, variety_noi
     t0, t1 = _f32(zv), _f32(ov)
     w_info = W_INFO if f.info else 0.0
     predict, disc, p4 = _forms(orc, D64, o, p, sb, _len(obs_len), Tp)
+    nl = n_codes(D64)                               # the info term's mean runs over nl codes per agent (train.py:486, 516)
     res = SimpleNamespace(kmin=None, l2_k=None)
 
     def d_fn():                                     # train.py:476-495
@@ -154,7 +168,7 @@ def step64(orc, D64, obsv, pred, sb, zv, ov, z, *, ss, obs_len=None, variety_noi
         fl, fc = disc(D64, ph)
         rl, _ = disc(D64, p4)
         d_fake, d_real = ((fl - t0) ** 2).sum() / Bg, ((rl - t1) ** 2).sum() / Bg
-        d_info = ((fc - zz[:, :NL]) ** 2).sum() / (NL * Bg)
+        d_info = ((fc - zz[:, :nl]) ** 2).sum() / (nl * Bg)
         return d_fake + d_real + w_info * d_info, [float(v.detach()) for v in (d_fake, d_info, d_real)]
 
     res.d_run, d_terms = _run(list(D64.named_parameters()), [D64], d_fn, seed, dtype)
@@ -164,7 +178,7 @@ def step64(orc, D64, obsv, pred, sb, zv, ov, z, *, ss, obs_len=None, variety_noi
         ph = predict(zz)
         gl, gc = disc(Dg, ph)
         sq = (ph[:, :, :2] - p) ** 2
-        g_fool, g_info, g_l2 = ((gl - t1) ** 2).sum() / Bg, ((gc - zz[:, :NL]) ** 2).sum() / (NL * Bg), sq.sum() / (2 * Tp * Bg)
+        g_fool, g_info, g_l2 = ((gl - t1) ** 2).sum() / Bg, ((gc - zz[:, :nl]) ** 2).sum() / (nl * Bg), sq.sum() / (2 * Tp * Bg)
         loss = g_fool + w_info * g_info
         if f.l2:
             loss = loss + W_L2 * g_l2
@@ -215,3 +229,49 @@ def bucket_grads(tr, d_bucket=None, g_bucket=None):
         for i, ((off, n), (k, q)) in enumerate(zip(m._slices, m.named_parameters())):
             out[name + "." + k] = m.true_view(i, flat[moff + off:moff + off + n].view(q.shape))
     return out
+
+
+# ---- ... of the wide and the generic engine (socialways_amd/wide.py, generic.py): same names and shapes, no padding -----------
+def _g_named(tr):
+    """[(module.name, parameter)] of the generator of a trainer (tr.G) or of an oracle, which holds the four modules itself."""
+    G = getattr(tr, "G", tr)
+    return [(n + "." + k, q) for n in G_NAMES for k, q in getattr(G, n).named_parameters()]
+
+
+def wide_grads(tr, d_flat=None, g_flat=None):
+    """WideTrainer: a packed D / generator gradient buffer (default: dp.gflat / gp.gflat as the step left them - the LAST D
+    update's gradient, the generator phase forms no D weight gradient, and the G gradient) cut into named tensors through the
+    offsets of _Flat -> ({name: gradient} of D, of the generator), float64 on the host."""
+    def cut(fl, flat, named):
+        flat = flat.detach().double().cpu()
+        assert flat.numel() == fl.gflat.numel()
+        return {k: flat[fl.off[id(q)]:fl.off[id(q)] + q.numel()].view(q.shape).clone() for k, q in named}
+    return (cut(tr.dp, tr.dp.gflat if d_flat is None else d_flat, list(tr.D.named_parameters())),
+            cut(tr.gp, tr.gp.gflat if g_flat is None else g_flat, _g_named(tr)))
+
+
+def tap_updates(tr):
+    """Record what every update of the next steps is made from -> (d_taps, g_taps), lists the caller clears between steps.
+    WideTrainer: the packed buffers an eager step hands to _allreduce (U + 1 x dp.gflat, then gp.gflat; a step replayed from
+    a graph in one process hands over nothing).  GenericTrainer: D's p.grad in front of _reduce_grads(D_optimizer) - it is set
+    to None at the end of the step - and the generator's in front of _reduce_grads(predictor_optimizer)."""
+    d_taps, g_taps = [], []
+    if hasattr(tr, "dp"):
+        def tap(buf):
+            (d_taps if buf.data_ptr() == tr.dp.gflat.data_ptr() else g_taps).append(buf.detach().clone())
+        tr._allreduce = tap
+    else:
+        real = tr._reduce_grads
+
+        def tap(optim):
+            named, taps = (list(tr.D.named_parameters()), d_taps) if optim is tr.D_optimizer else (_g_named(tr), g_taps)
+            taps.append({k: (torch.zeros_like(q) if q.grad is None else q.grad).detach().double().cpu() for k, q in named})
+            real(optim)
+        tr._reduce_grads = tap
+    return d_taps, g_taps
+
+
+def generic_grads(tr, d_tap):
+    """GenericTrainer: D's gradient as tap_updates recorded it, the generator's p.grad, which survives the step (a parameter
+    the step formed no gradient for - the social block of a batch without a pair - reads as zeros)."""
+    return d_tap, {k: (torch.zeros_like(q) if q.grad is None else q.grad).detach().double().cpu() for k, q in _g_named(tr)}

@@ -10,14 +10,26 @@ b. shard additivity in float64: the losses and gradients of the shards of shard_
    that the sharded GPU steps are held to.
 c. obs_len = To on every row is the dense reference.
 d. the three per-tensor bounds of test_gpu_step_dp_reference.py (REL_OF) are 4 x the fp32 CPU oracle's own error on those very
-   cases: the figures in their derivation are recomputed here."""
+   cases: the figures in their derivation are recomputed here.
+e. the cases of test_gpu_wide_step_reference.py (the wide and the generic engine: other hidden sizes, latent-code counts and
+   horizons), with the fp32 oracle of each width standing in for the trainer: the seed rule finds a seed with at most
+   MAX_AMBIGUOUS kink inputs, and every loss, the ADE/FDE row and every gradient tensor of step64(dtype=float32) stay within HALF
+   of the bound the GPU file uses (OUT_RT / OUT_AT, GRAD_REL of tests/_ref64.py), so the GPU file takes those bounds unchanged.
+   Recomputed here (pytest -s), seed; largest gradient error as a share of a tensor's largest entry; largest relative loss error,
+   none with a kink input near 0: h64-nl3 seed 2, 1.71e-6, 2.2e-7; h96 seed 1, 1.46e-6, 7.8e-8; h128 seed 1, 2.18e-6, 1.1e-7; h128-nl17 seed 2,
+   3.36e-6, 1.0e-7; h128-tp25 seed 2, 6.4e-7, 6.9e-8; h128-u2-l2 seed 1, 1.10e-6, 1.1e-7; h128-variety seed 1, 1.16e-6, 1.1e-7;
+   h160-tp10 seed 1, 1.38e-6, 1.3e-7; h160-tp10-noinfo seed 1, 1.55e-6, 1.3e-7; h80 seed 1, 1.67e-6, 5.4e-8; h256 seed 8, 3.66e-6,
+   1.8e-7 - the largest, against half of GRAD_REL = 1e-5 and half of OUT_RT = 5e-6.
+f. shard additivity in float64 (ADD_REL) at 3 and 17 latent codes, and the count read from the discriminator (2 by default).
+g. after one step at the real learning rates the oracle's U = 2 and U = 0 runs share D's Linear layers (the restore of
+   train.py:541-542) and neither D's LSTM nor the generator: what part e of the GPU file asserts of the two engines."""
 import numpy as np
 import pytest
 import torch
 
 import sw_oracle as O
 import _step_ref as S
-from _ref64 import scene_rows
+from _ref64 import GRAD_REL, MAX_AMBIGUOUS, OUT_AT, OUT_RT, close_grads_branch_consistent, scene_rows, wide_oracles
 
 SIZES43 = [1, 5, 17, 8, 3, 9]
 To, Tp = 8, 12
@@ -163,3 +175,115 @@ def test_the_per_case_bounds_are_four_times_the_fp32_oracles_own_error():
         assert abs(max(own.values()) - typed) <= 0.01 * typed, (own, typed)
         bounds.setdefault((name, epoch, batch, "G bucket"), {})[tensor] = 4 * typed
     assert bounds == DP.REL_OF
+
+
+# ---- e - g: the wide and the generic engine's cases (tests/test_gpu_wide_step_reference.py), from the oracle alone -----------------
+# id -> (H, n_latent_codes, Tp, flags): every width / code count / horizon the GPU file builds a trainer at, and the switches
+# that change which terms a step differentiates
+WIDE_HOST = {
+    "h64-nl3": (64, 3, 12, S.flags()), "h96": (96, 2, 12, S.flags()), "h128": (128, 2, 12, S.flags()),
+    "h128-u2-l2": (128, 2, 12, S.flags(U=2, l2=True)), "h128-variety": (128, 2, 12, S.flags(variety=True)),
+    "h128-nl17": (128, 17, 12, S.flags()), "h128-tp25": (128, 2, 25, S.flags()), "h160-tp10": (160, 2, 10, S.flags()),
+    "h160-tp10-noinfo": (160, 2, 10, S.flags(info=False)), "h80": (80, 2, 12, S.flags()), "h256": (256, 2, 12, S.flags())}
+
+
+@pytest.mark.parametrize("name", sorted(WIDE_HOST))
+def test_wide_cases_have_a_seed_and_the_fp32_oracle_stays_within_half_of_the_gpu_bounds(name):
+    H, nl, tp, f = WIDE_HOST[name]
+    sb = scene_rows(SIZES43)
+    o32, o64 = wide_oracles(H, nl, tp)
+    assert S.n_codes(o64.D) == nl == o64.n_latent_codes and o64.D.latent_decoder[2].out_features == nl
+    seed, draws, n_amb = S.pick_draws(S.make_draws(SIZES43, To, tp, H // 2), o64, sb, f)
+    assert n_amb <= MAX_AMBIGUOUS, (name, seed, n_amb)
+    obsv, pred, zv, ov, z, _ = draws[0]
+    assert z.shape == (43, H // 2)
+    r64 = S.step64(o64, o64.D, obsv, pred, sb, zv, ov, z, ss=SS, flags=f, seed=seed)
+    r32 = S.step64(o32, o32.D, obsv, pred, sb, zv, ov, z, ss=SS, flags=f, seed=seed, dtype=torch.float32)
+    assert len(r64.losses) == 3 * (f.U + 1) + 3
+    # outputs: half of rtol OUT_RT + atol OUT_AT * max|ref| (_close_out), element by element
+    got = np.concatenate([r32.losses, [r32.ade, r32.fde]])
+    want = np.concatenate([r64.losses, [r64.ade, r64.fde]])
+    for lo, hi in ((0, len(r64.losses)), (len(r64.losses), len(want))):          # the MSE terms, the ADE/FDE row
+        bound = 0.5 * (OUT_RT * np.abs(want[lo:hi]) + OUT_AT * np.abs(want[lo:hi]).max())
+        assert (np.abs(got[lo:hi] - want[lo:hi]) <= bound).all(), (name, got[lo:hi], want[lo:hi])
+    loss_err = float(np.abs(got / want - 1).max())
+    # gradients: half of GRAD_REL per tensor, through the comparison the GPU file uses (with no ambiguous unit: max|err|)
+    close_grads_branch_consistent({k: v.double() for k, v in r32.d_run.grads().items()}, r64.d_run, "host", name + ", D", GRAD_REL / 2)
+    close_grads_branch_consistent({k: v.double() for k, v in r32.g_run.grads().items()}, r64.g_run, "host", name + ", G", GRAD_REL / 2)
+    grad_err = 0.0
+    for a, b in ((r32.d_run.grads(), r64.d_run.grads()), (r32.g_run.grads(), r64.g_run.grads())):
+        for k, ref in b.items():
+            if not f.info and k.startswith("latent_decoder."):
+                assert not bool(ref.any()) and not bool(a[k].any()), k
+            else:
+                assert float(ref.abs().max()) > 0, k
+                grad_err = max(grad_err, _rel(a[k], ref))
+    print("%s: seed %d, %d kink inputs near 0; the fp32 oracle's step misses float64 by %.2e (gradients, of a tensor's largest "
+          "entry), %.1e (losses, ADE/FDE, relative)" % (name, seed, n_amb, grad_err, loss_err))
+
+
+@pytest.fixture(scope="module", params=[(64, 3), (128, 17)], ids=["h64-nl3", "h128-nl17"])
+def o64_nl(request):
+    H, nl = request.param
+    return wide_oracles(H, nl, Tp)[1]
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("name,f", [("plain", S.flags()), ("l2-variety", S.flags(l2=True, variety=True))])
+def test_shards_add_up_at_other_latent_code_counts(o64_nl, name, f, world):
+    from socialways_amd.data import shard_scenes
+    orc, B, sb = o64_nl, 43, scene_rows(SIZES43)
+    nl, H = orc.n_latent_codes, orc.encoder.hidden_size
+    assert nl != 2
+    obsv, pred, zv, ov, z, _ = S.make_draws(SIZES43, To, Tp, H // 2)(8)[0]
+    full = S.step64(orc, orc.D, obsv, pred, sb, zv, ov, z, ss=SS, flags=f)
+    d_full, g_full = full.d_run.grads(), full.g_run.grads()
+    losses, ade, fde = np.zeros_like(full.losses), 0.0, 0.0
+    d_sum = {k: torch.zeros_like(v) for k, v in d_full.items()}
+    g_sum = {k: torch.zeros_like(v) for k, v in g_full.items()}
+    owners = []
+    for lo, hi in shard_scenes(sb, world):
+        r0, r1 = int(sb[lo, 0]), int(sb[hi - 1, 1])
+        owners.append(r0 <= 19 < r1)
+        part = S.step64(orc, orc.D, obsv[r0:r1], pred[r0:r1], sb[lo:hi] - r0, zv, ov, z[r0:r1], ss=SS, flags=f, global_B=B,
+                        global_row0=r0)
+        losses, ade, fde = losses + part.losses, ade + part.ade, fde + part.fde
+        for acc, run in ((d_sum, part.d_run), (g_sum, part.g_run)):
+            for k, v in run.grads().items():
+                acc[k] += v
+    assert sum(owners) == 1
+    assert np.abs(losses - full.losses).max() <= ADD_REL * np.abs(full.losses).max()
+    assert abs(ade - full.ade) <= ADD_REL * full.ade and abs(fde - full.fde) <= ADD_REL * full.fde
+    for acc, ref in ((d_sum, d_full), (g_sum, g_full)):
+        for k in ref:
+            assert float(ref[k].abs().max()) > 0
+            assert _rel(acc[k], ref[k]) <= ADD_REL, (nl, name, world, k, _rel(acc[k], ref[k]))
+    # ... and the info term does run over nl codes: with the count of the fused path it is another number
+    two = ((full.d_run.grads()["latent_decoder.2.bias"]) * nl / 2)
+    assert _rel(two, d_full["latent_decoder.2.bias"]) > 0.1
+
+
+def test_the_latent_code_count_is_the_discriminators_and_two_by_default():
+    o32 = O.SocialWaysOracle(Tp)
+    assert S.n_codes(o32.D) == 2 == S.NL and S.n_codes(object()) == 2 and S.oracle_of(o32, o32.D, Tp).n_latent_codes == 2
+    o5 = O.SocialWaysOracle(Tp, n_latent_codes=5)
+    o64 = S.oracle_of(o5, o5.D, Tp)
+    assert S.n_codes(o5.D) == 5 and o64.n_latent_codes == 5 and o64.D.latent_decoder[2].weight.dtype == torch.float64
+
+
+def test_unrolling_changes_the_oracles_generator_update_and_restores_the_linear_layers_of_d():
+    """What test_gpu_wide_step_reference.py (part e) compares between a U = 2 and a U = 0 trainer, on the oracle: after one
+    step from the same weights D's Linear layers are equal (the restore of train.py:541-542), D's LSTM is not - and neither is
+    the generator, whose update differentiates through the D of the step's last update."""
+    sb = scene_rows(SIZES43)
+    obsv, pred, zv, ov, z, _ = S.make_draws(SIZES43, To, Tp)(1)[0]
+    after = {}
+    for U in (2, 0):
+        torch.manual_seed(79)
+        orc = O.SocialWaysOracle(Tp, use_social=True, n_unrolling_steps=U)
+        orc.train_step(obsv, pred, sb, zv, ov, z, SS)
+        after[U] = orc
+    for (k, a), (_, b) in zip(after[2].D.named_parameters(), after[0].D.named_parameters()):
+        assert torch.equal(a, b) == ("lstm" not in k), k
+    differ = [k for (k, a), (_, b) in zip(S._g_named(after[2]), S._g_named(after[0])) if not torch.equal(a, b)]
+    assert len(differ) >= 20, differ
