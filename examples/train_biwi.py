@@ -19,6 +19,8 @@
 * `--risk DIST`: the generator as a collision predictor (evaluate_risk): every held-out agent with company is the ego once, its
   true future the plan, the others' K draws the crowd; the predicted chance of coming within DIST of somebody against what
   happened (Brier score, against the index-paired estimate and the constant base rate).
+* `--walls FILE[:DIST]`: the static map (`x0 y0 x1 y1` lines, world coordinates): the share of the K draws that walk through a
+  wall (evaluate_walls); with `--refine` the walls join the refinement (evaluate_refine(walls=...)).
 * `--refine DIST`: plan refinement (evaluate_refine): every held-out agent with company is the ego once, its naive plan the
   constant-velocity extrapolation of its track, moved away from the others' K draws by gradient descent on the expected
   clearance penalty at DIST - does the refined plan collide less with what the others really did?
@@ -93,6 +95,10 @@ def main(argv=None):
     ap.add_argument("--refine", type=float, default=None, metavar="DIST",
                     help="also refine every held-out agent's constant-velocity plan against the K draws of the others (clearance "
                          "penalty at DIST, world units) and report predicted risk and true collisions before and after")
+    ap.add_argument("--walls", default=None, metavar="FILE[:DIST]",
+                    help="the static map of the recording: a text file of `x0 y0 x1 y1` lines in world coordinates (# comments); "
+                         "also report how many of the K draws come within DIST (default 0.1, world units) of a wall "
+                         "(evaluate_walls); with --refine the refinement keeps the plans off the walls too")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -119,6 +125,14 @@ def main(argv=None):
             ap.error("--clearance-loss takes DIST or DIST:W, got %r" % args.clearance_loss)
         if args.hidden_size != 64:
             ap.error("--clearance-loss: the clearance term is implemented for the fused 64-unit path (--hidden-size 64)")
+    wall_file, wall_dist = args.walls, 0.1
+    if args.walls is not None:
+        head, sep, tail = args.walls.rpartition(":")
+        try:
+            if sep and head:
+                wall_file, wall_dist = head, float(tail)
+        except ValueError:               # a colon that belongs to the file name
+            pass
     if args.ragged_fused and not args.train_ragged:
         ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
@@ -176,6 +190,7 @@ def main(argv=None):
                      data.n_past, data.n_train_samples))
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
+    walls = data.walls_from_world(sw.load_walls(wall_file)) if wall_file is not None else None
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
                               process_group=pg, **(dict(ragged_fused=True) if args.ragged_fused else {}))
     if args.device_noise is not None:     # the same seed on every rank: the union of the shards is the single-process z
@@ -229,12 +244,21 @@ def main(argv=None):
                       % (args.k, args.risk, rk["risk_mean"], 100 * rk["col_gt_agent"], rk["brier"], rk["brier_diag"], rk["brier_base"],
                          rk["risk_hit"], rk["risk_miss"], rk["t_first_err"], rk["n_ego"]))
             if args.refine is not None:
-                rf = tr.evaluate_refine(data, n_gen_samples=args.k, dist=args.refine)
+                rf = tr.evaluate_refine(data, n_gen_samples=args.k, dist=args.refine, walls=walls)
                 print("Plan refinement (leave-one-out, %d draws, penalty within %.2f, conflict within %.2f): predicted risk %.3f -> %.3f | "
                       "collisions with the true futures %.1f %% -> %.1f %% | expected penalty %.3f -> %.3f | mean largest move %.3f | "
                       "%d agents with company"
                       % (args.k, args.refine, rf["coll_dist"], rf["risk_cv"], rf["risk_ref"], 100 * rf["col_cv"], 100 * rf["col_ref"],
                          rf["pen_cv"], rf["pen_ref"], rf["moved"], rf["n_ego"]))
+                if walls is not None:
+                    print("  with %d walls: plans within %.2f of a wall %.1f %% -> %.1f %% | wall penalty %.3f -> %.3f"
+                          % (walls.shape[0], rf["coll_dist"], 100 * rf["wall_cv"], 100 * rf["wall_ref"], rf["penw_cv"], rf["penw_ref"]))
+            if walls is not None:
+                wl = tr.evaluate_walls(data, walls, n_gen_samples=args.k, wall_dist=wall_dist)
+                print("Walls (%d segments, within %.2f): %.1f %% of the draws, %.1f %% of the agents in some draw, %.1f %% in every draw "
+                      "(ground truth %.1f %%) | Min(%d) ADE,FDE over the clear draws = (%.3f, %.3f) | first conflict at frame %.2f"
+                      % (walls.shape[0], wall_dist, 100 * wl["wall_draws"], 100 * wl["wall_agents"], 100 * wl["wall_blocked"],
+                         100 * wl["wall_gt"], args.k, wl["ade_min_free"], wl["fde_min_free"], wl["t_first"]))
             if ragged is not None:
                 hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
                 print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"

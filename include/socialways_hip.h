@@ -526,6 +526,74 @@ int sw_plan_refine(const float* pos, int pstride, const float* start /*[B,sstrid
                    const int* q_ego /*[Q] or NULL*/, int Q, int P, float inv_ss, float d0, int n_iter, float lr,
                    float w_track, float w_smooth, float max_move,
                    float* out /*[Q,P,Tp,2]*/, float* cost /*[Q,P,2,3]*/, float* moved /*[Q,P]*/, void* stream);
+/* WALLS: the static map of a recording - walls, kerbs, benches - as M line segments, one set per call (one recording has one
+ * map).  walls [M,2,2] fp32 holds the segments [w0, w1] in the coordinates of the trajectories and plans (normalised ones);
+ * inv_ss turns a distance into the units of `dist`, as everywhere else.  M = 0 is allowed (walls may then be NULL); a wall of
+ * zero length is a post; M <= SW_WALLS_MAX, so that the set fits LDS (16 bytes per wall) next to what the refinement holds.
+ * CLOSEST APPROACH of a moving point to a wall within one segment: the path point moves linearly from p0 to p1, the wall is
+ * static.  e = p1 - p0, f = w1 - w0, a x b = a.x b.y - a.y b.x.  Five candidates (s, c) - s in [0, 1] the place on the path
+ * segment, c the path point minus the wall point - tried in this order; the first is the best so far, a later one replaces
+ * the best only if its |c|^2 is STRICTLY smaller (a NaN compares false and replaces nothing):
+ *   1. s = 0:  c = p0 - (w0 + u f),  u = clamp((p0 - w0).f / |f|^2, 0, 1), u = 0 when |f|^2 = 0;
+ *   2. s = 1:  the same with p1;
+ *   3. the end w0 against the path:  s = clamp((w0 - p0).e / |e|^2, 0, 1), s = 0 when |e|^2 = 0,  c = p0 + s e - w0;
+ *   4. the end w1 likewise;
+ *   5. a proper crossing:  d1 = f x (p0 - w0), d2 = f x (p1 - w0), d3 = e x (w0 - p0), d4 = e x (w1 - p0); if d1, d2 have
+ *      strictly opposite signs and d3, d4 have strictly opposite signs:  c = 0, |c|^2 = 0, s = d1 / (d1 - d2).
+ * Touching and collinear contact reach distance 0 through candidates 1 - 4.  The reciprocals of |f|^2, |e|^2 and d1 - d2 are
+ * the hardware's (1 ulp), as in sw_scene_clearance: u and s only place a point on a segment.
+ * PENALTY of a (path segment, wall) pair at the distance dw:  u = max(0, 1 - |c|^2 / dw^2),  phi = u^2, counted where
+ * |c|^2 < dw^2.  By the envelope argument of sw_clearance_grad (the candidate's free parameter minimises |c|^2):
+ *   d phi / d p1 = -(4 u / dw^2) s c,    d phi / d p0 = -(4 u / dw^2) (1 - s) c.
+ * phi is C1 at |c| = dw and the gradient is finite everywhere.  It is exactly 0 where the path crosses the wall (c = 0):
+ * descent cannot undo a crossing - crossings are reported (sw_path_walls), not repaired.  Where two candidates tie - a path
+ * parallel to a wall - |c|^2 is unique but s is not: the order above decides which end point takes the gradient, while the
+ * sum over both end points, -(4 u / dw^2) c, does not depend on it.  This discontinuity is the twin of the "pair without
+ * relative motion" one (tau = 0 when dv.dv = 0).                                                                         */
+#define SW_WALLS_MAX 1024
+/* PATH WALLS: the clearance of R = K B paths to the walls in one launch.  pos, pstride, start, sstride, the path of (k, a) and
+ * len are as in sw_scene_clearance_len: with a start point (start != NULL) the path has Tp segments and segment j (from point
+ * j to point j + 1) ends at future frame j, without one Tp - 1 segments and segment j ends at frame j + 1; a segment counts
+ * only while its frame t < len[a] (clamped into 1 .. Tp, NULL meaning Tp), and what lies behind a length, NaN included,
+ * reaches nothing (every contribution is gated by a select).  Per path (k, a), over its counted segments and all M walls:
+ *   clear [K,B]        inv_ss * sqrtf(the smallest |c|^2); +inf with M = 0 or nothing counted;
+ *   first [K,B] int32  the frame at which the first segment with a wall closer than dist ends, -1 if none;
+ *   nseg  [K,B] int32  the number of (segment, wall) pairs closer than dist.
+ * "Closer" is the fp32 comparison sqrtf(|c|^2) * inv_ss < dist, as in sw_plan_risk.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, clear, first, nseg, or walls with M > 0; K < 1;
+ * B < 0; Tp < 1; M < 0; pstride not 2 or 4; pos off its 8-byte alignment; start with sstride < 2; inv_ss <= 0 or NaN; dist < 0
+ * or NaN.  SW_ESHAPE: M > SW_WALLS_MAX.  B == 0: SW_OK without a launch.
+ * One 256-thread workgroup per 64 paths: a lane owns a path, its points in registers; the four waves take the wall slices
+ * w, w + 4, ... of the same 64 paths, the walls read from LDS as the wave-uniform partner.  What is accumulated is a minimum
+ * and two integers, folded over the waves in the order 0 .. 3; no atomics: two calls give the same bits.                  */
+int sw_path_walls(const float* pos, int pstride, const float* start /*[B,sstride] or NULL*/, int sstride,
+                  const int* len /*[B] or NULL*/, int K, int B, int Tp, const float* walls /*[M,2,2]*/, int M,
+                  float inv_ss, float dist, float* clear /*[K,B]*/, int* first /*[K,B]*/, int* nseg /*[K,B]*/, void* stream);
+/* PLAN REFINEMENT WITH WALLS: sw_plan_refine with one more term in the objective,
+ *   J(X) = pen(X) + (w_track / d0^2) trk(X) + (w_smooth / d0^2) smo(X) + w_wall wal(X),
+ *   wal(X) = the sum over the plan's segments s = 1 .. T (from x_{s-1} to x_s; x_0 = plan_start is data) and the M walls of
+ *            phi at the distance dw (WALLS above) - no 1 / K: the walls are certain.
+ * The iteration is sw_plan_refine's with the wall gradient inside the step,
+ *   step_t = lr [ (1 / K) sum 4 u {tau | 1 - tau} c  +  w_wall (d0^2 / dw^2) sum over the walls of -4 u_w ( s c of segment t
+ *            + (1 - s) c of segment t + 1 )  +  2 w_track (x_t - x0_t)  +  2 w_smooth (acc_{t-1} - 2 acc_t + acc_{t+1}) ],
+ * capped at max_move d0 as before; the wall term is added last, to the sum sw_plan_refine forms.  The stability rule is unchanged: the wall term is bounded and not quadratic.
+ * cost is [Q,P,2,4]: the three columns of sw_plan_refine, then wal, unweighted.  n_iter = 0 returns the plans' bits; M = 0
+ * returns, bit for bit, what sw_plan_refine returns in out, moved and the first three cost columns, and wal = 0.
+ * Checked before the device is touched: everything sw_plan_refine checks, and SW_EARG: M < 0; walls NULL with M > 0; dw <= 0
+ * or not finite (or dw^2 or 1 / dw^2 outside fp32's range); w_wall negative or not finite, or w_wall d0^2 / dw^2 not
+ * finite.  SW_ESHAPE: M > SW_WALLS_MAX.
+ * The same kernel as sw_plan_refine, instantiated with the wall evaluation: per iteration the workgroup's threads take
+ * (wall slice, plan segment) pairs - 256 / Tp slices, a slice the walls c, c + 256 / Tp, ... - and the slices are added in
+ * ascending order: every sum in a fixed order, no atomics, two calls give the same bits, a plan's result independent of
+ * the rest of the batch.  LDS: sw_plan_refine's, rounded up to 16, + 16 M + 16 (max(256 / Tp, 1) Tp + 1) bytes - 90 256 at
+ * Tp = 1024, M = 1024, inside the 160 KB of a CU.                                                                        */
+int sw_plan_refine_walls(const float* pos, int pstride, const float* start /*[B,sstride]*/, int sstride,
+                         const int* scene_off /*[S+1]*/, const int* len /*[B] or NULL*/, int S, int B, int K, int Tp,
+                         const float* plans /*[Q,P,Tp,2]*/, const float* plan_start /*[Q,2]*/, const int* q_scene /*[Q]*/,
+                         const int* q_ego /*[Q] or NULL*/, int Q, int P, float inv_ss, float d0, int n_iter, float lr,
+                         float w_track, float w_smooth, float max_move, const float* walls /*[M,2,2]*/, int M, float dw,
+                         float w_wall, float* out /*[Q,P,Tp,2]*/, float* cost /*[Q,P,2,4]*/, float* moved /*[Q,P]*/,
+                         void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

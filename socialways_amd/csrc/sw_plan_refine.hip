@@ -1,11 +1,13 @@
 // sw_plan_refine.hip - gradient descent on the expected clearance penalty of candidate ego paths against the K sampled
 // futures of a scene, every iteration inside one launch: per (query, plan) the penalty of sw_clearance_grad against every
 // (draw, agent) path, averaged over the draws (the draws of different agents are independent given the observations), plus a
-// tracking and a smoothness term.  The segment arithmetic is sw_scene_dev.h's; the lane layout is sw_plan_risk.hip's.  Does
-// not depend on the hidden size.
+// tracking and a smoothness term - and, in the instance with walls, the penalty of the plan's own segments against a static
+// map of line segments (sw_wall_dev.h).  The segment arithmetic is sw_scene_dev.h's; the lane layout is sw_plan_risk.hip's.
+// Does not depend on the hidden size.
 #include "../../include/socialways_hip.h"
 #include "sw_common.h"
 #include "sw_scene_dev.h"
+#include "sw_wall_dev.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -28,13 +30,23 @@ struct RfArgs {
   int Kb, APB;                 // draws and agents of a lane batch (Kb * APB <= 256)
   int n_iter;
   float inv_ss, d02, inv_d02, inv_K, lr, wt2, ws2, cap, cap2;      // wt2 = 2 w_track, ws2 = 2 w_smooth, cap = max_move d0
+  // the instance with walls only
+  const float* walls;
+  int M, NSL, NW;              // walls, wall slices (NSL * Tp <= 256, or 1), walls of a slice = ceil(M / NSL)
+  float dw2, inv_dw2, ww;      // ww = w_wall d0^2 / dw^2
 };
 
 // LDS of a workgroup: three rows of Tp + 2 points (X0, and X twice: an iteration reads one and writes the other) and one row
 // of partial gradients per wave, each with a slot behind its last point that takes the stores of idle lanes; then 4 floats
 // for the block sums.
-__host__ __device__ inline int rf_row(int Tp) { return Tp + 2; }
-__host__ __device__ inline int rf_lds_bytes(int Tp) { return 8 * (3 + RF_WAVES) * rf_row(Tp) + 16; }
+__host__ __device__ constexpr int rf_row(int Tp) { return Tp + 2; }
+__host__ __device__ constexpr int rf_lds_bytes(int Tp) { return 8 * (3 + RF_WAVES) * rf_row(Tp) + 16; }
+// With walls, behind that (rounded up to 16 bytes): the M walls, then per (wall slice, plan segment) the shares of the
+// segment's two end points in the slice's wall gradient - two arrays of NSL * Tp float2, each with a slot behind its last
+// element that takes the stores of idle threads.
+__host__ __device__ constexpr int rf_wall_slices(int Tp) { return Tp < RF_THREADS ? RF_THREADS / Tp : 1; }
+__host__ __device__ constexpr int rf_wall_off(int Tp) { return (rf_lds_bytes(Tp) + 15) & ~15; }
+__host__ __device__ constexpr int rf_lds_bytes_walls(int Tp, int M) { return rf_wall_off(Tp) + 16 * M + 2 * 8 * (rf_wall_slices(Tp) * Tp + 1); }
 
 // acc_i = x_{i+1} - 2 x_i + x_{i-1} for 1 <= i <= Tp - 1, else 0: clamped reads, the value selected afterwards
 __device__ __forceinline__ float2 rf_acc(const float2* x, int i, int Tp) {
@@ -77,6 +89,14 @@ __device__ __forceinline__ float rf_wave_sum(float v) {
 //   quadratic terms, caps the step and writes the other copy of X; a second barrier ends the iteration.  There are
 //   n_iter + 1 evaluations: the first also gives the costs of X0, the last only the costs of the result.  Every barrier sits in
 //   uniform control flow; there is no early exit at all - a query without agents runs the loops over no lanes' worth of work.
+//   WALLS (sw_plan_refine_walls; the instance without is sw_plan_refine's and carries none of this): every evaluation also
+//   walks the plan's OWN segments against the walls, staged in LDS once.  Tp is usually 12 and M tens to hundreds, so the work
+//   item is a (wall slice c, plan segment s) pair, item = c * Tp + s over the workgroup's threads, NSL = 256 / Tp slices (1
+//   above 256 steps, the threads then loop over the segments); slice c takes the walls c, c + NSL, ... in ascending order,
+//   every item ceil(M / NSL) of them with the index clamped and the contribution selected, so the trip count is uniform.  The
+//   item writes the two end points' shares of its slice to LDS (an idle thread to the slot behind); behind the barrier the
+//   thread of waypoint t adds, slices ascending, the share of segment t-1's second end and of segment t's first end.
+template <bool WALLS>
 __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float* __restrict__ out, float* __restrict__ cost,
                                                                  float* __restrict__ moved) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rf_lds[];
@@ -90,6 +110,10 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
   float2* gw = xn + ROW;                                     // RF_WAVES rows
   float* red = reinterpret_cast<float*>(gw + RF_WAVES * ROW);
   float2* gmine = gw + wave * ROW;
+  float4* wl = reinterpret_cast<float4*>(rf_lds + rf_wall_off(Tp));      // WALLS only
+  const int NIT = WALLS ? A.NSL * Tp : 0;                    // (slice, segment) items; slot NIT takes the idle stores
+  float2* wg0 = reinterpret_cast<float2*>(wl + (WALLS ? A.M : 0));
+  float2* wg1 = wg0 + NIT + 1;
 
   const int sc = A.q_scene[q];
   int s0 = 0, n = 0;
@@ -112,6 +136,7 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
     xn[i] = v;
   }
   for (int i = tid; i < RF_WAVES * ROW; i += RF_THREADS) gw[i] = float2{0.f, 0.f};
+  if constexpr (WALLS) wl_stage(wl, A.walls, A.M, tid, RF_THREADS);
   __syncthreads();
 
   const int al = tid / A.Kb, kk = tid - al * A.Kb;
@@ -179,6 +204,33 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
       }
     }
 
+    float wphi = 0.f;
+    if constexpr (WALLS) {
+      // ---- the walls: item (c, s) = segment s of xc against the walls of slice c -------------------------------------------
+      for (int ib = 0; ib < NIT; ib += RF_THREADS) {
+        const int i = ib + tid, ic = i < NIT ? i : NIT - 1;
+        const int c = ic / Tp, s = ic - c * Tp;
+        const float2 p0 = xc[s], p1 = xc[s + 1];
+        float2 g0 = float2{0.f, 0.f}, g1 = float2{0.f, 0.f};
+        for (int jw = 0; jw < A.NW; ++jw) {                  // uniform
+          const int m = c + jw * A.NSL, mc = m < A.M ? m : A.M - 1;
+          float sw_, cx, cy, cc;
+          wl_closest(p0, p1, wl[mc], sw_, cx, cy, cc);
+          const bool on = i < NIT && m < A.M && cc < A.dw2;
+          const float u = fmaxf(1.f - cc * A.inv_dw2, 0.f);
+          const float wx = -4.f * u * cx, wy = -4.f * u * cy;
+          g1.x += on ? sw_ * wx : 0.f;
+          g1.y += on ? sw_ * wy : 0.f;
+          g0.x += on ? (1.f - sw_) * wx : 0.f;
+          g0.y += on ? (1.f - sw_) * wy : 0.f;
+          wphi += on ? u * u : 0.f;
+        }
+        const int slot = i < NIT ? i : NIT;                  // slot NIT is write-only: whatever the idle threads leave there is never read
+        wg0[slot] = g0;
+        wg1[slot] = g1;
+      }
+    }
+
     const bool first = it == 0, last = it == A.n_iter;       // uniform
     if (first || last) {
       // the costs of xc: pen | trk / d0^2 | smo / d0^2, and the largest displacement
@@ -197,14 +249,19 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
       const float pen = sw_block_sum(phi, red) * A.inv_K;
       trk = sw_block_sum(trk, red) * A.inv_d02;
       smo = sw_block_sum(smo, red) * A.inv_d02;
-      float* c = cost + (size_t)blockIdx.x * 6;
+      constexpr int NC = WALLS ? 4 : 3;
+      float wpen = 0.f;
+      if constexpr (WALLS) wpen = sw_block_sum(wphi, red);
+      float* c = cost + (size_t)blockIdx.x * (2 * NC);
       if (first && tid == 0) {
         c[0] = pen; c[1] = trk; c[2] = smo;
+        if constexpr (WALLS) c[3] = wpen;
       }
       if (last) {
         far = sw_block_max(far, red);
         if (tid == 0) {
-          c[3] = pen; c[4] = trk; c[5] = smo;
+          c[NC] = pen; c[NC + 1] = trk; c[NC + 2] = smo;
+          if constexpr (WALLS) c[NC + 3] = wpen;
           moved[blockIdx.x] = sqrtf(far) * A.inv_ss;
         }
         break;
@@ -225,8 +282,25 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
       }
       const float2 x = xc[tc], xo = x0[tc];
       const float2 am = rf_acc(xc, tc - 1, Tp), a0 = rf_acc(xc, tc, Tp), ap = rf_acc(xc, tc + 1, Tp);
-      float sx = A.lr * (gx * A.inv_K + A.wt2 * (x.x - xo.x) + A.ws2 * (am.x - 2.f * a0.x + ap.x));
-      float sy = A.lr * (gy * A.inv_K + A.wt2 * (x.y - xo.y) + A.ws2 * (am.y - 2.f * a0.y + ap.y));
+      float sx, sy;
+      if constexpr (WALLS) {
+        float hx = 0.f, hy = 0.f;                            // the wall gradient of waypoint tc, slices ascending
+        const bool inner = tc < Tp;                          // segment tc exists: its first end is waypoint tc
+        const int s1 = inner ? tc : Tp - 1;
+        for (int c = 0; c < A.NSL; ++c) {
+          const float2 v1 = wg1[c * Tp + tc - 1], v0 = wg0[c * Tp + s1];
+          hx += v1.x;
+          hy += v1.y;
+          hx += inner ? v0.x : 0.f;
+          hy += inner ? v0.y : 0.f;
+        }
+        // the wall term LAST, behind the sum the instance without walls forms: a wall gradient of 0 leaves that sum's bits
+        sx = A.lr * ((gx * A.inv_K + A.wt2 * (x.x - xo.x) + A.ws2 * (am.x - 2.f * a0.x + ap.x)) + A.ww * hx);
+        sy = A.lr * ((gy * A.inv_K + A.wt2 * (x.y - xo.y) + A.ws2 * (am.y - 2.f * a0.y + ap.y)) + A.ww * hy);
+      } else {
+        sx = A.lr * (gx * A.inv_K + A.wt2 * (x.x - xo.x) + A.ws2 * (am.x - 2.f * a0.x + ap.x));
+        sy = A.lr * (gy * A.inv_K + A.wt2 * (x.y - xo.y) + A.ws2 * (am.y - 2.f * a0.y + ap.y));
+      }
       const float n2 = sx * sx + sy * sy;
       const float sc_ = n2 > A.cap2 ? A.cap / sqrtf(n2) : 1.f;
       sx = n2 > A.cap2 ? sx * sc_ : sx;
@@ -243,11 +317,12 @@ __global__ __launch_bounds__(RF_THREADS) void plan_refine_kernel(RfArgs A, float
   for (int i = tid; i < Tp; i += RF_THREADS) o[i] = xc[i + 1];
 }
 
-extern "C" int sw_plan_refine(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
-                              const int* len, int S, int B, int K, int Tp, const float* plans, const float* plan_start,
-                              const int* q_scene, const int* q_ego, int Q, int P, float inv_ss, float d0, int n_iter, float lr,
-                              float w_track, float w_smooth, float max_move, float* out, float* cost, float* moved,
-                              void* stream) {
+// the argument checks and the launch of both entry points; walls == NULL with M < 0: the instance without walls
+static int rf_run(const float* pos, int pstride, const float* start, int sstride, const int* scene_off, const int* len, int S,
+                  int B, int K, int Tp, const float* plans, const float* plan_start, const int* q_scene, const int* q_ego, int Q,
+                  int P, float inv_ss, float d0, int n_iter, float lr, float w_track, float w_smooth, float max_move,
+                  const float* walls, int M, float dw, float w_wall, float* out, float* cost, float* moved, void* stream) {
+  const bool with_walls = M >= 0;
   if (!pos || !start || !scene_off || !plans || !plan_start || !q_scene || !out || !cost || !moved) return SW_EARG;
   if (S < 0 || B < 0 || Q < 0 || K < 1 || Tp < 1 || P < 1 || !(inv_ss > 0.f)) return SW_EARG;
   if ((pstride != 2 && pstride != 4) || sstride < 2) return SW_EARG;
@@ -259,7 +334,15 @@ extern "C" int sw_plan_refine(const float* pos, int pstride, const float* start,
   const float par[4] = {lr, w_track, w_smooth, max_move};
   for (float v : par)
     if (!(v >= 0.f) || !isfinite(v)) return SW_EARG;
+  float dw2 = 1.f;
+  if (with_walls) {
+    if (M > 0 && !walls) return SW_EARG;
+    if (!(dw > 0.f) || !isfinite(dw) || !(w_wall >= 0.f) || !isfinite(w_wall)) return SW_EARG;
+    dw2 = dw * dw;
+    if (!(dw2 > 0.f) || !isfinite(dw2) || !isfinite(1.f / dw2) || !isfinite(w_wall * (d02 / dw2))) return SW_EARG;
+  }
   if (K > RF_MAXK || Tp > RF_MAXT) return SW_ESHAPE;
+  if (with_walls && M > SW_WALLS_MAX) return SW_ESHAPE;
   if (Q == 0) return SW_OK;
   if ((long long)Q * P > 0x7fffffffLL) return SW_EARG;
   RfArgs A = {};
@@ -273,8 +356,43 @@ extern "C" int sw_plan_refine(const float* pos, int pstride, const float* start,
   A.lr = lr; A.wt2 = 2.f * w_track; A.ws2 = 2.f * w_smooth;
   A.cap = max_move * d0;
   A.cap2 = A.cap * A.cap;                                    // +inf for a huge max_move: no step is capped
-  const int lds = rf_lds_bytes(Tp);                          // 57 472 bytes at Tp = 1024: inside the default limit
-  SW_LAUNCH(plan_refine_kernel, dim3((unsigned)(Q * P)), dim3(RF_THREADS), lds, (hipStream_t)stream, A, out, cost, moved);
-  SW_CHECK_LAUNCH("plan_refine_kernel");
+  if (!with_walls) {
+    const int lds = rf_lds_bytes(Tp);                        // 57 472 bytes at Tp = 1024: inside the default limit
+    SW_LAUNCH_AS("plan_refine_kernel", plan_refine_kernel<false>, dim3((unsigned)(Q * P)), dim3(RF_THREADS), lds,
+                 (hipStream_t)stream, A, out, cost, moved);
+    SW_CHECK_LAUNCH("plan_refine_kernel");
+    return SW_OK;
+  }
+  A.walls = walls; A.M = M;
+  A.NSL = rf_wall_slices(Tp);
+  A.NW = (M + A.NSL - 1) / A.NSL;
+  A.dw2 = dw2; A.inv_dw2 = 1.f / dw2; A.ww = w_wall * (d02 / dw2);
+  static_assert(rf_lds_bytes_walls(RF_MAXT, SW_WALLS_MAX) <= 160 * 1024, "the largest plan and map fit the LDS of a CU");
+  const int lds = rf_lds_bytes_walls(Tp, M);                 // 90 256 bytes at Tp = 1024, M = 1024
+  if (lds > 160 * 1024) return SW_ESHAPE;
+  static int have = 0;
+  if (int rc = sw_set_lds((const void*)plan_refine_kernel<true>, lds, have)) return rc;
+  SW_LAUNCH_AS("plan_refine_walls_kernel", plan_refine_kernel<true>, dim3((unsigned)(Q * P)), dim3(RF_THREADS), lds,
+               (hipStream_t)stream, A, out, cost, moved);
+  SW_CHECK_LAUNCH("plan_refine_walls_kernel");
   return SW_OK;
+}
+
+extern "C" int sw_plan_refine(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
+                              const int* len, int S, int B, int K, int Tp, const float* plans, const float* plan_start,
+                              const int* q_scene, const int* q_ego, int Q, int P, float inv_ss, float d0, int n_iter, float lr,
+                              float w_track, float w_smooth, float max_move, float* out, float* cost, float* moved,
+                              void* stream) {
+  return rf_run(pos, pstride, start, sstride, scene_off, len, S, B, K, Tp, plans, plan_start, q_scene, q_ego, Q, P, inv_ss, d0,
+                n_iter, lr, w_track, w_smooth, max_move, nullptr, -1, 0.f, 0.f, out, cost, moved, stream);
+}
+
+extern "C" int sw_plan_refine_walls(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
+                                    const int* len, int S, int B, int K, int Tp, const float* plans, const float* plan_start,
+                                    const int* q_scene, const int* q_ego, int Q, int P, float inv_ss, float d0, int n_iter,
+                                    float lr, float w_track, float w_smooth, float max_move, const float* walls, int M,
+                                    float dw, float w_wall, float* out, float* cost, float* moved, void* stream) {
+  if (M < 0) return SW_EARG;
+  return rf_run(pos, pstride, start, sstride, scene_off, len, S, B, K, Tp, plans, plan_start, q_scene, q_ego, Q, P, inv_ss, d0,
+                n_iter, lr, w_track, w_smooth, max_move, walls, M, dw, w_wall, out, cost, moved, stream);
 }

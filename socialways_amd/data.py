@@ -109,6 +109,13 @@ class SceneDataset:
         self.pred_len = torch.from_numpy(check_pred_len(host, self.pred.shape[0], self.n_next)).to(self.pred.device)
         return self
 
+    def walls_from_world(self, segments):
+        """The static map of the recording in the coordinates of this dataset: world-coordinate segments (M, 4) - x0 y0 x1 y1 -
+        or (M, 2, 2) - [w0, w1] -, M = 0 included, pass through the dataset's Scale.normalize (shift included) like the tracks
+        -> float32 (M, 2, 2) on the device of the tracks: what path_walls / refine_plans / evaluate_walls take as `walls`."""
+        seg = wall_segments(np.array(segments, dtype=np.float32, copy=True))
+        return torch.from_numpy(self.scale.normalize(seg)).to(self.obsv.device)
+
     @classmethod
     def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None, train=False):
         """Windows that a model trained on `like` is evaluated on: EVERY scene is a test scene (no training part), the
@@ -155,6 +162,32 @@ class SceneDataset:
                 a = int(subs[0][0])
                 yield a, int(subs[-1][1]), np.asarray(subs, dtype=np.int64) - a
                 acc, subs = 0, []
+
+
+def wall_segments(x):
+    """The one shape rule of a map: a numpy array or a tensor (M, 4) - x0 y0 x1 y1 - or (M, 2, 2) - [w0, w1] -, M = 0 included
+    -> its view (M, 2, 2), or ValueError."""
+    sh = tuple(x.shape)
+    n = int(np.prod(sh))
+    if n and (len(sh) not in (2, 3) or n // sh[0] != 4 or n % sh[0]):
+        raise ValueError("walls must be (M, 2, 2) or (M, 4): the segments [w0, w1] = x0 y0 x1 y1, got %s" % (sh,))
+    return x.reshape(-1, 2, 2)
+
+
+def load_walls(path):
+    """A map file -> world-coordinate segments (M, 4) float32: one `x0 y0 x1 y1` line per wall, `#` starts a comment, blank
+    lines are skipped; a file without walls gives (0, 4).  SceneDataset.walls_from_world() takes them into a dataset's
+    coordinates."""
+    rows = []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.split("#", 1)[0].split()
+            if not line:
+                continue
+            if len(line) != 4:
+                raise ValueError("%s:%d: a wall is `x0 y0 x1 y1`, got %d fields" % (path, n, len(line)))
+            rows.append([float(v) for v in line])
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 4)
 
 
 def synth_tracks(n_scenes, agents, n_past=8, n_next=12, seed=1234):

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .data import check_obs_len
+from .data import check_obs_len, wall_segments
 
 
 class SceneIndex:
@@ -922,11 +922,77 @@ def plan_risk(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, coll_dis
 DESCENT_DEFAULTS = dict(n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5)
 
 
-def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5):
+def check_walls(walls, device=None):
+    """The map of a call, checked without touching the device: walls (M, 2, 2) float32 - the segments [w0, w1] in the
+    coordinates of the paths, M = 0 .. 1024 (SW_WALLS_MAX), on `device` when one is given -> (walls contiguous, M)."""
+    if not isinstance(walls, torch.Tensor) or walls.dtype != torch.float32 or walls.dim() != 3 or tuple(walls.shape[1:]) != (2, 2):
+        raise ValueError("walls must be a float32 tensor (M, 2, 2): the segments [w0, w1]")
+    if device is not None and walls.device != device:
+        raise ValueError("walls must be on the device of pos")
+    M = walls.shape[0]
+    if M > L.WALLS_MAX:
+        raise ValueError("a call takes at most %d walls, got %d" % (L.WALLS_MAX, M))
+    return walls.contiguous(), M
+
+
+def walls_arg(walls, device):
+    """The map as the layers above take it - a tensor (SceneDataset.walls_from_world) or host data, (M, 2, 2) or (M, 4), M = 0
+    included, in the coordinates of the paths - checked without touching the device -> float32 (M, 2, 2) on `device`."""
+    w = torch.as_tensor(walls if isinstance(walls, torch.Tensor) else np.asarray(walls), dtype=torch.float32)
+    return check_walls(wall_segments(w))[0].to(device)
+
+
+def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
+    """The clearance of paths - the K draws, true futures, ego plans - to a static map of line segments (sw_path_walls), one
+    launch for all K * B paths.  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or None: the point
+    in front of the Tp positions (any row stride, as scene_clearance), giving Tp segments instead of Tp - 1; walls (M, 2, 2)
+    float32 on the device of pos, M = 0 .. 1024: the segments [w0, w1] in the coordinates of pos, a zero-length one being a
+    post; lens (B,) int32 on the device: ragged futures, as scene_clearance(lens=...).  Within a segment the path point moves
+    linearly and the wall stands still.
+    Returns (clear (K, B): inv_ss * the smallest distance to any wall, +inf without walls or counted segments; first (K, B)
+    int32: the frame at which the first segment closer than dist ends, -1 without; nseg (K, B) int32: the (segment, wall) pairs
+    closer than dist)."""
+    if pos.dim() not in (3, 4) or K < 1 or (pos.dim() == 3 and pos.shape[0] % K):
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, got %s" % (K, tuple(pos.shape)))
+    B = pos.shape[1] if pos.dim() == 4 else pos.shape[0] // K
+    Tp, pstride = _check_pos(pos, K, B)
+    if not float(dist) >= 0.0:
+        raise ValueError("dist must be >= 0, got %r" % (dist,))
+    if not float(inv_ss) > 0.0:
+        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    walls, M = check_walls(walls, pos.device)
+    start, sstride = _start_arg(start, B, pos.device)
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    L.require_gpu(pos)
+    pos = pos.float().contiguous()
+    clear = torch.empty(K, B, device=pos.device)
+    first = torch.empty(K, B, dtype=torch.int32, device=pos.device)
+    nseg = torch.empty(K, B, dtype=torch.int32, device=pos.device)
+    if B == 0:
+        return clear, first, nseg
+    L.call("sw_path_walls", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, L.ptr(walls), M,
+           float(inv_ss), float(dist), L.ptr(clear), L.ptr(first), L.ptr(nseg), L.stream())
+    return clear, first, nseg
+
+
+def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5, **wall):
     """The descent parameters of plan_refine, checked on the host before anything is sampled or launched -> (d0, n_iter, lr,
     w_track, w_smooth, max_move).  Beyond what sw_plan_refine itself refuses: the quadratic part of the objective must be
     stable: lr (2 w_track + 32 w_smooth) < 2 (the largest eigenvalue of the acceleration operator is 16; below 1 no mode of
-    the quadratic part overshoots, between 1 and 2 the stiffest ones alternate while they decay)."""
+    the quadratic part overshoots, between 1 and 2 the stiffest ones alternate while they decay).  The wall term of
+    plan_refine(walls=...) is bounded and not quadratic: it leaves the rule as it is; its keywords wall_d0 (> 0, finite, its
+    square and the inverse fp32 numbers) and w_wall (>= 0, finite) are checked here when given and are not returned."""
+    if set(wall) - {"wall_d0", "w_wall"}:
+        raise TypeError("check_descent() got unexpected keyword arguments %s" % sorted(set(wall) - {"wall_d0", "w_wall"}))
+    if wall.get("wall_d0") is not None:
+        dw = float(wall["wall_d0"])
+        dw2 = np.float32(dw) * np.float32(dw)
+        with np.errstate(over="ignore", divide="ignore"):
+            if not (dw > 0.0 and np.isfinite(dw) and dw2 > 0 and np.isfinite(dw2) and np.isfinite(np.float32(1) / dw2)):
+                raise ValueError("the wall distance must be finite and > 0 (its square and the inverse of it fp32 numbers), got %r" % (dw,))
+    if "w_wall" in wall and not (float(wall["w_wall"]) >= 0.0 and np.isfinite(float(wall["w_wall"]))):
+        raise ValueError("w_wall must be finite and >= 0, got %r" % (wall["w_wall"],))
     if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 0 <= int(n_iter) <= 1024:
         raise ValueError("n_iter must be an integer in 0 .. 1024, got %r" % (n_iter,))
     d0 = float(d0)
@@ -945,7 +1011,7 @@ def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.
 
 
 def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, inv_ss=1.0, lens=None, n_iter=32, lr=0.1,
-                w_track=0.05, w_smooth=0.5, max_move=0.5):
+                w_track=0.05, w_smooth=0.5, max_move=0.5, walls=None, wall_d0=None, w_wall=1.0):
     """Candidate ego paths moved away from the K sampled futures of a scene (sw_plan_refine): n_iter steps of gradient descent,
     all in one launch, on  J(X) = the expected clearance penalty - per pedestrian draw and segment max(0, 1 - |c|^2 / d0^2)^2 of
     the closest approach c, averaged over the K draws; given the observations the agents' draws are independent, so this is
@@ -956,9 +1022,21 @@ def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, in
     REQUIRED (the start point is data and does not move) and there are no plan_lens.  d0 > 0 in the coordinates of pos; lr,
     w_track, w_smooth, max_move are dimensionless, lr (2 w_track + 32 w_smooth) < 2.
     Returns (refined (Q, P, Tp, 2); cost (Q, P, 2, 3): before | after x expected penalty | sum |x - x0|^2 / d0^2 | sum |acc|^2 /
-    d0^2, unweighted; moved (Q, P): inv_ss * the largest displacement of a waypoint).  n_iter = 0 returns the plans' bits."""
+    d0^2, unweighted; moved (Q, P): inv_ss * the largest displacement of a waypoint).  n_iter = 0 returns the plans' bits.
+    walls (M, 2, 2) float32 on the device of pos, M = 0 .. 1024 (as path_walls): the objective gains  w_wall * the sum over the
+    plan's segments and the walls of max(0, 1 - |c|^2 / wall_d0^2)^2, c the closest approach of the moving waypoint to the
+    wall - no 1 / K: walls are certain - inside the same single launch (sw_plan_refine_walls), and cost is (Q, P, 2, 4) with the
+    unweighted wall sum last.  wall_d0 (default d0) in the coordinates of pos; w_wall >= 0.  The wall gradient is exactly 0
+    where a segment of the plan CROSSES a wall (c = 0): descent cannot undo a crossing - crossings are reported (path_walls),
+    not repaired.  walls=None: the launch without walls and its (Q, P, 2, 3) cost; an empty tensor takes the new entry point
+    and returns the same bits in refined, moved and cost[..., :3]."""
     B = scenes.B
     Tp, pstride = _check_pos(pos, K, B)
+    M = -1
+    if walls is not None:
+        wall_d0 = float(d0 if wall_d0 is None else wall_d0)
+        check_descent(d0, n_iter, lr, w_track, w_smooth, max_move, wall_d0=wall_d0, w_wall=w_wall)
+        walls, M = check_walls(walls, pos.device)
     d0, n_iter, lr, w_track, w_smooth, max_move = check_descent(d0, n_iter, lr, w_track, w_smooth, max_move)
     if not float(inv_ss) > 0.0:
         raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
@@ -986,9 +1064,15 @@ def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, in
     pos, plans = pos.float().contiguous(), plans.contiguous()
     dev = pos.device
     refined = torch.empty(Q, P, Tp, 2, device=dev)
-    cost = torch.empty(Q, P, 2, 3, device=dev)
+    cost = torch.empty(Q, P, 2, 3 if walls is None else 4, device=dev)
     moved = torch.empty(Q, P, device=dev)
     if Q == 0:
+        return refined, cost, moved
+    if walls is not None:
+        L.call("sw_plan_refine_walls", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), L.ptr(lens),
+               scenes.S, B, K, Tp, L.ptr(plans), L.ptr(plan_start), L.ptr(q_scene), L.ptr(q_ego), Q, P, float(inv_ss), d0, n_iter,
+               lr, w_track, w_smooth, max_move, L.ptr(walls), M, wall_d0, float(w_wall), L.ptr(refined), L.ptr(cost),
+               L.ptr(moved), L.stream())
         return refined, cost, moved
     L.call("sw_plan_refine", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), L.ptr(lens), scenes.S, B,
            K, Tp, L.ptr(plans), L.ptr(plan_start), L.ptr(q_scene), L.ptr(q_ego), Q, P, float(inv_ss), d0, n_iter, lr, w_track,

@@ -283,8 +283,33 @@ def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None,
     return ops.plan_risk(t, start, scenes, K, p, plan_start, scene, ego, coll_dist, float(scale), lens=lens, plan_lens=plan_lens)
 
 
+def path_walls(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cuda"):
+    """How close do paths come to the static map (`sw_path_walls`), for trajectories from anywhere: trajs (K, B, T, 2 | 4) or
+    (B, T, 2 | 4), x and y first - draws, true futures or plans; walls (M, 2, 2): line segments [w0, w1] in the units of trajs, a
+    zero-length one being a post, M = 0 .. 1024; start (B, 2) or None: a point in front of every path, giving T segments
+    instead of T - 1; distances are multiplied by `scale`; lens (B,) or None: the frames every agent is present for, as
+    scene_clearance_len().  Within a segment the path point moves linearly and the wall stands still.
+    Returns device tensors shaped like the leading axes of trajs: clear - the smallest distance to any wall, +inf without
+    walls; first int32 - the frame at which the first segment closer than dist ends, -1 without; nseg int32 - the (segment,
+    wall) pairs closer than dist."""
+    if not float(dist) >= 0.0 or not float(scale) > 0.0:
+        raise ValueError("dist must be >= 0 and scale > 0, got %r and %r" % (dist, scale))
+    t = _dev(trajs, device)
+    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    lead = tuple(t.shape[:-2])
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    w = ops.walls_arg(walls, device)
+    start = _start_arg(start, B, device)
+    lens = _lens_arg(lens, B, T, t.device)
+    L.require_gpu(t)
+    return tuple(o.reshape(lead) for o in ops.path_walls(t, start, K, w, dist, float(scale), lens=lens))
+
+
 def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None, ego=None, scale=1.0, lens=None, device="cuda",
-                 **descent):
+                 walls=None, wall_dist=None, w_wall=1.0, **descent):
     """The nearest paths that stay clear of the sampled futures (`sw_plan_refine`), for trajectories from anywhere: every plan
     is moved by n_iter steps of gradient descent, in one launch, on the expected clearance penalty against the K draws - the
     penalty of clearance_penalty() at distance `dist`, averaged over each agent's draws - plus a term that keeps it near the
@@ -295,11 +320,18 @@ def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None,
     The draws are OPEN-LOOP: the pedestrians do not react to the plan.
     Returns device tensors (refined (Q, P, T, 2) in the units of trajs; cost (Q, P, 2, 3): before | after x expected penalty |
     sum |x - x0|^2 / dist^2 | sum |x_{t+1} - 2 x_t + x_{t-1}|^2 / dist^2, unweighted; moved (Q, P): the largest displacement of a
-    waypoint, times scale)."""
+    waypoint, times scale).
+    walls (M, 2, 2) as path_walls(): the same launch also descends w_wall * the penalty of the plan's own segments against the
+    walls at the distance wall_dist (default dist; in the units of scale * trajs) - `sw_plan_refine_walls` - and cost is
+    (Q, P, 2, 4), the unweighted wall penalty last.  Where a plan CROSSES a wall the gradient is exactly 0: descent cannot undo a
+    crossing; path_walls() reports it."""
     dist, scale = float(dist), float(scale)
     if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
         raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
-    ops.check_descent(dist / scale, **descent)
+    wall = {}
+    if walls is not None:
+        wall = dict(walls=ops.walls_arg(walls, device), wall_d0=(dist if wall_dist is None else float(wall_dist)) / scale, w_wall=w_wall)
+    ops.check_descent(dist / scale, **{k: v for k, v in wall.items() if k != "walls"}, **descent)
     t = _dev(trajs, device)
     if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
         raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
@@ -325,4 +357,4 @@ def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None,
     ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
     lens = _lens_arg(lens, B, T, t.device)
     L.require_gpu(t)
-    return ops.plan_refine(t, start, scenes, K, p, plan_start, scene, ego, dist / scale, scale, lens=lens, **descent)
+    return ops.plan_refine(t, start, scenes, K, p, plan_start, scene, ego, dist / scale, scale, lens=lens, **wall, **descent)

@@ -235,6 +235,15 @@ def _plan_queries(n_next, obsv_p, plans, n_samples, sub_batches, scene, ego, pla
     return K, B, plans, sb, scene, ego, plan_start
 
 
+def _plan_walls(both, plan_start, walls, dist, inv_ss, lens=None):
+    """ONE sw_path_walls launch on plans laid side by side: both (Q, N, T, 2) with their start points plan_start (Q, 2) and
+    lens (Q,) or None -> (clear (Q, N), first (Q, N) int32, nseg (Q, N) int32)."""
+    Q, N = both.shape[0], both.shape[1]
+    clear, first, nseg = ops.path_walls(both.reshape(Q * N, both.shape[2], 2), plan_start.repeat_interleave(N, 0), 1, walls, dist,
+                                        inv_ss, lens=None if lens is None else lens.repeat_interleave(N))
+    return clear.view(Q, N), first.view(Q, N), nseg.view(Q, N)
+
+
 def _refuse_ragged(data, what, why):
     """Calls without ragged kernels behind them refuse a dataset that carries obs_len, loudly, before any launch."""
     if getattr(data, "obs_len", None) is not None:
@@ -262,6 +271,7 @@ class SocialWaysTrainer:
     ragged_fused = False    # step(obs_len=...): D updates in one launch (sw_disc_update_ragged) and, with use_graph, captured steps
     clearance_loss = None   # (dist, weight): the scene-clearance term of the generator loss (set_clearance_loss()); None = off
     last_clearance = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_clearance_grad's outputs)
+    last_walls = None       # refine_plans(walls=...): (clear (Q, P, 2), first (Q, P, 2) int32) before | after; None without walls
 
     def __new__(cls, n_next=None, hidden_size=64, *args, **kw):
         """Widths above the fused kernels' 64 units and latent-code counts other than 2 (train.py:42-44, 65) train on
@@ -1797,7 +1807,7 @@ class SocialWaysTrainer:
         return out
 
     def refine_plans(self, obsv_p, plans, n_samples, dist, coll_dist=None, sub_batches=[], scene=None, ego=None, plan_start=None,
-                     noise=None, row0=0, scale=1.0, obs_len=None, **descent):
+                     noise=None, row0=0, scale=1.0, obs_len=None, walls=None, wall_dist=None, w_wall=1.0, **descent):
         """"What is the nearest path that does NOT run into somebody?" - plan_risk() turned round: every candidate path is moved
         away from the K sampled futures of the scene's pedestrians by gradient descent on the expected clearance penalty (the
         penalty of set_clearance_loss() at distance `dist`, averaged over each agent's K draws - given the observations the
@@ -1810,14 +1820,25 @@ class SocialWaysTrainer:
         and the refined plans side by side (ops.plan_risk at coll_dist).  The draws are OPEN-LOOP: the pedestrians do not
         react to the plan, neither to the original nor to the refined one.
         Returns (refined (Q, P, n_next, 2), risk (Q, P, 2) before | after, cost (Q, P, 2, 3) and moved (Q, P) - the columns of
-        ops.plan_refine -, trajs (K, B, n_next, 4)).  Works at any hidden size: it needs only Generator.sample()."""
+        ops.plan_refine -, trajs (K, B, n_next, 4)).  Works at any hidden size: it needs only Generator.sample().
+        walls (M, 2, 2) or (M, 4), a tensor (SceneDataset.walls_from_world) or host data in the coordinates of obsv_p: the static
+        map.  The refine launch then also descends w_wall * the penalty of the plan's own segments against the walls at the
+        distance wall_dist (default dist; the units of scale * obsv_p) - ops.plan_refine(walls=...), cost (Q, P, 2, 4) with the
+        unweighted wall penalty last - and ONE more launch (ops.path_walls at coll_dist) measures the original and the refined
+        plans side by side: self.last_walls = (clear (Q, P, 2), first (Q, P, 2) int32), before | after; None after a call
+        without walls.  Where a plan CROSSES a wall the wall gradient is exactly 0: descent cannot undo a crossing, last_walls
+        reports it.  The tuple returned keeps its arity."""
         dist = float(dist)
         coll_dist = dist if coll_dist is None else coll_dist
         if not float(coll_dist) >= 0.0:
             raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
         K, B, plans, sb, scene, ego, plan_start = _plan_queries(self.n_next, obsv_p, plans, n_samples, sub_batches, scene, ego,
                                                                 plan_start, scale)
-        ops.check_descent(dist / float(scale), **descent)
+        wall = {}
+        if walls is not None:
+            wall = dict(walls=ops.walls_arg(walls, obsv_p.device), wall_d0=(dist if wall_dist is None else float(wall_dist)) / float(scale),
+                        w_wall=w_wall)
+        ops.check_descent(dist / float(scale), **{k: v for k, v in wall.items() if k != "walls"}, **descent)
         dev = obsv_p.device
         L.require_gpu(obsv_p)
         if obs_len is not None:
@@ -1835,14 +1856,19 @@ class SocialWaysTrainer:
             P = plans.shape[1]
             ph = self.G.sample(obsv_p, K, self.n_next, sub_batches, noise, row0=row0, obs_len=obs_len)
             refined, cost, moved = ops.plan_refine(ph, obsv_p[:, -1], scenes, K, plans, plan_start, q_scene, q_ego,
-                                                   dist / float(scale), inv_ss=float(scale), **descent)
-            risk = ops.plan_risk(ph, obsv_p[:, -1], scenes, K, torch.cat([plans, refined], 1), plan_start, q_scene, q_ego,
-                                 coll_dist, inv_ss=float(scale))[0]
+                                                   dist / float(scale), inv_ss=float(scale), **wall, **descent)
+            both = torch.cat([plans, refined], 1)
+            risk = ops.plan_risk(ph, obsv_p[:, -1], scenes, K, both, plan_start, q_scene, q_ego, coll_dist, inv_ss=float(scale))[0]
+            self.last_walls = None
+            if walls is not None:
+                clear, first, _ = _plan_walls(both, plan_start.float(), wall["walls"], coll_dist, float(scale))
+                self.last_walls = (torch.stack([clear[:, :P], clear[:, P:]], dim=2), torch.stack([first[:, :P], first[:, P:]], dim=2))
             return refined, torch.stack([risk[:, :P], risk[:, P:]], dim=2), cost, moved, ph
 
     REFINE_KEYS = ("risk_cv", "risk_ref", "col_cv", "col_ref", "pen_cv", "pen_ref", "moved")
 
-    def evaluate_refine(self, data, n_gen_samples=20, dist=0.5, coll_dist=0.1, just_one=False, collect=None, noise=None, **descent):
+    def evaluate_refine(self, data, n_gen_samples=20, dist=0.5, coll_dist=0.1, just_one=False, collect=None, noise=None, walls=None,
+                        wall_dist=None, w_wall=1.0, **descent):
         """evaluate() plus an answer to: does refining a naive plan against the PREDICTED futures make it collide less with the
         TRUE ones?  Leave-one-out like evaluate_risk(): every held-out agent of a scene of two or more agents is the ego once.
         Its naive plan is the constant-velocity extrapolation of its observations (predict_cv: the preds_lnr of the records; on
@@ -1861,16 +1887,28 @@ class SocialWaysTrainer:
         futures): a pedestrian counts while it is present, in the refinement and in both risks, and both risks count the ego's
         frames as evaluate_risk() does.  Sums are float64 on the device,
         one host sync at the end.  With `collect` every record of evaluate() also has `plan_ref` (n, n_next, 2; denormalised),
-        `risk_plan`, `hit_plan` (n, 2: naive | refined) and `moved` (n,)."""
+        `risk_plan`, `hit_plan` (n, 2: naive | refined) and `moved` (n,).
+        walls (the static map in the coordinates of the dataset: data.walls_from_world()): the refinement carries the wall term
+        (refine_plans(walls=...): wall_dist, default dist, in world units; w_wall), one more launch per chunk (ops.path_walls)
+        measures both plans, and the dict gains
+          wall_cv, wall_ref    the share of egos whose naive / refined plan comes within coll_dist of a wall;
+          penw_cv, penw_ref    the mean wall penalty of the two;
+        the records `wall_plan` (n, 2): the clearance of the two plans to the walls, in world units, and `penw_plan` (n, 2):
+        their wall penalties."""
         if not float(coll_dist) >= 0.0:
             raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
         ss = float(data.ss)
-        d0 = ops.check_descent(float(dist) * ss, **descent)[0]      # world units -> the coordinates of the dataset
+        wall = {}
+        if walls is not None:
+            wall = dict(walls=ops.walls_arg(walls, self.device), wall_d0=(float(dist) if wall_dist is None else float(wall_dist)) * ss,
+                        w_wall=w_wall)
+        d0 = ops.check_descent(float(dist) * ss, **{k: v for k, v in wall.items() if k != "walls"}, **descent)[0]      # world units -> the dataset's
         dn = self._device_noise(noise)
         dev, K = self.device, int(n_gen_samples)
         inv_ss = 1.0 / ss
         base = _EvalSums(dev)
-        acc = torch.zeros(len(self.REFINE_KEYS), dtype=torch.float64, device=dev)
+        keys = self.REFINE_KEYS + (self.REFINE_WALL_KEYS if walls is not None else ())
+        acc = torch.zeros(len(keys), dtype=torch.float64, device=dev)
         zero = torch.zeros((), dtype=torch.float64, device=dev)
         for c in self._eval_draws(data, K, just_one, dn, base):
             q_scene, multi = c.scenes.row_scene()
@@ -1881,23 +1919,87 @@ class SocialWaysTrainer:
                 naive = torch.where((c.obs_len <= 2)[:, None, None], predict_cv(c.obsv[:, -2:], self.n_next), naive)
             naive, pstart = naive[:, None, :, :2].contiguous(), start[:, :2].contiguous()
             refined, cost, moved = ops.plan_refine(c.ph, start, c.scenes, K, naive, pstart, q_scene, q_ego, d0, inv_ss,
-                                                   lens=c.pred_len, **descent)
+                                                   lens=c.pred_len, **wall, **descent)
             both = torch.cat([naive, refined], 1)
             risk = ops.plan_risk(c.ph, start, c.scenes, K, both, pstart, q_scene, q_ego, coll_dist, inv_ss, lens=c.pred_len,
                                  plan_lens=c.pred_len)[0]
             hit = ops.plan_risk(c.pred, start, c.scenes, 1, both, pstart, q_scene, q_ego, coll_dist, inv_ss, lens=c.pred_len,
                                 plan_lens=c.pred_len)[2][:, :, 0] > 0
             rows = torch.cat([risk.double(), hit.double(), cost[:, 0, :, 0].double(), moved.double()], dim=1)      # (n, 7)
+            extra = {}
+            if walls is not None:
+                wclear, wfirst, _ = _plan_walls(both, pstart, wall["walls"], coll_dist, inv_ss, c.pred_len)
+                rows = torch.cat([rows, (wfirst >= 0).double(), cost[:, 0, :, 3].double()], dim=1)      # (n, 11)
+                extra = dict(wall_plan=(wclear, 0), penw_plan=(cost[:, 0, :, 3], 0))
             acc += torch.where(multi[:, None], rows, zero).sum(0)
             if collect is not None:
                 for rec in self._eval_records(data, c, c.ph, dict(plan_ref=(refined[:, 0], 0), risk_plan=(risk, 0), hit_plan=(hit, 0),
-                                                                  moved=(moved[:, 0], 0))):
+                                                                  moved=(moved[:, 0], 0), **extra)):
                     rec["plan_ref"] = data.scale.denormalize(rec["plan_ref"])
                     collect.append(rec)
         n_ego = sum(b - a for a, b in base.scenes if b - a > 1)
         out = base.result(data)
-        out.update(zip(self.REFINE_KEYS, (acc / max(n_ego, 1)).tolist()))
+        out.update(zip(keys, (acc / max(n_ego, 1)).tolist()))
         out.update(n_ego=n_ego, K=K, dist=float(dist), coll_dist=float(coll_dist))
+        return out
+
+    REFINE_WALL_KEYS = ("wall_cv", "wall_ref", "penw_cv", "penw_ref")
+    WALL_KEYS = ("wall_draws", "wall_agents", "wall_blocked", "wall_gt", "ade_min_free", "fde_min_free", "t_first")
+
+    def evaluate_walls(self, data, walls, n_gen_samples=20, wall_dist=0.1, just_one=False, collect=None, noise=None):
+        """evaluate() plus the ENVIRONMENT collision rate of the K draws: how many of them walk through the static map of the
+        recording?  walls: the map in the coordinates of the dataset (data.walls_from_world(load_walls(file))); wall_dist in
+        world units through data.ss like the coll_dist of evaluate_scenes().  A draw CONFLICTS when a segment of it - from
+        the last observed position on, the agent moving linearly between frames - comes closer than wall_dist to a wall.
+        Returns a dict:
+          ade_avg, fde_avg, ade_min, fde_min  the numbers of evaluate() from the same RNG state, bit for bit;
+          wall_draws      the share of (draw, agent) that conflict;
+          wall_agents     the share of agents with at least one conflicting draw;
+          wall_blocked    the share of agents with NO clear draw;
+          wall_gt         the same share for the true futures - 0 when the map fits the data;
+          ade_min_free, fde_min_free   the best of the CLEAR draws, over the agents that have one (0 without such agents);
+          t_first         the mean frame at which the first conflicting segment ends, over the conflicting draws (0 without);
+          n_agents, n_free, K, wall_dist.
+        Chunking, noise streams and sampling launches are evaluate()'s; per chunk ONE path-walls launch on the draws where
+        they are (ops.path_walls) and one on the ground truth; the small reductions are torch ops on the device, float64 sums,
+        one host sync at the end; the trajectories go to the host only when `collect` asks.  A dataset with pred_len (ragged
+        futures): a segment counts while the agent is present, for the draws and the truth alike.  With `collect` every
+        record of evaluate() also has `wall_clear` (K, n): the clearance of every draw to the walls, in world units,
+        `wall_first` (K, n) and `err` (K, n, 2): the ADE | FDE of every draw as the sampling launch formed them.  Excluding the conflicting draws from sample_ranked() / sample_composed() / sample_modes() is score
+        masking by the caller (score.masked_fill(clear < d, -inf)), not part of this call.  The wide and generic trainers take
+        it through their sampling hook, like evaluate_scenes(): there the four numbers agree with evaluate() to rounding."""
+        if not float(wall_dist) >= 0.0:
+            raise ValueError("wall_dist must be >= 0, got %r" % (wall_dist,))
+        walls = ops.walls_arg(walls, self.device)
+        dn = self._device_noise(noise)
+        dev, K = self.device, int(n_gen_samples)
+        inv_ss = 1.0 / float(data.ss)
+        base = _EvalSums(dev)
+        # conflicting draws | agents with one | agents with no clear draw | conflicting truths | sum min ADE, FDE of the clear
+        # draws | agents with a clear draw | sum of the first frames
+        acc = torch.zeros(8, dtype=torch.float64, device=dev)
+        inf = torch.full((), float("inf"), device=dev)
+        for c in self._eval_draws(data, K, just_one, dn, base):
+            start = c.obsv[:, -1]
+            clear, first, _ = ops.path_walls(c.ph, start, K, walls, wall_dist, inv_ss, lens=c.pred_len)
+            gt_first = ops.path_walls(c.pred, start, 1, walls, wall_dist, inv_ss, lens=c.pred_len)[1][0]
+            hit = first >= 0                                                       # (K, n)
+            nhit = hit.sum(0)
+            free = nhit < K
+            best = torch.where(hit[:, :, None], inf, c.err).min(0)[0].double()     # (n, 2): the best of the clear draws
+            best = torch.where(free[:, None], best, torch.zeros((), dtype=torch.float64, device=dev))
+            acc += torch.stack([nhit.sum().double(), (nhit > 0).sum().double(), (~free).sum().double(), (gt_first >= 0).sum().double(),
+                                best[:, 0].sum(), best[:, 1].sum(), free.sum().double(),
+                                torch.where(hit, first, torch.zeros_like(first)).sum().double()])
+            if collect is not None:
+                collect.extend(self._eval_records(data, c, c.ph, dict(wall_clear=(clear, 1), wall_first=(first, 1), err=(c.err, 1))))
+        n_agents = sum(b - a for a, b in base.scenes)
+        out = base.result(data)
+        draws, agents, blocked, gt, ade, fde, n_free, tsum = acc.tolist()
+        na = max(n_agents, 1)
+        out.update(wall_draws=draws / (K * na), wall_agents=agents / na, wall_blocked=blocked / na, wall_gt=gt / na,
+                   ade_min_free=ade / n_free if n_free else 0.0, fde_min_free=fde / n_free if n_free else 0.0,
+                   t_first=tsum / draws if draws else 0.0, n_agents=n_agents, n_free=int(n_free), K=K, wall_dist=float(wall_dist))
         return out
 
     # ------------------------------------------------------------------------------------------
