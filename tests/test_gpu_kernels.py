@@ -153,14 +153,30 @@ def test_module_level_api_matches_reference_ops():
         assert_close(dec(h, s_.to(dev), z_.to(dev)).cpu(), odec(h.cpu(), s_, z_), RT, AT, "decoder")
 
 
-@pytest.mark.parametrize("B", [37, 2048, 40000])
+@pytest.mark.parametrize("B", [37, 2048, 40000, 45000])
 def test_loss_and_ade_reductions_any_batch_size(B):
     """sw_gan_loss / sw_ade_fde (train.py:484-494, 546-551) against float64 torch sums: the one-workgroup
     path (small B, or no scratch) and the multi-workgroup two-stage path (large B with scratch) agree
-    and the multi-workgroup path is run-to-run deterministic."""
+    and the multi-workgroup path is run-to-run deterministic.  B = 45 000 is 540 000 items: more than the RED_BLOCKS
+    workgroups of 8 192 take in one trip, so ade_fde_kernel's outer loop runs a second trip of 15 712."""
+    from socialways_amd import _lib as L
+    if B == 45000:
+        assert B * 12 > L.RED_BLOCKS * 8192
+    _loss_and_ade_case(B, 12)
+
+
+def test_ade_fde_second_trip_with_fde_rows_across_the_trip_boundary():
+    """Tp = 25 does not divide the 524 288 items of a first trip: the agent whose steps straddle the boundary has its last
+    step - the FDE row - in the second trip (737 items), where `i % Tp == Tp - 1` and the tail guard `i < n` run."""
+    from socialways_amd import _lib as L
+    B, Tp = 21001, 25
+    assert B * Tp > L.RED_BLOCKS * 8192 and (L.RED_BLOCKS * 8192) % Tp != 0
+    _loss_and_ade_case(B, Tp)
+
+
+def _loss_and_ade_case(B, Tp):
     from socialways_amd import _lib as L
     g = torch.Generator().manual_seed(B)
-    Tp = 12
     la, lb = torch.rand(B, generator=g).cuda(), torch.rand(B, generator=g).cuda()
     code, z = torch.rand(B, 2, generator=g).cuda(), torch.rand(B, 32, generator=g).cuda()
     tg = torch.tensor([0.05, 0.93]).cuda()

@@ -235,6 +235,29 @@ def test_exact_duplicates_are_suppressed_at_radius_zero(metric, Tp, M):
                 assert np.array_equal(pos[k, a], pos[got[0][a, got[3][a, k]], a])
 
 
+def equidistant_leftover():
+    """One row, one step, five draws on the x axis at 0, 8, 4, 0.5, 5 with descending scores, M = 2, radius 1: the picks are
+    draws 0 and 1, draw 3 joins pick 0, and of the leftovers draw 2 is exactly 4 from both picks - the lowest m takes it -
+    while draw 4 is nearer to pick 1.  Small integers and halves: fp32 and float64 see the same distances
+    (tests/test_nms_host.py)."""
+    pos = np.zeros((5, 1, 1, 2), dtype=np.float32)
+    pos[:, 0, 0, 0] = [0.0, 8.0, 4.0, 0.5, 5.0]
+    score = np.array([5.0, 4.0, 3.0, 2.0, 1.0], dtype=np.float32).reshape(5, 1)
+    return pos, score, 2, 1.0
+
+
+@pytest.mark.parametrize("metric", ["fde", "ade"])
+def test_a_leftover_between_equally_near_picks_goes_to_the_lowest_m(metric):
+    """The tie rule of the leftover loop (`D < bd`, the first minimum): the seeded fault "the later pick takes an
+    equidistant leftover" (tools/mutants/nms_leftover_tie.diff) passed every other case of this module, whose leftovers
+    never sit at equal distances."""
+    pos, score, M, radius = equidistant_leftover()
+    want = nms_reference(pos, score, [(0, 1)], M, radius, metric)
+    assert want[0].tolist() == [[0, 1]] and want[3].tolist() == [[0, 1, 0, 0, 1]]
+    got = run_kernel(pos, score, 5, M, radius, metric)
+    assert_exact(got, want, metric)
+
+
 def test_the_largest_k():
     """K = M = 4096: the whole LDS budget of the launch (131 072 B per workgroup), a partial workgroup."""
     K, B = 4096, 3

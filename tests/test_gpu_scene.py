@@ -262,6 +262,29 @@ def test_scene_reduce_first_k_on_an_exact_tie():
     check_reduce(got, best, err, clear, SIZES, 0.5)
 
 
+def clearances_on_the_threshold(K=20, coll=0.5):
+    """err (K, B, 2) and clear (K, B) on the grid of 1/8 in [0, 1]: a ninth of the clearances EQUAL coll (a binary
+    fraction: the fp32 comparison sees equality), and draw 0 of every scene has its smallest clearance exactly there."""
+    rng = np.random.RandomState(8)
+    B = int(np.sum(SIZES))
+    err = rng.rand(K, B, 2).astype(np.float32) + 0.1
+    clear = (rng.randint(0, 9, size=(K, B)) / 8.0).astype(np.float32)
+    clear[0] = np.maximum(clear[0], np.float32(coll))
+    clear[0, np.concatenate([[0], np.cumsum(SIZES)[:-1]])] = coll
+    return err, clear, coll
+
+
+def test_scene_reduce_a_clearance_equal_to_coll_dist_is_no_collision():
+    """Definition 3 counts `clear < coll_dist`, strictly.  Random clearances never equal the threshold, so the seeded fault
+    "`<=` in the per-agent count" (tools/mutants/scene_coll_strict.diff) passed every other case; here 11 % of the entries
+    sit on it (tests/test_scene_host.py checks that the two readings differ by far more than the 1e-5 of check_reduce)."""
+    err, clear, coll = clearances_on_the_threshold()
+    got, best = run_reduce(err, clear, SIZES, coll)
+    check_reduce(got, best, err, clear, SIZES, coll)
+    got0, _ = run_reduce(err[:1], clear[:1], SIZES, coll)                       # draw 0 alone: nothing is below the threshold
+    assert (got0[:, [2, 3, 5]] == 0).all()
+
+
 def test_scene_c_abi_argument_checks_on_the_device():
     from socialways_amd import _lib as L
     lib = L.load()

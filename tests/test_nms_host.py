@@ -106,3 +106,19 @@ def test_top_m_outside_1_to_k_is_refused(top_m):
             cls.evaluate_diverse(me, data, n_gen_samples=6, top_m=top_m)
     with pytest.raises(ValueError, match="metric"):
         sw.SocialWaysTrainer.evaluate_diverse(me, data, n_gen_samples=6, top_m=2, metric="mse")
+
+
+def test_the_equidistant_leftover_case_is_exact_in_float32():
+    """What tests/test_gpu_nms.py's tie case relies on: every distance of its input is the same number in fp32 and float64,
+    draw 2 is equally far from both picks and strictly outside the radius, and draw 4 is strictly nearer to pick 1."""
+    from test_gpu_nms import equidistant_leftover, nms_reference, pair_dist
+    pos, score, M, radius = equidistant_leftover()
+    for metric in ("fde", "ade"):
+        for c in (0, 1):
+            d64 = pair_dist(pos, c, metric)
+            x = pos[..., 0, 0]
+            d32 = np.abs(x - x[c]).astype(np.float32)                  # one step, y = 0: the distance is |dx|, exact
+            assert np.array_equal(d64, d32.astype(np.float64))
+        d0, d1 = pair_dist(pos, 0, metric)[:, 0], pair_dist(pos, 1, metric)[:, 0]
+        assert d0[2] == d1[2] == 4.0 > radius and d1[4] < d0[4] and d0[3] <= radius
+        assert nms_reference(pos, score, [(0, 1)], M, radius, metric)[3].tolist() == [[0, 1, 0, 0, 1]]

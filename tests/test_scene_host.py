@@ -54,3 +54,20 @@ def test_public_surface():
     assert list(inspect.signature(ops.scene_metrics).parameters) == ["err", "pred4", "obsv", "scenes", "K", "n_next", "inv_ss",
                                                                    "coll_dist"]
     assert inspect.signature(ops.gen_sample).parameters["keep_pred"].default is False
+
+
+def test_the_threshold_case_separates_strict_from_non_strict():
+    """What tests/test_gpu_scene.py's threshold case relies on: its clearances hit coll_dist exactly, and in every scene of
+    two or more agents the per-agent collision share with `<` (the definition) and with `<=` differ by far more than the
+    relative 1e-5 of check_reduce."""
+    import numpy as np
+    from test_gpu_scene import SIZES, clearances_on_the_threshold, scene_reference
+    err, clear, coll = clearances_on_the_threshold()
+    assert clear.dtype == np.float32 and np.float32(coll) == coll and 0.05 < (clear == np.float32(coll)).mean() < 0.2
+    want, _ = scene_reference(err, clear, SIZES, coll)
+    o = np.concatenate([[0], np.cumsum(SIZES)])
+    for s, n in enumerate(SIZES):
+        if n > 1:
+            loose = (clear[:, o[s]:o[s + 1]] <= np.float32(coll)).mean()
+            assert loose - want[s, 5] > 1e-3 * max(want[s, 5], 1e-3), (s, n, loose, want[s, 5])
+    assert clear[0].min() == np.float32(coll)
