@@ -39,6 +39,9 @@
 * `--clearance-loss DIST[:W]`: train against collisions - the generator loss gains the scene-clearance term
   (set_clearance_loss(DIST, W), W default 1: pairs of predicted futures that come closer than DIST world units within a
   segment are pushed apart), and every test prints col_joint and col_agent of evaluate_scenes(coll_dist=DIST) beside ADE/FDE.
+* `--wall-loss DIST[:W]` (with `--walls FILE`): train against the map - the generator loss gains the wall term
+  (set_wall_loss(walls, DIST, W), W default 1: predicted segments closer than DIST world units to a wall are pushed off it);
+  the numbers `--walls` prints at every test (wall_draws, wall_agents, wall_blocked) show what it buys.
 """
 import argparse
 import os
@@ -115,7 +118,21 @@ def main(argv=None):
     ap.add_argument("--clearance-loss", default=None, metavar="DIST[:W]",
                     help="add the scene-clearance term to the generator loss: futures of one scene closer than DIST (world "
                          "units) are penalised with weight W (default 1); reports the collision rates at DIST")
+    ap.add_argument("--wall-loss", default=None, metavar="DIST[:W]",
+                    help="with --walls FILE: add the wall term to the generator loss: predicted segments closer than DIST (world "
+                         "units) to a wall of the map are penalised with weight W (default 1)")
     args = ap.parse_args(argv)
+    wall_loss = None
+    if args.wall_loss is not None:
+        try:
+            dist, _, w = args.wall_loss.partition(":")
+            wall_loss = (float(dist), float(w) if w else 1.0)
+        except ValueError:
+            ap.error("--wall-loss takes DIST or DIST:W, got %r" % args.wall_loss)
+        if args.walls is None:
+            ap.error("--wall-loss needs --walls FILE: the map to train against")
+        if args.hidden_size != 64:
+            ap.error("--wall-loss: the wall term is implemented for the fused 64-unit path (--hidden-size 64)")
     clearance = None
     if args.clearance_loss is not None:
         try:
@@ -197,6 +214,10 @@ def main(argv=None):
         tr.noise = sw.DeviceNoise(args.device_noise)
     if clearance is not None:
         tr.set_clearance_loss(*clearance)
+    if wall_loss is not None:
+        tr.set_wall_loss(walls, *wall_loss)
+        if rank == 0:
+            print("Wall loss: %d walls, dist %.2f, weight %.2f" % (walls.shape[0], wall_loss[0], wall_loss[1]))
     for epoch in range(1, args.epochs + 1):
         t0 = time.perf_counter()
         if train_set is not None:

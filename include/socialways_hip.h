@@ -594,6 +594,42 @@ int sw_plan_refine_walls(const float* pos, int pstride, const float* start /*[B,
                          float w_track, float w_smooth, float max_move, const float* walls /*[M,2,2]*/, int M, float dw,
                          float w_wall, float* out /*[Q,P,Tp,2]*/, float* cost /*[Q,P,2,4]*/, float* moved /*[Q,P]*/,
                          void* stream);
+/* WALL PENALTY of the generator loss and its gradient with respect to the positions: the training-side counterpart of
+ * sw_path_walls, as sw_clearance_grad is that of sw_scene_clearance.  R = K B paths against the M walls of the call, all fp32.
+ * Paths, segments and the gating by len are those of sw_path_walls: with a start point (start != NULL) the path of (k, a) has
+ * Tp segments, without one Tp - 1; a segment counts only while its frame t < len[a] (clamped into 1 .. Tp, NULL meaning Tp),
+ * and what lies behind a length, NaN included, reaches nothing (every contribution goes through a select).
+ * Per counted (segment, wall) pair: (s, c, |c|^2) are those of the CLOSEST APPROACH above (one device function, shared with
+ * sw_path_walls and sw_plan_refine_walls) and nothing else;  u = max(0, 1 - |c|^2 / dw^2),  phi = u^2;  the pair is COUNTED
+ * where |c|^2 < dw^2.  dw is in the units of pos, like d0 of sw_clearance_grad.
+ *   dpos   [K,B,Tp,dstride], dstride 2 or 4, 8-byte aligned:  dpos[r][t][0:2] += scale * g_t,
+ *            g_t = sum over the walls of [ -(4 u / dw^2) s c of the segment that ends at point t
+ *                                          -(4 u / dw^2) (1 - s) c of the segment that starts at point t ]
+ *          (each over counted pairs only).  With start, the start point is data and takes nothing; without, pos[.][0] takes
+ *          the (1 - s) share of segment 1.  Components 2 and 3 of a 4-float row are neither read nor written;
+ *   pos    [K,B,Tp,pstride], pstride 2 or 4 floats (x, y first), 8-byte aligned;  start [B,sstride] or NULL, sstride >= 2;
+ *   loss   [K,B] or NULL: loss[r] = the sum of phi over the path's counted pairs, unscaled - no 1/2: a path owns its pairs alone;
+ *   count  [K,B] int32 or NULL: the number of counted pairs.
+ * phi is C1 at |c| = dw, the gradient finite everywhere and exactly 0 where the path crosses the wall (c = 0); where two
+ * candidates tie the order of the candidates decides which end point takes the gradient (WALLS above).
+ * STORES ARE SKIPPED, not +0: per path and chunk of 16 segments, the dpos rows of the chunk are read and written only if one
+ * of its (segment, wall)s is counted, and then only the rows of points a counted segment can reach (none behind len).  A
+ * path with count == 0 leaves its dpos rows bit for bit as they were, and so does every path when M = 0: M = 0 returns SW_OK,
+ * writes loss 0 and count 0 and touches no dpos.
+ * One 256-thread workgroup per 64 paths, a lane per path, the four waves taking the wall slices w, w + 4, ..; a wave adds its
+ * walls, then the chunk's segments, in ascending order, the waves' partial sums are added in the order 0 .. 3 and wave 0 makes
+ * the one read-modify-write of a chunk's rows (the point two chunks share: twice by the same thread, in chunk order).  One
+ * owner per dpos row, loss[r] and count[r], no atomics; the order in which a point's contributions are added depends on
+ * (Tp, M) only, never on K, B or the grid: two calls give the same bits, and a path's outputs do not depend on the rest of
+ * the batch.  LDS: 16 KB of walls + 3 * 64 * 17 * 8 bytes of partial sums + 1.5 KB.
+ * Checked before the device is touched - SW_EARG: a NULL pointer among pos, dpos, or walls with M > 0; K < 1; B < 0; Tp < 1;
+ * M < 0; dw <= 0 or not finite (or dw^2 or 1 / dw^2 outside fp32's range); scale not finite; pstride or dstride not 2 or 4;
+ * pos or dpos off their 8-byte alignment; start with sstride < 2.  SW_ESHAPE: M > SW_WALLS_MAX.  B == 0: SW_OK without a
+ * launch.                                                                                                                */
+int sw_wall_grad(const float* pos, int pstride, const float* start /*[B,sstride] or NULL*/, int sstride,
+                 const int* len /*[B] or NULL*/, int K, int B, int Tp, const float* walls /*[M,2,2]*/, int M,
+                 float dw, float scale, float* dpos /*[K,B,Tp,dstride], += */, int dstride,
+                 float* loss /*[K,B] or NULL*/, int* count /*[K,B] or NULL*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

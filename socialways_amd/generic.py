@@ -547,6 +547,18 @@ class GenericTrainer(SocialWaysTrainer):
                                        "fused 64-unit SocialWaysTrainer only (hidden_size <= 64, n_latent_codes = 2); leave "
                                        "clearance_loss = None" % type(self).__name__)
 
+    # ... and the wall term (set_wall_loss())
+    @property
+    def wall_loss(self):
+        return None
+
+    @wall_loss.setter
+    def wall_loss(self, value):
+        if value is not None:
+            raise L.SocialWaysHipError("%s does not take a wall loss: the wall term is implemented for the fused 64-unit "
+                                       "SocialWaysTrainer only (hidden_size <= 64, n_latent_codes = 2); leave wall_loss = None"
+                                       % type(self).__name__)
+
     def evaluate(self, data, n_gen_samples=20, write_to_file=None, just_one=False, collect=None, noise=None):
         """The contract of SocialWaysTrainer.evaluate(); at these widths it is test() (no sampling kernels)."""
         self._device_noise(noise)

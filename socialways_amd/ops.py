@@ -976,6 +976,50 @@ def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
     return clear, first, nseg
 
 
+def wall_grad(pos, start, K, walls, dw, scale, dpos, loss=None, count=None, lens=None):
+    """The wall penalty and its gradient (sw_wall_grad): dpos[r, t, 0:2] += scale * d/d(pos[r, t]) of the sum over the path's
+    counted segments and the M walls of max(0, 1 - |c|^2 / dw^2)^2, c the closest approach of the segment to the wall (the
+    quantity path_walls measures).  pos and dpos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), float32, x and y first; dpos is
+    contiguous, accumulated into in place and returned; columns 2 and 3 of a 4-wide dpos are not touched.  start (B, >= 2) or
+    None: the point in front of the Tp positions (any row stride: a view such as obsv[:, -1] is read in place); it is data and
+    takes no gradient.  walls (M, 2, 2) float32 on the device of pos, M = 0 .. 1024; dw > 0 in the units of pos; lens (B,)
+    int32 on the device: ragged futures, as path_walls(lens=...).  loss float32 / count int32, (K, B) or (K * B,), or None:
+    written with the path's unscaled penalty and its number of (segment, wall)s closer than dw.  Rows of paths with nothing
+    closer than dw - every row when M = 0 - are not written."""
+    if pos.dim() not in (3, 4) or K < 1 or (pos.dim() == 3 and pos.shape[0] % K):
+        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, got %s" % (K, tuple(pos.shape)))
+    B = pos.shape[1] if pos.dim() == 4 else pos.shape[0] // K
+    Tp, pstride = _check_pos(pos, K, B)
+    if dpos.dim() not in (3, 4) or tuple(dpos.shape[:-1]) not in ((K * B, Tp), (K, B, Tp)) or dpos.shape[-1] not in (2, 4):
+        raise ValueError("dpos must hold the K * B = %d paths of Tp = %d steps of pos, 2 or 4 wide, got %s"
+                         % (K * B, Tp, tuple(dpos.shape)))
+    if pos.dtype != torch.float32 or dpos.dtype != torch.float32:
+        raise ValueError("pos and dpos must be float32")
+    if not dpos.is_contiguous():
+        raise ValueError("dpos is accumulated into in place: it must be contiguous")
+    dstride = dpos.shape[-1]
+    dw, scale = float(dw), float(scale)
+    if not (dw > 0.0 and np.isfinite(dw)) or not np.isfinite(scale):
+        raise ValueError("dw must be finite and > 0 and scale finite, got dw = %r, scale = %r" % (dw, scale))
+    walls, M = check_walls(walls, pos.device)
+    start, sstride = _start_arg(start, B, pos.device)
+    for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
+        if t is not None and (tuple(t.shape) not in ((K, B), (K * B,)) or t.dtype != dt or not t.is_contiguous()
+                              or t.device != pos.device):
+            raise ValueError("%s must be a contiguous %s tensor (K, B) or (K * B,) on the device of pos" % (name, dt))
+    if dpos.device != pos.device:
+        raise ValueError("dpos must be on the device of pos")
+    if lens is not None:
+        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    L.require_gpu(pos)
+    pos = pos.contiguous()
+    if B == 0:
+        return dpos
+    L.call("sw_wall_grad", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, L.ptr(walls), M, dw, scale,
+           L.ptr(dpos), dstride, L.ptr(loss), L.ptr(count), L.stream())
+    return dpos
+
+
 def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5, **wall):
     """The descent parameters of plan_refine, checked on the host before anything is sampled or launched -> (d0, n_iter, lr,
     w_track, w_smooth, max_move).  Beyond what sw_plan_refine itself refuses: the quadratic part of the objective must be

@@ -10,7 +10,8 @@ quantity behind the collision rates of `SocialWaysTrainer.evaluate_scenes()`, fo
 `compose_scenes`, the collision-free choice of one draw per agent behind `SocialWaysTrainer.sample_composed()`, and
 `clearance_penalty`, the pairwise clearance penalty and its gradient behind `SocialWaysTrainer.set_clearance_loss()`, and
 `plan_risk`, the collision risk of candidate ego paths against the K draws behind `SocialWaysTrainer.plan_risk()`, and
-`refine_plans`, the descent that moves such paths away from the draws behind `SocialWaysTrainer.refine_plans()`."""
+`refine_plans`, the descent that moves such paths away from the draws behind `SocialWaysTrainer.refine_plans()`, and
+`path_walls` / `wall_penalty`, the clearance of paths to a static map and the penalty behind `SocialWaysTrainer.set_wall_loss()`."""
 import os
 
 import numpy as np
@@ -306,6 +307,38 @@ def path_walls(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cud
     lens = _lens_arg(lens, B, T, t.device)
     L.require_gpu(t)
     return tuple(o.reshape(lead) for o in ops.path_walls(t, start, K, w, dist, float(scale), lens=lens))
+
+
+def wall_penalty(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cuda"):
+    """The wall penalty SocialWaysTrainer.set_wall_loss() trains against, for trajectories from anywhere (`sw_wall_grad`): per
+    segment of a path and per wall, max(0, 1 - (scale |c|)^2 / dist^2)^2 with c the closest approach of path_walls() - the
+    path point moving linearly within the segment, the wall standing still.  trajs (K, B, T, 2 | 4) or (B, T, 2 | 4), x and y
+    first - the K draws, true futures or plans; walls (M, 2, 2) as path_walls(), M = 0 .. 1024; start (B, 2) or None: a point in
+    front of every path (the last observed position; it takes no gradient), giving T segments instead of T - 1; `scale`
+    converts trajs to the units of `dist`, as in clearance_penalty(); lens (B,) or None: the frames every agent is present
+    for, as path_walls().  Returns device tensors (loss, grad, count): loss and count (int32) shaped like the leading axes of
+    trajs - the path's penalty (no 1/2: a path owns its pairs alone) and its number of (segment, wall)s closer than dist - and
+    grad (.., T, 2): the gradient of loss.sum() with respect to trajs[..., :2] in the units of trajs, exactly 0 where a path
+    crosses a wall."""
+    dist, scale = float(dist), float(scale)
+    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
+    t = _dev(trajs, device)
+    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
+        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    lead = tuple(t.shape[:-2])
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    w = ops.walls_arg(walls, device)
+    start = _start_arg(start, B, device)
+    lens = _lens_arg(lens, B, T, t.device)
+    L.require_gpu(t)
+    grad = torch.zeros(K, B, T, 2, device=t.device)
+    loss = torch.zeros(K, B, device=t.device)
+    count = torch.zeros(K, B, dtype=torch.int32, device=t.device)
+    ops.wall_grad(t, start, K, w, dist / scale, 1.0, grad, loss, count, lens=lens)      # |scale c| < dist  <=>  |c| < dist / scale
+    return loss.reshape(lead), grad.reshape(lead + (T, 2)), count.reshape(lead)
 
 
 def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None, ego=None, scale=1.0, lens=None, device="cuda",

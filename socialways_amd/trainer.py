@@ -262,6 +262,11 @@ _PRED_LEN_TRAIN = ("a truncated future has no discriminator input (D encodes the
                    "min_next) and evaluate the short futures with evaluate*() / evaluate_horizon()")
 
 
+def _wall_key(wall):
+    """The wall term's entry of the graph key: None, or (the address of the walls, M, dist, weight)."""
+    return None if wall is None else (wall[0].data_ptr(), int(wall[0].shape[0]), wall[1], wall[2])
+
+
 class SocialWaysTrainer:
     STEPS_PER_LAUNCH = 4    # train_epoch: consecutive packed batches of one scene layout per graph launch (step_many)
     Z_COLS = 32             # noise columns of the kernels (hidden size 64: train.py:81); smaller models are zero-padded
@@ -271,6 +276,8 @@ class SocialWaysTrainer:
     ragged_fused = False    # step(obs_len=...): D updates in one launch (sw_disc_update_ragged) and, with use_graph, captured steps
     clearance_loss = None   # (dist, weight): the scene-clearance term of the generator loss (set_clearance_loss()); None = off
     last_clearance = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_clearance_grad's outputs)
+    wall_loss = None        # (walls (M, 2, 2) on the device, dist, weight): the wall term of the generator loss (set_wall_loss()); None = off
+    last_wall_loss = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_wall_grad's outputs)
     last_walls = None       # refine_plans(walls=...): (clear (Q, P, 2), first (Q, P, 2) int32) before | after; None without walls
 
     def __new__(cls, n_next=None, hidden_size=64, *args, **kw):
@@ -319,6 +326,38 @@ class SocialWaysTrainer:
         if not (np.isfinite(weight) and weight >= 0.0):
             raise ValueError("set_clearance_loss: weight must be finite and >= 0, got %r" % weight)
         self.clearance_loss = (dist, weight)
+
+    def set_wall_loss(self, walls, dist=None, weight=1.0):
+        """Train against the map: the generator loss gains L_wall = weight / (Bg * Tp) * the sum over the agents of the packed
+        batch, the Tp segments of an agent's predicted future - the path starting at its last observed position, the agent
+        moving linearly between frames - and the M walls of max(0, 1 - |c|^2 / dw^2)^2, c the closest approach of the segment
+        to the wall (the quantity behind wall_* of evaluate_walls(), sw_wall_grad), with dw = dist * ss: `dist` is in world
+        units like evaluate_walls()'s wall_dist, Bg the agents of the global packed batch (the normalisation of the L2 and
+        clearance terms).  walls: the static map in the dataset's coordinates (data.walls_from_world(...)), a tensor or host
+        data, (M, 2, 2) or (M, 4), M = 0 .. 1024 (an empty map is accepted); it is copied to the trainer's device unless it is a
+        float32 (M, 2, 2) tensor there already, and the trainer holds it.  A captured step bakes in the tensor's address: writing
+        into that tensor in place is seen by the replays; a new map is a new set_wall_loss() call.
+        The penalty is C1 where a segment reaches dw, its gradient finite everywhere and exactly 0 where a path CROSSES a wall:
+        descent keeps paths off the walls, it cannot undo a crossing.  One extra launch per step behind the other terms on
+        d/d(pred_hat) (the clearance term, when both are on, comes first), the generator's backward pass then running un-fused
+        from the D pass as with use_l2_loss; dense and ragged steps, eager and captured, single process and data parallel
+        (the map is the same on every rank, rows are rank-local).  `last_wall_loss` = (loss (B,), count (B,) int32) then holds
+        the last step's per-agent unscaled sums and numbers of (segment, wall)s closer than dw - views of buffers the next step
+        overwrites; L_wall = weight / (Bg * Tp) * loss.sum().  weight 0 measures without training on it.  set_wall_loss(None)
+        switches the term off: the step then makes exactly the launches it made before.  The loss rows step() returns do not
+        show the term."""
+        if walls is None:
+            self.wall_loss = None
+            self.last_wall_loss = None
+            return
+        if dist is None:
+            raise ValueError("set_wall_loss: a map needs its dist")
+        dist, weight = float(dist), float(weight)
+        if not (np.isfinite(dist) and dist > 0.0):
+            raise ValueError("set_wall_loss: dist must be finite and > 0, got %r" % dist)
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("set_wall_loss: weight must be finite and >= 0, got %r" % weight)
+        self.wall_loss = (ops.walls_arg(walls, self.device), dist, weight)      # shape and M <= 1024: ValueError
 
     def _pad_z(self, z):
         return z if z.shape[-1] == self.Z_COLS else torch.nn.functional.pad(z, (0, self.Z_COLS - z.shape[-1]))
@@ -574,7 +613,7 @@ class SocialWaysTrainer:
         return (scenes.key, To, float(ss), float(Bg), self._row0, K, self.n_unrolling_steps, self.use_info_loss,
                 self.loss_info_w, self.use_l2_loss, self.use_variety_loss, self.loss_l2_w, self.variety_k,
                 og["lr"], tuple(og["betas"]), og["eps"], og.get("weight_decay", 0), od["lr"], tuple(od["betas"]), od["eps"],
-                od.get("weight_decay", 0), getattr(self, "clearance_loss", None),
+                od.get("weight_decay", 0), _wall_key(getattr(self, "wall_loss", None)), getattr(self, "clearance_loss", None),
                 ops.scene_wg(scenes, self.use_social, ragged), bool(ragged), bool(zdev))
 
     def _graphs_current(self):
@@ -794,6 +833,7 @@ class SocialWaysTrainer:
                 if buf is not None:
                     self._allreduce(buf)
             self.last_clearance = st["clearance"]              # the replayed launches wrote the buffers the capture saw
+            self.last_wall_loss = st["wall_loss"]
         elif st["n"] < 2:          # first steps of a layout run eagerly (lazy inits, workspace growth)
             st["n"] += 1
             for j in range(K):
@@ -838,6 +878,7 @@ class SocialWaysTrainer:
                     self._allreduce(buf)
         if not replayed:
             st["clearance"] = self.last_clearance              # set by _step_body (eager warm-up steps and the capture)
+            st["wall_loss"] = self.last_wall_loss
         st["done"][k].record()
         return st["outs"]
 
@@ -961,8 +1002,9 @@ class SocialWaysTrainer:
         dfuse = None
         one_pass = ops.disc_dpred_supported(Tp)
         clr = self.clearance_loss                               # an extra term on d/d(pred_hat), like use_l2_loss
+        wall = self.wall_loss                                   # ... and another (set_wall_loss())
         if (ops.DFUSE and one_pass and KV == 1 and not self.use_l2_loss and self.use_variety_loss is False
-                and obsv.shape[2] == 2 and ol is None and clr is None):
+                and obsv.shape[2] == 2 and ol is None and clr is None and wall is None):
             dfuse = (D._flat, pred_hat, targets, 1, noise, g_label, g_code, out[U + 1])
         dpred = None
         if dfuse is None and one_pass:
@@ -992,6 +1034,12 @@ class SocialWaysTrainer:
             closs, ccount = ws.get("clr_loss", B)[:B], ws.get("clr_count", B)[:B].view(torch.int32)
             ops.clearance_grad(pred_hat, obsv[:, -1], scenes, clr[0] * float(ss), clr[1] / (Bg * Tp), dpred[:B], closs, ccount)
             self.last_clearance = (closs, ccount)
+        self.last_wall_loss = None
+        if wall is not None:
+            # the wall term (set_wall_loss()), on the same prediction and rows; its outputs live in the workspace likewise
+            wloss, wcount = ws.get("wall_loss", B)[:B], ws.get("wall_count", B)[:B].view(torch.int32)
+            ops.wall_grad(pred_hat, obsv[:, -1], 1, wall[0], wall[1] * float(ss), wall[2] / (Bg * Tp), dpred[:B], wloss, wcount)
+            self.last_wall_loss = (wloss, wcount)
         restore = None
         if self.n_unrolling_steps > 0:     # D.load(backup) restores the Linear layers only (train.py:311-316, 541-542); D is
             if self._lin_maskf is None:    # not read again in this step: done by idle workgroups of the decode BPTT launch

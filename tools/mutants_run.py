@@ -35,12 +35,13 @@ COVER = {
     "sw_wgrad.h": ["kernels", "disc_reference", "step_reference", "launch_tails"],
     "sw_clearance_grad.hip": ["clearance_loss"],
     "sw_scene.hip": ["scene"],
-    "sw_scene_dev.h": ["scene", "compose", "clearance_loss", "plan_risk"],
+    "sw_scene_dev.h": ["scene", "compose", "clearance_loss", "plan_risk", "wall_loss"],
     "sw_compose.hip": ["compose"],
     "sw_plan_risk.hip": ["plan_risk"],
     "sw_plan_refine.hip": ["refine", "walls"],
     "sw_walls.hip": ["walls"],
-    "sw_wall_dev.h": ["walls"],
+    "sw_wall_dev.h": ["walls", "wall_loss"],
+    "sw_wall_grad.hip": ["wall_loss"],
     "sw_nms.hip": ["nms"],
     "sw_noise.hip": ["noise"],
     "sw_generic.hip": ["modules_reference", "wide_reference", "trainer"],
@@ -51,7 +52,7 @@ COVER = {
 SECONDS = {T % m: s for m, s in {
     "clearance_loss": 3, "compose": 6, "disc_reference": 3, "gen_images": 1, "gen_reference": 8, "kernels": 10, "launch_tails": 1,
     "lstm_zero_state": 1, "modules_reference": 2, "nms": 1, "noise": 1, "plan_risk": 1, "ragged_next": 4, "rank": 1, "refine": 2,
-    "sample": 5, "scene": 4, "scene_wg": 1, "stats": 1, "step_reference": 6, "trainer": 28, "walls": 8, "wgrad_bounds": 1,
+    "sample": 5, "scene": 4, "scene_wg": 1, "stats": 1, "step_reference": 6, "trainer": 28, "wall_loss": 9, "walls": 8, "wgrad_bounds": 1,
     "wgrad_fixed": 1, "wide_reference": 5, "wide_step_reference": 7}.items()}
 FULL_SECONDS = 900       # the whole -m gpu suite: 315 s
 HIP_ERRORS = ("HIP error", "hipError", "illegal memory access", "Memory access fault", "HSA_STATUS_ERROR", "Aborted", "Segmentation fault")
