@@ -42,6 +42,11 @@
 * `--wall-loss DIST[:W]` (with `--walls FILE`): train against the map - the generator loss gains the wall term
   (set_wall_loss(walls, DIST, W), W default 1: predicted segments closer than DIST world units to a wall are pushed off it);
   the numbers `--walls` prints at every test (wall_draws, wall_agents, wall_blocked) show what it buys.
+* several recordings: give `--obsmat` more than once, and `--walls` as often and in the same order - one model on all of them
+  (SceneDataset.from_recordings: one scale, the first 4/5 of every recording's scenes train, every row knows its recording);
+  the maps become one WallMaps in the dataset's coordinates (data.maps_from_world) and the wall numbers are printed per
+  recording: the held-out scenes of recording i against its own map (evaluate_walls(data.test_part(i), maps[i])).  The wall
+  calls take one map per call, so `--wall-loss`, `--refine` and the ragged options stay with one recording.
 """
 import argparse
 import os
@@ -74,7 +79,9 @@ def ragged_windows(npz, like, train):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--obsmat", default=None, help="BIWI obsmat.txt; default: a synthetic recording written to --out")
+    ap.add_argument("--obsmat", default=None, action="append",
+                    help="BIWI obsmat.txt; default: a synthetic recording written to --out; more than once: one model on several "
+                         "recordings")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch-size", type=int, default=256)           # train.py --batch-size (agents per packed batch)
     ap.add_argument("--hidden-size", type=int, default=64)
@@ -98,10 +105,11 @@ def main(argv=None):
     ap.add_argument("--refine", type=float, default=None, metavar="DIST",
                     help="also refine every held-out agent's constant-velocity plan against the K draws of the others (clearance "
                          "penalty at DIST, world units) and report predicted risk and true collisions before and after")
-    ap.add_argument("--walls", default=None, metavar="FILE[:DIST]",
+    ap.add_argument("--walls", default=None, metavar="FILE[:DIST]", action="append",
                     help="the static map of the recording: a text file of `x0 y0 x1 y1` lines in world coordinates (# comments); "
                          "also report how many of the K draws come within DIST (default 0.1, world units) of a wall "
-                         "(evaluate_walls); with --refine the refinement keeps the plans off the walls too")
+                         "(evaluate_walls); with --refine the refinement keeps the plans off the walls too; with several "
+                         "--obsmat: one per recording, in their order")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -142,14 +150,23 @@ def main(argv=None):
             ap.error("--clearance-loss takes DIST or DIST:W, got %r" % args.clearance_loss)
         if args.hidden_size != 64:
             ap.error("--clearance-loss: the clearance term is implemented for the fused 64-unit path (--hidden-size 64)")
-    wall_file, wall_dist = args.walls, 0.1
-    if args.walls is not None:
-        head, sep, tail = args.walls.rpartition(":")
+    wall_files, wall_dist = [], 0.1
+    for entry in args.walls or []:
+        head, sep, tail = entry.rpartition(":")
         try:
             if sep and head:
-                wall_file, wall_dist = head, float(tail)
+                entry, wall_dist = head, float(tail)
         except ValueError:               # a colon that belongs to the file name
             pass
+        wall_files.append(entry)
+    obsmats = args.obsmat or [None]
+    many = len(obsmats) > 1
+    if wall_files and len(wall_files) != len(obsmats):
+        ap.error("--walls is given once per --obsmat, in the same order: %d maps for %d recordings" % (len(wall_files), len(obsmats)))
+    if many and (args.min_past is not None or args.min_next is not None or args.train_ragged or args.refine is not None
+                 or wall_loss is not None):
+        ap.error("several --obsmat: --min-past, --min-next, --train-ragged, --refine and --wall-loss take one recording")
+    wall_file = wall_files[0] if wall_files else None
     if args.ragged_fused and not args.train_ragged:
         ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
@@ -167,17 +184,19 @@ def main(argv=None):
         torch.distributed.init_process_group("nccl", device_id=dev)
         pg = torch.distributed.group.WORLD
     os.makedirs(args.out, exist_ok=True)
-    obsmat = args.obsmat
+    obsmat = obsmats[0]
     if obsmat is None:
         obsmat = os.path.join(args.out, "obsmat.txt")
         if rank == 0:
             fr, ids, pos, vel = sw.synth_crowd_frames(n_frames=400, n_ped=160, interval=6, seed=args.seed + 3)
             sw.write_biwi_obsmat(obsmat, fr, ids, pos, vel)
     npz = os.path.join(args.out, "crowd-8-12.npz")
+    npzs = [npz] + [os.path.join(args.out, "crowd-8-12-%d.npz" % i) for i in range(1, len(obsmats))]
     if rank == 0:
-        obsvs, preds, times, batches = sw.biwi_to_npz(obsmat, npz, 8, 12)
-        print("%s: %d samples in %d scenes (largest %d agents)" % (obsmat, len(obsvs), len(batches),
-                                                                    int(np.max(batches[:, 1] - batches[:, 0]))))
+        for o, f in zip([obsmat] + obsmats[1:], npzs):
+            obsvs, preds, times, batches = sw.biwi_to_npz(o, f, 8, 12)
+            print("%s: %d samples in %d scenes (largest %d agents)" % (o, len(obsvs), len(batches),
+                                                                        int(np.max(batches[:, 1] - batches[:, 0]))))
     if world > 1:
         torch.distributed.barrier()
     ragged_npz = os.path.join(args.out, "crowd-8-12-ragged.npz")
@@ -189,7 +208,11 @@ def main(argv=None):
                               min_next=args.min_next)
     if world > 1:
         torch.distributed.barrier()
-    data = sw.SceneDataset.from_npz(npz, device=dev)
+    if many:
+        parts = [np.load(f) for f in npzs]
+        data = sw.SceneDataset.from_recordings([(d["obsvs"], d["preds"], d["batches"], d["times"]) for d in parts], device=dev)
+    else:
+        data = sw.SceneDataset.from_npz(npz, device=dev)
     ragged = train_set = short = None
     if args.min_next is not None and rank == 0:
         short = ragged_windows(next_npz, data, train=False)
@@ -208,6 +231,9 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     walls = data.walls_from_world(sw.load_walls(wall_file)) if wall_file is not None else None
+    maps = None
+    if many and wall_files:               # one map per recording: its held-out scenes are judged against its own
+        walls, maps = None, data.maps_from_world([sw.load_walls(f) for f in wall_files])
     tr = sw.SocialWaysTrainer(data.n_next, hidden_size=args.hidden_size, use_social=bool(args.social), device=dev,
                               process_group=pg, **(dict(ragged_fused=True) if args.ragged_fused else {}))
     if args.device_noise is not None:     # the same seed on every rank: the union of the shards is the single-process z
@@ -280,6 +306,15 @@ def main(argv=None):
                       "(ground truth %.1f %%) | Min(%d) ADE,FDE over the clear draws = (%.3f, %.3f) | first conflict at frame %.2f"
                       % (walls.shape[0], wall_dist, 100 * wl["wall_draws"], 100 * wl["wall_agents"], 100 * wl["wall_blocked"],
                          100 * wl["wall_gt"], args.k, wl["ade_min_free"], wl["fde_min_free"], wl["t_first"]))
+            for i in range(len(maps) if maps is not None else 0):
+                part = data.test_part(i)
+                if not part.n_test_samples:       # a recording too short to hold a scene out
+                    continue
+                wl = tr.evaluate_walls(part, maps[i], n_gen_samples=args.k, wall_dist=wall_dist)
+                print("Walls of recording %d (%d segments, within %.2f, %d held-out agents): %.1f %% of the draws, %.1f %% of the agents "
+                      "in some draw, %.1f %% in every draw (ground truth %.1f %%)"
+                      % (i, maps[i].shape[0], wall_dist, wl["n_agents"], 100 * wl["wall_draws"], 100 * wl["wall_agents"],
+                         100 * wl["wall_blocked"], 100 * wl["wall_gt"]))
             if ragged is not None:
                 hist = tr.evaluate_history(ragged, n_gen_samples=args.k)
                 print("Ragged held-out set: Avg ADE,FDE = (%.3f, %.3f) | Min(%d) ADE,FDE = (%.3f, %.3f) | by history length: %s"

@@ -3,8 +3,12 @@ schema of create_toy.py:187 / create_dataset.py:14): npz {obsvs (N,To,2), preds 
 batches (S,2)} -> normalised device tensors + scene ranges, the greedy scene packing of train(),
 and synthetic generators for the benchmark shapes (no dataset ships with the reference).
 """
+import copy
+
 import numpy as np
 import torch
+
+from ._lib import WALLS_MAX
 
 
 class Scale(object):
@@ -116,6 +120,110 @@ class SceneDataset:
         seg = wall_segments(np.array(segments, dtype=np.float32, copy=True))
         return torch.from_numpy(self.scale.normalize(seg)).to(self.obsv.device)
 
+    def maps_from_world(self, list_of_segments):
+        """The maps of several recordings in the coordinates of this dataset: a sequence of world-coordinate wall sets, each as
+        walls_from_world() takes it -> a WallMaps on the device of the tracks (set i = walls_from_world(list_of_segments[i]))."""
+        return WallMaps([self.walls_from_world(s) for s in list_of_segments], self.obsv.device)
+
+    # which map of a WallMaps every row sees (from_recordings(): the recording of the row): int32 (N,) on the device, or None.
+    # Read by test_part(); the training and evaluation calls take one map and do not look at it.
+    wall_map = None
+
+    def set_wall_map(self, ids):
+        """Attach the map index of every row: ids (N,) per row, or (S,) per scene of the_batches (every row of a scene then
+        sees its scene's map) - list, numpy array or tensor of integers; an index outside the WallMaps it is used with means
+        "no map".  Uploaded as int32; None detaches it.  Works on held_out() datasets too.  Returns self."""
+        if ids is None:
+            self.wall_map = None
+            return self
+        a = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids)
+        if a.dtype.kind not in "iu":
+            raise ValueError("wall_map ids must hold integers, got dtype %s" % a.dtype)
+        N, S = self.obsv.shape[0], len(self.the_batches)
+        if a.shape == (S,) and a.shape != (N,):
+            sizes = self.the_batches[:, 1] - self.the_batches[:, 0]
+            if int(sizes.sum()) != N:
+                raise ValueError("per-scene ids need the_batches to cover the %d rows, they cover %d" % (N, int(sizes.sum())))
+            rows = np.empty(N, dtype=a.dtype)
+            for (lo, hi), v in zip(self.the_batches, a):
+                rows[lo:hi] = v
+            a = rows
+        if a.shape != (N,):
+            raise ValueError("wall_map ids must be (N,) = (%d,) per row or (S,) = (%d,) per scene, got %s" % (N, S, a.shape))
+        self.wall_map = torch.from_numpy(a.astype(np.int32)).to(self.obsv.device)
+        return self
+
+    def test_part(self, i):
+        """This dataset with the held-out scenes that see map i alone (a scene's map is that of its first row): the same
+        tensors and coordinates, rows where they were - a DeviceNoise draws what it draws for the whole set -, test_batches
+        and n_test_samples cut down.  evaluate_walls(data.test_part(i), maps[i]) judges recording i against its own map;
+        the shares of the whole held-out set are the n_agents-weighted means of the parts."""
+        if self.wall_map is None:
+            raise ValueError("test_part() needs wall_map (SceneDataset.from_recordings, set_wall_map)")
+        wm = self.wall_map.cpu().numpy()
+        d = copy.copy(self)
+        keep = [k for k, (a, b) in enumerate(self.test_batches) if int(wm[int(a)]) == int(i)]
+        d.test_batches = self.test_batches[keep]
+        d.n_test_samples = int(sum(int(b - a) for a, b in d.test_batches))
+        return d
+
+    @classmethod
+    def from_recordings(cls, parts, device="cuda"):
+        """One dataset from several recordings: parts = [(obsvs, preds, batches, times[, obs_len]), ...] in WORLD coordinates,
+        each as the constructor takes it (batches covering the part's rows in order).  One Scale over all parts; the training
+        part is the first 4/5 of EACH recording's scenes (at least one), and scenes and rows are laid out as all training
+        scenes, recording by recording, then all test scenes, recording by recording: the_batches, train_batches,
+        test_batches, n_train_samples and packed_steps() work as for one recording, and a recording's scenes stay adjacent (a
+        packed batch holds the scenes of two recordings only where one ends).  wall_map = the recording of every row, the
+        index into maps_from_world([...]) given in the same order.  times with one entry per row follow their rows, any other
+        times are concatenated as they are; obs_len is given for every part or for none."""
+        parts = [tuple(p) for p in parts]
+        if not parts or any(len(p) not in (4, 5) for p in parts):
+            raise ValueError("from_recordings takes a non-empty list of (obsvs, preds, batches, times[, obs_len])")
+        if len(set(len(p) == 5 and p[4] is not None for p in parts)) != 1:
+            raise ValueError("from_recordings: obs_len is given for every recording or for none")
+        ragged = len(parts[0]) == 5 and parts[0][4] is not None
+        obs = [np.asarray(p[0], dtype=np.float32) for p in parts]
+        prd = [np.asarray(p[1], dtype=np.float32) for p in parts]
+        bat = [np.asarray(p[2]).astype(np.int64).reshape(-1, 2) for p in parts]
+        if any(len(b) == 0 for b in bat):
+            raise ValueError("from_recordings: a recording without scenes")
+        split = [max(1, (len(b) * 4) // 5) for b in bat]
+        order = [(i, s) for i, b in enumerate(bat) for s in range(split[i])] \
+            + [(i, s) for i, b in enumerate(bat) for s in range(split[i], len(b))]
+        rows = [(i, int(bat[i][s, 0]), int(bat[i][s, 1])) for i, s in order]
+        ends = np.cumsum([hi - lo for _, lo, hi in rows])
+        d = cls.__new__(cls)
+        d.the_batches = np.stack([ends - np.asarray([hi - lo for _, lo, hi in rows]), ends], axis=1).astype(np.int64)
+        d.times = None
+        if all(p[3] is not None for p in parts):
+            tms = [np.asarray(p[3]) for p in parts]
+            if all(len(t) == len(o) for t, o in zip(tms, obs)):      # one per row: they follow their rows (test() labels by row)
+                d.times = np.concatenate([tms[i][lo:hi] for i, lo, hi in rows])
+            else:
+                d.times = np.concatenate(tms)
+        d.train_size = int(sum(split))
+        d.train_batches, d.test_batches = d.the_batches[:d.train_size], d.the_batches[d.train_size:]
+        obsvs = np.concatenate([obs[i][lo:hi] for i, lo, hi in rows])
+        preds = np.concatenate([prd[i][lo:hi] for i, lo, hi in rows])
+        d.n_past, d.n_next = obsvs.shape[1], preds.shape[1]
+        d.n_train_samples = int(d.the_batches[d.train_size - 1][1])
+        d.n_test_samples = obsvs.shape[0] - d.n_train_samples
+        sc = Scale()
+        sc.max_x = max(np.max(obsvs[:, :, 0]), np.max(preds[:, :, 0]))
+        sc.min_x = min(np.min(obsvs[:, :, 0]), np.min(preds[:, :, 0]))
+        sc.max_y = max(np.max(obsvs[:, :, 1]), np.max(preds[:, :, 1]))
+        sc.min_y = min(np.min(obsvs[:, :, 1]), np.min(preds[:, :, 1]))
+        sc.calc_scale(keep_ratio=True)
+        d.scale, d.ss = sc, sc.sx
+        d.obsv = torch.from_numpy(sc.normalize(obsvs)).to(device)
+        d.pred = torch.from_numpy(sc.normalize(preds)).to(device)
+        d.obs_len = None
+        if ragged:
+            ol = np.concatenate([np.asarray(parts[i][4])[lo:hi] for i, lo, hi in rows])
+            d.obs_len = torch.from_numpy(check_obs_len(ol, obsvs.shape[0], d.n_past, 2)).to(device)
+        return d.set_wall_map(np.concatenate([np.full(hi - lo, i, dtype=np.int32) for i, lo, hi in rows]))
+
     @classmethod
     def held_out(cls, like, obsvs, preds, batches, times=None, obs_len=None, train=False):
         """Windows that a model trained on `like` is evaluated on: EVERY scene is a test scene (no training part), the
@@ -172,6 +280,43 @@ def wall_segments(x):
     if n and (len(sh) not in (2, 3) or n // sh[0] != 4 or n % sh[0]):
         raise ValueError("walls must be (M, 2, 2) or (M, 4): the segments [w0, w1] = x0 y0 x1 y1, got %s" % (sh,))
     return x.reshape(-1, 2, 2)
+
+
+class WallMaps:
+    """A set of maps for batches whose agents see different ones - scenes of several recordings in one packed batch:
+    maps = a sequence of n_maps >= 1 wall sets, each what a single-map call takes - a tensor or host data, (M_i, 2, 2) or
+    (M_i, 4), M_i = 0 .. 1024 (SW_WALLS_MAX), in the coordinates of the paths.  Checked on the host (ValueError).
+      walls    (Mtot, 2, 2) float32 on `device`: the sets one after the other; Mtot is not capped, only int32;
+      ptr      (n_maps + 1,) int32 on `device`: set i = walls[ptr[i]:ptr[i + 1]]; ptr_host: its numpy copy;
+      n_maps, len(maps);  maps[i]: the view of set i - a valid `walls` of every single-map call.
+    Which set a row sees is given per row, like obs_len: SceneDataset.wall_map (N,) int32, an index outside 0 .. n_maps - 1
+    meaning "this agent has no map".  The wall calls take ONE map per call (path_walls, wall_penalty, set_wall_loss,
+    evaluate_walls, refine_plans): a mixed set is worked through map by map - maps[i] on the rows with wall_map == i."""
+
+    def __init__(self, maps, device="cuda"):
+        sets = []
+        for m in maps:
+            w = torch.as_tensor(m if isinstance(m, torch.Tensor) else np.asarray(m), dtype=torch.float32)
+            w = wall_segments(w)
+            if w.shape[0] > WALLS_MAX:
+                raise ValueError("a map holds at most %d walls, got %d" % (WALLS_MAX, w.shape[0]))
+            sets.append(w)
+        if not sets:
+            raise ValueError("WallMaps needs at least one map (an empty one counts)")
+        ptr = np.concatenate([[0], np.cumsum([w.shape[0] for w in sets], dtype=np.int64)])
+        if ptr[-1] > 0x7fffffff:
+            raise ValueError("the maps hold %d walls in all: more than int32 offsets reach" % ptr[-1])
+        self.n_maps = len(sets)
+        self.ptr_host = ptr.astype(np.int32)
+        self.walls = torch.cat([w.to(device) for w in sets]).contiguous()
+        self.ptr = torch.from_numpy(self.ptr_host).to(device)
+
+    def __len__(self):
+        return self.n_maps
+
+    def __getitem__(self, i):
+        i = range(self.n_maps)[i]
+        return self.walls[int(self.ptr_host[i]):int(self.ptr_host[i + 1])]
 
 
 def load_walls(path):
