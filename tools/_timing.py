@@ -5,9 +5,11 @@ call), the alternation of the sides, the table cell, evaluate()'s chunks re-deri
 and the write-out - and the A/B of two BUILDS of the package: two trees cannot share a process, so each side runs in child
 processes of its own, one at a time and alternating, and this file is the child.
 
-Run by itself it is that A/B over the whole evaluation family: test(), evaluate(), evaluate_scenes(), evaluate_ranked() and
-evaluate_diverse() (per agent and per scene) on the host noise stream and on a DeviceNoise(2019), what every call returns
-(repr, equal or not) and its time in both builds (each median inside the other's range or not).
+Run by itself it is that A/B over the whole evaluation family: test(), evaluate(),
+evaluate_scenes(), evaluate_ranked(), evaluate_diverse() (per agent and per scene), evaluate_history(), evaluate_horizon(),
+evaluate_composed(), evaluate_risk(), evaluate_refine() (without and with walls) and evaluate_walls() on the host noise stream
+and on a DeviceNoise(2019), what every call returns (repr, equal or not) and its time in both builds (each median inside the
+other's range or not).
 
     python tools/_timing.py --parent-tree ab_old [--rounds 3] [--repeats 7] [--out profiles/eval_refactor_ab.txt]
 """
@@ -31,7 +33,11 @@ SHAPES = (("throughput: 256 held-out scenes x 8 agents, K = 20, full set", 256, 
           ("latency: same set, K = 128, first scene only (the driver's call every five epochs)", 256, 8, 128, True),
           ("dense: 16 held-out scenes x 64 agents, K = 20, full set", 16, 64, 20, False))
 COLL, TOP_M, RADIUS, METRIC = 0.2, 5, 0.5, "fde"      # the settings the tools time the family with
+SWEEPS, DIST = 8, 0.5                                 # evaluate_composed(); evaluate_refine()
 PER_LAUNCH = "%9.4f [%8.4f, %8.4f]"                   # cell(fmt=): ms per launch
+# the map of the two wall calls, world coordinates (x0 y0 x1 y1): six segments through the square synth_tracks starts its agents in
+WALLS = ((2.0, 0.0, 2.0, 6.0), (5.0, 4.0, 5.0, 10.0), (8.0, 0.0, 8.0, 6.0), (0.0, 8.0, 4.0, 8.0), (6.0, 2.0, 10.0, 2.0),
+         (3.0, 3.0, 7.0, 7.0))
 
 # the evaluation family: name -> (trainer, data, K, just_one) -> what it returns
 CALLS = {
@@ -43,6 +49,16 @@ CALLS = {
                                                                      metric=METRIC, joint=False, just_one=one),
     "evaluate_diverse, joint": lambda tr, data, K, one: tr.evaluate_diverse(data, n_gen_samples=K, top_m=TOP_M, radius=RADIUS,
                                                                             metric=METRIC, joint=True, just_one=one),
+    "evaluate_history": lambda tr, data, K, one: tr.evaluate_history(data, n_gen_samples=K, just_one=one),
+    "evaluate_horizon": lambda tr, data, K, one: tr.evaluate_horizon(data, n_gen_samples=K, just_one=one),
+    "evaluate_composed": lambda tr, data, K, one: tr.evaluate_composed(data, n_gen_samples=K, coll_dist=COLL, sweeps=SWEEPS,
+                                                                       just_one=one),
+    "evaluate_risk": lambda tr, data, K, one: tr.evaluate_risk(data, n_gen_samples=K, coll_dist=COLL, just_one=one),
+    "evaluate_refine": lambda tr, data, K, one: tr.evaluate_refine(data, n_gen_samples=K, dist=DIST, coll_dist=COLL, just_one=one),
+    "evaluate_refine, walls": lambda tr, data, K, one: tr.evaluate_refine(data, n_gen_samples=K, dist=DIST, coll_dist=COLL,
+                                                                          just_one=one, walls=data.timing_walls),
+    "evaluate_walls": lambda tr, data, K, one: tr.evaluate_walls(data, data.timing_walls, n_gen_samples=K, wall_dist=COLL,
+                                                                 just_one=one),
 }
 
 
@@ -65,10 +81,12 @@ def trainer():
 
 
 def held_out_set(n_test_scenes, agents, device="cuda:0"):
-    """SceneDataset keeps the last fifth of the scenes for testing: 5 x n scenes give n held-out ones."""
+    """SceneDataset keeps the last fifth of the scenes for testing: 5 x n scenes give n held-out ones.  timing_walls: WALLS in
+    the dataset's coordinates, for the two wall calls of CALLS."""
     tracks = sw.synth_tracks(5 * n_test_scenes, agents, 8, 12, seed=4321)
     data = sw.SceneDataset(tracks["obsvs"], tracks["preds"], tracks["batches"], tracks["times"], device=device)
     assert len(data.test_batches) == n_test_scenes
+    data.timing_walls = data.walls_from_world(WALLS)
     return data
 
 
@@ -202,7 +220,8 @@ def main():
     res = across_builds(a.parent_tree, a.rounds, a.repeats, a.warmup, tuple(CALLS), ("host", "device"))
     lines = ["the evaluation family, parent build vs this build: %d alternating child processes of each, %d timed calls per child "
              "after %d warm-up calls; host clock around the call, ms; seed 123 before every call, device stream DeviceNoise(2019); "
-             "coll_dist %.1f, top_m %d, radius %.2f, %s" % (a.rounds, a.repeats, a.warmup, COLL, TOP_M, RADIUS, METRIC),
+             "coll_dist %.1f, top_m %d, radius %.2f, %s, %d sweeps, dist %.1f, a map of %d walls"
+             % (a.rounds, a.repeats, a.warmup, COLL, TOP_M, RADIUS, METRIC, SWEEPS, DIST, len(WALLS)),
              "%-88s %-6s %-24s %28s %28s %-8s %s" % ("shape", "stream", "call", "parent median [min, max]", "this median [min, max]",
                                                    "inside", "equal")]
     for (shape, stream, call), r in res.items():
