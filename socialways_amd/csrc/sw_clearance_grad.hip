@@ -104,17 +104,14 @@ __global__ __launch_bounds__(64) void clearance_grad_kernel(const float* __restr
 extern "C" int sw_clearance_grad(const float* pos, int pstride, const float* start, int sstride, const int* scene_off, int S,
                                  int B, int Tp, float d0, float scale, float* dpos, int dstride, float* loss, int* count,
                                  void* stream) {
-  if (!pos || !scene_off || !dpos || S < 0 || B < 0 || Tp < 1) return SW_EARG;
-  if (!(d0 > 0.f) || !isfinite(d0) || !isfinite(scale)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (dstride != 2 && dstride != 4)) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)dpos & 7)) return SW_EARG;                 // rows are read and written as float2
-  if (start && sstride < 2) return SW_EARG;
-  const float d02 = d0 * d0;
-  if (!(d02 > 0.f) || !isfinite(d02) || !isfinite(1.f / d02)) return SW_EARG;        // d0^2 and its inverse are fp32 numbers
+  float d02, inv_d02;
+  if (!sw_paths_ok(pos, pstride, start, sstride) || !sw_penalty_dist(d0, d02, inv_d02) || !isfinite(scale)) return SW_EARG;
+  if (!scene_off || !dpos || S < 0 || B < 0 || Tp < 1) return SW_EARG;
+  if ((dstride != 2 && dstride != 4) || ((uintptr_t)dpos & 7)) return SW_EARG;       // rows are written as float2
   if (B == 0 || S == 0) return SW_OK;
   const int tiles = (B + 63) / 64;                         // no scene has more
   SW_LAUNCH(clearance_grad_kernel, dim3((unsigned)S, (unsigned)(tiles < CG_MAX_TILES ? tiles : CG_MAX_TILES)), dim3(64), 0,
-            (hipStream_t)stream, pos, pstride, start, sstride, scene_off, Tp, d02, 1.f / d02, scale, dpos, dstride, loss, count);
+            (hipStream_t)stream, pos, pstride, start, sstride, scene_off, Tp, d02, inv_d02, scale, dpos, dstride, loss, count);
   SW_CHECK_LAUNCH("clearance_grad_kernel");
   return SW_OK;
 }

@@ -297,10 +297,9 @@ extern "C" int sw_scene_compose(const float* pos, int pstride, const float* star
                                 const int* scene_off, const int* len, int S, int B, int K, int Tp, float inv_ss,
                                 float coll_dist, int sweeps, const float* err, int* sel, int* sel0, float* clear,
                                 int* per_scene, float* per_row, void* stream) {
-  if (!pos || !score || !scene_off || !sel || !clear || !per_scene) return SW_EARG;
+  if (!sw_paths_ok(pos, pstride, start, sstride) || !score || !scene_off || !sel || !clear || !per_scene) return SW_EARG;
   if (S < 0 || B < 0 || K < 1 || Tp < 1 || sweeps < 1 || !(inv_ss > 0.f) || !(coll_dist >= 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (start && sstride < 2) || (per_row && !err)) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)err & 7)) return SW_EARG;                  // positions and errors are read as float2
+  if ((per_row && !err) || ((uintptr_t)err & 7)) return SW_EARG;                     // errors are read as float2
   if (K > SW_COMPOSE_MAXK) return SW_ESHAPE;
   if (B == 0 || S == 0) return SW_OK;
   const int first = start ? 0 : 1;

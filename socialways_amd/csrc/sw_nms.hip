@@ -4,6 +4,7 @@
 // written out is a draw index, an integer count or one integer ratio.  Does not depend on the hidden size.
 #include "../../include/socialways_hip.h"
 #include "sw_common.h"
+#include "sw_scene_dev.h"
 #include <stdint.h>
 
 #define SW_NMS_MAXK 4096
@@ -157,10 +158,10 @@ __global__ __launch_bounds__(256) void sample_nms_kernel(const float* __restrict
 extern "C" int sw_sample_nms(const float* pos, int pstride, const float* score, const int* scene_off, int S, int B, int K,
                              int Tp, int M, int metric, float inv_ss, float radius, const float* err, const int* best,
                              int* order, int* count, float* weight, int* assign, float* per_row, void* stream) {
-  if (!pos || !score || !order || !count || !weight || !assign || B < 0 || K < 1 || M < 1 || M > K || Tp < 1) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (metric != 0 && metric != 1) || !(radius >= 0.f) || !(inv_ss > 0.f)) return SW_EARG;
-  if ((per_row && !err) || (scene_off && S < 0)) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)err & 7)) return SW_EARG;                  // positions and errors are read as float2
+  if (!sw_paths_ok(pos, pstride, nullptr, 0)) return SW_EARG;
+  if (!score || !order || !count || !weight || !assign || B < 0 || K < 1 || M < 1 || M > K || Tp < 1) return SW_EARG;
+  if ((metric != 0 && metric != 1) || !(radius >= 0.f) || !(inv_ss > 0.f)) return SW_EARG;
+  if ((per_row && !err) || (scene_off && S < 0) || ((uintptr_t)err & 7)) return SW_EARG;      // errors are read as float2
   if (K > SW_NMS_MAXK) return SW_ESHAPE;
   const int G = scene_off ? S : B;
   if (B == 0 || G == 0) return SW_OK;

@@ -323,23 +323,18 @@ static int rf_run(const float* pos, int pstride, const float* start, int sstride
                   int P, float inv_ss, float d0, int n_iter, float lr, float w_track, float w_smooth, float max_move,
                   const float* walls, int M, float dw, float w_wall, float* out, float* cost, float* moved, void* stream) {
   const bool with_walls = M >= 0;
-  if (!pos || !start || !scene_off || !plans || !plan_start || !q_scene || !out || !cost || !moved) return SW_EARG;
+  float d02, inv_d02, dw2 = 1.f, inv_dw2 = 1.f;
+  if (!start || !sw_paths_ok(pos, pstride, start, sstride) || !sw_penalty_dist(d0, d02, inv_d02)) return SW_EARG;
+  if (!scene_off || !plan_start || !q_scene || !out || !cost || !moved) return SW_EARG;
+  if (!plans || ((uintptr_t)plans & 7)) return SW_EARG;                              // plans are read as float2
   if (S < 0 || B < 0 || Q < 0 || K < 1 || Tp < 1 || P < 1 || !(inv_ss > 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || sstride < 2) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)plans & 7)) return SW_EARG;                // positions and plans are read as float2
   if (n_iter < 0 || n_iter > RF_MAXIT) return SW_EARG;
-  if (!(d0 > 0.f) || !isfinite(d0)) return SW_EARG;
-  const float d02 = d0 * d0;
-  if (!(d02 > 0.f) || !isfinite(d02) || !isfinite(1.f / d02)) return SW_EARG;        // d0^2 and its inverse are fp32 numbers
   const float par[4] = {lr, w_track, w_smooth, max_move};
   for (float v : par)
     if (!(v >= 0.f) || !isfinite(v)) return SW_EARG;
-  float dw2 = 1.f;
   if (with_walls) {
     if (M > 0 && !walls) return SW_EARG;
-    if (!(dw > 0.f) || !isfinite(dw) || !(w_wall >= 0.f) || !isfinite(w_wall)) return SW_EARG;
-    dw2 = dw * dw;
-    if (!(dw2 > 0.f) || !isfinite(dw2) || !isfinite(1.f / dw2) || !isfinite(w_wall * (d02 / dw2))) return SW_EARG;
+    if (!sw_penalty_dist(dw, dw2, inv_dw2) || !(w_wall >= 0.f) || !isfinite(w_wall) || !isfinite(w_wall * (d02 / dw2))) return SW_EARG;
   }
   if (K > RF_MAXK || Tp > RF_MAXT) return SW_ESHAPE;
   if (with_walls && M > SW_WALLS_MAX) return SW_ESHAPE;
@@ -352,7 +347,7 @@ static int rf_run(const float* pos, int pstride, const float* start, int sstride
   A.Kb = K < RF_THREADS ? K : RF_THREADS;
   A.APB = RF_THREADS / A.Kb;
   A.n_iter = n_iter;
-  A.inv_ss = inv_ss; A.d02 = d02; A.inv_d02 = 1.f / d02; A.inv_K = 1.f / (float)K;
+  A.inv_ss = inv_ss; A.d02 = d02; A.inv_d02 = inv_d02; A.inv_K = 1.f / (float)K;
   A.lr = lr; A.wt2 = 2.f * w_track; A.ws2 = 2.f * w_smooth;
   A.cap = max_move * d0;
   A.cap2 = A.cap * A.cap;                                    // +inf for a huge max_move: no step is capped
@@ -366,7 +361,7 @@ static int rf_run(const float* pos, int pstride, const float* start, int sstride
   A.walls = walls; A.M = M;
   A.NSL = rf_wall_slices(Tp);
   A.NW = (M + A.NSL - 1) / A.NSL;
-  A.dw2 = dw2; A.inv_dw2 = 1.f / dw2; A.ww = w_wall * (d02 / dw2);
+  A.dw2 = dw2; A.inv_dw2 = inv_dw2; A.ww = w_wall * (d02 / dw2);
   static_assert(rf_lds_bytes_walls(RF_MAXT, SW_WALLS_MAX) <= 160 * 1024, "the largest plan and map fit the LDS of a CU");
   const int lds = rf_lds_bytes_walls(Tp, M);                 // 90 256 bytes at Tp = 1024, M = 1024
   if (lds > 160 * 1024) return SW_ESHAPE;

@@ -209,11 +209,10 @@ extern "C" int sw_plan_risk(const float* pos, int pstride, const float* start, i
                             const int* len, int S, int B, int K, int Tp, const float* plans, const float* plan_start,
                             const int* plan_len, const int* q_scene, const int* q_ego, int Q, int P, float inv_ss,
                             float coll_dist, float* risk, float* clear_min, int* counts, void* stream) {
-  if (!pos || !scene_off || !plans || !q_scene || !risk || !clear_min || !counts) return SW_EARG;
+  if (!sw_paths_ok(pos, pstride, start, sstride) || !scene_off || !q_scene || !risk || !clear_min || !counts) return SW_EARG;
+  if (!plans || ((uintptr_t)plans & 7)) return SW_EARG;                              // plans are read as float2
   if ((start == nullptr) != (plan_start == nullptr)) return SW_EARG;                 // a start point on both sides or on neither
   if (S < 0 || B < 0 || Q < 0 || K < 1 || Tp < 1 || P < 1 || !(inv_ss > 0.f) || !(coll_dist >= 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (start && sstride < 2)) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)plans & 7)) return SW_EARG;                // positions and plans are read as float2
   if (K > SW_RISK_MAXK) return SW_ESHAPE;
   if (Q == 0) return SW_OK;
   PrArgs A = {};

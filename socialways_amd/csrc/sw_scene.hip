@@ -76,9 +76,8 @@ __global__ __launch_bounds__(64) void scene_clearance_kernel(const float* __rest
 // both entries: the dense launch without lengths
 extern "C" int sw_scene_clearance_len(const float* pos, int pstride, const float* start, int sstride, const int* scene_off,
                                       const int* len, int S, int B, int K, int Tp, float inv_ss, float* clear, void* stream) {
-  if (!pos || !scene_off || !clear || S < 0 || B < 0 || K < 1 || Tp < 1 || !(inv_ss > 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || ((uintptr_t)pos & 7)) return SW_EARG;       // positions are read as float2
-  if (start && sstride < 2) return SW_EARG;
+  if (!sw_paths_ok(pos, pstride, start, sstride)) return SW_EARG;
+  if (!scene_off || !clear || S < 0 || B < 0 || K < 1 || Tp < 1 || !(inv_ss > 0.f)) return SW_EARG;
   if ((long long)S * K > 0x7fffffffLL) return SW_EARG;
   if (B == 0 || S == 0) return SW_OK;
   if (len) {

@@ -2,10 +2,12 @@
 // the closest approach of two linearly moving points within one segment, the lane layout of a scene, and the walk over the
 // pairs of a scene (the chunk of a pair, a lane's own points, the partner tile).  sw_scene.hip and sw_compose.hip form a
 // clearance from these and nothing else, so a clearance of sw_scene_compose carries the bits sw_scene_clearance gives the
-// same two paths.
+// same two paths.  Behind them, the host part: the two argument checks every entry point of the family makes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #define SC_TC 16               // segments per time chunk: a lane keeps the SC_TC + 1 points of its own path in registers
 #define SC_NP (SC_TC + 1)
@@ -123,4 +125,18 @@ __device__ __forceinline__ void sc_stage_row(float2* trow, const float2 (&own)[S
     for (int p = 0; p < SC_NP; ++p)
       if (p <= nseg) trow[p] = sc_point(pos, pstride, start, sstride, brow, bagent, Tp, t0 + p);
   }
+}
+
+// ---- host: what the entry points of the family (scene clearance and its gradient, composition, suppression, plan risk and
+// refinement, the wall calls) check of their arguments, each once ----------------------------------------------------------
+// Are pos and start readable as paths of float2: pos there, its rows 2 or 4 floats apart and on an 8-byte boundary, and a
+// start - when there is one - with rows at least 2 floats apart?
+static inline bool sw_paths_ok(const float* pos, int pstride, const float* start, int sstride) {
+  return pos && (pstride == 2 || pstride == 4) && !((uintptr_t)pos & 7) && !(start && sstride < 2);
+}
+// Is d a usable penalty distance: finite and > 0, and d^2 and 1 / d^2 fp32 numbers?  Hands both back.
+static inline bool sw_penalty_dist(float d, float& d2, float& inv_d2) {
+  d2 = d * d;
+  inv_d2 = 1.f / d2;
+  return d > 0.f && isfinite(d) && d2 > 0.f && isfinite(d2) && isfinite(inv_d2);
 }

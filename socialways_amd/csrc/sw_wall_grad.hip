@@ -127,14 +127,10 @@ __global__ __launch_bounds__(WG_THREADS) void wall_grad_kernel(WgArgs A, float* 
 extern "C" int sw_wall_grad(const float* pos, int pstride, const float* start, int sstride, const int* len, int K, int B,
                             int Tp, const float* walls, int M, float dw, float scale, float* dpos, int dstride, float* loss,
                             int* count, void* stream) {
-  if (!pos || !dpos || (M > 0 && !walls)) return SW_EARG;
-  if (K < 1 || B < 0 || Tp < 1 || M < 0) return SW_EARG;
-  if (!(dw > 0.f) || !isfinite(dw) || !isfinite(scale)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (dstride != 2 && dstride != 4)) return SW_EARG;
-  if (((uintptr_t)pos & 7) || ((uintptr_t)dpos & 7)) return SW_EARG;                 // rows are read and written as float2
-  if (start && sstride < 2) return SW_EARG;
-  const float dw2 = dw * dw;
-  if (!(dw2 > 0.f) || !isfinite(dw2) || !isfinite(1.f / dw2)) return SW_EARG;        // dw^2 and its inverse are fp32 numbers
+  float dw2, inv_dw2;
+  if (!sw_paths_ok(pos, pstride, start, sstride) || !sw_penalty_dist(dw, dw2, inv_dw2) || !isfinite(scale)) return SW_EARG;
+  if (!dpos || (M > 0 && !walls) || K < 1 || B < 0 || Tp < 1 || M < 0) return SW_EARG;
+  if ((dstride != 2 && dstride != 4) || ((uintptr_t)dpos & 7)) return SW_EARG;       // rows are written as float2
   if (M > SW_WALLS_MAX) return SW_ESHAPE;
   if (B == 0) return SW_OK;
   const long long R = (long long)K * B;
@@ -144,7 +140,7 @@ extern "C" int sw_wall_grad(const float* pos, int pstride, const float* start, i
   A.pstride = pstride; A.sstride = sstride; A.dstride = dstride; A.B = B; A.Tp = Tp; A.M = M; A.R = R;
   A.front = start ? 1 : 0;                                   // points in front of pos row 0
   A.NS = Tp - 1 + A.front;                                   // segments of a path
-  A.dw2 = dw2; A.inv_dw2 = 1.f / dw2; A.scale = scale;
+  A.dw2 = dw2; A.inv_dw2 = inv_dw2; A.scale = scale;
   SW_LAUNCH(wall_grad_kernel, dim3((unsigned)((R + 63) / 64)), dim3(WG_THREADS), 0, (hipStream_t)stream, A, dpos, loss, count);
   SW_CHECK_LAUNCH("wall_grad_kernel");
   return SW_OK;

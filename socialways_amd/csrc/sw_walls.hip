@@ -85,10 +85,8 @@ __global__ __launch_bounds__(PW_THREADS) void path_walls_kernel(PwArgs A, float*
 extern "C" int sw_path_walls(const float* pos, int pstride, const float* start, int sstride, const int* len, int K, int B,
                              int Tp, const float* walls, int M, float inv_ss, float dist, float* clear, int* first, int* nseg,
                              void* stream) {
-  if (!pos || !clear || !first || !nseg || (M > 0 && !walls)) return SW_EARG;
+  if (!sw_paths_ok(pos, pstride, start, sstride) || !clear || !first || !nseg || (M > 0 && !walls)) return SW_EARG;
   if (K < 1 || B < 0 || Tp < 1 || M < 0 || !(inv_ss > 0.f) || !(dist >= 0.f)) return SW_EARG;
-  if ((pstride != 2 && pstride != 4) || (start && sstride < 2)) return SW_EARG;
-  if ((uintptr_t)pos & 7) return SW_EARG;                    // positions are read as float2
   if (M > SW_WALLS_MAX) return SW_ESHAPE;
   if (B == 0) return SW_OK;
   const long long R = (long long)K * B;

@@ -521,15 +521,20 @@ def gen_sample(enc_w, emb_w, att_w, dec_w, obsv, noise_k, scenes, n_next, use_so
     return pred4, (per_agent, best, err)
 
 
-def _check_pos(pos, K, B, score=None):
+def _check_pos(pos, K, B=None, score=None):
     """The K draws' positions as the scene-level wrappers take them, checked without touching the device: pos (K * B, Tp, 2 | 4)
-    or (K, B, Tp, 2 | 4), x and y first, on the device of `score` when one is given -> (Tp, pstride)."""
+    or (K, B, Tp, 2 | 4), x and y first, on the device of `score` when one is given -> (B, Tp, pstride).  B None: as many
+    agents as pos holds - K >= 1 divides the rows of a 3-d pos (path_walls, wall_grad)."""
     sh = tuple(pos.shape)
+    if B is None:
+        if len(sh) not in (3, 4) or K < 1 or (len(sh) == 3 and sh[0] % K):
+            raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, got %s" % (K, sh))
+        B = sh[1] if len(sh) == 4 else sh[0] // K
     if len(sh) not in (3, 4) or sh[-1] not in (2, 4) or sh[-2] < 1 or (sh[:2] != (K, B) if len(sh) == 4 else sh[0] != K * B):
         raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, B = %d, got %s" % (K, B, sh))
     if score is not None and pos.device != score.device:
         raise ValueError("pos must be on the device of score")
-    return sh[-2], sh[-1]
+    return B, sh[-2], sh[-1]
 
 
 def _start_arg(start, B, device, of="pos"):
@@ -545,6 +550,64 @@ def _start_arg(start, B, device, of="pos"):
     return start, start.stride(0)
 
 
+def _lens_arg(lens, B, device):
+    """lens (B,) int32 on `device` or None - ragged futures, as _check_pred_len_tensor takes them."""
+    return None if lens is None else _check_pred_len_tensor(lens, B, device, "lens")
+
+
+def check_positive(name, v):
+    """The scale of a distance (inv_ss): > 0."""
+    if not float(v) > 0.0:
+        raise ValueError("%s must be > 0, got %r" % (name, v))
+
+
+def check_distance(name, v):
+    """A threshold on a distance (coll_dist, radius, dist): >= 0."""
+    if not float(v) >= 0.0:
+        raise ValueError("%s must be >= 0, got %r" % (name, v))
+
+
+def check_penalty_distance(d, what="the distance", fp32=True):
+    """The distance of a penalty max(0, 1 - |c|^2 / d^2)^2: finite and > 0 -> float; fp32: its square and the inverse of that are
+    fp32 numbers as well (what the entry points demand; the gradient calls leave that part to them)."""
+    d = float(d)
+    ok = d > 0.0 and np.isfinite(d)
+    if ok and fp32:
+        with np.errstate(over="ignore", divide="ignore"):
+            d2 = np.float32(d) * np.float32(d)
+            ok = d2 > 0 and np.isfinite(d2) and np.isfinite(np.float32(1) / d2)
+    if not ok:
+        raise ValueError("%s must be finite and > 0%s, got %r"
+                         % (what, " (its square and the inverse of it fp32 numbers)" if fp32 else "", d))
+    return d
+
+
+def _grad_scalars(name, d, scale):
+    """d0 / dw and scale of the gradient calls -> floats: the distance finite and > 0, scale finite."""
+    d, scale = check_penalty_distance(d, name, fp32=False), float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    return d, scale
+
+
+def _check_grad_outputs(pos, dpos, leads, loss, count, shapes):
+    """What the gradient calls write: dpos float32 like pos - its leading axes one of `leads`, 2 or 4 wide, contiguous (it is
+    accumulated into in place), on the device of pos - and loss float32 / count int32 or None, contiguous, one of `shapes`, on
+    that device -> dstride."""
+    if tuple(dpos.shape[:-1]) not in leads or dpos.shape[-1] not in (2, 4):
+        raise ValueError("dpos must hold the paths and steps of pos %s, 2 or 4 wide, got %s" % (leads[0], tuple(dpos.shape)))
+    if pos.dtype != torch.float32 or dpos.dtype != torch.float32:
+        raise ValueError("pos and dpos must be float32")
+    if not dpos.is_contiguous():
+        raise ValueError("dpos is accumulated into in place: it must be contiguous")
+    if dpos.device != pos.device:
+        raise ValueError("dpos must be on the device of pos")
+    for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
+        if t is not None and (tuple(t.shape) not in shapes or t.dtype != dt or not t.is_contiguous() or t.device != pos.device):
+            raise ValueError("%s must be a contiguous %s tensor %s on the device of pos" % (name, dt, " or ".join(map(str, shapes))))
+    return dpos.shape[-1]
+
+
 def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     """clear (K, B): per draw and agent the closest approach to another agent of its scene, times inv_ss; +inf in
     single-agent scenes (sw_scene_clearance).  pos (K * B, Tp, 2 | 4) or (K, B, Tp, 2 | 4), x and y first; start (B, >= 2) or
@@ -552,11 +615,9 @@ def scene_clearance(pos, start, scenes, K, inv_ss=1.0, lens=None):
     lens (B,) int32 on the device: ragged futures - agent a is present for its first lens[a] frames (in every draw), and the
     segment of a pair that ends at frame t counts only if both are present at t; +inf where nothing counts
     (sw_scene_clearance_len).  None: the dense launch."""
-    B = scenes.B
-    Tp, pstride = _check_pos(pos, K, B)
+    B, Tp, pstride = _check_pos(pos, K, scenes.B)
     start, sstride = _start_arg(start, B, pos.device)
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
     pos = pos.contiguous()
     clear = torch.empty(K, B, device=pos.device)
@@ -574,23 +635,12 @@ def clearance_grad(pos, start, scenes, d0, scale, dpos, loss=None, count=None):
     place); it is data and takes no gradient.  d0 > 0 in the units of pos.  loss (B,) float32 / count (B,) int32 or None:
     written with the agent's share of the unscaled penalty (loss.sum() = the penalty) and its number of (partner, segment)s
     closer than d0.  Rows of agents with nothing closer than d0 are not written."""
-    for name, t in (("pos", pos), ("dpos", dpos)):
-        if t.dim() != 3 or t.shape[0] != scenes.B or t.shape[1] < 1 or t.shape[2] not in (2, 4) or t.dtype != torch.float32:
-            raise ValueError("%s must be float32 (B, Tp, 2 or 4) with B = %d, got %s" % (name, scenes.B, tuple(t.shape)))
-    B, Tp, pstride, dstride = pos.shape[0], pos.shape[1], pos.shape[2], dpos.shape[2]
-    if dpos.shape[1] != Tp:
-        raise ValueError("dpos must hold the Tp = %d steps of pos, got %s" % (Tp, tuple(dpos.shape)))
-    if not dpos.is_contiguous():
-        raise ValueError("dpos is accumulated into in place: it must be contiguous")
-    d0, scale = float(d0), float(scale)
-    if not (d0 > 0.0 and np.isfinite(d0)) or not np.isfinite(scale):
-        raise ValueError("d0 must be finite and > 0 and scale finite, got d0 = %r, scale = %r" % (d0, scale))
+    if pos.dim() != 3:
+        raise ValueError("pos must be float32 (B, Tp, 2 or 4) with B = %d, got %s" % (scenes.B, tuple(pos.shape)))
+    B, Tp, pstride = _check_pos(pos, 1, scenes.B)
+    dstride = _check_grad_outputs(pos, dpos, ((B, Tp),), loss, count, ((B,),))
+    d0, scale = _grad_scalars("d0", d0, scale)
     start, sstride = _start_arg(start, B, pos.device)
-    for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
-        if t is not None and (tuple(t.shape) != (B,) or t.dtype != dt or not t.is_contiguous() or t.device != pos.device):
-            raise ValueError("%s must be a contiguous %s tensor (B,) on the device of pos" % (name, dt))
-    if dpos.device != pos.device:
-        raise ValueError("dpos must be on the device of pos")
     L.require_gpu(pos)
     pos = pos.contiguous()
     L.call("sw_clearance_grad", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(scenes.scene_off), scenes.S, B, Tp,
@@ -783,11 +833,9 @@ def sample_nms(pos, score, K, M, radius, metric="fde", scenes=None, inv_ss=1.0, 
     B, best = _check_picks(score, K, M, err, best)
     if metric not in NMS_METRICS:
         raise ValueError("metric must be one of %s, got %r" % (sorted(NMS_METRICS), metric))
-    if not float(radius) >= 0.0:
-        raise ValueError("radius must be >= 0, got %r" % (radius,))
-    if not float(inv_ss) > 0.0:
-        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
-    Tp, pstride = _check_pos(pos, K, B, score)
+    check_distance("radius", radius)
+    check_positive("inv_ss", inv_ss)
+    _, Tp, pstride = _check_pos(pos, K, B, score)
     if scenes is not None and scenes.B != B:
         raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
     L.require_gpu(score)
@@ -824,18 +872,15 @@ def scene_compose(pos, start, score, scenes, K, coll_dist, inv_ss=1.0, sweeps=8,
     agents that moved | sweeps that changed something; per_row (B, 4) or None without err: ADE | FDE of draw sel0, ADE | FDE
     of draw sel)."""
     B, _ = _check_picks(score, K, None, err)
-    if not float(coll_dist) >= 0.0:
-        raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
-    if not float(inv_ss) > 0.0:
-        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    check_distance("coll_dist", coll_dist)
+    check_positive("inv_ss", inv_ss)
     if int(sweeps) < 1:
         raise ValueError("sweeps must be at least 1, got %r" % (sweeps,))
-    Tp, pstride = _check_pos(pos, K, B, score)
+    _, Tp, pstride = _check_pos(pos, K, B, score)
     if scenes.B != B:
         raise ValueError("scenes index %d rows, score has B = %d" % (scenes.B, B))
     start, sstride = _start_arg(start, B, score.device, "score")
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, score.device, "lens")
+    lens = _lens_arg(lens, B, score.device)
     L.require_gpu(score)
     score, pos = score.float().contiguous(), pos.float().contiguous()
     dev = score.device
@@ -862,6 +907,29 @@ def _check_query_tensor(t, Q, device, name):
     return t.contiguous()
 
 
+def _check_queries(pos, Tp, plans, plan_start, q_scene, q_ego, plan_lens=None):
+    """What plan_risk and plan_refine take per query, checked without touching the device: plans float32 (Q, P >= 1, Tp, 2) or
+    (P, Tp, 2) for Q = 1, plan_start (Q, 2) or None, q_scene and, when given, q_ego and plan_lens int32 (Q,), all on the device of
+    pos -> (plans (Q, P, Tp, 2), plan_start float32 contiguous, q_scene, q_ego, plan_lens, Q, P)."""
+    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.float32 or plans.dim() not in (3, 4) or plans.device != pos.device:
+        raise ValueError("plans must be a float32 tensor (Q, P, Tp, 2) or (P, Tp, 2) on the device of pos")
+    if plans.dim() == 3:
+        plans = plans.unsqueeze(0)
+    Q, P = plans.shape[0], plans.shape[1]
+    if P < 1 or tuple(plans.shape[2:]) != (Tp, 2):
+        raise ValueError("plans must be (Q, P >= 1, Tp, 2) with Tp = %d, got %s" % (Tp, tuple(plans.shape)))
+    if plan_start is not None:
+        if not isinstance(plan_start, torch.Tensor) or tuple(plan_start.shape) != (Q, 2) or plan_start.device != pos.device:
+            raise ValueError("plan_start must be (Q, 2) = (%d, 2) on the device of pos" % Q)
+        plan_start = plan_start.float().contiguous()
+    q_scene = _check_query_tensor(q_scene, Q, pos.device, "q_scene")
+    if q_ego is not None:
+        q_ego = _check_query_tensor(q_ego, Q, pos.device, "q_ego")
+    if plan_lens is not None:
+        plan_lens = _check_query_tensor(plan_lens, Q, pos.device, "plan_lens")
+    return plans.contiguous(), plan_start, q_scene, q_ego, plan_lens, Q, P
+
+
 def plan_risk(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, coll_dist, inv_ss=1.0, lens=None, plan_lens=None):
     """The risk of candidate ego paths against the K sampled futures of a scene (sw_plan_risk): how likely is a plan - a path
     that is NOT one of the draws - to come closer than coll_dist to somebody, inv_ss * the closest approach along the paths,
@@ -878,35 +946,16 @@ def plan_risk(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, coll_dis
     without one;  counts (Q, P, 4) int32: draws k in which some agent's draw k conflicts (the index-paired estimate is
     counts[..., 0] / K) | the frame at which the earliest conflicting segment ends, -1 without | the absolute row with the most
     conflicting draws, the lowest of equal ones, -1 without | that row's number of conflicting draws)."""
-    B = scenes.B
-    Tp, pstride = _check_pos(pos, K, B)
-    if not float(coll_dist) >= 0.0:
-        raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
-    if not float(inv_ss) > 0.0:
-        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
-    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.float32 or plans.dim() not in (3, 4) or plans.device != pos.device:
-        raise ValueError("plans must be a float32 tensor (Q, P, Tp, 2) or (P, Tp, 2) on the device of pos")
-    if plans.dim() == 3:
-        plans = plans.unsqueeze(0)
-    Q, P = plans.shape[0], plans.shape[1]
-    if P < 1 or tuple(plans.shape[2:]) != (Tp, 2):
-        raise ValueError("plans must be (Q, P >= 1, Tp, 2) with Tp = %d, got %s" % (Tp, tuple(plans.shape)))
+    B, Tp, pstride = _check_pos(pos, K, scenes.B)
+    check_distance("coll_dist", coll_dist)
+    check_positive("inv_ss", inv_ss)
     if (start is None) != (plan_start is None):
         raise ValueError("start and plan_start go together: a point in front of the paths and of the plans, or of neither")
+    plans, plan_start, q_scene, q_ego, plan_lens, Q, P = _check_queries(pos, Tp, plans, plan_start, q_scene, q_ego, plan_lens)
     start, sstride = _start_arg(start, B, pos.device)
-    if plan_start is not None:
-        if not isinstance(plan_start, torch.Tensor) or tuple(plan_start.shape) != (Q, 2) or plan_start.device != pos.device:
-            raise ValueError("plan_start must be (Q, 2) = (%d, 2) on the device of pos" % Q)
-        plan_start = plan_start.float().contiguous()
-    q_scene = _check_query_tensor(q_scene, Q, pos.device, "q_scene")
-    if q_ego is not None:
-        q_ego = _check_query_tensor(q_ego, Q, pos.device, "q_ego")
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
-    if plan_lens is not None:
-        plan_lens = _check_query_tensor(plan_lens, Q, pos.device, "plan_lens")
+    lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
-    pos, plans = pos.float().contiguous(), plans.contiguous()
+    pos = pos.float().contiguous()
     dev = pos.device
     risk = torch.empty(Q, P, device=dev)
     clear_min = torch.empty(Q, P, device=dev)
@@ -952,18 +1001,12 @@ def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
     Returns (clear (K, B): inv_ss * the smallest distance to any wall, +inf without walls or counted segments; first (K, B)
     int32: the frame at which the first segment closer than dist ends, -1 without; nseg (K, B) int32: the (segment, wall) pairs
     closer than dist)."""
-    if pos.dim() not in (3, 4) or K < 1 or (pos.dim() == 3 and pos.shape[0] % K):
-        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, got %s" % (K, tuple(pos.shape)))
-    B = pos.shape[1] if pos.dim() == 4 else pos.shape[0] // K
-    Tp, pstride = _check_pos(pos, K, B)
-    if not float(dist) >= 0.0:
-        raise ValueError("dist must be >= 0, got %r" % (dist,))
-    if not float(inv_ss) > 0.0:
-        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
+    B, Tp, pstride = _check_pos(pos, K)
+    check_distance("dist", dist)
+    check_positive("inv_ss", inv_ss)
     walls, M = check_walls(walls, pos.device)
     start, sstride = _start_arg(start, B, pos.device)
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
     pos = pos.float().contiguous()
     clear = torch.empty(K, B, device=pos.device)
@@ -986,31 +1029,12 @@ def wall_grad(pos, start, K, walls, dw, scale, dpos, loss=None, count=None, lens
     int32 on the device: ragged futures, as path_walls(lens=...).  loss float32 / count int32, (K, B) or (K * B,), or None:
     written with the path's unscaled penalty and its number of (segment, wall)s closer than dw.  Rows of paths with nothing
     closer than dw - every row when M = 0 - are not written."""
-    if pos.dim() not in (3, 4) or K < 1 or (pos.dim() == 3 and pos.shape[0] % K):
-        raise ValueError("pos must be (K * B, Tp, 2 or 4) or (K, B, Tp, 2 or 4) with K = %d, got %s" % (K, tuple(pos.shape)))
-    B = pos.shape[1] if pos.dim() == 4 else pos.shape[0] // K
-    Tp, pstride = _check_pos(pos, K, B)
-    if dpos.dim() not in (3, 4) or tuple(dpos.shape[:-1]) not in ((K * B, Tp), (K, B, Tp)) or dpos.shape[-1] not in (2, 4):
-        raise ValueError("dpos must hold the K * B = %d paths of Tp = %d steps of pos, 2 or 4 wide, got %s"
-                         % (K * B, Tp, tuple(dpos.shape)))
-    if pos.dtype != torch.float32 or dpos.dtype != torch.float32:
-        raise ValueError("pos and dpos must be float32")
-    if not dpos.is_contiguous():
-        raise ValueError("dpos is accumulated into in place: it must be contiguous")
-    dstride = dpos.shape[-1]
-    dw, scale = float(dw), float(scale)
-    if not (dw > 0.0 and np.isfinite(dw)) or not np.isfinite(scale):
-        raise ValueError("dw must be finite and > 0 and scale finite, got dw = %r, scale = %r" % (dw, scale))
+    B, Tp, pstride = _check_pos(pos, K)
+    dstride = _check_grad_outputs(pos, dpos, ((K * B, Tp), (K, B, Tp)), loss, count, ((K, B), (K * B,)))
+    dw, scale = _grad_scalars("dw", dw, scale)
     walls, M = check_walls(walls, pos.device)
     start, sstride = _start_arg(start, B, pos.device)
-    for name, t, dt in (("loss", loss, torch.float32), ("count", count, torch.int32)):
-        if t is not None and (tuple(t.shape) not in ((K, B), (K * B,)) or t.dtype != dt or not t.is_contiguous()
-                              or t.device != pos.device):
-            raise ValueError("%s must be a contiguous %s tensor (K, B) or (K * B,) on the device of pos" % (name, dt))
-    if dpos.device != pos.device:
-        raise ValueError("dpos must be on the device of pos")
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
     pos = pos.contiguous()
     if B == 0:
@@ -1030,20 +1054,12 @@ def check_descent(d0, n_iter=32, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.
     if set(wall) - {"wall_d0", "w_wall"}:
         raise TypeError("check_descent() got unexpected keyword arguments %s" % sorted(set(wall) - {"wall_d0", "w_wall"}))
     if wall.get("wall_d0") is not None:
-        dw = float(wall["wall_d0"])
-        dw2 = np.float32(dw) * np.float32(dw)
-        with np.errstate(over="ignore", divide="ignore"):
-            if not (dw > 0.0 and np.isfinite(dw) and dw2 > 0 and np.isfinite(dw2) and np.isfinite(np.float32(1) / dw2)):
-                raise ValueError("the wall distance must be finite and > 0 (its square and the inverse of it fp32 numbers), got %r" % (dw,))
+        check_penalty_distance(wall["wall_d0"], "the wall distance")
     if "w_wall" in wall and not (float(wall["w_wall"]) >= 0.0 and np.isfinite(float(wall["w_wall"]))):
         raise ValueError("w_wall must be finite and >= 0, got %r" % (wall["w_wall"],))
     if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 0 <= int(n_iter) <= 1024:
         raise ValueError("n_iter must be an integer in 0 .. 1024, got %r" % (n_iter,))
-    d0 = float(d0)
-    d02 = np.float32(d0) * np.float32(d0)
-    with np.errstate(over="ignore", divide="ignore"):
-        if not (d0 > 0.0 and np.isfinite(d0) and d02 > 0 and np.isfinite(d02) and np.isfinite(np.float32(1) / d02)):
-            raise ValueError("the distance must be finite and > 0 (its square and the inverse of it fp32 numbers), got %r" % (d0,))
+    d0 = check_penalty_distance(d0)
     vals = dict(lr=float(lr), w_track=float(w_track), w_smooth=float(w_smooth), max_move=float(max_move))
     for name, v in vals.items():
         if not (v >= 0.0 and np.isfinite(v)):
@@ -1074,38 +1090,23 @@ def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, in
     where a segment of the plan CROSSES a wall (c = 0): descent cannot undo a crossing - crossings are reported (path_walls),
     not repaired.  walls=None: the launch without walls and its (Q, P, 2, 3) cost; an empty tensor takes the new entry point
     and returns the same bits in refined, moved and cost[..., :3]."""
-    B = scenes.B
-    Tp, pstride = _check_pos(pos, K, B)
+    B, Tp, pstride = _check_pos(pos, K, scenes.B)
     M = -1
     if walls is not None:
         wall_d0 = float(d0 if wall_d0 is None else wall_d0)
         check_descent(d0, n_iter, lr, w_track, w_smooth, max_move, wall_d0=wall_d0, w_wall=w_wall)
         walls, M = check_walls(walls, pos.device)
     d0, n_iter, lr, w_track, w_smooth, max_move = check_descent(d0, n_iter, lr, w_track, w_smooth, max_move)
-    if not float(inv_ss) > 0.0:
-        raise ValueError("inv_ss must be > 0, got %r" % (inv_ss,))
-    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.float32 or plans.dim() not in (3, 4) or plans.device != pos.device:
-        raise ValueError("plans must be a float32 tensor (Q, P, Tp, 2) or (P, Tp, 2) on the device of pos")
-    if plans.dim() == 3:
-        plans = plans.unsqueeze(0)
-    Q, P = plans.shape[0], plans.shape[1]
-    if P < 1 or tuple(plans.shape[2:]) != (Tp, 2):
-        raise ValueError("plans must be (Q, P >= 1, Tp, 2) with Tp = %d, got %s" % (Tp, tuple(plans.shape)))
+    check_positive("inv_ss", inv_ss)
     if K > 4096 or Tp > 1024:
         raise ValueError("plan_refine takes K <= 4096 draws and Tp <= 1024 steps, got K = %d, Tp = %d" % (K, Tp))
     if start is None or plan_start is None:
         raise ValueError("plan_refine needs a start point in front of the paths (start) and of the plans (plan_start)")
+    plans, plan_start, q_scene, q_ego, _, Q, P = _check_queries(pos, Tp, plans, plan_start, q_scene, q_ego)
     start, sstride = _start_arg(start, B, pos.device)
-    if not isinstance(plan_start, torch.Tensor) or tuple(plan_start.shape) != (Q, 2) or plan_start.device != pos.device:
-        raise ValueError("plan_start must be (Q, 2) = (%d, 2) on the device of pos" % Q)
-    plan_start = plan_start.float().contiguous()
-    q_scene = _check_query_tensor(q_scene, Q, pos.device, "q_scene")
-    if q_ego is not None:
-        q_ego = _check_query_tensor(q_ego, Q, pos.device, "q_ego")
-    if lens is not None:
-        lens = _check_pred_len_tensor(lens, B, pos.device, "lens")
+    lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
-    pos, plans = pos.float().contiguous(), plans.contiguous()
+    pos = pos.float().contiguous()
     dev = pos.device
     refined = torch.empty(Q, P, Tp, 2, device=dev)
     cost = torch.empty(Q, P, 2, 3 if walls is None else 4, device=dev)

@@ -107,7 +107,21 @@ def calc_and_store_stats(main_dir, real_samples, n_past=2, n_next=2, stats_file=
     return stats_1nn, stats_wst
 
 
-# ---- the argument front of the public forms below: host data or tensors from anywhere -> checked device tensors ------------
+# ---- the argument front of the public forms below: host data or tensors from anywhere -> device tensors, every check written
+# once.  What only this layer knows: what is read on the host (lens, the queries), the default scene of a query, the division by
+# scale.  The scalar checks are ops' own (ops.check_*).  The shape checks that ops makes again behind a form stay, because they
+# stand in front of the form's require_gpu: on a CPU tensor their ValueError is what the caller gets, and
+# tests/test_geometry_args_host.py holds every form to that. -------------------------------------------------------------------
+def _trajs_arg(trajs, device, ranks=(4,), empty=False):
+    """trajs (K >= 1, B, T, 2 | 4) or - with 3 among `ranks` - (B, T, 2 | 4), x and y first -> (the 4-d tensor on the device, the
+    leading axes of what was given); empty: a 3-d input may hold no rows (the scene index refuses it behind this)."""
+    t = _dev(trajs, device)
+    if t.dim() not in ranks or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or (t.shape[0] < 1 and not (empty and t.dim() == 3)):
+        raise ValueError("trajs must be %s, got %s" % (" or ".join({4: "(K >= 1, B, T, 2 or 4)", 3: "(B, T, 2 or 4)"}[r] for r in ranks),
+                                                      tuple(t.shape)))
+    return (t if t.dim() == 4 else t.unsqueeze(0)), tuple(t.shape[:-2])
+
+
 def _start_arg(start, B, device):
     """start (B, 2) or None: a point in front of every path."""
     if start is None:
@@ -128,12 +142,51 @@ def _lens_arg(lens, B, T, device):
 
 def _scored_arg(trajs, score, device):
     """trajs (K >= 1, B, T, 2 | 4) and score (K, B) -> both on the device."""
-    t, s = _dev(trajs, device), _dev(score, device)
-    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    t, s = _trajs_arg(trajs, device)[0], _dev(score, device)
     if tuple(s.shape) != tuple(t.shape[:2]):
         raise ValueError("score must be (K, B) = (%d, %d), got %s" % (t.shape[0], t.shape[1], tuple(s.shape)))
     return t, s
+
+
+def _dist_over_scale(dist, scale):
+    """dist and scale, both finite and > 0 -> (dist / scale, scale): |scale c| < dist  <=>  |c| < dist / scale."""
+    dist, scale = ops.check_penalty_distance(dist, "dist", fp32=False), ops.check_penalty_distance(scale, "scale", fp32=False)
+    return dist / scale, scale
+
+
+def _query_arg(x, Q, name, device):
+    """A per-query integer argument (Q,) - list, numpy array or tensor - checked on the host -> int32 on the device."""
+    host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
+    if host.shape != (Q,) or host.dtype.kind not in "iu":
+        raise ValueError("%s must hold Q = %d integers, got shape %s dtype %s" % (name, Q, host.shape, host.dtype))
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def _query_front(trajs, sub_batches, plans, plan_start, start, scene, ego, lens, device):
+    """What plan_risk() and refine_plans() share: the draws, the scene index, the plans (Q, P >= 1, T, 2) or (P, T, 2) with their
+    start points, and the queries - scene None: query q belongs to scene q, Q = S -> (trajs, start, scenes, K, plans, plan_start,
+    scene, ego, lens) as ops.plan_risk() takes them."""
+    t = _trajs_arg(trajs, device)[0]
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
+    p = _dev(plans, device)
+    if p.dim() == 3:
+        p = p.unsqueeze(0)
+    if p.dim() != 4 or p.shape[1] < 1 or tuple(p.shape[2:]) != (T, 2):
+        raise ValueError("plans must be (Q, P >= 1, T, 2) or (P, T, 2) with T = %d, got %s" % (T, tuple(p.shape)))
+    Q = p.shape[0]
+    start = _start_arg(start, B, device)
+    if plan_start is not None:
+        plan_start = _dev(plan_start, device)
+        if tuple(plan_start.shape) != (Q, 2):
+            raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
+    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
+    if scene is None:
+        if Q != scenes.S:
+            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, scenes.S))
+        scene = np.arange(Q)
+    scene = _query_arg(scene, Q, "scene", t.device)
+    ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
+    return t, start, scenes, K, p, plan_start, scene, ego, _lens_arg(lens, B, T, t.device)
 
 
 def scene_clearance(trajs, sub_batches, start=None, scale=1.0, device="cuda"):
@@ -152,18 +205,12 @@ def scene_clearance_len(trajs, sub_batches, lens, start=None, scale=1.0, device=
     padding and reaches no output).  A collision needs both agents present: the segment of a pair that ends at frame t counts
     only if t < min(lens[a], lens[b]).  An agent for which no segment counts has clearance +inf.  Everything else as
     scene_clearance(), which is this call with lens None."""
-    t = _dev(trajs, device)
-    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
-        raise ValueError("trajs must be (K, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    t4 = t if t.dim() == 4 else t.unsqueeze(0)
-    K, B, T = t4.shape[0], t4.shape[1], t4.shape[2]
-    if K < 1:
-        raise ValueError("no draws")
+    t, lead = _trajs_arg(trajs, device, (4, 3), empty=True)
+    K, B, T = t.shape[0], t.shape[1], t.shape[2]
     lens = _lens_arg(lens, B, T, t.device)
     start = _start_arg(start, B, device)
     L.require_gpu(t)
-    clear = ops.scene_clearance(t4, start, ops.SceneIndex.get(sub_batches, B, t.device), K, float(scale), lens=lens)
-    return clear if t.dim() == 4 else clear[0]
+    return ops.scene_clearance(t, start, ops.SceneIndex.get(sub_batches, B, t.device), K, float(scale), lens=lens).reshape(lead)
 
 
 def clearance_penalty(trajs, sub_batches, dist, start=None, scale=1.0, device="cuda"):
@@ -175,20 +222,16 @@ def clearance_penalty(trajs, sub_batches, dist, start=None, scale=1.0, device="c
     trajs to the units of `dist`, as in scene_clearance().  Returns device tensors (loss (B,), grad (B, T, 2), count (B,)
     int32): the agent's share of the penalty (loss.sum() = the sum over pairs and segments), its gradient with respect to
     trajs[..., :2] in the units of trajs, and the agent's number of (partner, segment)s closer than dist."""
-    t = _dev(trajs, device)
-    if t.dim() != 3 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1:
-        raise ValueError("trajs must be (B, T, 2 or 4), got %s" % (tuple(t.shape),))
+    t = _trajs_arg(trajs, device, (3,), empty=True)[0].squeeze(0)
     B, T = t.shape[0], t.shape[1]
-    dist, scale = float(dist), float(scale)
-    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
-        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
+    d0, _ = _dist_over_scale(dist, scale)
     start = _start_arg(start, B, device)
     L.require_gpu(t)
     grad = torch.zeros(B, T, 2, device=t.device)
     loss = torch.zeros(B, device=t.device)
     count = torch.zeros(B, dtype=torch.int32, device=t.device)
     scenes = ops.SceneIndex.get(sub_batches, B, t.device)
-    ops.clearance_grad(t, start, scenes, dist / scale, 1.0, grad, loss, count)        # |scale c| < dist  <=>  |c| < dist / scale
+    ops.clearance_grad(t, start, scenes, d0, 1.0, grad, loss, count)
     return loss, grad, count
 
 
@@ -229,14 +272,6 @@ def compose_scenes(trajs, score, sub_batches, coll_dist, start=None, scale=1.0, 
     return ops.scene_compose(t, start, s, scenes, K, coll_dist, float(scale), int(sweeps), lens=lens)[:4]
 
 
-def _query_arg(x, Q, name, device):
-    """A per-query integer argument (Q,) - list, numpy array or tensor - checked on the host -> int32 on the device."""
-    host = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
-    if host.shape != (Q,) or host.dtype.kind not in "iu":
-        raise ValueError("%s must hold Q = %d integers, got shape %s dtype %s" % (name, Q, host.shape, host.dtype))
-    return torch.from_numpy(host.astype(np.int32)).to(device)
-
-
 def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None, scene=None, ego=None, scale=1.0, lens=None,
               plan_lens=None, device="cuda"):
     """How likely is a candidate ego path to run into somebody (`sw_plan_risk`), for trajectories from anywhere.  trajs
@@ -252,34 +287,13 @@ def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None,
     Returns device tensors (risk (Q, P): 1 - the product over the other agents of the share of their draws that stay clear;
     clear_min (Q, P): the closest approach to any draw; counts (Q, P, 4) int32: draws k with a conflict of some agent's draw k |
     frame of the earliest conflict, -1 | the row with the most conflicting draws, -1 | its number of them)."""
-    if not float(coll_dist) >= 0.0 or not float(scale) > 0.0:
-        raise ValueError("coll_dist must be >= 0 and scale > 0, got %r and %r" % (coll_dist, scale))
-    t = _dev(trajs, device)
-    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    K, B, T = t.shape[0], t.shape[1], t.shape[2]
-    p = _dev(plans, device)
-    if p.dim() == 3:
-        p = p.unsqueeze(0)
-    if p.dim() != 4 or p.shape[1] < 1 or tuple(p.shape[2:]) != (T, 2):
-        raise ValueError("plans must be (Q, P >= 1, T, 2) or (P, T, 2) with T = %d, got %s" % (T, tuple(p.shape)))
-    Q = p.shape[0]
+    ops.check_distance("coll_dist", coll_dist)
+    ops.check_positive("scale", scale)
     if (start is None) != (plan_start is None):
         raise ValueError("start and plan_start go together: a point in front of the paths and of the plans, or of neither")
-    start = _start_arg(start, B, device)
-    if plan_start is not None:
-        plan_start = _dev(plan_start, device)
-        if tuple(plan_start.shape) != (Q, 2):
-            raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
-    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
-    if scene is None:
-        if Q != scenes.S:
-            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, scenes.S))
-        scene = np.arange(Q)
-    scene = _query_arg(scene, Q, "scene", t.device)
-    ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
-    lens = _lens_arg(lens, B, T, t.device)
-    plan_lens = _lens_arg(plan_lens, Q, T, t.device)
+    t, start, scenes, K, p, plan_start, scene, ego, lens = _query_front(trajs, sub_batches, plans, plan_start, start, scene, ego, lens,
+                                                                        device)
+    plan_lens = _lens_arg(plan_lens, p.shape[0], t.shape[2], t.device)
     L.require_gpu(t)
     return ops.plan_risk(t, start, scenes, K, p, plan_start, scene, ego, coll_dist, float(scale), lens=lens, plan_lens=plan_lens)
 
@@ -293,14 +307,9 @@ def path_walls(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cud
     Returns device tensors shaped like the leading axes of trajs: clear - the smallest distance to any wall, +inf without
     walls; first int32 - the frame at which the first segment closer than dist ends, -1 without; nseg int32 - the (segment,
     wall) pairs closer than dist."""
-    if not float(dist) >= 0.0 or not float(scale) > 0.0:
-        raise ValueError("dist must be >= 0 and scale > 0, got %r and %r" % (dist, scale))
-    t = _dev(trajs, device)
-    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    lead = tuple(t.shape[:-2])
-    if t.dim() == 3:
-        t = t.unsqueeze(0)
+    ops.check_distance("dist", dist)
+    ops.check_positive("scale", scale)
+    t, lead = _trajs_arg(trajs, device, (4, 3))
     K, B, T = t.shape[0], t.shape[1], t.shape[2]
     w = ops.walls_arg(walls, device)
     start = _start_arg(start, B, device)
@@ -320,15 +329,8 @@ def wall_penalty(trajs, walls, dist, start=None, scale=1.0, lens=None, device="c
     trajs - the path's penalty (no 1/2: a path owns its pairs alone) and its number of (segment, wall)s closer than dist - and
     grad (.., T, 2): the gradient of loss.sum() with respect to trajs[..., :2] in the units of trajs, exactly 0 where a path
     crosses a wall."""
-    dist, scale = float(dist), float(scale)
-    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
-        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
-    t = _dev(trajs, device)
-    if t.dim() not in (3, 4) or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4) or (B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    lead = tuple(t.shape[:-2])
-    if t.dim() == 3:
-        t = t.unsqueeze(0)
+    dw, _ = _dist_over_scale(dist, scale)
+    t, lead = _trajs_arg(trajs, device, (4, 3))
     K, B, T = t.shape[0], t.shape[1], t.shape[2]
     w = ops.walls_arg(walls, device)
     start = _start_arg(start, B, device)
@@ -337,7 +339,7 @@ def wall_penalty(trajs, walls, dist, start=None, scale=1.0, lens=None, device="c
     grad = torch.zeros(K, B, T, 2, device=t.device)
     loss = torch.zeros(K, B, device=t.device)
     count = torch.zeros(K, B, dtype=torch.int32, device=t.device)
-    ops.wall_grad(t, start, K, w, dist / scale, 1.0, grad, loss, count, lens=lens)      # |scale c| < dist  <=>  |c| < dist / scale
+    ops.wall_grad(t, start, K, w, dw, 1.0, grad, loss, count, lens=lens)
     return loss.reshape(lead), grad.reshape(lead + (T, 2)), count.reshape(lead)
 
 
@@ -358,36 +360,14 @@ def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None,
     walls at the distance wall_dist (default dist; in the units of scale * trajs) - `sw_plan_refine_walls` - and cost is
     (Q, P, 2, 4), the unweighted wall penalty last.  Where a plan CROSSES a wall the gradient is exactly 0: descent cannot undo a
     crossing; path_walls() reports it."""
-    dist, scale = float(dist), float(scale)
-    if not (dist > 0.0 and np.isfinite(dist)) or not (scale > 0.0 and np.isfinite(scale)):
-        raise ValueError("dist and scale must be finite and > 0, got %r and %r" % (dist, scale))
+    d0, scale = _dist_over_scale(dist, scale)
     wall = {}
     if walls is not None:
-        wall = dict(walls=ops.walls_arg(walls, device), wall_d0=(dist if wall_dist is None else float(wall_dist)) / scale, w_wall=w_wall)
-    ops.check_descent(dist / scale, **{k: v for k, v in wall.items() if k != "walls"}, **descent)
-    t = _dev(trajs, device)
-    if t.dim() != 4 or t.shape[-1] not in (2, 4) or t.shape[-2] < 1 or t.shape[0] < 1:
-        raise ValueError("trajs must be (K >= 1, B, T, 2 or 4), got %s" % (tuple(t.shape),))
-    K, B, T = t.shape[0], t.shape[1], t.shape[2]
-    p = _dev(plans, device)
-    if p.dim() == 3:
-        p = p.unsqueeze(0)
-    if p.dim() != 4 or p.shape[1] < 1 or tuple(p.shape[2:]) != (T, 2):
-        raise ValueError("plans must be (Q, P >= 1, T, 2) or (P, T, 2) with T = %d, got %s" % (T, tuple(p.shape)))
-    Q = p.shape[0]
+        wall = dict(walls=ops.walls_arg(walls, device), wall_d0=d0 if wall_dist is None else float(wall_dist) / scale, w_wall=w_wall)
+    ops.check_descent(d0, **{k: v for k, v in wall.items() if k != "walls"}, **descent)
     if start is None or plan_start is None:
         raise ValueError("refine_plans needs start (B, 2) and plan_start (Q, 2): the points in front of the paths and of the plans")
-    start = _start_arg(start, B, device)
-    plan_start = _dev(plan_start, device)
-    if tuple(plan_start.shape) != (Q, 2):
-        raise ValueError("plan_start must be (Q, 2) = (%d, 2), got %s" % (Q, tuple(plan_start.shape)))
-    scenes = ops.SceneIndex.get(sub_batches, B, t.device)
-    if scene is None:
-        if Q != scenes.S:
-            raise ValueError("without `scene` query q belongs to scene q: plans hold Q = %d queries, there are %d scenes" % (Q, scenes.S))
-        scene = np.arange(Q)
-    scene = _query_arg(scene, Q, "scene", t.device)
-    ego = _query_arg(ego, Q, "ego", t.device) if ego is not None else None
-    lens = _lens_arg(lens, B, T, t.device)
+    t, start, scenes, K, p, plan_start, scene, ego, lens = _query_front(trajs, sub_batches, plans, plan_start, start, scene, ego, lens,
+                                                                        device)
     L.require_gpu(t)
-    return ops.plan_refine(t, start, scenes, K, p, plan_start, scene, ego, dist / scale, scale, lens=lens, **wall, **descent)
+    return ops.plan_refine(t, start, scenes, K, p, plan_start, scene, ego, d0, scale, lens=lens, **wall, **descent)

@@ -35,6 +35,52 @@ def test_library_exports_every_header_symbol():
     assert isinstance(lib.sw_last_error(), bytes)
 
 
+C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+           "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint,
+           "unsigned long long": ctypes.c_ulonglong, "void": None}
+
+
+def c_type(decl, ret=False):
+    """The ctypes type of one C parameter or return type as the header spells it: `const char*` returned and `char*` are
+    c_char_p, any other pointer c_void_p, the scalars by name (a parameter's own name dropped)."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        base = decl[:decl.index("*")].replace("const", "").strip()
+        return ctypes.c_char_p if base == "char" and (ret or "const" not in decl) else ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    for n in (len(words), len(words) - 1):                # with and without a parameter name behind the type
+        if " ".join(words[:n]) in C_TYPES:
+            return C_TYPES[" ".join(words[:n])]
+    raise AssertionError("include/socialways_hip.h: no ctypes type for %r" % decl)
+
+
+def header_prototypes():
+    """name -> (restype, [argtypes]) of every `ret name(args);` the header declares, comments and preprocessor lines dropped."""
+    src = open(os.path.join(ROOT, "include", "socialways_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    src = "\n".join(ln for ln in src.splitlines() if not ln.lstrip().startswith("#"))
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(sw_\w+)\s*\(([^()]*)\)\s*;", src):
+        args = [a for a in (x.strip() for x in args.split(",")) if a and a != "void"]
+        assert name not in out, name
+        out[name] = (c_type(ret, ret=True), [c_type(a) for a in args])
+    return out
+
+
+def test_ctypes_table_matches_the_header_type_for_type():
+    """socialways_amd/_lib.py spells restype and argtypes out by hand, positionally: a float for an int or an int for a
+    long long would hand a kernel garbage without any error.  Every entry must equal what the header declares."""
+    from socialways_amd import _lib as L
+    want = header_prototypes()
+    have = dict(L.PROTOTYPES, **L.DEBUG_PROTOTYPES)
+    assert sorted(want) == sorted(have) and len(want) >= 121
+    for name, (res, args) in want.items():
+        assert have[name][0] is res, "%s returns %s in the header, %s in _lib.py" % (name, res, have[name][0])
+        assert len(have[name][1]) == len(args), "%s takes %d arguments in the header, %d in _lib.py" % (name, len(args), len(have[name][1]))
+        for i, (h, b) in enumerate(zip(args, have[name][1])):
+            assert h is b, "%s argument %d is %s in the header, %s in _lib.py" % (name, i, h, b)
+
+
 def test_argument_validation_without_gpu():
     """Entry points reject bad arguments before touching the device (no compute call is made here)."""
     from socialways_amd import _lib as L

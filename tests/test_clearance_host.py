@@ -112,7 +112,13 @@ def test_entry_point_checks_its_arguments_before_the_device():
     assert call(pos=None) == -1 and call(dpos=None) == -1 and call(scene_off=None) == -1
     assert call(d0=0.0) == -1 and call(d0=-1.0) == -1 and call(d0=math.inf) == -1 and call(d0=math.nan) == -1
     assert call(pstride=3) == -1 and call(dstride=1) == -1 and call(start=p, sstride=1) == -1 and call(Tp=0) == -1
+    assert call(d0=1e-30) == -1 and call(d0=1e30) == -1, "d0^2 and its inverse are fp32 numbers"
+    assert call(scale=math.inf) == -1 and call(scale=math.nan) == -1 and call(dstride=3) == -1 and call(pstride=0) == -1
+    assert call(pos=p + 4) == -1 and call(dpos=p + 4) == -1 and call(S=-1) == -1 and call(B=-1) == -1
+    for kw in (dict(pos=None), dict(d0=0.0), dict(pstride=3), dict(dpos=p + 4), dict(start=p, sstride=1), dict(scale=math.nan)):
+        assert call(B=0, **kw) == -1 and call(S=0, **kw) == -1, "the checks come before the early return"
     assert call(B=0) == 0 and call(S=0) == 0, "an empty batch is SW_OK without a launch"
+    assert call(B=0, start=p, sstride=2) == 0 and call(B=0, pstride=4, dstride=4) == 0 and call(S=0, sstride=1) == 0      # sstride is read only with a start
 
 
 def test_ops_and_stats_check_shapes_and_refuse_cpu_tensors():

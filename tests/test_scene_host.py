@@ -33,6 +33,9 @@ def test_scene_entry_points_reject_bad_arguments_without_a_device():
                dict(inv_ss=float("nan")), dict(S=1 << 30, K=4)):
         assert clearance(**kw) == EARG, kw
     assert clearance(B=0) == 0 and clearance(S=0) == 0          # a successful no-op, still without a device
+    assert clearance(B=0, start=None, sstride=0) == 0 and clearance(S=0, pstride=4) == 0
+    for kw in (dict(pos=p + 4), dict(pstride=3), dict(sstride=1), dict(inv_ss=0.0)):
+        assert clearance(B=0, **kw) == EARG and clearance(S=0, **kw) == EARG, kw      # the checks come before the early return
 
     def reduce(err=p, clear=p, scene_off=o, S=2, B=4, K=1, coll=0.1, per_scene=p, best=None):
         return lib.sw_scene_reduce(err, clear, scene_off, S, B, K, coll, per_scene, best, None)

@@ -138,7 +138,10 @@ def test_entry_point_checks_its_arguments_before_the_device():
     assert call(pstride=3) == EARG and call(dstride=1) == EARG and call(dstride=3) == EARG
     assert call(pos=p + 4) == EARG and call(dpos=p + 4) == EARG
     assert call(start=p, sstride=1) == EARG
-    assert call(M=1025) == ESHAPE
+    assert call(M=1025) == ESHAPE and call(M=1025, B=0) == ESHAPE
+    for kw in (dict(dw=0.0), dict(dw=1e-30), dict(scale=math.nan), dict(pstride=3), dict(pos=p + 4), dict(dpos=p + 4), dict(start=p, sstride=1),
+               dict(dstride=3)):
+        assert call(M=1025, **kw) == EARG and call(B=0, **kw) == EARG, kw      # the argument checks come first
     assert call(B=0) == 0 and call(B=0, M=0, walls=None) == 0, "an empty batch is SW_OK without a launch"
 
 

@@ -209,6 +209,8 @@ def test_argument_validation_without_gpu():
                dict(dist=nan)):
         assert walls(**kw) == -1, kw
     assert walls(M=L.WALLS_MAX + 1) == -2 and L.WALLS_MAX >= 1024
+    for kw in (dict(pstride=3), dict(pos=p + 4), dict(sstride=1), dict(inv_ss=0.0), dict(clear=None)):
+        assert walls(M=L.WALLS_MAX + 1, **kw) == -1, kw          # the argument checks come first
 
     good = dict(pos=p, pstride=2, start=p, sstride=2, scene_off=p, len=None, S=1, B=2, K=4, Tp=3, plans=p, plan_start=p,
                 q_scene=p, q_ego=None, Q=0, P=2, inv_ss=1.0, d0=0.5, n_iter=4, lr=0.1, w_track=0.05, w_smooth=0.5, max_move=0.5,
@@ -223,6 +225,8 @@ def test_argument_validation_without_gpu():
                dict(dw=1e-30), dict(dw=1e30), dict(w_wall=-1.0), dict(w_wall=nan), dict(w_wall=inf), dict(w_wall=1e38, dw=1e-3, d0=1e3),
                dict(d0=0.0), dict(lr=-0.1), dict(n_iter=1025), dict(pstride=3)):
         assert refine(**kw) == -1, kw
+    for kw in (dict(start=None), dict(sstride=1), dict(pos=p + 4), dict(plans=p + 4), dict(d0=1e-30), dict(d0=1e30), dict(d0=inf), dict(d0=nan)):
+        assert refine(**kw) == -1 and refine(M=L.WALLS_MAX + 1, **kw) == -1, kw      # the argument checks come first
     for kw in (dict(M=L.WALLS_MAX + 1), dict(K=4097), dict(Tp=1025)):
         assert refine(**kw) == -2, kw
 
