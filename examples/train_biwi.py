@@ -39,7 +39,12 @@
 * `--clearance-loss DIST[:W]`: train against collisions - the generator loss gains the scene-clearance term
   (set_clearance_loss(DIST, W), W default 1: pairs of predicted futures that come closer than DIST world units within a
   segment are pushed apart), and every test prints col_joint and col_agent of evaluate_scenes(coll_dist=DIST) beside ADE/FDE.
-* `--wall-loss DIST[:W]` (with `--walls FILE`): train against the map - the generator loss gains the wall term
+* `--map-image FILE[:HFILE]` (in place of `--walls`): the map from an obstacle image, as BIWI/ETH ship it (`map.png`, `H.txt`): the
+  image (a `.npy` array, or any format PIL reads) is traced into the runs of its obstacle boundary (trace_occupancy), the runs go
+  through the 3 x 3 homography of HFILE - ETH's acts on (row, col, 1) - and under a grid (data.wall_grid_from_world): thousands
+  of walls, no cap, and the wall calls look only at the walls within `--map-reach D` (world units, default 1) of a path.
+  `--refine` leaves such a map out: the refinement takes at most 1024 walls.
+* `--wall-loss DIST[:W]` (with `--walls FILE` or `--map-image FILE`): train against the map - the generator loss gains the wall term
   (set_wall_loss(walls, DIST, W), W default 1: predicted segments closer than DIST world units to a wall are pushed off it);
   the numbers `--walls` prints at every test (wall_draws, wall_agents, wall_blocked) show what it buys.
 * several recordings: give `--obsmat` more than once, and `--walls` as often and in the same order - one model on all of them
@@ -110,6 +115,11 @@ def main(argv=None):
                          "also report how many of the K draws come within DIST (default 0.1, world units) of a wall "
                          "(evaluate_walls); with --refine the refinement keeps the plans off the walls too; with several "
                          "--obsmat: one per recording, in their order")
+    ap.add_argument("--map-image", default=None, metavar="FILE[:HFILE]",
+                    help="the map from an obstacle image (.npy, or what PIL reads) and its homography file (3 x 3, on (row, col, 1) "
+                         "as ETH's H.txt; none: pixels are world units): traced and put under a grid; takes the place of --walls")
+    ap.add_argument("--map-reach", type=float, default=1.0, metavar="D",
+                    help="with --map-image: the largest distance (world units) a wall call may ask about")
     ap.add_argument("--min-past", type=int, default=None, metavar="M",
                     help="also evaluate on held-out windows that keep the pedestrians seen for only M .. 7 frames (ragged "
                          "histories) and report the errors per history length; training stays on full windows unless "
@@ -137,8 +147,8 @@ def main(argv=None):
             wall_loss = (float(dist), float(w) if w else 1.0)
         except ValueError:
             ap.error("--wall-loss takes DIST or DIST:W, got %r" % args.wall_loss)
-        if args.walls is None:
-            ap.error("--wall-loss needs --walls FILE: the map to train against")
+        if args.walls is None and args.map_image is None:
+            ap.error("--wall-loss needs --walls FILE or --map-image FILE: the map to train against")
         if args.hidden_size != 64:
             ap.error("--wall-loss: the wall term is implemented for the fused 64-unit path (--hidden-size 64)")
     clearance = None
@@ -167,6 +177,8 @@ def main(argv=None):
                  or wall_loss is not None):
         ap.error("several --obsmat: --min-past, --min-next, --train-ragged, --refine and --wall-loss take one recording")
     wall_file = wall_files[0] if wall_files else None
+    if args.map_image is not None and (wall_files or many):
+        ap.error("--map-image takes the place of --walls and one recording")
     if args.ragged_fused and not args.train_ragged:
         ap.error("--ragged-fused needs --train-ragged")
     if args.train_ragged and args.min_past is None:
@@ -231,6 +243,20 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     walls = data.walls_from_world(sw.load_walls(wall_file)) if wall_file is not None else None
+    if args.map_image is not None:        # image -> boundary runs -> world coordinates -> a grid over them
+        image, sep, hfile = args.map_image.rpartition(":")
+        if not sep or not image or not os.path.exists(hfile):      # no homography file: the whole argument is the image
+            image, hfile = args.map_image, None
+        to_world = None
+        if hfile is not None:
+            to_world = np.loadtxt(hfile).reshape(3, 3)[:, [1, 0, 2]]       # H acts on (row, col, 1), the tracer gives (x = col, y = row, 1)
+        runs = sw.trace_occupancy(sw.load_occupancy(image), to_world)
+        walls = data.wall_grid_from_world(runs, args.map_reach)
+        if rank == 0:
+            print("Map image %s: %d boundary runs under a grid of %d x %d cells (cell %.3f, reach %.3f world units)"
+                  % (image, walls.M, walls.nx, walls.ny, walls.cell / data.ss, args.map_reach))
+    n_walls = 0 if walls is None else walls.M if isinstance(walls, sw.WallGrid) else walls.shape[0]
+    flat_walls = None if isinstance(walls, sw.WallGrid) else walls           # what the refinement takes
     maps = None
     if many and wall_files:               # one map per recording: its held-out scenes are judged against its own
         walls, maps = None, data.maps_from_world([sw.load_walls(f) for f in wall_files])
@@ -243,7 +269,7 @@ def main(argv=None):
     if wall_loss is not None:
         tr.set_wall_loss(walls, *wall_loss)
         if rank == 0:
-            print("Wall loss: %d walls, dist %.2f, weight %.2f" % (walls.shape[0], wall_loss[0], wall_loss[1]))
+            print("Wall loss: %d walls, dist %.2f, weight %.2f" % (n_walls, wall_loss[0], wall_loss[1]))
     for epoch in range(1, args.epochs + 1):
         t0 = time.perf_counter()
         if train_set is not None:
@@ -291,20 +317,20 @@ def main(argv=None):
                       % (args.k, args.risk, rk["risk_mean"], 100 * rk["col_gt_agent"], rk["brier"], rk["brier_diag"], rk["brier_base"],
                          rk["risk_hit"], rk["risk_miss"], rk["t_first_err"], rk["n_ego"]))
             if args.refine is not None:
-                rf = tr.evaluate_refine(data, n_gen_samples=args.k, dist=args.refine, walls=walls)
+                rf = tr.evaluate_refine(data, n_gen_samples=args.k, dist=args.refine, walls=flat_walls)
                 print("Plan refinement (leave-one-out, %d draws, penalty within %.2f, conflict within %.2f): predicted risk %.3f -> %.3f | "
                       "collisions with the true futures %.1f %% -> %.1f %% | expected penalty %.3f -> %.3f | mean largest move %.3f | "
                       "%d agents with company"
                       % (args.k, args.refine, rf["coll_dist"], rf["risk_cv"], rf["risk_ref"], 100 * rf["col_cv"], 100 * rf["col_ref"],
                          rf["pen_cv"], rf["pen_ref"], rf["moved"], rf["n_ego"]))
-                if walls is not None:
+                if flat_walls is not None:
                     print("  with %d walls: plans within %.2f of a wall %.1f %% -> %.1f %% | wall penalty %.3f -> %.3f"
-                          % (walls.shape[0], rf["coll_dist"], 100 * rf["wall_cv"], 100 * rf["wall_ref"], rf["penw_cv"], rf["penw_ref"]))
+                          % (n_walls, rf["coll_dist"], 100 * rf["wall_cv"], 100 * rf["wall_ref"], rf["penw_cv"], rf["penw_ref"]))
             if walls is not None:
                 wl = tr.evaluate_walls(data, walls, n_gen_samples=args.k, wall_dist=wall_dist)
                 print("Walls (%d segments, within %.2f): %.1f %% of the draws, %.1f %% of the agents in some draw, %.1f %% in every draw "
                       "(ground truth %.1f %%) | Min(%d) ADE,FDE over the clear draws = (%.3f, %.3f) | first conflict at frame %.2f"
-                      % (walls.shape[0], wall_dist, 100 * wl["wall_draws"], 100 * wl["wall_agents"], 100 * wl["wall_blocked"],
+                      % (n_walls, wall_dist, 100 * wl["wall_draws"], 100 * wl["wall_agents"], 100 * wl["wall_blocked"],
                          100 * wl["wall_gt"], args.k, wl["ade_min_free"], wl["fde_min_free"], wl["t_first"]))
             for i in range(len(maps) if maps is not None else 0):
                 part = data.test_part(i)

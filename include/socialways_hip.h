@@ -630,6 +630,52 @@ int sw_wall_grad(const float* pos, int pstride, const float* start /*[B,sstride]
                  const int* len /*[B] or NULL*/, int K, int B, int Tp, const float* walls /*[M,2,2]*/, int M,
                  float dw, float scale, float* dpos /*[K,B,Tp,dstride], += */, int dstride,
                  float* loss /*[K,B] or NULL*/, int* count /*[K,B] or NULL*/, void* stream);
+/* GRID: sw_path_walls and sw_wall_grad for a map of any size - M has no cap but int32 - whose walls stay in global memory under
+ * a uniform grid (socialways_amd.WallGrid builds and validates it on the host): nx x ny square cells of edge 1 / inv_cell, cell
+ * (ix, iy) covering [x0 + ix cell, x0 + (ix + 1) cell) x [y0 + iy cell, ...), nx ny <= 2^20;
+ *   wall_cells [M,4] int32   (ix0, iy0, ix1, iy1): the cell range of wall m's bounding box, clamped into the grid;
+ *   cell_ptr [nx ny + 1], cell_walls [cell_ptr[nx ny]] int32: cell c = iy nx + ix lists cell_walls[cell_ptr[c] .. cell_ptr[c + 1])
+ *              = the walls whose range holds (ix, iy) - wall m is listed in EVERY cell of its range - in ascending order;
+ *   reach      the largest distance, in the coordinates of the walls, a call may ask about.
+ * Paths, segments, start, the gating by len, the thresholds and the outputs are those of the flat entries; the pair arithmetic
+ * is the CLOSEST APPROACH above and nothing else, the decisions are the flat kernels' expressions |c|^2 < dw^2 and
+ * sqrtf(|c|^2) * inv_ss < dist.  What differs is which pairs are looked at:
+ * QUERY RANGE of a counted segment p0 -> p1: the cell range of its bounding box inflated by reach,
+ *   floor((min(p0.x, p1.x) - reach - x0) / cell) .. floor((max(p0.x, p1.x) + reach - x0) / cell), likewise in y, formed in fp32
+ *   as c = ((v -+ reach) - x0) * inv_cell and widened by the slack 2^-21 (|c| + |x0| inv_cell) on either side - twice the bound
+ *   4 u |c| + u |x0| / cell, u = 2^-24, of the three roundings and of inv_cell - c itself held inside +-2^22 before the slack, so that it stays finite - then clamped to 0 .. nx - 1; empty when it
+ *   lies wholly outside the grid or a bound is NaN.  The clamps come before the float-to-int conversion: NaN or huge points
+ *   index nothing out of range.  The cells are walked row-major (iy outer, ix inner), a cell's list in ascending order.
+ * VISIT-ONCE RULE: wall m is visited in cell (ix, iy) only if ix == max(wall_cells[m].ix0, qx0) and iy == max(wall_cells[m].iy0,
+ *   qy0) - the first cell of the intersection of the two ranges.  A wall within reach of the segment has a bounding box that
+ *   meets the inflated box of the segment, so the two ranges intersect and their first common cell lists the wall: every pair
+ *   with |c|^2 < reach^2 is visited exactly once, no pair twice, whatever the cell size.
+ * REFUSED (SW_EARG): dw, or dist / inv_ss, that is not <= reach (1 - 1e-5); the margin covers the rounding of the square root
+ *   and the product, so that every pair a decision can count is a visited one.
+ * OUTPUTS: nseg, first and count are the flat entries' numbers.  loss and dpos are the flat entries' sums over the same counted
+ *   pairs in another fixed order - segments ascending, within a segment the walls in the order of the walk, phi summed per
+ *   segment and then added - so they agree with the flat entries to rounding, not bit for bit.  The one documented difference is
+ *   clear: inv_ss * sqrtf(the smallest visited |c|^2) if that is below reach^2, else +inf - it does not depend on the cells -
+ *   where the flat call reports the distance to the nearest wall however far.  Stores are skipped as in sw_wall_grad.
+ * A lane owns a path, its points and gradient accumulators of a time chunk in registers; walls are read from global memory as
+ * float4 (walls and wall_cells on 16-byte boundaries); no LDS, no barrier, no atomics, one owner per output row: two calls give
+ * the same bits and a path's outputs do not depend on the rest of the batch.  Every loop is bounded by the clamped ranges and
+ * by cell_ptr; what the index arrays hold is the builder's to validate.
+ * Checked before the device is touched - SW_EARG: everything the flat entry refuses of its other arguments; M < 0; cell_ptr
+ * NULL; walls, cell_walls or wall_cells NULL with M > 0; walls or wall_cells off a 16-byte boundary; nx or ny < 1 or
+ * nx ny > 2^20; x0, y0 not finite; inv_cell not finite or <= 0; reach (or its square) not finite or <= 0; the refusal above.
+ * M = 0 is legal (a 1 x 1 grid with an empty list).  B == 0: SW_OK without a launch.                                          */
+int sw_path_walls_grid(const float* pos, int pstride, const float* start /*[B,sstride] or NULL*/, int sstride,
+                       const int* len /*[B] or NULL*/, int K, int B, int Tp, const float* walls /*[M,2,2]*/, int M,
+                       const int* cell_ptr /*[nx ny + 1]*/, const int* cell_walls /*[L]*/, const int* wall_cells /*[M,4]*/,
+                       int nx, int ny, float x0, float y0, float inv_cell, float reach,
+                       float inv_ss, float dist, float* clear /*[K,B]*/, int* first /*[K,B]*/, int* nseg /*[K,B]*/, void* stream);
+int sw_wall_grad_grid(const float* pos, int pstride, const float* start /*[B,sstride] or NULL*/, int sstride,
+                      const int* len /*[B] or NULL*/, int K, int B, int Tp, const float* walls /*[M,2,2]*/, int M,
+                      const int* cell_ptr /*[nx ny + 1]*/, const int* cell_walls /*[L]*/, const int* wall_cells /*[M,4]*/,
+                      int nx, int ny, float x0, float y0, float inv_cell, float reach,
+                      float dw, float scale, float* dpos /*[K,B,Tp,dstride], += */, int dstride,
+                      float* loss /*[K,B] or NULL*/, int* count /*[K,B] or NULL*/, void* stream);
 int sw_dec_rollout_bwd(const float* dpred4 /*[B,Tp,4]*/, const float* enc_w, const float* dec_w,
                        const float* gsave, int B, int To, int Tp, float* gdelta,
                        float* dhT, float* dcT, float* dS_pool /*[B,64]*/, void* stream);

@@ -62,6 +62,9 @@ PROTOTYPES = {
     "sw_plan_refine_walls": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _vp, _i, _f, _f,
                                   _vp, _vp, _vp, _vp]),
     "sw_wall_grad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _f, _vp, _i, _vp, _vp, _vp]),
+    "sw_path_walls_grid": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "sw_wall_grad_grid": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _i, _vp, _vp,
+                               _vp]),
     "sw_dec_rollout_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sw_dec_rollout_bwd_aux": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "sw_gen_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

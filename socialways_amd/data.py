@@ -120,6 +120,13 @@ class SceneDataset:
         seg = wall_segments(np.array(segments, dtype=np.float32, copy=True))
         return torch.from_numpy(self.scale.normalize(seg)).to(self.obsv.device)
 
+    def wall_grid_from_world(self, segments, reach, cell=None):
+        """A map of any size in the coordinates of this dataset, under a grid: world-coordinate segments as walls_from_world()
+        takes them, reach and cell in world units (both are multiplied by ss) -> a WallGrid on the device of the tracks."""
+        ss = float(self.ss)
+        return WallGrid(self.walls_from_world(segments), float(reach) * ss, None if cell is None else float(cell) * ss,
+                        self.obsv.device)
+
     def maps_from_world(self, list_of_segments):
         """The maps of several recordings in the coordinates of this dataset: a sequence of world-coordinate wall sets, each as
         walls_from_world() takes it -> a WallMaps on the device of the tracks (set i = walls_from_world(list_of_segments[i]))."""
@@ -317,6 +324,180 @@ class WallMaps:
     def __getitem__(self, i):
         i = range(self.n_maps)[i]
         return self.walls[int(self.ptr_host[i]):int(self.ptr_host[i + 1])]
+
+
+def check_wall_grid(cell_ptr, cell_walls, wall_cells, nx, ny, M):
+    """What the grid kernels index, checked on the host (numpy integer arrays): cell_ptr (nx ny + 1,) starts at 0, never
+    descends and ends at len(cell_walls); every index of cell_walls lies in [0, M); wall_cells is (M, 4) and every range
+    ix0 <= ix1, iy0 <= iy1 lies inside the nx x ny grid.  ValueError otherwise."""
+    cell_ptr, cell_walls, wall_cells = np.asarray(cell_ptr), np.asarray(cell_walls), np.asarray(wall_cells)
+    if nx < 1 or ny < 1 or nx * ny > WallGrid.MAX_CELLS:
+        raise ValueError("a wall grid has 1 .. %d cells, got %d x %d" % (WallGrid.MAX_CELLS, nx, ny))
+    if cell_ptr.shape != (nx * ny + 1,) or cell_ptr[0] != 0 or (np.diff(cell_ptr) < 0).any():
+        raise ValueError("cell_ptr must be (nx ny + 1,), start at 0 and never descend")
+    if cell_walls.ndim != 1 or int(cell_ptr[-1]) != cell_walls.shape[0]:
+        raise ValueError("cell_ptr must end at the length of cell_walls, got %d and %d" % (cell_ptr[-1], cell_walls.size))
+    if cell_walls.size and (cell_walls.min() < 0 or cell_walls.max() >= M):
+        raise ValueError("cell_walls must hold wall indices in [0, %d)" % M)
+    if wall_cells.shape != (M, 4):
+        raise ValueError("wall_cells must be (M, 4) = (%d, 4), got %s" % (M, wall_cells.shape))
+    if M and ((wall_cells[:, :2] < 0).any() or (wall_cells[:, 0] > wall_cells[:, 2]).any() or (wall_cells[:, 1] > wall_cells[:, 3]).any()
+              or (wall_cells[:, 2] >= nx).any() or (wall_cells[:, 3] >= ny).any()):
+        raise ValueError("every range of wall_cells must lie inside the %d x %d grid" % (nx, ny))
+
+
+class WallGrid:
+    """A map of any size under a uniform grid - the second form of "the map of a call": wherever a single-map call takes a
+    (M, 2, 2) tensor as `walls` (ops / stats path_walls, wall_grad / wall_penalty, set_wall_loss, evaluate_walls) it takes a
+    WallGrid, and then runs the grid kernels (sw_path_walls_grid, sw_wall_grad_grid), which visit only the walls near each path
+    segment.  walls: a tensor or host data, (M, 2, 2) or (M, 4), in the coordinates of the paths, M >= 0 with no cap but int32.
+    reach > 0, finite: the largest distance, in the walls' coordinates, any call may ask about (dw of the penalty, dist / inv_ss
+    of path_walls - each must stay below reach by a relative 1e-5); kept as the fp32 number the kernels see.  cell: the edge of
+    the square cells, default DEFAULT_CELL * reach (of reach, 2 reach and 4 reach the best over the launches measured: DESIGN.md section 9); the grid
+    covers the bounding box of the walls and has at most MAX_CELLS cells - a smaller `cell` is enlarged to fit: `cell` holds
+    the edge in use, `cell_asked` what was asked for.  Built with numpy in float64 from the float32 coordinates,
+    deterministically, and checked on the host (ValueError).
+      walls (M, 2, 2) float32, cell_ptr (nx ny + 1,) int32, cell_walls (L,) int32, wall_cells (M, 4) int32 on `device`: wall m
+      is listed in EVERY cell of the cell range wall_cells[m] = (ix0, iy0, ix1, iy1) of its bounding box, cell c = iy nx + ix
+      lists cell_walls[cell_ptr[c]:cell_ptr[c + 1]] in ascending order; cell_ptr_host, cell_walls_host, wall_cells_host: their
+      numpy copies; origin (x0, y0): the fp32 lower corner; nx, ny, M, L, inv_cell (fp32).
+    M = 0 gives a 1 x 1 grid with an empty list.  clear of path_walls saturates at +inf beyond reach (the one documented
+    difference from a tensor map); refine_plans / plan_refine keep their walls in LDS and refuse a WallGrid."""
+    MAX_CELLS = 1 << 20
+    DEFAULT_CELL = 4.0       # in units of reach
+
+    def __init__(self, walls, reach, cell=None, device="cuda"):
+        w = torch.as_tensor(walls if isinstance(walls, torch.Tensor) else np.asarray(walls), dtype=torch.float32)
+        host = np.ascontiguousarray(wall_segments(w).detach().cpu().numpy())
+        M = host.shape[0]
+        if not np.isfinite(host).all():
+            raise ValueError("the walls of a WallGrid must be finite")
+        if M > 0x7fffffff // 4:
+            raise ValueError("a WallGrid holds %d walls: more than int32 offsets reach" % M)
+        with np.errstate(over="ignore"):
+            r32 = np.float32(reach)
+            ok = np.isfinite(r32) and r32 > 0 and np.isfinite(r32 * r32) and r32 * r32 > 0
+        if not ok:
+            raise ValueError("reach must be finite and > 0 (and its square an fp32 number), got %r" % (reach,))
+        self.reach = float(r32)
+        asked = self.DEFAULT_CELL * self.reach if cell is None else float(cell)
+        if not (np.isfinite(asked) and asked > 0.0):
+            raise ValueError("cell must be finite and > 0, got %r" % (cell,))
+        pts = host.reshape(-1, 2).astype(np.float64)
+        lo = pts.min(0) if M else np.zeros(2)
+        ext = pts.max(0) - lo if M else np.zeros(2)
+        c = asked
+
+        def dims(c):
+            return int(np.floor(ext[0] / c)) + 1, int(np.floor(ext[1] / c)) + 1
+        with np.errstate(over="ignore", divide="ignore"):
+            while not (np.isfinite(ext / c).all() and dims(c)[0] * dims(c)[1] <= self.MAX_CELLS):
+                c *= 1.25                                          # the cell cap: enlarge until the box fits
+            inv32 = np.float32(1.0 / c)
+        if not (np.isfinite(inv32) and inv32 > 0):
+            raise ValueError("cell %r has no fp32 inverse" % c)
+        nx, ny = dims(c)
+        self.cell_asked, self.cell, self.inv_cell = asked, float(c), float(inv32)
+        self.origin, self.nx, self.ny, self.M = (float(lo[0]), float(lo[1])), nx, ny, M
+        # the cell range of every wall's bounding box, clamped into the grid
+        seg = host.astype(np.float64)
+        i0 = np.floor((seg.min(1) - lo) / c).astype(np.int64)
+        i1 = np.floor((seg.max(1) - lo) / c).astype(np.int64)
+        top = np.array([nx - 1, ny - 1])
+        i0, i1 = np.clip(i0, 0, top), np.clip(i1, 0, top)
+        wc = np.concatenate([i0, i1], 1).reshape(M, 4)
+        wx, wy = i1[:, 0] - i0[:, 0] + 1, i1[:, 1] - i0[:, 1] + 1
+        n = wx * wy
+        Ltot = int(n.sum())
+        if Ltot > 0x7fffffff:
+            raise ValueError("the cell lists hold %d entries: more than int32 offsets reach - use a larger cell" % Ltot)
+        wid = np.repeat(np.arange(M, dtype=np.int64), n)
+        local = np.arange(Ltot, dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+        cid = (i0[wid, 1] + local // wx[wid]) * nx + i0[wid, 0] + local % wx[wid]
+        order = np.argsort(cid, kind="stable")                    # wid ascends: the indices ascend within a cell
+        self.cell_walls_host = wid[order].astype(np.int32)
+        self.cell_ptr_host = np.concatenate([[0], np.cumsum(np.bincount(cid, minlength=nx * ny))]).astype(np.int32)
+        self.wall_cells_host = wc.astype(np.int32)
+        self.L = Ltot
+        check_wall_grid(self.cell_ptr_host, self.cell_walls_host, self.wall_cells_host, nx, ny, M)
+        self.walls = torch.from_numpy(host).to(device).contiguous()
+        self.cell_ptr = torch.from_numpy(self.cell_ptr_host).to(device)
+        self.cell_walls = torch.from_numpy(self.cell_walls_host).to(device)
+        self.wall_cells = torch.from_numpy(self.wall_cells_host).to(device)
+
+    @property
+    def device(self):
+        return self.walls.device
+
+    def key(self):
+        """The device addresses and sizes a captured launch bakes in: the grid's part of a graph key."""
+        return (self.walls.data_ptr(), self.M, self.cell_ptr.data_ptr(), self.cell_walls.data_ptr(), self.L, self.wall_cells.data_ptr(),
+                self.nx, self.ny, self.origin, self.inv_cell, self.reach)
+
+
+def trace_occupancy(occ, to_world=None):
+    """An obstacle image -> the walls around its obstacles: occ (H, W) boolean, True = occupied; pixel (r, c) covers
+    [c, c + 1] x [r, r + 1], x the column and y the row; what lies outside the array is free.  A unit edge is a wall where
+    exactly one of the two pixels it separates is occupied, and consecutive edges on one grid line merge into one maximal
+    run.  Returns (M, 4) float32 `x0 y0 x1 y1`: the horizontal runs ordered by (y, x0), then the vertical ones by (x, y0).
+    to_world: a 3 x 3 homography applied to (x, y, 1) of the end points (divided by the third component).  ETH's H.txt acts
+    on (row, col, 1): swapping the first two columns of that matrix (`H[:, [1, 0, 2]]`) is the caller's."""
+    occ = np.asarray(occ)
+    if occ.ndim != 2 or occ.dtype != np.bool_:
+        raise ValueError("occ must be a boolean (H, W) array, got %s %s" % (occ.dtype, occ.shape))
+    P = np.pad(occ, 1)
+
+    def runs(edge):
+        """edge (n_lines, n): -> (line, first, behind-last) of every maximal run of True, in row-major order"""
+        d = np.diff(np.pad(edge, ((0, 0), (1, 1))).astype(np.int8), axis=1)
+        line, a = np.nonzero(d == 1)
+        _, b = np.nonzero(d == -1)
+        return line, a, b
+    y, xa, xb = runs(P[:-1, 1:-1] != P[1:, 1:-1])                  # line y separates rows y - 1 and y
+    x, ya, yb = runs((P[1:-1, :-1] != P[1:-1, 1:]).T)              # line x separates columns x - 1 and x
+    seg = np.concatenate([np.stack([xa, y, xb, y], 1), np.stack([x, ya, x, yb], 1)]).astype(np.float64).reshape(-1, 4)
+    if to_world is not None:
+        Hm = np.asarray(to_world, np.float64)
+        if Hm.shape != (3, 3):
+            raise ValueError("to_world must be a 3 x 3 homography, got %s" % (Hm.shape,))
+        p = np.concatenate([seg.reshape(-1, 2), np.ones((2 * seg.shape[0], 1))], 1) @ Hm.T
+        seg = (p[:, :2] / p[:, 2:]).reshape(-1, 4)
+    return seg.astype(np.float32)
+
+
+def synth_occupancy(seed=0, H=480, W=640, n_rect=40, n_disc=30):
+    """A synthetic obstacle image for trace_occupancy(): n_rect axis-aligned rectangles (sides 8 .. 60 pixels) and n_disc discs
+    (radii 5 .. 30) at seeded random places of an (H, W) boolean array - the map the timing tools trace."""
+    rng = np.random.RandomState(seed)
+    occ = np.zeros((H, W), dtype=np.bool_)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for _ in range(n_rect):
+        h, w = rng.randint(8, 61, 2)
+        r, c = rng.randint(0, H - h), rng.randint(0, W - w)
+        occ[r:r + h, c:c + w] = True
+    for _ in range(n_disc):
+        rad = rng.randint(5, 31)
+        r, c = rng.randint(rad, H - rad), rng.randint(rad, W - rad)
+        occ |= (yy - r) ** 2 + (xx - c) ** 2 <= rad * rad
+    return occ
+
+
+def load_occupancy(path, threshold=128, invert=False):
+    """An obstacle image file -> (H, W) boolean for trace_occupancy(): a `.npy` array always, any image format through PIL when
+    PIL is importable (imported here, not a dependency).  A boolean array is taken as it is, anything else is occupied where
+    its value (grey level) >= threshold; invert flips the result."""
+    if str(path).lower().endswith(".npy"):
+        a = np.load(path)
+    else:
+        try:
+            from PIL import Image
+        except ImportError:
+            raise ValueError("%s: reading an image needs PIL, which is not installed - convert it to a .npy array" % path)
+        a = np.asarray(Image.open(path).convert("L"))
+    if a.ndim != 2:
+        raise ValueError("%s: an occupancy map is (H, W), got %s" % (path, a.shape))
+    occ = a if a.dtype == np.bool_ else a >= threshold
+    return ~occ if invert else occ
 
 
 def load_walls(path):

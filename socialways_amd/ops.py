@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .data import check_obs_len, wall_segments
+from .data import WallGrid, check_obs_len, wall_segments
 
 
 class SceneIndex:
@@ -987,8 +987,35 @@ def check_walls(walls, device=None):
 def walls_arg(walls, device):
     """The map as the layers above take it - a tensor (SceneDataset.walls_from_world) or host data, (M, 2, 2) or (M, 4), M = 0
     included, in the coordinates of the paths - checked without touching the device -> float32 (M, 2, 2) on `device`."""
+    if isinstance(walls, WallGrid):                           # the indexed form passes through: it was checked when it was built
+        return check_wall_grid_arg(walls, L.indexed_device(device))
     w = torch.as_tensor(walls if isinstance(walls, torch.Tensor) else np.asarray(walls), dtype=torch.float32)
     return check_walls(wall_segments(w))[0].to(device)
+
+
+def check_wall_grid_arg(grid, device, within=None, what="the distance"):
+    """A WallGrid as the map of a call, checked without touching the device: its tensors on `device`, and `within` - the
+    distance the call asks about, in the walls' coordinates, as the entry sees it - below the grid's reach by the relative
+    margin 1e-5 (sw_path_walls_grid) -> the grid."""
+    if grid.device != device:
+        raise ValueError("the WallGrid must be on the device of pos, got %s and %s" % (grid.device, device))
+    if within is not None and not float(within) <= grid.reach * (1.0 - 1e-5):
+        raise ValueError("%s %r is not below the reach %r of the WallGrid (by a relative 1e-5): build the grid with a larger reach"
+                         % (what, float(within), grid.reach))
+    return grid
+
+
+def refuse_wall_grid(walls, what):
+    """The refinement keeps its walls in LDS: a call that feeds it refuses a WallGrid, before anything is sampled or launched."""
+    if isinstance(walls, WallGrid):
+        raise ValueError("%s does not take a WallGrid: the refinement keeps its walls in LDS (a tensor of at most %d walls)"
+                         % (what, L.WALLS_MAX))
+
+
+def _grid_c_args(g):
+    """walls, M and the grid as sw_path_walls_grid / sw_wall_grad_grid take them"""
+    return (L.ptr(g.walls), g.M, L.ptr(g.cell_ptr), L.ptr(g.cell_walls), L.ptr(g.wall_cells), g.nx, g.ny, g.origin[0], g.origin[1],
+            g.inv_cell, g.reach)
 
 
 def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
@@ -1004,7 +1031,11 @@ def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
     B, Tp, pstride = _check_pos(pos, K)
     check_distance("dist", dist)
     check_positive("inv_ss", inv_ss)
-    walls, M = check_walls(walls, pos.device)
+    grid = walls if isinstance(walls, WallGrid) else None
+    if grid is not None:
+        check_wall_grid_arg(grid, pos.device, float(np.float32(dist)) / float(np.float32(inv_ss)), "dist / inv_ss")
+    else:
+        walls, M = check_walls(walls, pos.device)
     start, sstride = _start_arg(start, B, pos.device)
     lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
@@ -1013,6 +1044,10 @@ def path_walls(pos, start, K, walls, dist, inv_ss=1.0, lens=None):
     first = torch.empty(K, B, dtype=torch.int32, device=pos.device)
     nseg = torch.empty(K, B, dtype=torch.int32, device=pos.device)
     if B == 0:
+        return clear, first, nseg
+    if grid is not None:
+        L.call("sw_path_walls_grid", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, *_grid_c_args(grid),
+               float(inv_ss), float(dist), L.ptr(clear), L.ptr(first), L.ptr(nseg), L.stream())
         return clear, first, nseg
     L.call("sw_path_walls", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, L.ptr(walls), M,
            float(inv_ss), float(dist), L.ptr(clear), L.ptr(first), L.ptr(nseg), L.stream())
@@ -1032,12 +1067,20 @@ def wall_grad(pos, start, K, walls, dw, scale, dpos, loss=None, count=None, lens
     B, Tp, pstride = _check_pos(pos, K)
     dstride = _check_grad_outputs(pos, dpos, ((K * B, Tp), (K, B, Tp)), loss, count, ((K, B), (K * B,)))
     dw, scale = _grad_scalars("dw", dw, scale)
-    walls, M = check_walls(walls, pos.device)
+    grid = walls if isinstance(walls, WallGrid) else None
+    if grid is not None:
+        check_wall_grid_arg(grid, pos.device, float(np.float32(dw)), "dw")
+    else:
+        walls, M = check_walls(walls, pos.device)
     start, sstride = _start_arg(start, B, pos.device)
     lens = _lens_arg(lens, B, pos.device)
     L.require_gpu(pos)
     pos = pos.contiguous()
     if B == 0:
+        return dpos
+    if grid is not None:
+        L.call("sw_wall_grad_grid", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, *_grid_c_args(grid),
+               dw, scale, L.ptr(dpos), dstride, L.ptr(loss), L.ptr(count), L.stream())
         return dpos
     L.call("sw_wall_grad", L.ptr(pos), pstride, L.ptr_strided(start), sstride, L.ptr(lens), K, B, Tp, L.ptr(walls), M, dw, scale,
            L.ptr(dpos), dstride, L.ptr(loss), L.ptr(count), L.stream())
@@ -1092,6 +1135,7 @@ def plan_refine(pos, start, scenes, K, plans, plan_start, q_scene, q_ego, d0, in
     and returns the same bits in refined, moved and cost[..., :3]."""
     B, Tp, pstride = _check_pos(pos, K, scenes.B)
     M = -1
+    refuse_wall_grid(walls, "plan_refine")
     if walls is not None:
         wall_d0 = float(d0 if wall_d0 is None else wall_d0)
         check_descent(d0, n_iter, lr, w_track, w_smooth, max_move, wall_d0=wall_d0, w_wall=w_wall)

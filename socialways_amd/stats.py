@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .data import check_pred_len
+from .data import WallGrid, check_pred_len
 
 
 def _dev(x, device):
@@ -301,7 +301,8 @@ def plan_risk(trajs, sub_batches, plans, coll_dist, plan_start=None, start=None,
 def path_walls(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cuda"):
     """How close do paths come to the static map (`sw_path_walls`), for trajectories from anywhere: trajs (K, B, T, 2 | 4) or
     (B, T, 2 | 4), x and y first - draws, true futures or plans; walls (M, 2, 2): line segments [w0, w1] in the units of trajs, a
-    zero-length one being a post, M = 0 .. 1024; start (B, 2) or None: a point in front of every path, giving T segments
+    zero-length one being a post, M = 0 .. 1024 - or a WallGrid of any size (then `sw_path_walls_grid`, and clear is +inf beyond
+    the grid's reach); start (B, 2) or None: a point in front of every path, giving T segments
     instead of T - 1; distances are multiplied by `scale`; lens (B,) or None: the frames every agent is present for, as
     scene_clearance_len().  Within a segment the path point moves linearly and the wall stands still.
     Returns device tensors shaped like the leading axes of trajs: clear - the smallest distance to any wall, +inf without
@@ -312,6 +313,8 @@ def path_walls(trajs, walls, dist, start=None, scale=1.0, lens=None, device="cud
     t, lead = _trajs_arg(trajs, device, (4, 3))
     K, B, T = t.shape[0], t.shape[1], t.shape[2]
     w = ops.walls_arg(walls, device)
+    if isinstance(w, WallGrid):
+        ops.check_wall_grid_arg(w, t.device, float(np.float32(dist)) / float(np.float32(scale)), "dist / scale")
     start = _start_arg(start, B, device)
     lens = _lens_arg(lens, B, T, t.device)
     L.require_gpu(t)
@@ -322,7 +325,7 @@ def wall_penalty(trajs, walls, dist, start=None, scale=1.0, lens=None, device="c
     """The wall penalty SocialWaysTrainer.set_wall_loss() trains against, for trajectories from anywhere (`sw_wall_grad`): per
     segment of a path and per wall, max(0, 1 - (scale |c|)^2 / dist^2)^2 with c the closest approach of path_walls() - the
     path point moving linearly within the segment, the wall standing still.  trajs (K, B, T, 2 | 4) or (B, T, 2 | 4), x and y
-    first - the K draws, true futures or plans; walls (M, 2, 2) as path_walls(), M = 0 .. 1024; start (B, 2) or None: a point in
+    first - the K draws, true futures or plans; walls (M, 2, 2) as path_walls(), M = 0 .. 1024, or a WallGrid; start (B, 2) or None: a point in
     front of every path (the last observed position; it takes no gradient), giving T segments instead of T - 1; `scale`
     converts trajs to the units of `dist`, as in clearance_penalty(); lens (B,) or None: the frames every agent is present
     for, as path_walls().  Returns device tensors (loss, grad, count): loss and count (int32) shaped like the leading axes of
@@ -333,6 +336,8 @@ def wall_penalty(trajs, walls, dist, start=None, scale=1.0, lens=None, device="c
     t, lead = _trajs_arg(trajs, device, (4, 3))
     K, B, T = t.shape[0], t.shape[1], t.shape[2]
     w = ops.walls_arg(walls, device)
+    if isinstance(w, WallGrid):
+        ops.check_wall_grid_arg(w, t.device, float(np.float32(dw)), "dist / scale")
     start = _start_arg(start, B, device)
     lens = _lens_arg(lens, B, T, t.device)
     L.require_gpu(t)
@@ -361,6 +366,7 @@ def refine_plans(trajs, sub_batches, plans, dist, plan_start, start, scene=None,
     (Q, P, 2, 4), the unweighted wall penalty last.  Where a plan CROSSES a wall the gradient is exactly 0: descent cannot undo a
     crossing; path_walls() reports it."""
     d0, scale = _dist_over_scale(dist, scale)
+    ops.refuse_wall_grid(walls, "refine_plans")
     wall = {}
     if walls is not None:
         wall = dict(walls=ops.walls_arg(walls, device), wall_d0=d0 if wall_dist is None else float(wall_dist) / scale, w_wall=w_wall)

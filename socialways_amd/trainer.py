@@ -26,7 +26,7 @@ import torch.optim as opt
 
 from . import _lib as L
 from . import ops
-from .data import shard_scenes
+from .data import WallGrid, shard_scenes
 from .model import Discriminator, Generator, get_traj_4d, predict_cv, refuse_obs_len
 from .noise import EVAL, TRAIN, DeviceNoise
 
@@ -263,8 +263,20 @@ _PRED_LEN_TRAIN = ("a truncated future has no discriminator input (D encodes the
 
 
 def _wall_key(wall):
-    """The wall term's entry of the graph key: None, or (the address of the walls, M, dist, weight)."""
-    return None if wall is None else (wall[0].data_ptr(), int(wall[0].shape[0]), wall[1], wall[2])
+    """The wall term's entry of the graph key: None, or (the address of the walls, M, dist, weight) - with a WallGrid, its key()
+    in place of the first two."""
+    if wall is None:
+        return None
+    if isinstance(wall[0], WallGrid):
+        return wall[0].key() + (wall[1], wall[2])
+    return (wall[0].data_ptr(), int(wall[0].shape[0]), wall[1], wall[2])
+
+
+def _wall_reach(wall, ss):
+    """A step with a WallGrid behind the wall term asks about dw = dist * ss: refused on the host, before any launch, unless
+    the grid's reach covers it."""
+    if wall is not None and isinstance(wall[0], WallGrid):
+        ops.check_wall_grid_arg(wall[0], wall[0].device, float(np.float32(wall[1] * float(ss))), "set_wall_loss: dist * ss =")
 
 
 class SocialWaysTrainer:
@@ -276,7 +288,7 @@ class SocialWaysTrainer:
     ragged_fused = False    # step(obs_len=...): D updates in one launch (sw_disc_update_ragged) and, with use_graph, captured steps
     clearance_loss = None   # (dist, weight): the scene-clearance term of the generator loss (set_clearance_loss()); None = off
     last_clearance = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_clearance_grad's outputs)
-    wall_loss = None        # (walls (M, 2, 2) on the device, dist, weight): the wall term of the generator loss (set_wall_loss()); None = off
+    wall_loss = None        # (walls (M, 2, 2) on the device or a WallGrid, dist, weight): the wall term of the generator loss (set_wall_loss()); None = off
     last_wall_loss = None   # with the term on: (loss (B,), count (B,) int32) of the last step (sw_wall_grad's outputs)
     last_walls = None       # refine_plans(walls=...): (clear (Q, P, 2), first (Q, P, 2) int32) before | after; None without walls
 
@@ -334,7 +346,9 @@ class SocialWaysTrainer:
         to the wall (the quantity behind wall_* of evaluate_walls(), sw_wall_grad), with dw = dist * ss: `dist` is in world
         units like evaluate_walls()'s wall_dist, Bg the agents of the global packed batch (the normalisation of the L2 and
         clearance terms).  walls: the static map in the dataset's coordinates (data.walls_from_world(...)), a tensor or host
-        data, (M, 2, 2) or (M, 4), M = 0 .. 1024 (an empty map is accepted); it is copied to the trainer's device unless it is a
+        data, (M, 2, 2) or (M, 4), M = 0 .. 1024 (an empty map is accepted), or a WallGrid of any size on the trainer's device
+        (data.wall_grid_from_world(...); the step then launches sw_wall_grad_grid, and dist * ss must stay below the grid's
+        reach: ValueError from step() before any launch); a tensor is copied to the trainer's device unless it is a
         float32 (M, 2, 2) tensor there already, and the trainer holds it.  A captured step bakes in the tensor's address: writing
         into that tensor in place is seen by the replays; a new map is a new set_wall_loss() call.
         The penalty is C1 where a segment reaches dw, its gradient finite everywhere and exactly 0 where a path CROSSES a wall:
@@ -357,7 +371,8 @@ class SocialWaysTrainer:
             raise ValueError("set_wall_loss: dist must be finite and > 0, got %r" % dist)
         if not (np.isfinite(weight) and weight >= 0.0):
             raise ValueError("set_wall_loss: weight must be finite and >= 0, got %r" % weight)
-        self.wall_loss = (ops.walls_arg(walls, self.device), dist, weight)      # shape and M <= 1024: ValueError
+        walls = ops.walls_arg(walls, self.device)                               # shape and M <= 1024: ValueError
+        self.wall_loss = (walls, dist, weight)
 
     def _pad_z(self, z):
         return z if z.shape[-1] == self.Z_COLS else torch.nn.functional.pad(z, (0, self.Z_COLS - z.shape[-1]))
@@ -646,6 +661,7 @@ class SocialWaysTrainer:
         graph of its own beside the layout's dense graph, obs_len travelling by address through the pinned slot
         (sw_stage_step_ragged), an obs_len given as a device tensor never read by the host.  Still out: the D observation
         pass inside the decode forward launch and the generator-phase D pass inside the decode BPTT launch."""
+        _wall_reach(self.wall_loss, ss)
         self._resolve_collectives()
         B = obsv.shape[0]
         self._obs_len = None        # read by _step_body of this step only
@@ -713,6 +729,7 @@ class SocialWaysTrainer:
                 raise ValueError("step_many(obs_len=...) takes an obs_len for every batch or None, not a mix of both")
             if n_none:
                 obs_len = None
+        _wall_reach(self.wall_loss, ss)
         self._resolve_collectives()
         ols = obs_len if obs_len is not None else [None] * len(batches)
 
@@ -1876,6 +1893,7 @@ class SocialWaysTrainer:
         plans side by side: self.last_walls = (clear (Q, P, 2), first (Q, P, 2) int32), before | after; None after a call
         without walls.  Where a plan CROSSES a wall the wall gradient is exactly 0: descent cannot undo a crossing, last_walls
         reports it.  The tuple returned keeps its arity."""
+        ops.refuse_wall_grid(walls, "refine_plans")
         dist = float(dist)
         coll_dist = dist if coll_dist is None else coll_dist
         if not float(coll_dist) >= 0.0:
@@ -1946,6 +1964,7 @@ class SocialWaysTrainer:
         if not float(coll_dist) >= 0.0:
             raise ValueError("coll_dist must be >= 0, got %r" % (coll_dist,))
         ss = float(data.ss)
+        ops.refuse_wall_grid(walls, "evaluate_refine")
         wall = {}
         if walls is not None:
             wall = dict(walls=ops.walls_arg(walls, self.device), wall_d0=(float(dist) if wall_dist is None else float(wall_dist)) * ss,
@@ -2019,9 +2038,11 @@ class SocialWaysTrainer:
         if not float(wall_dist) >= 0.0:
             raise ValueError("wall_dist must be >= 0, got %r" % (wall_dist,))
         walls = ops.walls_arg(walls, self.device)
+        inv_ss = 1.0 / float(data.ss)
+        if isinstance(walls, WallGrid):          # a map of any size (data.wall_grid_from_world): the reach, before any launch
+            ops.check_wall_grid_arg(walls, walls.device, float(np.float32(wall_dist)) / float(np.float32(inv_ss)), "wall_dist * ss =")
         dn = self._device_noise(noise)
         dev, K = self.device, int(n_gen_samples)
-        inv_ss = 1.0 / float(data.ss)
         base = _EvalSums(dev)
         # conflicting draws | agents with one | agents with no clear draw | conflicting truths | sum min ADE, FDE of the clear
         # draws | agents with a clear draw | sum of the first frames
