@@ -199,6 +199,27 @@ def test_parallel_equal_motion_takes_tau_zero():
     assert torch.equal(count.cpu().long(), count64) and not bool(dpos[:, -1].any())
 
 
+def test_a_closest_approach_exactly_d0_is_not_an_active_pair():
+    """Two agents in step 0.5 apart: |c|^2 = 0.25 = d0^2 exactly at d0 = 0.5, `<` is strict, so count is 0 and the pre-filled
+    -0.0 of the dpos rows keeps its bits (a `+= 0` would leave +0.0); at d0 = 0.75 the same pair is active, against float64."""
+    a = torch.tensor([[0.0, 0.0], [1.0, 0.0]])
+    P = torch.stack([a, a + torch.tensor([0.0, 0.5])])
+    loss64, count64 = CR.penalty(P.double(), None, [], 0.5)
+    assert not bool(count64.any()) and not bool(loss64.any()) and not bool(CR.closed_form_grad(P.double(), None, [], 0.5).any())
+    dpos = torch.full((2, 2, 2), -0.0, device=DEV)
+    loss, count = _call(P.to(DEV), None, [2], 0.5, 1.0, dpos)
+    assert not bool(count.any()) and not bool(loss.any())
+    assert torch.equal(_bits(dpos), _bits(torch.full((2, 2, 2), -0.0, device=DEV))), "a pair that is not active makes no read-modify-write"
+    g64 = CR.closed_form_grad(P.double(), None, [], 0.75)
+    loss64, count64 = CR.penalty(P.double(), None, [], 0.75)
+    assert count64.tolist() == [1, 1] and float(g64.abs().max()) > 1.0
+    dpos = torch.zeros(2, 2, 2, device=DEV)
+    loss, count = _call(P.to(DEV), None, [2], 0.75, 1.0, dpos)
+    _close_grad(dpos, g64, "dpos", "b.exact", "d0 = 0.75")
+    _close_grad(loss, loss64, "loss", "b.exact", "d0 = 0.75")
+    assert torch.equal(count.cpu().long(), count64)
+
+
 # ---- c. stats --------------------------------------------------------------------------------------------------------------------
 def test_stats_clearance_penalty_is_the_ops_call():
     from socialways_amd import stats

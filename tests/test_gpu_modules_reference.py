@@ -171,6 +171,29 @@ def test_attention_weights_of_the_row_kernel(sizes, calls):
             assert float(block.diagonal().abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("score", [40.0, 100.0])
+def test_a_two_agent_scene_with_a_large_pair_score_subtracts_the_row_maximum(score, calls):
+    """One scene of 2 agents whose two pair scores are `score` (f_ij = score Wh_j / |Wh_j|^2; the diagonal is masked to
+    -1000), through the no-grad path - sw_attention_pool_dense, the scene kernels' softmax.  The float64 reference is finite
+    (asserted): the weights are (0, 1) to the last bit and S_i = h_j.  exp(40) = 2.4e17 is an fp32 number, so at 40 a softmax
+    without the subtraction of the row maximum still gives exp(40) / exp(40) = 1; exp(100) = 2.7e43 is not (fp32 ends at
+    3.4e38, exp(88.7)), and there it gives inf / inf: 40 holds the peaked weights to the reference, 100 the subtraction itself."""
+    att = _hip("att", 64)
+    o64 = M.oracle64("att", 64, M.cpu_state(att))
+    _, h, cot = M.att_inputs([2], 64)
+    with torch.no_grad():
+        Wh = o64.W(h.double())
+    f = (score * Wh / (Wh * Wh).sum(-1, keepdim=True))[None].expand(2, 2, 64).float().contiguous()
+    sigma = (f.double() * Wh[None]).sum(-1)
+    assert float((sigma - score).abs().max()) < 1e-3, "both pair scores are `score` after the rounding of f to fp32"
+    inp = (f, h, cot)
+    ref = M.run_att(o64, inp, [2], "cpu", F64, grad=False)
+    assert bool(torch.isfinite(ref["out"]["S"]).all()) and torch.equal(ref["out"]["S"], h.double().flip(0)), "S_i = h_j exactly"
+    got = M.run_att(att, inp, [2], _dev(), F32, grad=False)
+    _called(calls, "sw_attention_pool_dense", absent=["sw_attention_dense_fwd"])
+    M.compare(got, ref, "attention", "2 agents, pair score %g" % score)
+
+
 # ---- encoder --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("H", M.ENC_H)
 @pytest.mark.parametrize("B,T", M.ENC_SHAPES)

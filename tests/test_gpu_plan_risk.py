@@ -78,6 +78,26 @@ def test_constructed_cases_against_the_reference(name):
     assert not bool(zero[0].any()) and not bool(zero[2][..., 0].any()) and torch.equal(zero[1], out[1])
 
 
+def test_a_pair_counts_the_shorter_of_the_agents_and_the_plans_length():
+    """Finite frames behind a length, not NaN (a NaN folds into no minimum and hits nothing, whatever the gate says): one agent
+    and one plan per scene, Tp = 4, no start point, 2 apart on the first segment and 0.25 apart from frame 2 on.  Query 0: the
+    agent has 4 frames and the plan 2, query 1 the other way round - one countable segment either way, so no conflict and a
+    clearance of 2; with both at full length the same paths conflict at frame 2."""
+    t = np.arange(4, dtype=np.float32)
+    agent = np.stack([t, np.zeros(4, np.float32)], 1)
+    plan = np.stack([t, np.array([2.0, 2.0, 0.25, 0.25], np.float32)], 1)
+    case = dict(pos=np.stack([agent, agent])[None], start=None, plans=np.stack([plan, plan])[:, None], plan_start=None, sizes=[1, 1], K=1,
+                Tp=4, inv_ss=1.0, q_scene=np.arange(2, dtype=np.int32), q_ego=None, lens=np.array([4, 2], np.int32),
+                plan_lens=np.array([2, 4], np.int32))
+    want = R.run_reference(case)
+    assert (want["clear_min"] == 2.0).all() and (want["counts"] == [0, -1, -1, 0]).all() and not want["risk"].any()
+    compare("shorter length", case, run(case), want)
+    full = dict(case, lens=None, plan_lens=None)
+    want = R.run_reference(full)
+    assert (want["clear_min"] == 0.25).all() and (want["counts"] == [[[1, 2, 0, 1]], [[1, 2, 1, 1]]]).all() and (want["risk"] == 1.0).all()
+    compare("full length", full, run(full), want)
+
+
 def test_no_query_and_queries_that_name_no_scene():
     from socialways_amd import ops
     case = R.with_queries(CASES["p5"], [0, 1], None)

@@ -12,7 +12,8 @@ c. beyond   M = 2049 against the flat kernels on three slices of the walls: nseg
             non-negative one, clear the minimum under the saturation rule.
 d. exact    two calls, a path alone / in its batch / with the others permuted, the same integers and clear at every cell, rows
             with count 0 and paths outside the grid untouched, a point at 1e30 and NaN padding, posts at reach (1 - 1e-6) and at
-            dw (1 - 1e-6) from segments that straddle a cell line.
+            dw (1 - 1e-6) from segments that straddle a cell line; a wall EXACTLY dist, dw and reach away (no conflict, no pair,
+            clear +inf; profiles/seeded_faults_r2.txt), a segment whose query range loses the post's cell without the slack.
 e. stats    stats.path_walls / stats.wall_penalty = the ops calls, bit for bit.
 f. step     the setup of test_gpu_wall_loss.py part d with its 5 walls in a WallGrid: generator gradients against step64 + the
             float64 gradient of L_wall at that test's bound, D's gradients and the loss rows bit-identical to the step without the
@@ -335,6 +336,93 @@ def test_walls_just_inside_the_reach_across_a_cell_line_are_visited():
         if d == DW:
             assert int(cg.sum()) >= 12, "posts at dw (1 - 1e-6) are counted"
             assert int(_pw(pos, start, 1, grid, DW)[2].sum()) == int(_pw(pos, start, 1, walls, DW)[2].sum()) >= 12
+
+
+def _one_segment():
+    """(0, 0.5) -> (1, 0.5), no start point, above a wall on the x axis: |c|^2 = 0.25 exactly (asserted in float64)"""
+    pos, walls = np.array([[[0.0, 0.5], [1.0, 0.5]]], np.float32), np.array([[[-1.0, 0.0], [2.0, 0.0]]], np.float32)
+    assert float(W.closest(pos[0, 0].astype(np.float64), pos[0, 1].astype(np.float64), walls[0, 0], walls[0, 1])[2]) == 0.25
+    return pos, walls
+
+
+def test_a_wall_exactly_dist_or_dw_away_is_no_conflict_and_no_pair():
+    """The strictness of `< dist` and `< dw` where the reference's margin is 0: at dist = 0.5 the pair is no conflict (nseg 0,
+    first -1), at dw = 0.5 it is not counted and the pre-filled -0.0 of its dpos rows keeps its bits (a `+= 0` would leave +0.0);
+    at 0.75 both count it, the gradient against the float64 reference."""
+    pos, walls = _one_segment()
+    grid = _grid(walls, reach=1.0)
+    assert G.visited(pos[0, 0], pos[0, 1], grid) == [0]
+    assert W.path_walls_reference(pos[None], None, walls, 0.5)["margin"] == 0.0
+    clear, first, nseg = _pw(pos, None, 1, grid, 0.5)
+    assert float(clear[0]) == 0.5 and int(first[0]) == -1 and int(nseg[0]) == 0
+    clear, first, nseg = _pw(pos, None, 1, grid, 0.75)
+    assert float(clear[0]) == 0.5 and int(first[0]) == 1 and int(nseg[0]) == 1
+    ref = WR.reference(pos, None, walls, 0.5)
+    assert ref["count"][0] == 0 and not ref["grad"].any()
+    dpos = torch.full((1, 2, 2), -0.0, device=DEV)
+    loss, count = _grad(pos, None, 1, grid, 0.5, 1.0, dpos)
+    assert int(count[0]) == 0 and float(loss[0]) == 0.0
+    assert torch.equal(_bits(dpos), _bits(torch.full((1, 2, 2), -0.0, device=DEV))), "a pair that is not counted makes no read-modify-write"
+    ref = WR.reference(pos, None, walls, 0.75)
+    assert ref["count"][0] == 1 and abs(ref["grad"][0, 0, 1]) > 1.0
+    dpos = torch.zeros(1, 2, 2, device=DEV)
+    loss, count = _grad(pos, None, 1, grid, 0.75, 1.0, dpos)
+    WR.compare(dpos.cpu().numpy(), loss.cpu().numpy(), count.cpu().numpy(), ref)
+
+
+def test_clear_saturates_at_a_wall_exactly_reach_away():
+    """reach = 0.5 and the only wall at distance 0.5 exactly: the wall is visited (the numpy model of the walk says so) and
+    clear is +inf, `|c|^2 < reach^2` being strict; with a second wall at distance 0.25 it is 0.25."""
+    pos, walls = _one_segment()
+    grid = _grid(walls, reach=0.5)
+    assert G.visited(pos[0, 0], pos[0, 1], grid) == [0] and grid.reach == 0.5
+    clear, first, nseg = _pw(pos, None, 1, grid, 0.25)
+    assert float(clear[0]) == float("inf") and int(first[0]) == -1 and int(nseg[0]) == 0
+    both = np.concatenate([walls, [[[-1.0, 0.25], [2.0, 0.25]]]]).astype(np.float32)
+    grid = _grid(both, reach=0.5)
+    assert sorted(G.visited(pos[0, 0], pos[0, 1], grid)) == [0, 1]
+    clear, first, nseg = _pw(pos, None, 1, grid, 0.25)
+    assert float(clear[0]) == 0.25 and int(first[0]) == -1 and int(nseg[0]) == 0
+    clear, first, nseg = _pw(pos, None, 1, grid, 0.375)
+    assert float(clear[0]) == 0.25 and int(first[0]) == 1 and int(nseg[0]) == 1
+
+
+def test_the_slack_of_the_query_range_keeps_a_cell_the_fp32_floor_loses():
+    """A case where the slack of wq_axis decides an output.  Found on the CPU by a vectorised twin of G.axis_range over random
+    (v, reach, x0, cell) - cell uniform in 0.05 .. 2, reach / cell in 0.25 .. 1, |x0| / cell log-uniform in 1e3 .. 1e5, the post's
+    cell k log-uniform up to 3e5, the post on the first fp32 number inside cell k and the path's end v the first fp32 number
+    within reach (1 - 1e-5) of it - RandomState(1), the first hit among the first 1e6 candidates: the upper side's
+    c = ((v + reach) - x0) * fl(1 / cell) comes out below k = 13187 by the rounding of the product at |c| ~ 1.3e4, the float64
+    quotient lies above it.  Here the model says so with the slack and without, and the kernels are held to the flat ones."""
+    v, reach, x0, cell, k, post = -12390.9951171875, 1.8098340034484863, -38694.34375, 1.994779558380387, 13187, -12389.185546875
+    walls = np.array([[[x0, 0.0], [x0, 0.0]], [[post, 0.0], [post, 0.0]]], np.float32)
+    pos, start = np.array([[[v, 0.0]]], np.float32), np.array([[v - 0.5, 0.0]], np.float32)
+    assert float(pos[0, 0, 0]) == v and float(walls[1, 0, 0]) == post and float(np.float32(reach)) == reach
+    grid = _grid(walls, reach=reach, cell=cell)
+    assert grid.cell == cell and (grid.nx, grid.ny) == (k + 1, 1) and tuple(grid.wall_cells_host[1]) == (k, 0, k, 0)
+    d = (post - v) / reach
+    assert 0.999 < d <= 1 - 1e-5, "the post is within reach (1 - 1e-5) of the path's end in float64"
+    assert G.axis_range(v - 0.5, v, x0, grid.inv_cell, reach, grid.nx)[1] >= k and G.visited(start[0], pos[0, 0], grid) == [1]
+    slack, G.SLACK = G.SLACK, np.float32(0)
+    try:
+        assert G.axis_range(v - 0.5, v, x0, grid.inv_cell, reach, grid.nx)[1] == k - 1, "without the slack the post's cell is not asked about"
+    finally:
+        G.SLACK = slack
+    dist, dw = 0.9 * reach, 0.9999 * reach
+    flat, got = _pw(pos, start, 1, walls, dist), _pw(pos, start, 1, grid, dist)
+    want = W.path_walls_reference(pos[None], start, walls, dist)
+    assert abs(float(want["clear"][0, 0]) - (post - v)) < 1e-12 and int(want["nseg"][0, 0]) == 0
+    assert bool(torch.isfinite(got[0]).all()) and torch.equal(_bits(got[0]), _bits(flat[0])), "clear is the flat kernel's: the post was visited"
+    assert torch.equal(got[1], flat[1]) and torch.equal(got[2], flat[2])
+    ref = WR.reference(pos, start, walls, dw)
+    assert ref["count"][0] == 1 and not WR.reference(pos, start, walls, dw, want_masks=True)["near"][0]
+    # u = 1 - |c|^2 / dw^2 is 9e-5 here, a difference of two fp32 numbers near 1: the count is held to float64, dpos and
+    # loss to the flat kernel by the rule of part b
+    df, dg = torch.zeros(1, 1, 2, device=DEV), torch.zeros(1, 1, 2, device=DEV)
+    (lf, cf), (lg, cg) = _grad(pos, start, 1, walls, dw, 1.0, df), _grad(pos, start, 1, grid, dw, 1.0, dg)
+    assert int(cg[0]) == int(cf[0]) == ref["count"][0] and bool(dg.any())
+    _close_grad(dg, df, "dpos, grid against flat", "d.exact", "slack")
+    _close_grad(lg, lf, "loss, grid against flat", "d.exact", "slack")
 
 
 # ---- e. stats -----------------------------------------------------------------------------------------------------------------------

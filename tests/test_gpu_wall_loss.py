@@ -9,7 +9,8 @@ a. kernel   the rows of _wall_loss_ref.GPU_CASES: R = K B of 1, 63, 64, 65, 129 
             off the near mask; a split-ambiguous path (at most 5 % of a case, near at most 1 %, by the choice of the seed) is
             compared on loss, count and the sum of g over its points.
 b. exact    rows with count 0 and every row at M = 0 untouched, two calls, a path alone / in its batch / with the others
-            permuted, a crossing, a post, a motionless segment, the parallel corridor, count = nseg of ops.path_walls.
+            permuted, a crossing, a post, a motionless segment, the parallel corridor, a wall exactly dw away (not counted, its
+            rows not read: profiles/seeded_faults_r2.txt), count = nseg of ops.path_walls.
 c. stats    stats.wall_penalty = the ops call, bit for bit, for (B, .) and (K, B, .) inputs.
 d. step     trainers with lr_g = lr_d = 0 on [8, 3, 1, 17] (29 agents), To 8, Tp 12, dist 2 (dw = dist * ss = 0.5), weight 1.5,
             5 walls beside the agents' last observed positions: every generator gradient against step64(...).g_run + the
@@ -188,6 +189,35 @@ def test_the_parallel_corridor_ties_go_to_the_first_candidate():
     assert int(count[0]) == ref["count"][0] and not bool(dpos[0, -1].any()), "s = 0 wins every tie: the last point takes nothing"
     _close_grad(dpos.sum(1), torch.as_tensor(ref["grad"]).sum(1), "sum over the points", "b.exact", "parallel corridor")
     _close_grad(loss, torch.as_tensor(ref["loss"]), "loss", "b.exact", "parallel corridor")
+
+
+NEG0 = np.float32(-0.0).view(np.int32)      # the bits of a pre-filled -0.0: a row that took `+= 0` holds +0.0 instead
+
+
+def _written(dpos):
+    """(.., Tp, >= 2) pre-filled with -0.0 -> bool (.., Tp): the kernel made its read-modify-write of the row"""
+    return (_bits(dpos[..., :2].cpu()) != int(NEG0)).any(-1).numpy()
+
+
+def test_a_wall_exactly_dw_away_is_not_counted_and_its_rows_keep_their_bits():
+    """One segment (0, 0.5) -> (1, 0.5) above a wall on the x axis: |c|^2 = 0.25 = dw^2 exactly at dw = 0.5 (the reference's
+    margin is 0, asserted), so the pair is not counted and the pre-filled -0.0 of the dpos rows is not even read; at dw = 0.75
+    it is counted, u = 5 / 9: against the float64 reference, both rows rewritten."""
+    pos, walls = np.array([[[0.0, 0.5], [1.0, 0.5]]], np.float32), np.array([[[-1.0, 0.0], [2.0, 0.0]]], np.float32)
+    cc = W.closest(pos[0, 0].astype(np.float64), pos[0, 1].astype(np.float64), walls[0, 0], walls[0, 1])[2]
+    assert float(cc) == 0.25 == float(np.float32(0.5) * np.float32(0.5))
+    ref = WR.reference(pos, None, walls, 0.5)
+    assert ref["count"][0] == 0 and not ref["grad"].any()
+    dpos = torch.full((1, 2, 2), -0.0, device=DEV)
+    loss, count = _call(torch.as_tensor(pos).to(DEV), None, 1, walls, 0.5, 1.0, dpos)
+    assert int(count[0]) == 0 and float(loss[0]) == 0.0
+    assert not _written(dpos).any(), "a pair that is not counted makes no read-modify-write"
+    ref = WR.reference(pos, None, walls, 0.75)
+    assert ref["count"][0] == 1 and abs(ref["grad"][0, 0, 1]) > 1.0
+    dpos = torch.full((1, 2, 2), -0.0, device=DEV)
+    loss, count = _call(torch.as_tensor(pos).to(DEV), None, 1, walls, 0.75, 1.0, dpos)
+    WR.compare(dpos.cpu().numpy(), loss.cpu().numpy(), count.cpu().numpy(), ref)
+    assert _written(dpos).all()
 
 
 def test_count_is_nseg_of_path_walls():

@@ -23,25 +23,26 @@ T = "tests/test_gpu_%s.py"
 # test modules by touched file, the most specific first (-x stops at the first failure)
 COVER = {
     "sw_misc.hip": ["launch_tails", "stats", "kernels", "sample", "rank", "modules_reference", "gen_images"],
-    "sw_lstm.hip": ["modules_reference", "gen_reference", "kernels", "lstm_zero_state"],
-    "sw_lstm_dev.h": ["gen_reference", "disc_reference", "modules_reference", "kernels"],
-    "sw_decoder.hip": ["gen_reference", "kernels", "sample", "ragged_next", "modules_reference"],
+    "sw_lstm.hip": ["modules_reference", "gen_reference", "kernels", "lstm_zero_state", "ragged", "ragged_train"],
+    "sw_lstm_dev.h": ["gen_reference", "disc_reference", "modules_reference", "kernels", "ragged", "ragged_train", "ragged_fused"],
+    "sw_decoder.hip": ["gen_reference", "kernels", "sample", "ragged_next", "modules_reference", "ragged", "ragged_train"],
     "sw_social.hip": ["gen_reference", "modules_reference", "scene_wg", "kernels"],
-    "sw_disc.hip": ["disc_reference", "kernels", "rank"],
-    "sw_disc_dev.h": ["disc_reference", "kernels", "rank"],
+    "sw_disc.hip": ["disc_reference", "kernels", "rank", "ragged", "ragged_train", "ragged_fused"],
+    "sw_disc_dev.h": ["disc_reference", "kernels", "rank", "ragged", "ragged_train", "ragged_fused"],
     "sw_wide.hip": ["wide_reference", "wide_step_reference"],
     "sw_wgrad.hip": ["wgrad_bounds", "wgrad_fixed", "disc_reference", "gen_reference"],
     "sw_wgrad_dev.h": ["wgrad_bounds", "wgrad_fixed", "disc_reference", "gen_reference"],
     "sw_wgrad.h": ["kernels", "disc_reference", "step_reference", "launch_tails"],
     "sw_clearance_grad.hip": ["clearance_loss"],
     "sw_scene.hip": ["scene"],
-    "sw_scene_dev.h": ["scene", "compose", "clearance_loss", "plan_risk", "wall_loss"],
+    "sw_scene_dev.h": ["scene", "compose", "clearance_loss", "plan_risk", "wall_loss", "wall_grid", "walls", "ragged_next"],
     "sw_compose.hip": ["compose"],
     "sw_plan_risk.hip": ["plan_risk"],
     "sw_plan_refine.hip": ["refine", "walls"],
     "sw_walls.hip": ["walls"],
-    "sw_wall_dev.h": ["walls", "wall_loss"],
+    "sw_wall_dev.h": ["walls", "wall_loss", "wall_grid"],
     "sw_wall_grad.hip": ["wall_loss"],
+    "sw_wall_grid.hip": ["wall_grid"],
     "sw_nms.hip": ["nms"],
     "sw_noise.hip": ["noise"],
     "sw_generic.hip": ["modules_reference", "wide_reference", "trainer"],
@@ -51,8 +52,9 @@ COVER = {
 # wall seconds of each module on the unmodified library (pytest --durations, rounded up); a module not listed counts 120
 SECONDS = {T % m: s for m, s in {
     "clearance_loss": 3, "compose": 6, "disc_reference": 3, "gen_images": 1, "gen_reference": 8, "kernels": 10, "launch_tails": 1,
-    "lstm_zero_state": 1, "modules_reference": 2, "nms": 1, "noise": 1, "plan_risk": 1, "ragged_next": 4, "rank": 1, "refine": 2,
-    "sample": 5, "scene": 4, "scene_wg": 1, "stats": 1, "step_reference": 6, "trainer": 28, "wall_loss": 9, "walls": 8, "wgrad_bounds": 1,
+    "lstm_zero_state": 1, "modules_reference": 2, "nms": 1, "noise": 1, "plan_risk": 1, "ragged": 5, "ragged_fused": 3,
+    "ragged_next": 4, "ragged_train": 6, "rank": 1, "refine": 2, "sample": 5, "scene": 4, "scene_wg": 1, "stats": 1,
+    "step_reference": 6, "trainer": 28, "wall_grid": 10, "wall_loss": 9, "walls": 8, "wgrad_bounds": 1,
     "wgrad_fixed": 1, "wide_reference": 5, "wide_step_reference": 7}.items()}
 FULL_SECONDS = 900       # the whole -m gpu suite: 315 s
 HIP_ERRORS = ("HIP error", "hipError", "illegal memory access", "Memory access fault", "HSA_STATUS_ERROR", "Aborted", "Segmentation fault")
